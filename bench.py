@@ -72,6 +72,10 @@ def parse_args(argv=None):
                          "other recurrence is reported beside it under `variants`")
     ap.add_argument("--eisenstat", action="store_true", help="(accepted for compatibility: Eisenstat's form is the default since round 4)")
     ap.add_argument("--cpu-full", action="store_true", help="(default since round 3) time the reference on the full workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop returned as DIR/<name>.npy (float64): krylov_history "
+                         "(RESID of iterations 1 .. warmup + steps, the last line is the last timed step) and final "
+                         "([iterations, status, resid] of the last krylov_steps call); with N > 1 every rank writes <name>_rank<r>.npy")
     return ap.parse_args(argv)
 
 
@@ -195,6 +199,14 @@ def cpu_baseline(hip, np, n_sample, iters, cores, method=1, precond=1):
     return dict(per_iter=r["t_per_iter"], solver=r.get("t_solver"), setup=r.get("t_setup"),
                 matvec=r.get("t_matvec"), precond=r.get("t_precond"), ndof=3 * mesh.n_node, exe=exe,
                 history=[h for _, h in r.get("history", [])])
+
+
+def dump_outputs(d, rank, arrays):
+    """--dump-outputs: one float64 .npy per array (a few KB: the Krylov loop returns scalars and its residual history)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ("" if rank is None else "_rank%d" % rank) + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def main():
@@ -330,6 +342,9 @@ def main():
     assert np.isfinite(resid)
     headline_eis = bool(ctx.stats()["eisenstat"])       # the recurrence the timed loop really ran in (read before anything else touches the context)
     hist_gpu = ctx.krylov_history()                     # its ITERLOG lines 1 .. warmup + steps (outside the timed region)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank if world > 1 else None,
+                     {"krylov_history": hist_gpu, "final": np.array([it, status, resid], dtype=np.float64)})
     devices_used = 1
     ledger_check = None
     if world > 1:

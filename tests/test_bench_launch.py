@@ -39,6 +39,21 @@ def test_self_launch_fails_loudly_without_gpus():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]      # no JSON line, no wrong answer
 
 
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    """--dump-outputs DIR: one float64 .npy per array the timed loop returned, a rank suffix only for N > 1."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path) and bench.parse_args([]).dump_outputs is None
+    hist = np.array([1.0, 0.5, 0.25])
+    bench.dump_outputs(str(tmp_path / "one"), None, {"krylov_history": hist, "final": np.array([3, 0, 0.25])})
+    bench.dump_outputs(str(tmp_path / "two"), 1, {"final": [3, 0, 0.25]})
+    h = np.load(tmp_path / "one" / "krylov_history.npy")
+    assert h.dtype == np.float64 and np.array_equal(h, hist)
+    assert np.load(tmp_path / "one" / "final.npy").tolist() == [3.0, 0.0, 0.25]
+    assert sorted(os.listdir(tmp_path / "two")) == ["final_rank1.npy"]
+
+
 def test_decomposition_and_parser():
     sys.path.insert(0, ROOT)
     import bench
