@@ -240,6 +240,7 @@ static int context_init(fx_context *c) {
 // A/B measurement needs) and, under the same names, from the environment at fx_create.  Defaults and what was measured with
 // each knob: fx_internal.h.
 // ---------------------------------------------------------------------------
+static int spmv_walk(fx_context *c);
 struct FxOption { const char *name; void (*set)(fx_context *, double); };
 static const FxOption g_fx_options[] = {
     {"FX_ARENA_GB", [](fx_context *c, double v) { c->arena_min_bytes = v > 0.0 ? (size_t)(v * 1073741824.0) : 0; }},
@@ -255,7 +256,12 @@ static const FxOption g_fx_options[] = {
     {"FX_LAYOUT_DEVICE", [](fx_context *c, double v) { c->layout_device = (int)v != 0; }},
     {"FX_PIPE_SPMV", [](fx_context *c, double v) { c->pipe_spmv = (int)v != 0; }},
     {"FX_PIPE_SSOR", [](fx_context *c, double v) { c->pipe_ssor = (int)v != 0; }},
-    {"FX_SSOR_MODE", [](fx_context *c, double v) { c->ssor_mode = (int)v; }},
+    {"FX_SSOR_MODE", [](fx_context *c, double v) {
+       // the numbering is chosen by the symbolic set-up of the multicolour SSOR: a resident one built in the other numbering is
+       // invalidated (the next solve or fx_precond_setup rebuilds it; until then fx_precond_apply_* report it as not set up)
+       if ((int)v != c->ssor_mode && c->precond_kind == 1) c->precond_valid = false;
+       c->ssor_mode = (int)v;
+     }},
     {"FX_PIPE_MAX_SLICES", [](fx_context *c, double v) { c->pipe_max_slices = (int)v; }},
     {"FX_SSOR_BS", [](fx_context *c, double v) { c->ssor_bs = ((int)v == 64) ? 64 : 256; }},
     {"FX_SSOR_SPW", [](fx_context *c, double v) { c->ssor_spw = std::max(1, std::min(8, (int)v)); }},
@@ -273,6 +279,11 @@ static const FxOption g_fx_options[] = {
        // leaving the dataflow sweeps on a live context: their sweep vector is full of tags, and the level sweeps multiply a padding
        // block (value 0) with the row's own stale entry
        if (c->ssor.zs && hipSetDevice(c->device) == hipSuccess) (void)hipMemset(c->ssor.zs, 0, (size_t)3 * c->ssor.nslots * 8);
+       // entering them: the backward vector of a private-numbering sweep is allocated by the set-up only when it is asked for then
+       // (never inside an apply: that may be inside a graph capture)
+       const bool lvl = c->precond_kind == 10 || c->precond_kind == 11;
+       if (c->ssor.zs && !c->ssor.zb && ((lvl && c->df_mode >= 1) || (c->precond_kind == 1 && c->df_mode >= 2 && c->ord.kind != 1)))
+         (void)dev_alloc(&c->ssor.zb, (size_t)3 * c->ssor.nslots);
      }},
     {"FX_DF_SOA", [](fx_context *c, double v) { c->df_soa = (int)v != 0; }},
     {"FX_DF_GRID", [](fx_context *c, double v) { c->df_grid = (int)v; }},
@@ -294,7 +305,18 @@ static const FxOption g_fx_options[] = {
 extern "C" int fx_set_option(fx_context *c, const char *name, double value) {
   if (!c || !name) { g_fx_error = "fx_set_option: null argument"; return FX_ERROR_RUNTIME; }
   for (const FxOption &o : g_fx_options)
-    if (strcmp(o.name, name) == 0) { o.set(c, value); return 0; }
+    if (strcmp(o.name, name) == 0) {
+      const bool spatial = c->spmv_spatial;
+      const int bs = c->spmv_bs;
+      o.set(c, value);
+      // the SpMV's slice walk and workgroup lists of a resident layout follow these two at once (values untouched)
+      if (c->m_symbolic && (spatial != c->spmv_spatial || bs != c->spmv_bs)) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return spmv_walk(c);
+      }
+      return 0;
+    }
   g_fx_error = std::string("fx_set_option: unknown option ") + name;
   return FX_ERROR_UNSUPPORTED;
 }
@@ -626,6 +648,7 @@ static int bell_build_device(fx_context *c, Bell &b, int variant, int32_t nslots
 static int bell_fill_values(fx_context *c, Bell &b, const double *D = nullptr, const double *AL = nullptr,
                             const double *AU = nullptr) {
   if (b.nslices == 0) return 0;
+  b.values_filled = true;
   hipLaunchKernelGGL(k_bell_fill, dim3((b.nslices + 3) / 4), dim3(FX_BLOCK), 0, c->stream, b.nslices, b.pair_ptr,
                      b.src2, D ? D : c->A.D, AL ? AL : c->A.AL, AU ? AU : c->A.AU, b.val2);
   HIP_TRY(hipGetLastError());
@@ -698,6 +721,21 @@ static int build_full_bell(fx_context *c) {
     if (e < 0) return FX_ERROR_RUNTIME;
     if (e > 0 && bell_build2(c, c->M, o.nslots, &sr, count, fill)) return FX_ERROR_RUNTIME;  // a row longer than the device buffer
   }
+  if (spmv_walk(c)) return FX_ERROR_RUNTIME;
+  c->m_symbolic = true;
+  c->bell_valid = false;
+  return 0;
+}
+
+// The SpMV's walk over M's slices (FX_SPMV_SPATIAL) and, on a decomposed system, its interior / boundary workgroup lists (FX_SPMV_BS
+// slices each).  Neither touches M's values: fx_set_option re-runs it when one of the two knobs changes on a resident layout, so
+// the partial sums of the SpMV's dot products are grouped as a fresh context would group them.
+static int spmv_walk(fx_context *c) {
+  const Ordering &o = c->ord;
+  const int32_t *iU = c->h_indexU.data(), *jU = c->h_itemU.data();
+  const int32_t *sr = o.slot_node.data();
+  dev_free(c->M.slice_order); dev_free(c->M.wg_interior); dev_free(c->M.wg_boundary);
+  c->M.n_wg_interior = c->M.n_wg_boundary = 0;
   if (o.kind == 1 && c->spmv_spatial) {  // walk the slices by the mesh position of their rows, all colours of a region together
     const int32_t nsl = c->M.nslices;
     std::vector<int32_t> key((size_t)nsl, INT32_MAX), ordv((size_t)nsl);
@@ -738,8 +776,6 @@ static int build_full_bell(fx_context *c) {
     if (!wi.empty()) HIP_TRY(hipMemcpy(c->M.wg_interior, wi.data(), wi.size() * 4, hipMemcpyHostToDevice));
     if (!wb.empty()) HIP_TRY(hipMemcpy(c->M.wg_boundary, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
   }
-  c->m_symbolic = true;
-  c->bell_valid = false;
   return 0;
 }
 
@@ -750,8 +786,14 @@ static int spmv_launch(fx_context *c, int mode, int dot, double *x, const double
 static inline int spmv_nparts(fx_context *c);
 
 // Move every value array that lives in the context's arena to the same offsets of `to` (which becomes the context's arena; the
-// old one is returned in *from).  Only M holds values at the time this is used (the sweep layouts are filled after it).
-static void arena_switch(fx_context *c, DevArena &to, DevArena *from) {
+// old one is returned in *from).  Nothing is copied: only M may hold values at the time this is used (the sweep layouts are filled
+// after it, and the caller refills M); a sweep layout that already holds values is an error, not a silent loss of its values.
+static int arena_switch(fx_context *c, DevArena &to, DevArena *from) {
+  for (Bell *b : {&c->ssor.L, &c->ssor.U, &c->ssor.H})
+    if (b->arena_owner == c && b->val2_base && b->values_filled) {
+      g_fx_error = "arena_switch: a sweep layout already holds values (only M may, when the arena is switched)";
+      return FX_ERROR_RUNTIME;
+    }
   to.blocks = c->arena.blocks;
   for (Bell *b : {&c->M, &c->ssor.L, &c->ssor.U, &c->ssor.H})
     if (b->arena_owner == c && b->val2_base) {
@@ -762,6 +804,7 @@ static void arena_switch(fx_context *c, DevArena &to, DevArena *from) {
   *from = c->arena;
   from->blocks.clear();
   c->arena = to;
+  return 0;
 }
 
 // Verification of the arena (fx_context::arena_tries): see fx_internal.h.  M's values have just been filled.
@@ -797,14 +840,14 @@ static int arena_verify(fx_context *c) {
     if (hipMalloc((void **)&next.base, c->arena.bytes) != hipSuccess) { (void)hipGetLastError(); break; }
     next.bytes = c->arena.bytes;
     DevArena old;
-    arena_switch(c, next, &old);
+    if (arena_switch(c, next, &old)) { (void)hipFree(next.base); return FX_ERROR_RUNTIME; }
     c->arena_tried.push_back(old);
     if (best_k == -1) best_k = (int)c->arena_tried.size() - 1;  // the best so far is the one just left
     if (bell_fill_values(c, M)) return FX_ERROR_RUNTIME;
   }
   if (best_k >= 0) {  // an earlier arena was the fastest: back to it
     DevArena back = c->arena_tried[best_k], old;
-    arena_switch(c, back, &old);
+    if (arena_switch(c, back, &old)) return FX_ERROR_RUNTIME;
     c->arena_tried[best_k] = old;
     if (bell_fill_values(c, M)) return FX_ERROR_RUNTIME;
   }
@@ -1504,6 +1547,7 @@ static int ssor_setup_symbolic(fx_context *c, int ncolor_in) {
   if (c->df_mode >= 2 && dev_alloc(&S.zb, (size_t)3 * nslots)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpy(S.slot_node, slot_row.data(), (size_t)nslots * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(S.zs, 0, (size_t)3 * nslots * 8));
+  c->ssor_mode_built = c->ssor_mode;
   if (c->ssor_mode == 1) {  // the whole solver runs in this numbering (vectors, SpMV layout, halo lists)
     if (set_ordering(c, 1, &slot_row)) return FX_ERROR_RUNTIME;
   } else if (c->ord.kind != 0) {
@@ -1736,7 +1780,8 @@ extern "C" int fx_precond_setup(fx_context *c, const int32_t *Iarray, const doub
       g_fx_error = "PRECOND=" + std::to_string(precond) + " is not on the GPU hot path (1,2 SSOR, 3 DIAG, 10 ILU(0) are)";
       return FX_ERROR_INCONS_PC;
   }
-  const bool symbolic = (kind != c->precond_kind) || (kind == 1 && (c->ssor.ncolor == 0 || c->ssor_ncolor_in != ncolor_in)) ||
+  const bool symbolic = (kind != c->precond_kind) ||
+                        (kind == 1 && (c->ssor.ncolor == 0 || c->ssor_ncolor_in != ncolor_in || c->ssor_mode_built != c->ssor_mode)) ||
                         ((kind == 10 || kind == 11) && c->ssor.ncolor == 0);
   if (symbolic) { free_precond(c); c->precond_kind = kind; }
   if (kind == 3) {

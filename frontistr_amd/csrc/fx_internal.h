@@ -62,6 +62,7 @@ struct Bell {
   int64_t nblocks = 0;          // real (non padding) blocks
   size_t val2_bytes = 0;        // bytes val2_base was allocated with (its share of the arena, the power-of-two request, or the exact size)
   struct fx_context *arena_owner = nullptr;  // val2_base lies in this context's value arena (DevArena): released there, not with hipFree
+  bool values_filled = false;   // bell_fill_values has written val2 (arena_switch may only re-point arrays that hold no values yet)
   size_t bytes() const { return (size_t)npairs * 64 * (9 * 8 + 4) + (size_t)(nslices + 1) * 4; }
 };
 
@@ -299,6 +300,7 @@ struct fx_context {
   // Same-process A/B at 10.1M DOF with the tuned kernels: mode 0 336 it/s (SpMV 1.11 ms, SSOR 1.61 ms),
   // mode 1 351 it/s (SpMV 1.15 ms, SSOR 1.46 ms).
   int ssor_mode = 1;
+  int ssor_mode_built = -1;   // ssor_mode the resident multicolour SSOR was set up in (a live FX_SSOR_MODE change re-runs its symbolic set-up)
   int ssor_spw = 1;            // consecutive slices per wave in the big-colour sweeps (FX_SSOR_SPW)
   int ssor_bs = 64;            // workgroup size of the colour sweeps: 64 (default) or 256. Measured 10M DOF: 1.78 -> 1.61 ms per apply
   int pipe_max_slices = 1 << 30;  // colours with more slices use the plain row loop (with 64-thread groups: pipelined everywhere wins, 1.61 vs 1.64/1.69 ms)

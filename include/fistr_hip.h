@@ -175,7 +175,13 @@ int fx_solve_attempts(fx_context *ctx, int32_t cap, int32_t *n_attempts, int32_t
 int fx_solve_attempt_history(fx_context *ctx, int32_t attempt, double *hist, int32_t cap);
 /* Tuning knob of a live context (kernel variants, workgroup sizes, sweep modes: the FX_* names documented in
  * frontistr_amd/csrc/fx_internal.h; the same names are read from the environment at fx_create).  No counterpart in the
- * reference (its equivalents are build-time choices such as the OpenMP thread count).  Unknown name: FX_ERROR_UNSUPPORTED. */
+ * reference (its equivalents are build-time choices such as the OpenMP thread count).  Unknown name: FX_ERROR_UNSUPPORTED.
+ * A knob changed on a live context gives the answer a fresh context created with it gives: kernel choices take effect at the next
+ * apply / product / solve (a solve captures its graph again at its begin), layout choices (FX_SPMV_BS, FX_SPMV_SPATIAL,
+ * FX_LAYOUT_DEVICE) leave every row's sum unchanged, and the one numbering choice, FX_SSOR_MODE, takes effect at the next
+ * fx_precond_setup: changing it invalidates a resident multicolour SSOR, which the next solve or fx_precond_setup rebuilds in the
+ * new numbering (fx_precond_apply_* report it as not set up until then).  FX_DATAFLOW allocates the private backward vector the
+ * dataflow sweeps need when the resident preconditioner was set up without it. */
 int fx_set_option(fx_context *ctx, const char *name, double value);
 /* measured read-streaming rate (GB/s) of this device over the resident matrix values: the on-box
  * ceiling reported beside the 8 TB/s vendor peak */

@@ -796,7 +796,7 @@ def test_divergence_retries_against_reference_golden(hip, oracle, k):
 @pytest.mark.parametrize("deck", DECKS + ["cube12"])
 @pytest.mark.parametrize("sigma", [1.0, 1.3])
 def test_eisenstat_form_of_cg_ssor(hip, oracle, deck, sigma, monkeypatch):
-    """FX_EISENSTAT=1 (opt-in): CG + multicolour SSOR with the matrix streamed once per iteration (one backward and one forward
+    """FX_EISENSTAT=1 (the default since round 4; FX_EISENSTAT=0 opts out): CG + multicolour SSOR with the matrix streamed once per iteration (one backward and one forward
     triangular sweep deliver p, q = A p and (D~+L)^-1 q).  Same iterates in exact arithmetic, so the same checks as the standard
     loop against the oracle: history lines 1-10 to 1e-10, count +-1, field 1e-8 -- and against the standard GPU loop itself.
     SIGMA_DIAG /= 1 exercises the (D - D~) terms."""

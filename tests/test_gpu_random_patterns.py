@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 
 def random_system(nd, N, n_halo, seed, hub=True):
+    """hub: True = one hub row of up to 60 off-diagonal blocks; a sequence of sizes = one hub row per entry."""
     from oracle.refrun import BSR
     rng = np.random.default_rng(seed)
     NP = N + n_halo
@@ -19,9 +20,10 @@ def random_system(nd, N, n_halo, seed, hub=True):
     for _ in range(3 * N):
         i, j = rng.choice(live, 2, replace=False)
         edges.add((min(i, j), max(i, j)))
-    if hub:
-        h = int(live[len(live) // 2])
-        for j in rng.choice(live, min(60, len(live) - 1), replace=False):
+    sizes = (60,) if hub is True else tuple(hub or ())
+    for k, size in enumerate(sizes):
+        h = int(live[(k + 1) * len(live) // (len(sizes) + 1)])
+        for j in rng.choice(live, min(size, len(live) - 1), replace=False):
             if j != h:
                 edges.add((min(h, int(j)), max(h, int(j))))
     for k in range(n_halo):                     # each halo node hangs on two internal rows
