@@ -451,7 +451,7 @@ static void free_matrix(fx_context *c) {
   c->wlen = 0;
   c->max_partials = 0;
   c->have_profile = c->have_values = c->bell_valid = false;
-  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos);  // the scatter map belongs to the profile
+  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos); dev_free(c->asm_colors.dup);  // the scatter map belongs to the profile
   c->asm_colors = ElemColors();
 }
 
@@ -474,7 +474,7 @@ extern "C" void fx_destroy(fx_context *c) {
   graphs_destroy(c);
   nl_free(c);
   nn_free(c);
-  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos);
+  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos); dev_free(c->asm_colors.dup);
   c->asm_colors = ElemColors();
   free_precond(c);
   free_matrix(c);

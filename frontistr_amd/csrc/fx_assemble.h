@@ -146,6 +146,41 @@ __global__ void k_count_uncovered(int64_t n, const int32_t *__restrict__ m, unsi
   if (c) atomicAdd(count, c);
 }
 
+// Elements that name a node twice (collapsed hexahedra) are left out of the coloured launches: two of their 64 blocks are one block
+// of the matrix, and the lanes of k_assemble_c3d8 / k_nl_stiffness that share it would read-modify-write it at the same time.  Their
+// element matrices are computed in the Kout mode instead (Kel: 576 per position of `list`) and added here, one thread per element, all
+// 64 blocks in the reference's (ie, je) order (hecmw_mat_ass_elem, hecmw_mat_ass.f90:31-69).  One launch per colour: no two elements
+// of [p0, p1) share a node, so the sum stays bitwise reproducible.
+__global__ void k_add_elem_blocks(int32_t p0, int32_t p1, const int32_t *__restrict__ list, const double *__restrict__ Kel,
+                                  const int32_t *__restrict__ conn, const int32_t *__restrict__ pos_map,
+                                  const int32_t *__restrict__ indexL, const int32_t *__restrict__ itemL,
+                                  const int32_t *__restrict__ indexU, const int32_t *__restrict__ itemU, double *__restrict__ D,
+                                  double *__restrict__ AL, double *__restrict__ AU, int32_t *__restrict__ err) {
+  const int32_t p = p0 + (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= p1) return;
+  const int32_t elem = list[p];
+  const double *K = Kel + (size_t)576 * p;
+  for (int ie = 0; ie < 8; ie++) {
+    const int32_t inod = conn[(size_t)8 * elem + ie];
+    for (int je = 0; je < 8; je++) {
+      const int32_t jnod = conn[(size_t)8 * elem + je];
+      double *dst;
+      if (inod == jnod) dst = D + (size_t)9 * (inod - 1);
+      else {
+        const int32_t raw = pos_map ? pos_map[(size_t)64 * elem + 8 * ie + je] : 0;
+        int32_t k;
+        if (pos_map) k = raw < 0 ? raw : (raw & ~FXA_FIRST_BIT);
+        else if (jnod < inod) k = item_search(itemL, indexL[inod - 1], indexL[inod], jnod);
+        else k = item_search(itemU, indexU[inod - 1], indexU[inod], jnod);
+        if (k < 0) { if (err) atomicExch(err, 2); continue; }
+        dst = (jnod < inod ? AL : AU) + (size_t)9 * k;
+      }
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) dst[3 * i + j] += K[(size_t)(3 * ie + i) * 24 + 3 * je + j];
+    }
+  }
+}
+
 // Global derivatives of node b's shape function at a Gauss point from the stored inverse Jacobian: the expression of
 // hex8_global_deriv for one node (hex8n.f90:24-53, element.f90:693-744).
 __device__ __forceinline__ void hex8_node_deriv(int b, double xi, double et, double ze, const double *inv, double *g) {
@@ -198,7 +233,8 @@ __global__ __launch_bounds__(FXA_BS(ELEMOPT)) void k_assemble_c3d8(int32_t n_ele
                                                              const int32_t *__restrict__ elem_list, int32_t e0,
                                                              const int32_t *__restrict__ pos_map) {
   // elem_list != nullptr: positions [e0, n_elem) of elem_list are the elements of ONE colour (no shared nodes), scattered
-  // without atomics; nullptr: elements e0..n_elem-1 in their own order with hardware fp64 atomics
+  // without atomics; nullptr: elements e0..n_elem-1 in their own order with hardware fp64 atomics.  Kout: element matrices out,
+  // no scatter
   constexpr int EPB = FXA_EPB(ELEMOPT);
   constexpr bool IC = (ELEMOPT == 1);
   __shared__ double Jsh[EPB][8][10];                 // per Gauss point: inverse Jacobian (row-major), determinant
@@ -430,13 +466,14 @@ __global__ __launch_bounds__(FXA_BS(ELEMOPT)) void k_assemble_c3d8(int32_t n_ele
           K[3 * i + j] -= sm;
         }
     }
-    if (Kout) {
+    if (Kout) {  // by element id; with an element list (the collapsed elements, k_add_elem_blocks) by position in the list
+      const size_t ko = (size_t)(elem_list ? epos : elem) * 576;
 #pragma unroll
       for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) {
-          Kout[(size_t)elem * 576 + (size_t)(3 * a + i) * 24 + 3 * b + j] = K[3 * i + j];
-          if (st > 0) Kout[(size_t)elem * 576 + (size_t)(3 * b + j) * 24 + 3 * a + i] = K[3 * i + j];
+          Kout[ko + (size_t)(3 * a + i) * 24 + 3 * b + j] = K[3 * i + j];
+          if (st > 0) Kout[ko + (size_t)(3 * b + j) * 24 + 3 * a + i] = K[3 * i + j];
         }
       continue;
     }

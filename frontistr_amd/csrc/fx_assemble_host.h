@@ -166,6 +166,7 @@ static void elastic_constants(double E, double nu, double &D11, double &D12, dou
 static void elem_colors_free(ElemColors &ec) {
   dev_free(ec.order);
   dev_free(ec.pos);
+  dev_free(ec.dup);
   ec = ElemColors();
 }
 // the position map of k_scatter_map for the resident profile and the device connectivity d_conn (FX_ASM_MAP=0: search every time)
@@ -214,6 +215,30 @@ static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, con
   }
   return 0;
 }
+// Moves the elements that name a node twice out of the colour lists (order, off) into their own list (dups, dup_off), colour by
+// colour, each list keeping the colour order; an empty dup_off: there are none.  k_add_elem_blocks adds them after the colours.
+static bool names_a_node_twice(const int32_t *en) {
+  for (int x = 0; x < 8; x++)
+    for (int y = x + 1; y < 8; y++)
+      if (en[x] == en[y]) return true;
+  return false;
+}
+static void split_collapsed(const int32_t *conn, std::vector<int32_t> &order, std::vector<int32_t> &off, std::vector<int32_t> &dups,
+                            std::vector<int32_t> &dup_off) {
+  std::vector<int32_t> keep, koff(1, 0);
+  dups.clear();
+  dup_off.assign(1, 0);
+  keep.reserve(order.size());
+  for (size_t k = 0; k + 1 < off.size(); k++) {
+    for (int32_t q = off[k]; q < off[k + 1]; q++)
+      (names_a_node_twice(conn + (size_t)8 * order[q]) ? dups : keep).push_back(order[q]);
+    koff.push_back((int32_t)keep.size());
+    dup_off.push_back((int32_t)dups.size());
+  }
+  order.swap(keep);
+  off.swap(koff);
+  if (dups.empty()) dup_off.clear();
+}
 static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *conn, int32_t NP) {
   static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
   if (force_atomic || n_elem < 1) { elem_colors_free(ec); return 0; }
@@ -244,21 +269,24 @@ static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, con
   }
   if (ec.order && ec.n_elem == n_elem && ec.key == key && !ec.offsets.empty()) return 0;
   elem_colors_free(ec);
-  std::vector<int32_t> order, off;
+  std::vector<int32_t> order, off, dups, dup_off;
   if (!fxo::color_elements(n_elem, 8, conn, NP, order, off)) return 0;  // a node in more than 64 elements: atomics
-  if (dev_alloc(&ec.order, (size_t)n_elem)) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(ec.order, order.data(), (size_t)n_elem * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  ec.n_elem = n_elem; ec.key = key; ec.offsets = off;
   ec.dup_nodes = false;
   for (int q = 0; q < nchunk; q++) ec.dup_nodes |= dup[q];
+  if (ec.dup_nodes) split_collapsed(conn, order, off, dups, dup_off);
+  if (dev_alloc(&ec.order, std::max<size_t>(order.size(), 1)) || (!dups.empty() && dev_alloc(&ec.dup, dups.size())))
+    return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpyAsync(ec.order, order.data(), order.size() * 4, hipMemcpyHostToDevice, c->stream));
+  if (!dups.empty()) HIP_TRY(hipMemcpyAsync(ec.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  ec.n_elem = n_elem; ec.key = key; ec.offsets = off; ec.dup_off = dup_off;
   return 0;
 }
 
 template <int EO>
 static void launch_assemble(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
                             double D44, double *Kout, int32_t *err, const int32_t *elem_mat = nullptr,
-                            const double *mat_tab = nullptr, const ElemColors *ec = nullptr) {
+                            const double *mat_tab = nullptr, const ElemColors *ec = nullptr, double *dup_k = nullptr) {
   const DevCSR &A = c->A;
   if (ec && !ec->offsets.empty() && !Kout) {
     for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
@@ -267,6 +295,19 @@ static void launch_assemble(fx_context *c, int32_t n_elem, const double *coord, 
       hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3((e1 - e0 + FXA_EPB(EO) - 1) / FXA_EPB(EO)), dim3(FXA_BS(EO)), 0, c->stream, e1, coord,
                          conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
                          (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
+    }
+    if (!ec->dup_off.empty()) {  // collapsed elements: element matrices (dup_k, by position), then added colour by colour
+      const int32_t nd = ec->dup_off.back();
+      hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3((nd + FXA_EPB(EO) - 1) / FXA_EPB(EO)), dim3(FXA_BS(EO)), 0, c->stream, nd, coord,
+                         conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, dup_k, err, elem_mat, mat_tab,
+                         (const int32_t *)ec->dup, 0, (const int32_t *)nullptr);
+      for (size_t k = 0; k + 1 < ec->dup_off.size(); k++) {
+        const int32_t p0 = ec->dup_off[k], p1 = ec->dup_off[k + 1];
+        if (p1 > p0)
+          hipLaunchKernelGGL(k_add_elem_blocks, dim3((p1 - p0 + 63) / 64), dim3(64), 0, c->stream, p0, p1, (const int32_t *)ec->dup,
+                             (const double *)dup_k, conn, (const int32_t *)ec->pos, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL,
+                             A.AU, err);
+      }
     }
     return;
   }
@@ -310,6 +351,8 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   } else {
     elastic_constants(E, nu, D11, D12, D44);
   }
+  double *d_dupk = nullptr;  // element matrices of the collapsed elements
+  if (!c->asm_colors.dup_off.empty() && tmp.alloc(&d_dupk, (size_t)576 * c->asm_colors.dup_off.back())) return FX_ERROR_RUNTIME;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   // hecmw_mat_clear (fstr_StiffMatrix.f90:40)
   if (!(c->asm_colors.first_write && c->asm_colors.pos && !c->asm_colors.offsets.empty())) {  // first-write scatter: every block is stored before it is added to
@@ -317,9 +360,9 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
     HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
     HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
   }
-  if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
-  else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
-  else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
+  if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
+  else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
+  else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   HIP_TRY(hipGetLastError());
   if (load) HIP_TRY(hipMemcpyAsync(A.B, load, (size_t)3 * A.NP * 8, hipMemcpyHostToDevice, c->stream));
   else HIP_TRY(hipMemsetAsync(A.B, 0, (size_t)3 * A.NP * 8, c->stream));

@@ -177,6 +177,8 @@ struct ElemColors {
   std::vector<int32_t> offsets;     // host: first position of each colour (+ end); empty = not coloured (atomics)
   int32_t *pos = nullptr;           // device: 64 per element, position of block (a, b) in AL / AU (k_scatter_map), or null
   bool dup_nodes = false;           // an element names a node twice: two of its blocks coincide, no first-write flags
+  int32_t *dup = nullptr;           // device: those elements (collapsed hexahedra), colour by colour; they are not in `order`
+  std::vector<int32_t> dup_off;     // host: first position of each colour in `dup` (+ end); empty = none
   bool first_write = false;         // pos carries the first-write flags (k_scatter_first_flag) and every block of the profile is covered:
                                     // the coloured scatter stores the first contribution to a block and the matrix is not cleared first
 };
@@ -185,6 +187,7 @@ struct NlDev {
   bool ready = false;
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
   std::vector<int32_t> grp_off[3];    // per NLGEOM flag (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG): positions of its colours in order (+ end)
+  std::vector<int32_t> dup_off[3];    // per NLGEOM flag: its collapsed elements' colours in colors.dup (+ end); empty = none
   bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements): one range per group, fp64 atomics
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material
@@ -192,6 +195,7 @@ struct NlDev {
   std::vector<NlMat> h_mats;
   std::vector<double *> tabs;         // device tables of the materials
   int32_t n_elem = 0, n_bc = 0;
+  int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
   NlMat mat = {};
   double *tab = nullptr;
   double *coord = nullptr;

@@ -207,9 +207,11 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
                                                             double *__restrict__ Kout, int32_t *__restrict__ err,
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
-                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                            int kout_pos) {
   // positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one colour (no shared node),
   // scattered without atomics, see k_assemble_c3d8.  mats / emat: several sections, element e uses mats[emat[e] - 1].
+  // Kout: element matrices out instead of the scatter, by element id (kout_pos == 0) or by position in elem_list.
   const int lane8 = threadIdx.x & 7;
   int32_t epos = e0 + blockIdx.x * FXN_EPB + (threadIdx.x >> 3);
   const bool active = epos < n_elem;
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 #pragma unroll
       for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) Kout[(size_t)elem * 576 + (size_t)(3 * a + i) * 24 + 3 * b + j] = K[b][3 * i + j];
+        for (int j = 0; j < 3; j++) Kout[(size_t)(kout_pos ? epos : elem) * 576 + (size_t)(3 * a + i) * 24 + 3 * b + j] = K[b][3 * i + j];
     return;
   }
   int32_t inod = 0;

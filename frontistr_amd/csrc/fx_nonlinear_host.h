@@ -9,7 +9,7 @@ static void nl_free(fx_context *c) {
   dev_free(n.plstrain); dev_free(n.fstat); dev_free(n.istat);
   dev_free(n.unode); dev_free(n.dunode); dev_free(n.qforce); dev_free(n.GL);
   dev_free(n.bc_flag); dev_free(n.bc_val); dev_free(n.bc_node); dev_free(n.bc_dof); dev_free(n.bc_v); dev_free(n.err);
-  dev_free(n.colors.order); dev_free(n.colors.pos);
+  dev_free(n.colors.order); dev_free(n.colors.pos); dev_free(n.colors.dup);
   dev_free(n.mats); dev_free(n.emat);
   dev_free(n.bk_stress); dev_free(n.bk_strain); dev_free(n.bk_stress_bak); dev_free(n.bk_strain_bak);
   dev_free(n.bk_plstrain); dev_free(n.bk_fstat); dev_free(n.bk_istat);
@@ -88,28 +88,36 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
       off = {0, mesh->n_elem};
     }
     n.scatter_atomic = !coloured;
-    std::vector<int32_t> grouped;
+    // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
+    std::vector<int32_t> grouped, dups;
     grouped.reserve((size_t)mesh->n_elem);
     for (int g = 0; g < 3; g++) {
       n.grp_off[g].clear();
+      n.dup_off[g].clear();
+      std::vector<int32_t> doff(1, (int32_t)dups.size());
       bool any = false;
       for (size_t k = 0; k + 1 < off.size(); k++) {
         const size_t before = grouped.size();
         for (int32_t q = off[k]; q < off[k + 1]; q++) {
           const int32_t e = order[q];
           const int flag = n.h_mats[n_mat > 1 ? elem_mat[e] - 1 : 0].nlgeom;
-          if (flag == g) grouped.push_back(e);
+          if (flag == g) (coloured && names_a_node_twice(mesh->conn + (size_t)8 * e) ? dups : grouped).push_back(e);
         }
+        doff.push_back((int32_t)dups.size());
         if (grouped.size() > before || any) {
           if (!any) n.grp_off[g].push_back((int32_t)before);
           any = true;
           n.grp_off[g].push_back((int32_t)grouped.size());
         }
       }
+      if (doff.back() > doff.front()) n.dup_off[g] = doff;
     }
-    if (dev_alloc(&n.colors.order, (size_t)mesh->n_elem)) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(n.colors.order, grouped.data(), (size_t)mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // grouped is a host temporary
+    n.n_dup = (int32_t)dups.size();
+    if (dev_alloc(&n.colors.order, std::max<size_t>(grouped.size(), 1)) || (n.n_dup > 0 && dev_alloc(&n.colors.dup, dups.size())))
+      return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(n.colors.order, grouped.data(), grouped.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (n.n_dup > 0) HIP_TRY(hipMemcpyAsync(n.colors.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // grouped and dups are host temporaries
     n.colors.n_elem = mesh->n_elem;
     n.colors.offsets = {0, mesh->n_elem};       // marks the lists as built (ensure_scatter_map)
     if (ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn)) return FX_ERROR_RUNTIME;
@@ -141,11 +149,10 @@ extern "C" int fx_nl_init_sections(fx_context *c, const fx_mesh_view *mesh, int3
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }
 
 template <int G>
-static void nl_launch_stiffness_group(fx_context *c, double *Kout) {
+static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
   const std::vector<int32_t> &off = n.grp_off[G];
-  if (off.empty()) return;
   const bool one_range = Kout || n.scatter_atomic;  // element matrices out, or atomics: the group's colours in one launch
   for (size_t k = 0; k + 1 < off.size(); k++) {
     const int32_t e0 = one_range ? off.front() : off[k], e1 = one_range ? off.back() : off[k + 1];
@@ -153,27 +160,54 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout) {
       hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord,
                          n.conn, n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU,
                          A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos,
-                         n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+                         n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat, 0);
     if (one_range) break;
   }
+  // collapsed elements: their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter --
+  // added colour by colour (k_add_elem_blocks)
+  const std::vector<int32_t> &doff = n.dup_off[G];
+  if (doff.empty()) return;
+  const int32_t d0 = doff.front(), d1 = doff.back();
+  hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((d1 - d0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, d1, n.coord, n.conn,
+                     n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
+                     Kout ? Kout : dup_k, n.err, (const int32_t *)n.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
+                     (const int32_t *)n.emat, Kout ? 0 : 1);
+  if (Kout) return;
+  for (size_t k = 0; k + 1 < doff.size(); k++)
+    if (doff[k + 1] > doff[k])
+      hipLaunchKernelGGL(k_add_elem_blocks, dim3((doff[k + 1] - doff[k] + 63) / 64), dim3(64), 0, c->stream, doff[k], doff[k + 1],
+                         (const int32_t *)n.colors.dup, (const double *)dup_k, (const int32_t *)n.conn, (const int32_t *)n.colors.pos,
+                         A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
-static void nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
-  nl_launch_stiffness_group<0>(c, Kout);
-  nl_launch_stiffness_group<1>(c, Kout);
-  nl_launch_stiffness_group<2>(c, Kout);
+static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
+  DevScratch tmp;
+  double *dup_k = nullptr;
+  if (!Kout && c->nl.n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * c->nl.n_dup)) return FX_ERROR_RUNTIME;
+  nl_launch_stiffness_group<0>(c, Kout, dup_k);
+  nl_launch_stiffness_group<1>(c, Kout, dup_k);
+  nl_launch_stiffness_group<2>(c, Kout, dup_k);
+  if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
+  return 0;
 }
 template <int G>
 static void nl_launch_update_group(fx_context *c, double *qf_out) {
   NlDev &n = c->nl;
   const std::vector<int32_t> &off = n.grp_off[G];
-  if (off.empty() || off.back() <= off.front()) return;
-  const int32_t e0 = off.front(), e1 = off.back();
-  // a group that holds every element is walked in the elements' own order (contiguous history arrays); the internal force is
-  // scattered with atomics either way
-  const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;
-  hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn,
-                     n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce,
-                     qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  if (!off.empty() && off.back() > off.front()) {
+    const int32_t e0 = off.front(), e1 = off.back();
+    // a group that holds every element is walked in the elements' own order (contiguous history arrays); the internal force is
+    // scattered with atomics either way
+    const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;
+    hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn,
+                       n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce,
+                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  }
+  const std::vector<int32_t> &doff = n.dup_off[G];  // the collapsed elements of the group
+  if (!doff.empty())
+    hipLaunchKernelGGL((k_nl_update<G>), dim3((doff.back() - doff.front() + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream,
+                       doff.back(), n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain,
+                       n.fstat, n.istat, n.qforce, qf_out, (const int32_t *)n.colors.dup, doff.front(), (const NlMat *)n.mats,
+                       (const int32_t *)n.emat);
 }
 static void nl_launch_update(fx_context *c, double *qf_out) {
   nl_launch_update_group<0>(c, qf_out);
@@ -196,7 +230,7 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
   HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));  // hecmw_mat_clear
   HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
   HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
-  nl_launch_stiffness(c, nullptr);
+  if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(n.bc_flag, 0, (size_t)3 * A.NP, c->stream));
   HIP_TRY(hipMemsetAsync(n.bc_val, 0, (size_t)3 * A.NP * 8, c->stream));
@@ -433,7 +467,7 @@ extern "C" int fx_nl_element_tangents(fx_context *c, double *ke) {
   DevScratch tmp;
   double *d = nullptr;
   if (tmp.alloc(&d, (size_t)576 * n.n_elem)) return FX_ERROR_RUNTIME;
-  nl_launch_stiffness(c, d);
+  if (nl_launch_stiffness(c, d)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ke, d, (size_t)576 * n.n_elem * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

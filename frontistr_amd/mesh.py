@@ -59,3 +59,125 @@ def cube_blocks(n):
     N = m ** 3
     nb = (3 * m - 2) ** 3
     return N, (nb - N) // 2, (nb - N) // 2, nb
+
+
+class PieMesh:
+    """Solid cylinder of radius ``radius`` and height ``height`` meshed the way a hex-only mesher meshes a solid of
+    revolution: ``n_r`` rings of ``n_theta`` sectors on ``n_z`` layers, the innermost ring collapsed onto the axis.
+    Each layer has one axis node; ring node (ir, it) sits at radius radius * ir / n_r, angle 2 pi it / n_theta.
+    Element (ir, it) has the corners [(ir, it), (ir+1, it), (ir+1, it+1), (ir, it+1)], bottom face then top (positive
+    Jacobians); for ir = 0 nodes 0 and 3 (and 4 and 7) are the same axis node: a collapsed hexahedron naming a node
+    twice.  ``sectors`` < n_theta keeps only the first sectors columns (an open wedge; sectors=1, n_r=1, n_z=1 is a
+    single collapsed element).  Elements are numbered layer by layer, ring by ring, sector by sector.  Deterministic."""
+
+    def __init__(self, n_theta, n_r, n_z, radius=1.0, height=1.0, sectors=None):
+        self.n_theta, self.n_r, self.n_z = int(n_theta), int(n_r), int(n_z)
+        ns = self.n_theta if sectors is None else int(sectors)
+        closed = ns == self.n_theta
+        ncol = ns if closed else ns + 1              # ring node columns per ring
+        per_layer = 1 + self.n_r * ncol
+        self.n_node = per_layer * (self.n_z + 1)
+        xyz = np.zeros((self.n_node, 3))
+        for k in range(self.n_z + 1):
+            base = k * per_layer
+            xyz[base] = (0.0, 0.0, height * k / self.n_z)
+            for ir in range(1, self.n_r + 1):
+                for it in range(ncol):
+                    ang = 2.0 * np.pi * it / self.n_theta
+                    r = radius * ir / self.n_r
+                    xyz[base + 1 + (ir - 1) * ncol + it] = (r * np.cos(ang), r * np.sin(ang), height * k / self.n_z)
+        self.coord = np.ascontiguousarray(xyz)
+
+        def nid(k, ir, it):                          # 1-based
+            if ir == 0:
+                return 1 + k * per_layer
+            return 1 + k * per_layer + 1 + (ir - 1) * ncol + (it % ncol if closed else it)
+        conn = []
+        for k in range(self.n_z):
+            for ir in range(self.n_r):
+                for it in range(ns):
+                    face = [(ir, it), (ir + 1, it), (ir + 1, it + 1), (ir, it + 1)]
+                    conn.append([nid(k, *p) for p in face] + [nid(k + 1, *p) for p in face])
+        self.conn = np.ascontiguousarray(np.array(conn, dtype=np.int32))
+        self.n_elem = self.conn.shape[0]
+        self.bottom_nodes = (1 + np.arange(per_layer)).astype(np.int32)
+        self.top_nodes = (1 + self.n_z * per_layer + np.arange(per_layer)).astype(np.int32)
+        self.axis_nodes = (1 + per_layer * np.arange(self.n_z + 1)).astype(np.int32)
+
+    @property
+    def ndof(self):
+        return 3 * self.n_node
+
+    def dirichlet(self):
+        """(node, dof, value) triplets: z=0 face clamped."""
+        node = np.repeat(self.bottom_nodes, 3).astype(np.int32)
+        dof = np.tile(np.array([1, 2, 3], dtype=np.int32), self.bottom_nodes.size)
+        return node, dof, np.zeros(node.size, dtype=np.float64)
+
+    def load(self):
+        """Unit x-load on every node of the top face."""
+        b = np.zeros(3 * self.n_node, dtype=np.float64)
+        b[3 * (self.top_nodes - 1)] = 1.0
+        return b
+
+
+class RenumberedMesh:
+    """``mesh`` with its node ids and its element order permuted at random (``renumber``).  Coordinates, connectivity,
+    boundary conditions, load and the node sets a mesh names (bottom / top / axis nodes) follow the new numbering."""
+
+    def __init__(self, mesh, seed):
+        rng = np.random.default_rng(seed)
+        self.base = mesh
+        self.n_node, self.n_elem = mesh.n_node, mesh.conn.shape[0]
+        self.new_of_old = (1 + rng.permutation(self.n_node)).astype(np.int32)   # old id - 1 -> new id
+        self.elem_order = rng.permutation(self.n_elem)                          # new element -> old element
+        old_of_new = np.empty(self.n_node, dtype=np.int64)
+        old_of_new[self.new_of_old - 1] = np.arange(self.n_node)
+        self.coord = np.ascontiguousarray(mesh.coord[old_of_new])
+        self.conn = np.ascontiguousarray(self.new_of_old[mesh.conn[self.elem_order] - 1].astype(np.int32))
+        for name in ("bottom_nodes", "top_nodes", "axis_nodes"):
+            if hasattr(mesh, name):
+                setattr(self, name, self.new_of_old[getattr(mesh, name) - 1])
+
+    @property
+    def ndof(self):
+        return 3 * self.n_node
+
+    def dirichlet(self):
+        node, dof, val = self.base.dirichlet()
+        return self.new_of_old[node - 1].astype(np.int32), dof, val
+
+    def load(self):
+        return self.renumber_field(self.base.load())
+
+    def renumber_field(self, f):
+        """A nodal field (3 values per node) of the base mesh in the new numbering."""
+        out = np.empty_like(f)
+        out.reshape(-1, 3)[self.new_of_old - 1] = f.reshape(-1, 3)
+        return out
+
+
+def renumber(mesh, seed):
+    """Random permutation of the node ids and of the element order of ``mesh`` (np.random.default_rng(seed))."""
+    return RenumberedMesh(mesh, seed)
+
+
+def color_elements(conn, n_node):
+    """Python restatement of the host's greedy element colouring (fx_order.cpp color_elements): each element takes the
+    lowest of 64 colours no element sharing a node holds.  Returns the colour per element, or None when some element
+    finds all 64 taken (the library then scatters with atomics)."""
+    used = np.zeros(n_node + 1, dtype=np.uint64)
+    col = np.zeros(conn.shape[0], dtype=np.int32)
+    full = np.uint64(0xFFFFFFFFFFFFFFFF)
+    for e, nodes in enumerate(conn):
+        m = np.uint64(0)
+        for v in nodes:
+            m |= used[v]
+        if m == full:
+            return None
+        free = int(~m & full)
+        c = (free & -free).bit_length() - 1
+        col[e] = c
+        for v in nodes:
+            used[v] |= np.uint64(1) << np.uint64(c)
+    return col

@@ -58,3 +58,41 @@ def test_every_option_is_tested_or_exempted():
     assert live <= variants, sorted(live - variants)
     # every option of the variant table is also flipped on a live context
     assert variants - live == set(), sorted(variants - live)
+
+
+# FX_* environment variables the library reads itself (getenv under csrc/) that are not tuning knobs of g_fx_options: the test
+# that runs each of them, or why none does
+ENV_ONLY = {
+    "FX_ASM_ATOMIC": "atomic stiffness scatter: test_gpu_assembly_meshes.py (atomic, atomic_map0 children), "
+                     "test_assembly_coloured_scatter_is_reproducible_and_equals_atomic_scatter",
+    "FX_ASM_MAP": "binary-search scatter: test_gpu_assembly_meshes.py (map0, atomic_map0 children)",
+    "FX_ASM_FIRST": "read-modify-write scatter after clearing: test_gpu_assembly_meshes.py (first0 child)",
+    "FX_TIMING": "prints host phase timings to stderr: diagnostics only, no kernel or data change",
+    "FX_HOST_THREADS": "host thread count of the orderings and the profile build: same results for any count, no kernel change",
+    "FX_HALO_COMM": "0: halo exchange on the all-reduce communicator instead of a split one (ordering only, same data); "
+                    "the split communicator of multi-rank runs is the tested default (test_gpu_distributed)",
+    "FX_FORCE_COMM": "in-stream communicator on one rank: test_gpu_distributed (FX_FORCE_COMM=1 child)",
+    "FX_DEBUG_ARENA_GB": "size of the placement arena of the debug allocator (fx_debug_host.h): measurement tooling, not the product path",
+    "FX_MARCH_CHECK": "host self-check of every plane march program (always on for small systems, so test_march_* run it): "
+                      "verification only, no result change",
+}
+
+
+def library_getenv_names():
+    names = set()
+    d = os.path.join(ROOT, "frontistr_amd", "csrc")
+    for f in sorted(os.listdir(d)):
+        if f.endswith((".h", ".hip", ".cpp", ".c")):
+            names |= set(re.findall(r'getenv\("(FX_[A-Z0-9_]+)"\)', open(os.path.join(d, f)).read()))
+    return names
+
+
+def test_every_environment_switch_is_tested_or_exempted():
+    names = library_getenv_names()
+    options = set(library_options())
+    env_only = names - options
+    missing = sorted(env_only - set(ENV_ONLY))
+    assert not missing, "FX_* environment variables read outside g_fx_options with neither a test nor a reason: %s" % missing
+    stale = sorted(set(ENV_ONLY) - env_only)
+    assert not stale, "listed but not read by the library (or now an option of g_fx_options): %s" % stale
+    assert all(ENV_ONLY[n].strip() for n in ENV_ONLY)
