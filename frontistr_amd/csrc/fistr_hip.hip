@@ -2765,6 +2765,93 @@ extern "C" int fx_nn_matvec_resident(fx_context *c, int nrepeat, float *ms_per_c
   return 0;
 }
 
+// z = M^-1 r once for a generic-block system (hecmw_precond_setup + hecmw_precond_apply, hecmw_precond.f90:28, :75-123 with
+// the iterPREmax loop): upload, set up or reuse the preconditioner (PRECOND / SIGMA_DIAG / recycle flags as fx_solve reads
+// them), ZP = r on the internal rows and 0 on the halo, then the apply.  r, z: host, NDOF * NP doubles (z's halo part is 0).
+extern "C" int fx_nn_precond_apply(fx_context *c, const fx_matrix_view *m, const fx_comm_view *cm, int32_t *Iarray, double *Rarray,
+                                   const double *r, double *z) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (m->NDOF == 3 || m->NDOF < 1 || m->NDOF > 6) { g_fx_error = "fx_nn_precond_apply: NDOF must be 1, 2, 4, 5 or 6"; return FX_ERROR_UNSUPPORTED; }
+  c->view_petot = cm ? std::max(1, (int)cm->PETOT) : 1;
+  if (require_transport(c, "fx_nn_precond_apply")) return FX_ERROR_RUNTIME;
+  fx_matrix_view mv = *m;
+  mv.B = nullptr; mv.X = nullptr;
+  NnDev *n0 = nn_of(c);
+  const bool values_changed = Iarray[97] >= 1 || Iarray[96] >= 1 || !n0->have_matrix ||
+                              m->D != c->host_D || m->AL != c->host_AL || m->AU != c->host_AU;
+  if (nn_upload(c, &mv, cm, values_changed)) return FX_ERROR_RUNTIME;
+  if (values_changed) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
+  NnDev *n = nn_of(c);
+  n->cur_AL = m->AL; n->cur_AU = m->AU;
+  const int precond = Iarray[2], iterpremax = Iarray[4];
+  const double sigma = Rarray[1] < 0.0 ? 1.0 : Rarray[1];
+  if (iterpremax > 0 && (!n->precond_valid || Iarray[97] >= 1 || Iarray[96] >= 1 || n->sigma != sigma ||
+                         n->precond_kind != nn_precond_kind(precond))) {
+    if (int e = nn_precond_setup(c, precond, sigma, Iarray[33])) return e;
+  }
+  Iarray[97] = 0; Iarray[96] = 0;
+  n->iterpremax = iterpremax;
+  const size_t len = (size_t)n->ndof * n->NP;
+  HIP_TRY(hipMemcpyAsync(n->W[5], r, len * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(n->W[5] + (size_t)n->ndof * n->N, 0, (len - (size_t)n->ndof * n->N) * 8, c->stream));
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if (nn_precond_apply(c, iterpremax, n->W[5], n->W[6])) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!nn_df_take_error(c)) break;  // a timed-out dataflow sweep: redone with per-level launches
+  }
+  HIP_TRY(hipMemsetAsync(n->W[6] + (size_t)n->ndof * n->N, 0, (len - (size_t)n->ndof * n->N) * 8, c->stream));
+  HIP_TRY(hipMemcpyAsync(z, n->W[6], len * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// timed z = M^-1 r of the resident generic-block preconditioner (the one the last fx_solve / fx_nn_precond_apply set up) on
+// resident work vectors, iterPREmax of that call
+extern "C" int fx_nn_precond_apply_resident(fx_context *c, int nrepeat, float *ms_per_call) {
+  HIP_TRY(hipSetDevice(c->device));
+  NnDev *n = nn_of(c);
+  if (!n->have_matrix || !n->precond_valid) { g_fx_error = "fx_nn_precond_apply_resident: no generic-block preconditioner set up"; return FX_ERROR_RUNTIME; }
+  const int ipm = std::max(n->iterpremax, 1);
+  float ms = 0.f;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if (nn_precond_apply(c, ipm, n->W[5], n->W[6])) return FX_ERROR_RUNTIME;  // untimed first touch
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < nrepeat; i++)
+      if (nn_precond_apply(c, ipm, n->W[5], n->W[6])) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (!nn_df_take_error(c)) break;  // a timed-out dataflow sweep: timed again with per-level launches
+  }
+  if (ms_per_call) *ms_per_call = ms / std::max(nrepeat, 1);
+  return 0;
+}
+
+// out[0..9]: resident generic-block preconditioner kind (1 SSOR, 3 DIAG, 10 block ILU(0); 0 none) | levels (ILU) or colours
+// (SSOR) | sweep slices | longest L + U row in blocks (ILU) | factor kernel lanes per row (32 or 1) | padded L blocks |
+// padded U blocks | set-up wall time of the last ILU(0) set-up in microseconds | ILU sweep form now (1 dataflow, 0 per-level
+// launches) | workgroups of the last dataflow launch (after the co-residency clamp) in bits 0-31, timed-out dataflow sweeps
+// of this system in bits 32-63
+extern "C" int fx_nn_precond_stats(fx_context *c, int64_t out[10]) {
+  if (!c || !out) { g_fx_error = "fx_nn_precond_stats: null argument"; return FX_ERROR_RUNTIME; }
+  memset(out, 0, 10 * sizeof(int64_t));
+  if (!c->nn) return 0;
+  NnDev *n = nn_of(c);
+  if (!n->precond_valid) return 0;
+  out[0] = n->precond_kind;
+  out[1] = n->precond_kind == 3 ? 0 : n->ncolor;
+  out[2] = n->precond_kind == 3 ? 0 : n->L.nslices;
+  out[3] = n->precond_kind == 10 ? n->ilu_max_row_blocks : 0;
+  out[4] = n->precond_kind == 10 ? n->ilu_factor_lanes : 0;
+  out[5] = n->precond_kind == 3 ? 0 : n->L.nblocks_padded * 64;
+  out[6] = n->precond_kind == 3 ? 0 : n->U.nblocks_padded * 64;
+  out[7] = n->precond_kind == 10 ? (int64_t)(n->ilu_setup_ms * 1e3) : 0;
+  out[8] = n->precond_kind == 10 && c->df_mode >= 1 ? 1 : 0;
+  out[9] = n->precond_kind == 10 ? ((int64_t)n->ilu_df_grid_last | ((int64_t)n->ilu_df_fallbacks << 32)) : 0;
+  return 0;
+}
+
 // y = A x on resident work vectors, timed with HIP events on the solver stream.  variant: 0 plain (BiCGSTAB's products),
 // 1 with the fused partial of x.y (the launch of every CG iteration, hecmw_solver_CG.f90:204-211), 2 r = b - A x with the
 // partial of r.r (the residual recomputation).  The halo exchange of a multi-rank system is part of every call.

@@ -30,16 +30,29 @@ struct NnDev {
   int ndof = 0;
   int32_t N = 0, NP = 0, NPL = 0, NPU = 0, nn_internal = 0;
   bool have_matrix = false, precond_valid = false;
-  int precond_kind = 0;  // 1 SSOR, 3 DIAG
+  int precond_kind = 0;  // 1 SSOR, 3 DIAG, 10 block ILU(0) (fx_nn_ilu.h)
   double sigma = 1.0;
   NnBell M, L, U;
-  std::vector<int32_t> color_slice;  // first slice of each colour (+ end)
+  std::vector<int32_t> color_slice;  // first slice of each colour / ILU level (+ end)
   int ncolor = 0;
+  // block ILU(0): L / U above hold the factors in level order, color_slice / ncolor the levels
+  bool ilu_symbolic = false;          // the level layouts of L / U are built (not the SSOR ones)
+  int32_t ilu_max_row_blocks = 0;     // longest L + U row: <= 32 selects the 32-lanes-per-row factor
+  int ilu_factor_lanes = 0;           // factor kernel of the last set-up: 32 or 1
+  double ilu_setup_ms = 0.0;          // wall time of the last set-up (symbolic included when it ran)
+  int32_t *ilu_iL = nullptr, *ilu_jL = nullptr, *ilu_iU = nullptr, *ilu_jU = nullptr;  // device CSR profile (items 1-based)
+  int32_t *ilu_srcL = nullptr, *ilu_srcU = nullptr;  // layout entry -> CSR block (-1 padding)
+  double *ilu_AL = nullptr, *ilu_AU = nullptr;       // device CSR blocks during a set-up: caller's values, then the factors
+  double *ilu_zf = nullptr, *ilu_zb = nullptr;       // dataflow sweep vectors (forward / backward results, caller's numbering)
+  size_t ilu_zlen = 0;                               // doubles in each (even)
+  int ilu_df_grid_max = 1, ilu_df_grid_last = 0;     // co-resident workgroups of k_nn_tri_dataflow; grid of the last launch
+  int ilu_df_fallbacks = 0;                          // dataflow sweeps of this system that timed out and were redone per level
   double *D = nullptr, *alu = nullptr, *B = nullptr, *X = nullptr;
   double *W[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double *partials = nullptr, *scal = nullptr;
   double *extra = nullptr;  // GMRES basis / GPBiCG work vectors (count * NDOF * NP)
   double *scale = nullptr;  // SCALING=YES: 1 / sqrt(|d_ii|), NDOF * NP
+  double *X0 = nullptr;     // block ILU(0) with the dataflow sweep: the X an attempt starts from (redone if a sweep timed out)
   int extra_n = 0, iterpremax = 1;
   // halo tables in the caller's numbering (0-based)
   int32_t n_neighbor = 0, n_export = 0, n_import = 0;
@@ -72,8 +85,10 @@ static void nn_free(fx_context *c) {
   nn_bell_free(n->M); nn_bell_free(n->L); nn_bell_free(n->U);
   dev_free(n->D); dev_free(n->alu); dev_free(n->B); dev_free(n->X);
   for (auto &w : n->W) dev_free(w);
-  dev_free(n->partials); dev_free(n->scal); dev_free(n->extra); dev_free(n->scale);
+  dev_free(n->partials); dev_free(n->scal); dev_free(n->extra); dev_free(n->scale); dev_free(n->X0);
   dev_free(n->export_item); dev_free(n->import_item); dev_free(n->sendbuf); dev_free(n->recvbuf);
+  dev_free(n->ilu_iL); dev_free(n->ilu_jL); dev_free(n->ilu_iU); dev_free(n->ilu_jU);
+  dev_free(n->ilu_srcL); dev_free(n->ilu_srcU); dev_free(n->ilu_AL); dev_free(n->ilu_AU); dev_free(n->ilu_zf); dev_free(n->ilu_zb);
   if (n->h_send) (void)hipHostFree(n->h_send);
   if (n->h_recv) (void)hipHostFree(n->h_recv);
   delete n;
@@ -445,6 +460,11 @@ static int nn_upload(fx_context *c, const fx_matrix_view *m, const fx_comm_view 
       if (m->itemL[j] < 1 || m->itemL[j] > m->NP) { g_fx_error = "itemL out of range"; return FX_ERROR_RUNTIME; }
     for (int32_t j = 0; j < m->NPU; j++)
       if (m->itemU[j] < 1 || m->itemU[j] > m->NP) { g_fx_error = "itemU out of range"; return FX_ERROR_RUNTIME; }
+    // the level layouts follow the profile: new values alone keep them (the arrays are compared, not only their sizes)
+    if (!std::equal(n->h_indexL.begin(), n->h_indexL.end(), m->indexL) || (size_t)m->NP + 1 != n->h_indexL.size() ||
+        !std::equal(n->h_indexU.begin(), n->h_indexU.end(), m->indexU) || (size_t)m->NP + 1 != n->h_indexU.size() ||
+        !std::equal(n->h_itemL.begin(), n->h_itemL.end(), m->itemL) || !std::equal(n->h_itemU.begin(), n->h_itemU.end(), m->itemU))
+      n->ilu_symbolic = false;
     n->h_indexL.assign(m->indexL, m->indexL + m->NP + 1);
     n->h_indexU.assign(m->indexU, m->indexU + m->NP + 1);
     n->h_itemL.assign(m->itemL, m->itemL + m->NPL);
@@ -549,6 +569,7 @@ static inline int nn_vgrid(int64_t len) { return (int)std::max<int64_t>(1, std::
 // new numbering with halo columns dropped (hecmw_matrix_reorder.f90:50), rows of a colour padded to whole slices.
 static int nn_ssor_setup(fx_context *c, int ncolor_in) {
   NnDev *n = nn_of(c);
+  n->ilu_symbolic = false;  // L / U become the colour layouts
   const int nd = n->ndof, nd2 = nd * nd;
   const int32_t N = n->N;
   std::vector<int32_t> perm, cidx;
@@ -613,27 +634,39 @@ static int nn_ssor_setup(fx_context *c, int ncolor_in) {
   return 0;
 }
 
-static int nn_precond_setup(fx_context *c, int precond, double sigma, int ncolor_in) {
+#include "fx_nn_ilu.h"
+
+static inline int nn_precond_kind(int precond) { return precond == 3 ? 3 : precond == 10 ? 10 : 1; }
+
+// scaled: the solve has scaled D and the SpMV layout (nn_scaling); block ILU(0) then factors the scaled off-diagonal blocks
+static int nn_precond_setup(fx_context *c, int precond, double sigma, int ncolor_in, bool scaled = false) {
   NnDev *n = nn_of(c);
+  const double t0 = now_s();
   if (precond == 1 || precond == 2) {
     if (nn_ssor_setup(c, ncolor_in)) return FX_ERROR_RUNTIME;
     n->precond_kind = 1;
   } else if (precond == 3) {
     n->precond_kind = 3;
+  } else if (precond == 10 && n->ndof >= 4) {
+    if (!n->ilu_symbolic && nn_ilu_symbolic(c)) return FX_ERROR_RUNTIME;
+    n->precond_kind = 10;
   } else {
-    g_fx_error = "NDOF != 3: PRECOND must be 1/2 (SSOR) or 3 (DIAG) on the GPU path";
+    g_fx_error = "NDOF != 3: PRECOND must be 1/2 (SSOR), 3 (DIAG) or, for NDOF 4, 5, 6, 10 (block ILU(0)) on the GPU path";
     return FX_ERROR_INCONS_PC;
   }
   n->sigma = sigma;
   HIP_TRY(hipMemsetAsync(n->alu, 0, (size_t)n->ndof * n->ndof * std::max(n->NP, 1) * 8, c->stream));
+  // the LU of the sigma-scaled diagonal blocks: ILU1aNN / ILU1a44 / ILU1a66 compute exactly this too (Dlu of block ILU(0))
   if (n->N > 0) { NN_DISPATCH(n->ndof, hipLaunchKernelGGL((k_nn_lu<ND>), dim3((n->N + 127) / 128), dim3(128), 0, c->stream, n->N, n->D, sigma, n->alu)) }
   HIP_TRY(hipGetLastError());
+  if (n->precond_kind == 10 && nn_ilu_numeric(c, scaled)) return FX_ERROR_RUNTIME;
+  if (n->precond_kind == 10) n->ilu_setup_ms = (now_s() - t0) * 1e3;
   n->precond_valid = true;
   return 0;
 }
 
 // hecmw_precond_nn_apply: ZP = R (internal rows, halo rows 0), Z = 0, iterPREmax x { ZP <- M^-1 ZP; Z += ZP; ZP = R - A Z }
-static int nn_precond_apply(fx_context *c, int iterpremax, const double *r, double *z) {
+static int nn_precond_apply(fx_context *c, int iterpremax, const double *r, double *z, const int32_t *gate = nullptr, int32_t gate_val = 0) {
   NnDev *n = nn_of(c);
   const int nd = n->ndof;
   const int64_t nlen = (int64_t)nd * n->N;
@@ -648,6 +681,8 @@ static int nn_precond_apply(fx_context *c, int iterpremax, const double *r, doub
   for (int it = 1; it <= iterpremax; it++) {
     if (n->precond_kind == 3) {
       if (n->N > 0) { NN_DISPATCH(nd, hipLaunchKernelGGL((k_nn_diag_apply<ND>), dim3((n->N + 127) / 128), dim3(128), 0, c->stream, n->N, n->alu, zp)) }
+    } else if (n->precond_kind == 10) {
+      if (nn_ilu_sweeps(c, zp, gate, gate_val)) return FX_ERROR_RUNTIME;
     } else {
       for (int k = 0; k < n->ncolor; k++) {
         NN_DISPATCH(nd, nn_rows_launch<ND, 2>(c, n->L, n->color_slice[k], n->color_slice[k + 1], zp, nullptr, zp, n->alu))
@@ -723,7 +758,7 @@ static int nn_cg_iteration(fx_context *c, int it, int iterpremax) {  // hecmw_so
   double *X = n->X, *B = n->B, *R = n->W[0], *Z = n->W[1], *Q = n->W[1], *P = n->W[2];
   const int RECOMPUTE = 50, vgrid = grid_for(dlen, FX_BLOCK, 2048);
   int np;
-  if (nn_precond_apply(c, iterpremax, R, Z) || nn_dot_parts(c, R, Z, gate_status(c), 0, &np)) return FX_ERROR_RUNTIME;
+  if (nn_precond_apply(c, iterpremax, R, Z, gate_status(c), 0) || nn_dot_parts(c, R, Z, gate_status(c), 0, &np)) return FX_ERROR_RUNTIME;
   if (scalar_stage<OP_CG_RHO>(c, np, 0, RECOMPUTE)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_nn_cg_p, dim3(nn_vgrid(nlen)), dim3(FX_BLOCK), 0, c->stream, nlen, c->st, Z, P);
   if (nn_spmv(c, 0, P, nullptr, Q) || nn_dot_parts(c, P, Q, gate_status(c), 0, &np)) return FX_ERROR_RUNTIME;
@@ -753,10 +788,10 @@ static int nn_bicgstab_iteration(fx_context *c, int it, int iterpremax) {  // he
   int np;
   if (nn_dot_parts(c, R, RT, gate_status(c), 0, &np) || scalar_stage<OP_BI_RHO>(c, np, 0, RECOMPUTE)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_bi_update_p, dim3(vgrid), dim3(FX_BLOCK), 0, c->stream, dlen, c->st, R, V, P);
-  if (nn_precond_apply(c, iterpremax, P, PT) || nn_spmv(c, 0, PT, nullptr, V)) return FX_ERROR_RUNTIME;
+  if (nn_precond_apply(c, iterpremax, P, PT, gate_status(c), 0) || nn_spmv(c, 0, PT, nullptr, V)) return FX_ERROR_RUNTIME;
   if (nn_dot_parts(c, RT, V, gate_status(c), 0, &np) || scalar_stage<OP_BI_C2>(c, np, 0, RECOMPUTE)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_bi_update_s, dim3(vgrid), dim3(FX_BLOCK), 0, c->stream, dlen, c->st, R, V, S);
-  if (nn_precond_apply(c, iterpremax, S, ST) || nn_spmv(c, 0, ST, nullptr, T)) return FX_ERROR_RUNTIME;  // ST aliases R (:50)
+  if (nn_precond_apply(c, iterpremax, S, ST, gate_status(c), 0) || nn_spmv(c, 0, ST, nullptr, T)) return FX_ERROR_RUNTIME;  // ST aliases R (:50)
   hipLaunchKernelGGL(k_dot2, dim3(vgrid), dim3(FX_BLOCK), 0, c->stream, dlen, T, S, c->partials, c->max_partials, gate_status(c));
   if (scalar_stage<OP_BI_OMEGA>(c, vgrid, c->max_partials, RECOMPUTE)) return FX_ERROR_RUNTIME;
   if (it % RECOMPUTE == 0) {
@@ -791,15 +826,15 @@ static int nn_krylov(fx_context *c, int method, int MAXIT, double TOL, int iterp
   const int chunk = method == 1 ? 16 : 8;
   KrylovState s;
   memset(&s, 0, sizeof s);
-  if (MAXIT <= 0) { if (poll_state(c, &s)) return FX_ERROR_RUNTIME; }
+  if (MAXIT <= 0) { if (int pe = poll_state(c, &s)) return pe; }
   for (int it = 1; it <= MAXIT; it++) {
     if (method == 1 ? nn_cg_iteration(c, it, iterpremax) : nn_bicgstab_iteration(c, it, iterpremax)) return FX_ERROR_RUNTIME;
     if (it % chunk == 0 || it == MAXIT) {
-      if (poll_state(c, &s)) return FX_ERROR_RUNTIME;
+      if (int pe = poll_state(c, &s)) return pe;  // FX_DF_RETRY: a block ILU(0) dataflow sweep timed out (nn_solve redoes the attempt)
       if (s.status != 0) break;
     }
   }
-  if (s.status == 0 && poll_state(c, &s)) return FX_ERROR_RUNTIME;
+  if (s.status == 0) { if (int pe = poll_state(c, &s)) return pe; }
   o->iter = s.iter;
   o->resid = s.resid;
   o->error = s.status > 1 ? s.status : 0;
@@ -917,9 +952,16 @@ static int nn_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_view *
     if (Iarray[95] < Iarray[34]) { Iarray[96] = 0; Iarray[95]++; }
     else Iarray[95] = 0;
   }
-  double sigma = Rarray[1] < 0.0 ? 1.0 : Rarray[1];
-  if (iterpremax > 0 && (!n->precond_valid || Iarray[97] == 1 || Iarray[96] == 1 || n->sigma != sigma ||
-                         n->precond_kind != ((precond == 3) ? 3 : 1))) {
+  const bool auto_sigma = Rarray[1] < 0.0;  // hecmw_solver_Iterative.f90:68-73
+  const double sigma = auto_sigma ? 1.0 : Rarray[1];  // the factors of every attempt (see the retry below)
+  double sigma_attempt = sigma;
+  // with SCALING=YES every attempt sets up the preconditioner of the scaled matrix; block ILU(0) then skips the factor of the
+  // unscaled one here (PRECOND 1-3 keep their set-up: it also validates PRECOND before anything else runs)
+  // hecmw_precond_BILU_66_setup has no INITIALIZED test (BILU_66.f90:33-126, unlike BILU_44 / BILU_nn :49-57): at NDOF 6 the
+  // reference factors again on every set-up call, whatever the recycle flags say, and with the SIGMA_DIAG of the attempt
+  const bool ilu66 = precond == 10 && nd == 6;
+  if (iterpremax > 0 && (!n->precond_valid || Iarray[97] == 1 || Iarray[96] == 1 || n->sigma != sigma || ilu66 ||
+                         n->precond_kind != nn_precond_kind(precond)) && !(scaling && precond == 10 && nd >= 4)) {
     if (int e = nn_precond_setup(c, precond, sigma, Iarray[33])) return e;
   }
   Iarray[97] = 0; Iarray[96] = 0;
@@ -934,21 +976,39 @@ static int nn_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_view *
     if (scaling) {  // scale, then build the preconditioner of the scaled matrix (hecmw_solver_CG.f90:104-112)
       if (nn_scaling(c, 0)) return FX_ERROR_RUNTIME;
       if (iterpremax > 0) {
-        if (int pe = nn_precond_setup(c, precond, sigma, Iarray[33])) return pe;
+        if (int pe = nn_precond_setup(c, precond, ilu66 ? sigma_attempt : sigma, Iarray[33], true)) return pe;
         if (n->precond_kind == 1 && (nn_scale_bell(c, n->L, 0) || nn_scale_bell(c, n->U, 0))) return FX_ERROR_RUNTIME;  // built from the caller's values
       }
     }
-    if (method == 1) e = nn_cg(c, maxit, Rarray[0], iterpremax, &res);
-    else if (method == 2) e = nn_bicgstab(c, maxit, Rarray[0], iterpremax, &res);
-    else if (method == 3 || method == 4) {
-      HostKrylov hk;
-      e = (method == 3) ? gmres_solve_t(OpsNN{c}, maxit, Rarray[0], Iarray[5], &hk) : gpbicg_solve_t(OpsNN{c}, maxit, Rarray[0], &hk);
-      res.iter = hk.iter; res.resid = hk.resid; res.error = hk.error; res.hist = hk.hist;
-    } else { g_fx_error = "METHOD must be 1 (CG), 2 (BiCGSTAB), 3 (GMRES) or 4 (GPBiCG)"; return FX_ERROR_INCONS_PC; }
-    if (e) return e;
+    if (method < 1 || method > 4) { g_fx_error = "METHOD must be 1 (CG), 2 (BiCGSTAB), 3 (GMRES) or 4 (GPBiCG)"; return FX_ERROR_INCONS_PC; }
+    // a block ILU(0) dataflow sweep that times out leaves unusable iterates: the context switches to per-level launches and the
+    // attempt runs again from the X it started with
+    const bool df = iterpremax > 0 && n->precond_kind == 10 && c->df_mode >= 1;
+    if (df) {
+      if (!n->X0 && dev_alloc(&n->X0, (size_t)nd * std::max(n->NP, 1))) return FX_ERROR_RUNTIME;
+      HIP_TRY(hipMemcpyAsync(n->X0, n->X, (size_t)nd * n->NP * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    for (int df_try = 0;; df_try++) {
+      res = NnResult();
+      if (method == 1) e = nn_cg(c, maxit, Rarray[0], iterpremax, &res);
+      else if (method == 2) e = nn_bicgstab(c, maxit, Rarray[0], iterpremax, &res);
+      else {
+        HostKrylov hk;
+        e = (method == 3) ? gmres_solve_t(OpsNN{c}, maxit, Rarray[0], Iarray[5], &hk) : gpbicg_solve_t(OpsNN{c}, maxit, Rarray[0], &hk);
+        res.iter = hk.iter; res.resid = hk.resid; res.error = hk.error; res.hist = hk.hist;
+        if (df && nn_df_take_error(c)) e = FX_DF_RETRY;  // asked before e: tag values in the vectors cause breakdown codes
+      } 
+      if (e == FX_DF_RETRY && df && df_try == 0) {
+        if (method <= 2) n->ilu_df_fallbacks++;  // poll_state has switched the context already
+        HIP_TRY(hipMemcpyAsync(n->X, n->X0, (size_t)nd * n->NP * 8, hipMemcpyDeviceToDevice, c->stream));
+        continue;
+      }
+      break;
+    }
+    if (e) return e == FX_DF_RETRY ? FX_ERROR_RUNTIME : e;
     c->attempts.emplace_back();
     c->attempts.back().method = method;
-    c->attempts.back().sigma_diag = sigma;
+    c->attempts.back().sigma_diag = sigma_attempt;
     c->attempts.back().hist = res.hist;
     if (scaling) {  // x and b back, matrix restored (hecmw_solver_CG.f90:277); the preconditioner belonged to the scaled matrix
       if (nn_scaling(c, 1)) return FX_ERROR_RUNTIME;
@@ -956,7 +1016,20 @@ static int nn_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_view *
     }
     if (res.error == FX_ERROR_DIVERGE_PC || res.error == FX_ERROR_DIVERGE_MAT) {  // Iterative.f90:145-156
       Iarray[81] = 1;
-      if (method == 1 && method2 > 1) { method = method2; continue; }
+      // The ILU family's 'Increasing SIGMA_DIAG' retry, as the 3x3 path runs it: the reference's set-up returns early on a retry
+      // (hecmw_precond_BILU_nn.f90:49-57, the flags are already cleared), so every attempt keeps the FIRST SIGMA_DIAG's factors
+      // (NDOF 4, 5; BILU_66 factors again with the attempt's SIGMA_DIAG)
+      // and restarts from the X the failed attempt left.  `sigma_attempt` only decides how many retries there are.
+      if (precond >= 10 && precond < 20 && auto_sigma && sigma_attempt < 2.0) {
+        sigma_attempt += (double)0.1f;  // `SIGMA_DIAG = SIGMA_DIAG + 0.1` with a default-real literal (:147)
+        if (ilu66 && !scaling && nn_precond_setup(c, precond, sigma_attempt, Iarray[33])) return FX_ERROR_RUNTIME;  // BILU_66: see above
+        continue;
+      } else if (method == 1 && method2 > 1) {
+        if (auto_sigma) sigma_attempt = 1.0;  // :152
+        if (ilu66 && !scaling && nn_precond_setup(c, precond, sigma_attempt, Iarray[33])) return FX_ERROR_RUNTIME;
+        method = method2;
+        continue;
+      }
     }
     break;
   }

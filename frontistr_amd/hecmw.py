@@ -334,6 +334,43 @@ class SolverContext:
         _chk(lib().fx_krylov_history(self.h, _ptr(h), n.value, C.byref(n)))
         return h[:n.value]
 
+    def nn_precond_apply(self, hecMAT, r, hecMESH=None):
+        """NDOF != 3: hecmw_precond_setup + hecmw_precond_apply -- uploads hecMAT, sets up (or reuses) the preconditioner its
+        Iarray / Rarray select, returns z = M^-1 r (NDOF*NP doubles, halo part 0).  Iarray(97) / (98) are cleared as a set-up does."""
+        mv = hecMAT.view()
+        cv = hecMESH.comm_view() if hecMESH is not None else None
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.size == hecMAT.NDOF * hecMAT.NP
+        z = np.zeros_like(r)
+        _chk(lib().fx_nn_precond_apply(self.h, C.byref(mv), C.byref(cv) if cv is not None else None, _ptr(hecMAT.Iarray),
+                                       _ptr(hecMAT.Rarray), _ptr(r), _ptr(z)))
+        return z
+
+    def nn_precond_apply_ms(self, nrepeat=10):
+        """Timed applies of the resident NDOF != 3 preconditioner (ms per apply)."""
+        ms = C.c_float(0)
+        _chk(lib().fx_nn_precond_apply_resident(self.h, int(nrepeat), C.byref(ms)))
+        return ms.value
+
+    def nn_precond_stats(self):
+        out = (C.c_int64 * 10)()
+        _chk(lib().fx_nn_precond_stats(self.h, out))
+        keys = ("kind", "levels", "slices", "max_row_blocks", "factor_lanes", "L_blocks", "U_blocks", "setup_us", "dataflow")
+        st = {k: int(out[i]) for i, k in enumerate(keys)}
+        st["df_grid"], st["df_fallbacks"] = int(out[9]) & 0xFFFFFFFF, int(out[9]) >> 32
+        return st
+
+    def solve_attempts(self):
+        """(method, SIGMA_DIAG, ITERLOG lines) of every pass of the last solve's retry loop."""
+        n = C.c_int32(0)
+        _chk(lib().fx_solve_attempts(self.h, 0, C.byref(n), None, None, None))
+        k = n.value
+        meth = np.zeros(max(k, 1), dtype=np.int32)
+        sig = np.zeros(max(k, 1))
+        nh = np.zeros(max(k, 1), dtype=np.int32)
+        _chk(lib().fx_solve_attempts(self.h, k, C.byref(n), _ptr(meth), _ptr(sig), _ptr(nh)))
+        return [(int(meth[i]), float(sig[i]), int(nh[i])) for i in range(k)]
+
     def precond_apply(self, r):
         r = np.ascontiguousarray(r, dtype=np.float64)
         z = np.zeros_like(r)

@@ -97,7 +97,8 @@ int fx_device_synchronize(fx_context *ctx);
  * SCALING Iarray(7) /= 0: symmetric diagonal scaling around every attempt (las/hecmw_solver_scaling_33.f90);
  * SIGMA_DIAG Rarray(2) < 0: the reference's automatic retry for the ILU family; METHOD2 Iarray(8) take-over.
  * NDOF = 3 is the tuned path.  NDOF = 1, 2, 4, 5, 6 (hecmw_matvec_nn las_nn.f90:135, precond/nn + 11/22/44/66) take the
- * generic-block path: METHOD 1-4; PRECOND 1, 2, 3; SCALING; anything else E-1001 / FX_ERROR_UNSUPPORTED. */
+ * generic-block path: METHOD 1-4; PRECOND 1, 2, 3, and 10 (block ILU(0), with the SIGMA_DIAG retry) for NDOF 4, 5, 6;
+ * SCALING; anything else (PRECOND 11 / 12 at any size, 10 with NDOF 1 or 2) E-1001 / FX_ERROR_UNSUPPORTED. */
 int fx_solve(fx_context *ctx, const fx_matrix_view *mat, const fx_comm_view *comm, int32_t *Iarray,
              double *Rarray, fx_solve_info *info, double *hist, int32_t hist_len);
 
@@ -142,6 +143,20 @@ int fx_spmv_resident(fx_context *ctx, int variant, int nrepeat, float *ms_per_ca
 /* The same for the resident NDOF != 3 system of the last fx_solve / fx_matvec (hecmw_matvec_nn, las_nn.f90:135-310).
  * stats: NDOF, N, padded blocks of the layout, blocks of the matrix (N + NPL + NPU). */
 int fx_nn_matvec_resident(fx_context *ctx, int nrepeat, float *ms_per_call, int64_t stats[4]);
+/* hecmw_precond_setup + hecmw_precond_apply (hecmw_precond.f90:28, :75-123) for an NDOF != 3 system: uploads `mat`, sets up
+ * the preconditioner Iarray / Rarray select (or reuses the resident one, with the flags and SIGMA_DIAG fx_solve reads), then
+ * z = M^-1 r with iterPREmax = Iarray(5).  r, z: host arrays of NDOF*NP doubles; r's halo part is ignored (ZP(halo) = 0),
+ * z's is 0. */
+int fx_nn_precond_apply(fx_context *ctx, const fx_matrix_view *mat, const fx_comm_view *comm, int32_t *Iarray,
+                        double *Rarray, const double *r, double *z);
+/* Timed applies of the resident NDOF != 3 preconditioner on resident work vectors (HIP events, one untimed call first). */
+int fx_nn_precond_apply_resident(fx_context *ctx, int nrepeat, float *ms_per_call);
+/* out[0..9]: kind (1 SSOR, 3 DIAG, 10 block ILU(0), 0 none) | levels or colours | sweep slices | longest L + U row (ILU) |
+ * factor kernel lanes per row, 32 or 1 (ILU) | padded L blocks | padded U blocks | last ILU set-up, microseconds |
+ * ILU sweep form: 1 one persistent dataflow launch per apply (FX_DATAFLOW >= 1), 0 one launch per level (FX_DATAFLOW=0, or
+ * after a dataflow sweep timed out) | workgroups of the last dataflow launch (bits 0-31), timed-out sweeps (bits 32-63).
+ * The dataflow sweep honours FX_DATAFLOW, FX_DF_GRID and FX_DEBUG_DF_FAIL, none of the other FX_DF_* settings. */
+int fx_nn_precond_stats(fx_context *ctx, int64_t out[10]);
 int fx_precond_apply_resident(fx_context *ctx, int nrepeat, float *ms_per_call); /* z = M^-1 b, timed */
 int fx_precond_apply_host(fx_context *ctx, const double *r, double *z);   /* z = M^-1 r, 3*NP doubles */
 /* out[0..14]: N NP NPL NPU | M pairs, blocks, slices | ncolor | L pairs, blocks | U pairs, blocks | slices |
