@@ -2403,17 +2403,6 @@ static int krylov_steps(fx_context *c, int n, KrylovState *st_out) {
   return 0;
 }
 
-static int run_krylov(fx_context *c, int method, int maxit, double tol, KrylovState *fin) {
-  for (int attempt = 0;; attempt++) {
-    if (krylov_begin(c, method, maxit, tol)) return FX_ERROR_RUNTIME;
-    const int e = krylov_steps(c, maxit, fin);
-    // a dataflow sweep gave up: the iterates are unusable, the context has switched to the launch-per-level sweeps -- start the
-    // attempt again from the X it started with (krylov_begin re-reads it; nothing was written back)
-    if (e == FX_DF_RETRY && attempt == 0) continue;
-    return e ? FX_ERROR_RUNTIME : 0;
-  }
-}
-
 extern "C" int fx_krylov_begin(fx_context *c, const int32_t *Iarray, const double *Rarray) {
   HIP_TRY(hipSetDevice(c->device));
   if (require_transport(c, "fx_krylov_begin")) return FX_ERROR_RUNTIME;
@@ -2497,44 +2486,39 @@ static int scaling_apply(fx_context *c, bool back) {
   return 0;
 }
 
-extern "C" int fx_solve_resident(fx_context *c, int32_t *Iarray, double *Rarray, fx_solve_info *info, double *hist,
-                                 int32_t hist_len) {
-  HIP_TRY(hipSetDevice(c->device));
-  if (!c->have_values) { g_fx_error = "fx_solve_resident: no matrix resident"; return FX_ERROR_RUNTIME; }
-  if (require_transport(c, "fx_solve_resident")) return FX_ERROR_RUNTIME;
-  const int maxit = Iarray[0], precond = Iarray[2], method2 = Iarray[7], iterpremax = Iarray[4];
-  int method = Iarray[1];
-  const double tol = Rarray[0];
-  c->iterpremax = iterpremax;
-  c->clock.on = Iarray[21] >= 1;  // TIMELOG
-  c->clock.used = 0;
-  c->clock.acc[0] = c->clock.acc[1] = c->clock.acc[2] = 0.0;
-  int ret = 0, np;
-  double t0 = now_s();
-  // hecmw_solve_check_zerorhs (:242-278): warning 2002, X = 0, the solve continues
-  double rhs2 = 0.0, tmp;
-  if (c->max_partials < 4096 + 8) {  // the two checks below only need the partial-sum buffer
+static int ensure_partials(fx_context *c) {  // the partial-sum buffer of the scalar stages and of the solve's checks
+  if (c->max_partials < 4096 + 8) {
     dev_free(c->partials);
     if (dev_alloc(&c->partials, (size_t)(4096 + 8) * 3)) return FX_ERROR_RUNTIME;
     c->max_partials = 4096 + 8;
   }
-  {  // sum over the internal rows of B (natural numbering: independent of the solver numbering)
-    const int64_t n = (int64_t)3 * c->A.N;
-    np = grid_for(n, FX_BLOCK, 2048);
-    hipLaunchKernelGGL(k_dot, dim3(np), dim3(FX_BLOCK), 0, c->stream, n, c->A.B, c->A.B, c->partials, (const int32_t *)nullptr, 0);
-    HIP_TRY(hipGetLastError());
-  }
-  if (host_sum(c, np, 0, &rhs2, &tmp)) return FX_ERROR_RUNTIME;
+  return 0;
+}
+
+// One driver for every block size.  The path (Ops33 below, OpsNN in fx_nn_host.h) supplies what differs: the norms and the
+// zero-diagonal kernel, the preconditioner set-up before the loop / of the scaled matrix / on a retry, scaling, one attempt of
+// METHOD 1-4 (a timed-out dataflow sweep is redone inside it), where X lives, the final ||b - Ax||^2, ncolor and the clocks.
+// An attempt is recorded (fx_solve_attempts) once it has run; an error return leaves the records of the attempts before it.
+template <class Path>
+static int hecmw_solve_iterative(const Path &p, int32_t *Iarray, const double *Rarray, fx_solve_info *info, double *hist,
+                                 int32_t hist_len) {
+  fx_context *c = p.c;
+  const int precond = Iarray[2], method2 = Iarray[7], iterpremax = Iarray[4];
+  int method = Iarray[1];
+  int ret = 0;
+  const double t0 = now_s();
+  c->attempts.clear();
+  // hecmw_solve_check_zerorhs (:242-278): warning 2002, X = 0, the solve continues
+  double rhs2 = 0.0;
+  if (p.rhs_norm2(&rhs2)) return FX_ERROR_RUNTIME;
   if (rhs2 == 0.0) {
     ret = FX_ERROR_ZERO_RHS;
-    HIP_TRY(hipMemsetAsync(c->A.X, 0, (size_t)3 * c->A.NP * 8, c->stream));
+    if (p.zero_x()) return FX_ERROR_RUNTIME;
   }
-  // hecmw_solve_check_zerodiag (:212-240)
-  {
-    int32_t *flag = (int32_t *)(c->red_out + 8);
+  {  // hecmw_solve_check_zerodiag (:212-240)
+    int32_t *flag = (int32_t *)(c->red_out + 8), hflag = 0;
     HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_check_zero_diag, dim3(grid_for(c->A.N)), dim3(256), 0, c->stream, c->A.N, c->A.D, flag);
-    int32_t hflag = 0;
+    p.zero_diag(flag);
     HIP_TRY(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (multi_rank(c)) {  // MAX of 0/1 flags == (SUM > 0)
@@ -2554,144 +2538,214 @@ extern "C" int fx_solve_resident(fx_context *c, int32_t *Iarray, double *Rarray,
     if (Iarray[95] < Iarray[34]) { Iarray[96] = 0; Iarray[95]++; }
     else Iarray[95] = 0;
   }
-  // preconditioner: rebuild when the flags ask for it, reuse otherwise (SSOR_33.f90:71-79)
-  const int want_kind = (iterpremax <= 0) ? 0 : ((precond == 1 || precond == 2) ? (c->ssor_natural ? 11 : 1) : precond);
-  if (!c->precond_valid || Iarray[97] == 1 || Iarray[96] == 1 || c->precond_kind != want_kind) {  // each preconditioner type has its own state in the reference
-    int e = fx_precond_setup(c, Iarray, Rarray);
-    if (e) return e;
-  }
+  if (int e = p.setup(Iarray, Rarray, Iarray[97] == 1 || Iarray[96] == 1)) return e;
   Iarray[97] = 0; Iarray[96] = 0;
-  const double t_setup = now_s() - t0;
-  KrylovState s;
-  memset(&s, 0, sizeof s);
+  const double t_setup = now_s() - t0, t1 = now_s();
   const bool auto_sigma = Rarray[1] < 0.0;  // hecmw_solver_Iterative.f90:68-73
+  const bool scaling = Iarray[6] != 0;      // SCALING=YES (IDX_I_SCALING = 7)
   double sigma = auto_sigma ? 1.0 : Rarray[1];
-  double t1 = now_s();
-  const bool scaling = Iarray[6] != 0;  // SCALING=YES (IDX_I_SCALING = 7)
-  c->attempts.clear();
+  HostKrylov res;
   for (;;) {
     Iarray[80] = 0; Iarray[81] = 0;
-    int e;
-    c->attempts.emplace_back();
-    c->attempts.back().method = method;
-    c->attempts.back().sigma_diag = sigma;
-    if (scaling) {  // scale, then build the preconditioner of the scaled matrix (CG.f90:104-112)
-      if (scaling_apply(c, false)) return FX_ERROR_RUNTIME;
-      double R2[100];
-      memcpy(R2, Rarray, sizeof R2);
-      R2[1] = auto_sigma ? 1.0 : Rarray[1];  // every attempt scales the same matrix the same way: the first SIGMA_DIAG's factors (see the retry below)
-      if (int pe = fx_precond_setup(c, Iarray, R2)) return pe;
+    if (method < 1 || method > 4) { g_fx_error = "METHOD must be 1 (CG), 2 (BiCGSTAB), 3 (GMRES) or 4 (GPBiCG)"; return FX_ERROR_INCONS_PC; }
+    if (scaling) {  // scale, then build the preconditioner of the scaled matrix (hecmw_solver_CG.f90:104-112)
+      if (int e = p.scale(Iarray, Rarray, sigma)) return e;
     }
-    c->k_method_last = method;
-    if (method == 1 || method == 2) e = run_krylov(c, method, maxit, tol, &s);
-    else if (method == 3 || method == 4) {
-      HostKrylov hk;
-      e = (method == 3) ? gmres_solve(c, maxit, tol, Iarray[5], &hk) : gpbicg_solve(c, maxit, tol, &hk);
-      // a dataflow sweep of this attempt timed out: again with the launch-per-level sweeps (the solve re-reads its initial X).  Asked
-      // BEFORE looking at e: a timed-out sweep leaves tag values (NaN) in the vectors, which is what makes these methods return a
-      // breakdown code in the first place
-      if (df_take_error(c)) {
-        hk = HostKrylov();
-        e = (method == 3) ? gmres_solve(c, maxit, tol, Iarray[5], &hk) : gpbicg_solve(c, maxit, tol, &hk);
-      }
-      if (e) return e;
-      memset(&s, 0, sizeof s);
-      s.iter = hk.iter; s.resid = hk.resid; s.status = hk.status; s.n_hist = (int32_t)hk.hist.size();
-      memcpy(c->host_dbg, hk.dbg, sizeof hk.dbg);
-      c->host_dbg[14] = hk.status;
-      if (c->hist_cap < (int32_t)hk.hist.size()) {
-        dev_free(c->hist);
-        if (dev_alloc(&c->hist, hk.hist.size())) return FX_ERROR_RUNTIME;
-        c->hist_cap = (int32_t)hk.hist.size();
-      }
-      if (!hk.hist.empty()) HIP_TRY(hipMemcpy(c->hist, hk.hist.data(), hk.hist.size() * 8, hipMemcpyHostToDevice));
-    } else { g_fx_error = "METHOD must be 1 (CG), 2 (BiCGSTAB), 3 (GMRES) or 4 (GPBiCG)"; return FX_ERROR_INCONS_PC; }
-    if (e) return e;
-    if (s.n_hist > 0) {  // the pass's ITERLOG lines (kept per pass: a retry starts its history again at line 1)
-      c->attempts.back().hist.resize((size_t)s.n_hist);
-      HIP_TRY(hipMemcpy(c->attempts.back().hist.data(), c->hist, (size_t)s.n_hist * 8, hipMemcpyDeviceToHost));
-    }
-    if (scaling) {  // x <- D^-1/2 x, b and the matrix divided back (CG.f90:277); then everything resident is refreshed
-      if (from_slots(c, c->Xs, c->A.X) || scaling_apply(c, true) || ensure_solver(c)) return FX_ERROR_RUNTIME;
-      if (to_slots(c, c->A.B, c->Bs) || to_slots(c, c->A.X, c->Xs)) return FX_ERROR_RUNTIME;
-    }
-    if (s.status == FX_ERROR_DIVERGE_PC || s.status == FX_ERROR_DIVERGE_MAT) {  // :145-156
+    if (int e = p.attempt(Iarray, Rarray, method, &res)) return e;
+    c->attempts.push_back({method, sigma, res.hist});  // the pass's ITERLOG lines (a retry starts its history again at line 1)
+    if (scaling && p.unscale()) return FX_ERROR_RUNTIME;  // x <- D^-1/2 x, b and the matrix divided back (CG.f90:277)
+    if (res.error == FX_ERROR_DIVERGE_PC || res.error == FX_ERROR_DIVERGE_MAT) {  // :145-156
       Iarray[81] = 1;
-      // a retry continues from the X the failed attempt left behind (hecMAT%X is not reset), halo included
-      if (halo_update(c, c->Xs) || from_slots(c, c->Xs, c->A.X)) return FX_ERROR_RUNTIME;
       // The retries call the Krylov routine again; its hecmw_precond_setup finds Iarray(97) = Iarray(98) = 0 and returns early
-      // (hecmw_precond_BILU_33.f90:49-57; the hecmw_precond_clear at the end of every method is commented out,
-      // hecmw_solver_CG.f90:285), so the reference's retry keeps the factors of the FIRST SIGMA_DIAG and only restarts from the
-      // X the failed attempt left.  Reproduced literally (bit-exact oracle runs against the real reference:
-      // tests/golden/retry.npz); `sigma` is tracked because it decides how many retries there are.
+      // (hecmw_precond_BILU_33.f90:49-57, BILU_nn.f90:49-57; the hecmw_precond_clear at the end of every method is commented
+      // out, hecmw_solver_CG.f90:285), so the reference's retry keeps the factors of the FIRST SIGMA_DIAG and only restarts from
+      // the X the failed attempt left (hecMAT%X is not reset).  Reproduced literally (bit-exact oracle runs against the real
+      // reference: tests/golden/retry.npz, nn_ilu.npz); `sigma` is tracked because it decides how many retries there are.
       if (precond >= 10 && precond < 20 && auto_sigma && sigma < 2.0) {  // 'Increasing SIGMA_DIAG' retry of the ILU family
         sigma += (double)0.1f;  // `SIGMA_DIAG = SIGMA_DIAG + 0.1` with a default-real literal (:147): what the reference adds, and prints
-        continue;
       } else if (method == 1 && method2 > 1) {
         if (auto_sigma) sigma = 1.0;  // :152 (no set-up follows in the reference either)
         method = method2;
-        continue;
+      } else {
+        break;
       }
+      if (p.retry(Iarray, sigma)) return FX_ERROR_RUNTIME;
+      continue;
     }
     break;
   }
   // X halo (hecmw_update_m_R, hecmw_solver_CG.f90:280), then back to the caller's numbering
-  if (halo_update(c, c->Xs)) return FX_ERROR_RUNTIME;
-  if (from_slots(c, c->Xs, c->A.X)) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (p.finish_x()) return FX_ERROR_RUNTIME;
   const double t_sol = now_s() - t1;
-  if (s.status > 1) ret = s.status;
+  if (res.error > 1) ret = res.error;
   // final true residual (hecmw_rel_resid_L2, hecmw_solver_las.f90:129-158) -> Iarray(81)
-  double r2 = 0.0, b2 = rhs2;
-  if (b2 == 0.0) b2 = 1.0;
-  if (spmv(c, 1, 2, c->Xs, c->Bs, c->W[7], nullptr, 0)) return FX_ERROR_RUNTIME;
-  if (host_sum(c, spmv_nparts(c), 0, &r2, &tmp)) return FX_ERROR_RUNTIME;
-  const double resid2 = sqrt(r2 / b2);
+  double r2 = 0.0;
+  if (p.resid2(&r2)) return FX_ERROR_RUNTIME;
+  const double resid2 = sqrt(r2 / (rhs2 == 0.0 ? 1.0 : rhs2));
   if (resid2 < Rarray[0]) Iarray[80] = 1;
+  const int nh = hist ? std::max(0, std::min((int)hist_len, (int)res.hist.size())) : 0;
   if (info) {
     memset(info, 0, sizeof *info);
-    info->iterations = s.iter;
+    info->iterations = res.iter;
     info->method = method; info->precond = precond;
-    info->ncolor = (c->precond_kind == 1 || level_sched(c)) ? c->ssor.ncolor : 0;  // SSOR colours / ILU levels
-    info->resid = s.resid;
+    info->resid = res.resid;
     info->rel_resid = resid2;
     info->time_setup = t_setup; info->time_sol = t_sol;
-    if (c->clock.on) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      clock_collect(c);
-      info->time_matvec = c->clock.acc[0]; info->time_precond = c->clock.acc[1]; info->time_comm = c->clock.acc[2];
-    }
-    c->clock.on = false;
-    const int nh = std::max(0, std::min((int)hist_len, (int)s.n_hist));
-    info->n_hist = hist ? nh : 0;
+    info->n_hist = nh;
+    if (p.fill_info(info)) return FX_ERROR_RUNTIME;
   }
-  if (hist && hist_len > 0) {
-    const int nh = std::max(0, std::min((int)hist_len, (int)s.n_hist));
-    if (nh > 0) HIP_TRY(hipMemcpy(hist, c->hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
-  }
+  if (nh > 0) memcpy(hist, res.hist.data(), (size_t)nh * 8);
   return ret;
+}
+
+// --- the 3x3 path: vectors in slot order, the resident preconditioners ---------------------------------------------------
+int Ops33::rhs_norm2(double *b2) const {  // sum over the internal rows of B (natural numbering: independent of the solver numbering)
+  if (ensure_partials(c)) return FX_ERROR_RUNTIME;
+  const int64_t n = (int64_t)3 * c->A.N;
+  const int np = grid_for(n, FX_BLOCK, 2048);
+  hipLaunchKernelGGL(k_dot, dim3(np), dim3(FX_BLOCK), 0, c->stream, n, c->A.B, c->A.B, c->partials, (const int32_t *)nullptr, 0);
+  HIP_TRY(hipGetLastError());
+  double tmp;
+  return host_sum(c, np, 0, b2, &tmp);
+}
+int Ops33::zero_x() const {
+  HIP_TRY(hipMemsetAsync(c->A.X, 0, (size_t)3 * c->A.NP * 8, c->stream));
+  return 0;
+}
+void Ops33::zero_diag(int32_t *flag) const {
+  hipLaunchKernelGGL(k_check_zero_diag, dim3(grid_for(c->A.N)), dim3(256), 0, c->stream, c->A.N, c->A.D, flag);
+}
+// rebuild when the flags ask for it, reuse otherwise (SSOR_33.f90:71-79); each preconditioner type has its own state
+int Ops33::setup(const int32_t *I, const double *R, bool asked) const {
+  const int precond = I[2];
+  const int want_kind = (I[4] <= 0) ? 0 : ((precond == 1 || precond == 2) ? (c->ssor_natural ? 11 : 1) : precond);
+  if (c->precond_valid && !asked && c->precond_kind == want_kind) return 0;
+  return fx_precond_setup(c, I, R);
+}
+int Ops33::scale(const int32_t *I, const double *R, double) const {
+  if (scaling_apply(c, false)) return FX_ERROR_RUNTIME;
+  double R2[100];
+  memcpy(R2, R, sizeof R2);
+  R2[1] = R[1] < 0.0 ? 1.0 : R[1];  // every attempt scales the same matrix the same way: the first SIGMA_DIAG's factors
+  return fx_precond_setup(c, I, R2);
+}
+int Ops33::unscale() const {  // then everything resident is refreshed
+  if (from_slots(c, c->Xs, c->A.X) || scaling_apply(c, true) || ensure_solver(c)) return FX_ERROR_RUNTIME;
+  return (to_slots(c, c->A.B, c->Bs) || to_slots(c, c->A.X, c->Xs)) ? FX_ERROR_RUNTIME : 0;
+}
+int Ops33::attempt(const int32_t *I, const double *R, int method, HostKrylov *res) const {
+  const int maxit = I[0];
+  const double tol = R[0];
+  c->k_method_last = method;
+  KrylovState s;
+  int e;
+  for (int redo = 0;; redo++) {
+    *res = HostKrylov();
+    if (method <= 2) {
+      if (krylov_begin(c, method, maxit, tol)) return FX_ERROR_RUNTIME;
+      e = krylov_steps(c, maxit, &s);
+    } else {
+      e = (method == 3) ? gmres_solve_t(*this, maxit, tol, I[5], res) : gpbicg_solve_t(*this, maxit, tol, res);
+      // asked BEFORE looking at e: a timed-out sweep leaves tag values (NaN) in the vectors, which is what makes these methods
+      // return a breakdown code in the first place
+      if (df_take_error(c)) e = FX_DF_RETRY;
+    }
+    // a dataflow sweep gave up: the iterates are unusable, the context has switched to the launch-per-level sweeps -- the
+    // attempt runs again from the X it started with (every method re-reads it from A.X; nothing was written back)
+    if (e != FX_DF_RETRY || redo > 0) break;
+  }
+  if (e) return e == FX_DF_RETRY ? FX_ERROR_RUNTIME : e;
+  if (method >= 3) {
+    memcpy(c->host_dbg, res->dbg, sizeof res->dbg);
+    c->host_dbg[14] = res->status;
+    return 0;
+  }
+  res->iter = s.iter; res->resid = s.resid; res->status = s.status;
+  res->error = s.status > 1 ? s.status : 0;
+  res->hist.resize((size_t)std::max(0, s.n_hist));
+  if (s.n_hist > 0) HIP_TRY(hipMemcpy(res->hist.data(), c->hist, (size_t)s.n_hist * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+int Ops33::retry(const int32_t *, double) const {  // from the X the failed attempt left, halo included
+  return (halo_update(c, c->Xs) || from_slots(c, c->Xs, c->A.X)) ? FX_ERROR_RUNTIME : 0;
+}
+int Ops33::finish_x() const {
+  if (halo_update(c, c->Xs) || from_slots(c, c->Xs, c->A.X)) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int Ops33::resid2(double *r2) const {
+  if (::spmv(c, 1, 2, c->Xs, c->Bs, c->W[7], nullptr, 0)) return FX_ERROR_RUNTIME;
+  double tmp;
+  return host_sum(c, spmv_nparts(c), 0, r2, &tmp);
+}
+int Ops33::fill_info(fx_solve_info *info) const {
+  info->ncolor = (c->precond_kind == 1 || level_sched(c)) ? c->ssor.ncolor : 0;  // SSOR colours / ILU levels
+  if (c->clock.on) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    clock_collect(c);
+    info->time_matvec = c->clock.acc[0]; info->time_precond = c->clock.acc[1]; info->time_comm = c->clock.acc[2];
+  }
+  c->clock.on = false;
+  return 0;
+}
+
+extern "C" int fx_solve_resident(fx_context *c, int32_t *Iarray, double *Rarray, fx_solve_info *info, double *hist,
+                                 int32_t hist_len) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->have_values) { g_fx_error = "fx_solve_resident: no matrix resident"; return FX_ERROR_RUNTIME; }
+  if (require_transport(c, "fx_solve_resident")) return FX_ERROR_RUNTIME;
+  c->iterpremax = Iarray[4];
+  c->clock.on = Iarray[21] >= 1;  // TIMELOG
+  c->clock.used = 0;
+  c->clock.acc[0] = c->clock.acc[1] = c->clock.acc[2] = 0.0;
+  return hecmw_solve_iterative(Ops33{c}, Iarray, Rarray, info, hist, hist_len);
+}
+
+// hecmw_solve (hecmw_solver.f90:9): Iarray(99) = 1 selects the iterative solvers; the direct ones are outside the GPU hot path
+static int refuse_direct(const int32_t *Iarray) {
+  if (Iarray[98] == 1) return 0;
+  g_fx_error = "Iarray(99) selects a direct solver: outside the GPU hot path";
+  return FX_ERROR_UNSUPPORTED;
+}
+
+// The values of hecMAT changed: the flags say so, nothing is resident yet (`resident`), or another hecMAT of the same shape came
+// without the flags raised (the reference would multiply with it, with the preconditioner it happens to have) -- recognised by
+// the identity of the caller's arrays
+static bool values_changed(const fx_context *c, const fx_matrix_view *m, const int32_t *Iarray, bool resident) {
+  return Iarray[97] >= 1 || Iarray[96] >= 1 || !resident || m->D != c->host_D || m->AL != c->host_AL || m->AU != c->host_AU;
 }
 
 #include "fx_nn_host.h"
 
+// X goes back to the caller unless the solve stopped before it had one: a run-time failure, E-2001 or E-1001
+static int download_x_unless_failed(fx_context *c, const fx_matrix_view *m, int ret) {
+  if (ret < 0 || ret == FX_ERROR_ZERO_DIAG || ret == FX_ERROR_INCONS_PC) return ret;
+  if (m->NDOF == 3) {
+    const int e = fx_download_x(c, m->X, 3 * m->NP);
+    return e ? e : ret;
+  }
+  NnDev *n = nn_of(c);
+  HIP_TRY(hipMemcpy(m->X, n->X, (size_t)n->ndof * n->NP * 8, hipMemcpyDeviceToHost));
+  return ret;
+}
+
 // hecmw_solve (hecmw_solver.f90:9): host arrays in, host X out.
 extern "C" int fx_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_view *cm, int32_t *Iarray, double *Rarray,
                         fx_solve_info *info, double *hist, int32_t hist_len) {
-  if (Iarray[98] != 1) { g_fx_error = "Iarray(99) selects a direct solver: outside the GPU hot path"; return FX_ERROR_UNSUPPORTED; }
-  if (m->NDOF != 3) return nn_solve(c, m, cm, Iarray, Rarray, info, hist, hist_len);  // select case(NDOF): the nn path
-  int what = FX_UP_RHS | FX_UP_X;
-  if (Iarray[97] >= 1 || !c->have_profile) what |= FX_UP_PROFILE;  // symbolic: profile changed
-  if (Iarray[96] >= 1 || !c->have_values) what |= FX_UP_VALUES;    // numeric: values changed
-  // another hecMAT of the same shape without the flags raised (the reference would multiply with it, with the preconditioner
-  // it happens to have): recognised by the identity of the caller's arrays
-  if (m->D != c->host_D || m->AL != c->host_AL || m->AU != c->host_AU) what |= FX_UP_VALUES;
-  int e = fx_upload(c, m, cm, what);
-  if (e) return e;
-  if (what & FX_UP_VALUES) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
-  const int ret = fx_solve_resident(c, Iarray, Rarray, info, hist, hist_len);
-  if (ret < 0 || ret == FX_ERROR_ZERO_DIAG || ret == FX_ERROR_INCONS_PC) return ret;
-  e = fx_download_x(c, m->X, 3 * m->NP);
-  return e ? e : ret;
+  if (int e = refuse_direct(Iarray)) return e;
+  int ret;
+  if (m->NDOF != 3) {
+    ret = nn_solve(c, m, cm, Iarray, Rarray, info, hist, hist_len);  // select case(NDOF): the nn path
+  } else {
+    int what = FX_UP_RHS | FX_UP_X;
+    if (Iarray[97] >= 1 || !c->have_profile) what |= FX_UP_PROFILE;  // symbolic: profile changed
+    if (values_changed(c, m, Iarray, c->have_values)) what |= FX_UP_VALUES;
+    if (int e = fx_upload(c, m, cm, what)) return e;
+    if (what & FX_UP_VALUES) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
+    ret = fx_solve_resident(c, Iarray, Rarray, info, hist, hist_len);
+  }
+  return download_x_unless_failed(c, m, ret);
 }
 
 // hecmw_solve for a system whose MATRIX was produced on the device (fx_nl_stiffness_at / fx_assemble_c3d8) and whose right-hand
@@ -2701,7 +2755,7 @@ extern "C" int fx_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_vi
 extern "C" int fx_solve_device_matrix(fx_context *c, const fx_matrix_view *m, const fx_comm_view *cm, int32_t n_bc, const int32_t *bc_node,
                                       const int32_t *bc_dof, const double *bc_val, int32_t *Iarray, double *Rarray, fx_solve_info *info,
                                       double *hist, int32_t hist_len) {
-  if (Iarray[98] != 1) { g_fx_error = "Iarray(99) selects a direct solver: outside the GPU hot path"; return FX_ERROR_UNSUPPORTED; }
+  if (int e = refuse_direct(Iarray)) return e;
   if (m->NDOF != 3) { g_fx_error = "fx_solve_device_matrix: NDOF = 3 only"; return FX_ERROR_UNSUPPORTED; }
   if (!c->have_profile || !c->have_values || c->A.N != m->N || c->A.NP != m->NP || c->A.NPL != m->NPL || c->A.NPU != m->NPU) {
     g_fx_error = "fx_solve_device_matrix: no device-assembled matrix of this shape is resident";
@@ -2713,10 +2767,7 @@ extern "C" int fx_solve_device_matrix(fx_context *c, const fx_matrix_view *m, co
   if (e) return e;
   if ((e = fx_mat_ass_bc(c, n_bc, bc_node, bc_dof, bc_val))) return e;
   c->host_D = nullptr; c->host_AL = nullptr; c->host_AU = nullptr;  // the resident values are nobody's host arrays: a later fx_solve uploads its own
-  const int ret = fx_solve_resident(c, Iarray, Rarray, info, hist, hist_len);
-  if (ret < 0 || ret == FX_ERROR_ZERO_DIAG || ret == FX_ERROR_INCONS_PC) return ret;
-  e = fx_download_x(c, m->X, 3 * m->NP);
-  return e ? e : ret;
+  return download_x_unless_failed(c, m, fx_solve_resident(c, Iarray, Rarray, info, hist, hist_len));
 }
 
 extern "C" int fx_matvec(fx_context *c, const fx_matrix_view *m, const fx_comm_view *cm, double *x, double *y,
@@ -2776,11 +2827,9 @@ extern "C" int fx_nn_precond_apply(fx_context *c, const fx_matrix_view *m, const
   if (require_transport(c, "fx_nn_precond_apply")) return FX_ERROR_RUNTIME;
   fx_matrix_view mv = *m;
   mv.B = nullptr; mv.X = nullptr;
-  NnDev *n0 = nn_of(c);
-  const bool values_changed = Iarray[97] >= 1 || Iarray[96] >= 1 || !n0->have_matrix ||
-                              m->D != c->host_D || m->AL != c->host_AL || m->AU != c->host_AU;
-  if (nn_upload(c, &mv, cm, values_changed)) return FX_ERROR_RUNTIME;
-  if (values_changed) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
+  const bool changed = values_changed(c, m, Iarray, nn_of(c)->have_matrix);
+  if (nn_upload(c, &mv, cm, changed)) return FX_ERROR_RUNTIME;
+  if (changed) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
   NnDev *n = nn_of(c);
   n->cur_AL = m->AL; n->cur_AU = m->AU;
   const int precond = Iarray[2], iterpremax = Iarray[4];

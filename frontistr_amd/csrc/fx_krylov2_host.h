@@ -51,7 +51,7 @@ __global__ void k_gp_w1(int64_t n, double beta, const double *__restrict__ tt, c
     w1[i] = tt[i] + beta * pt[i];
 }
 
-struct HostKrylov {
+struct HostKrylov {  // the outcome of one attempt of any method (hecmw_solve_iterative)
   int iter = 0, status = 1, error = 0;
   double resid = 0.0;
   std::vector<double> hist;
@@ -88,8 +88,9 @@ static int hk_prepare(fx_context *c, int maxit, double tol, int extra) {
   return 0;
 }
 
-// The two solvers are written against a small set of operations so that the 3x3 path (Ops33: slot-ordered vectors, the
-// device-resident preconditioners) and the generic-block path (OpsNN in fx_nn_host.h) share them.
+// The two solvers -- and hecmw_solve_iterative (fistr_hip.hip) -- are written against a small set of operations so that the 3x3
+// path (Ops33: slot-ordered vectors, the device-resident preconditioners) and the generic-block path (OpsNN in fx_nn_host.h)
+// share them.
 struct Ops33 {
   fx_context *c;
   double *X() const { return c->Xs; }
@@ -103,6 +104,18 @@ struct Ops33 {
   int precond(const double *r, double *z) const { int np; return precond_apply(c, r, z, false, &np); }
   int dot(const double *x, const double *y, double *out) const { return hk_dot(c, x, y, out); }
   int prepare(int maxit, double tol, int extra) const { return hk_prepare(c, maxit, tol, extra); }
+  // hecmw_solve_iterative (defined with it in fistr_hip.hip)
+  int rhs_norm2(double *b2) const;
+  int zero_x() const;
+  void zero_diag(int32_t *flag) const;
+  int setup(const int32_t *I, const double *R, bool asked) const;
+  int scale(const int32_t *I, const double *R, double sigma) const;
+  int unscale() const;
+  int attempt(const int32_t *I, const double *R, int method, HostKrylov *res) const;
+  int retry(const int32_t *I, double sigma) const;
+  int finish_x() const;
+  int resid2(double *r2) const;
+  int fill_info(fx_solve_info *info) const;
 };
 
 #define VLAUNCH(kern, ...) hipLaunchKernelGGL(kern, dim3(vgrid), dim3(256), 0, c->stream, n3, __VA_ARGS__)
@@ -289,8 +302,3 @@ static int gpbicg_solve_t(const Ops &o, int MAXIT, double TOL, HostKrylov *out) 
   return 0;
 }
 #undef VLAUNCH
-
-static int gmres_solve(fx_context *c, int MAXIT, double TOL, int NREST, HostKrylov *out) {
-  return gmres_solve_t(Ops33{c}, MAXIT, TOL, NREST, out);
-}
-static int gpbicg_solve(fx_context *c, int MAXIT, double TOL, HostKrylov *out) { return gpbicg_solve_t(Ops33{c}, MAXIT, TOL, out); }

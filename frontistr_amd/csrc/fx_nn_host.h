@@ -6,7 +6,7 @@
 //   hecmw_precond_nn_apply     hecmw1/src/solver/precond/nn/hecmw_precond_nn.f90 (additive Schwarz loop over iterPREmax)
 //   hecmw_solve_CG / BiCGSTAB  hecmw1/src/solver/iterative/hecmw_solver_CG.f90:19-312, hecmw_solver_BiCGSTAB.f90:16-297
 //   hecmw_solve_GMRES / GPBiCG hecmw_solver_GMRES.f90:17-458, hecmw_solver_GPBiCG.f90:17-505 (fx_krylov2_host.h through OpsNN)
-//   hecmw_solve_iterative      hecmw1/src/solver/iterative/hecmw_solver_Iterative.f90:13-210 (checks, flags, final residual)
+//   hecmw_solve_iterative      hecmw1/src/solver/iterative/hecmw_solver_Iterative.f90:13-210 (the driver in fistr_hip.hip through OpsNN)
 //
 // Layout: the same sliced block-ELL idea as the 3x3 path -- one thread per block row, 64 rows per slice, slice width =
 // longest row of the slice -- with the NDOF*NDOF entries of a block stored entry-major across the 64 lanes
@@ -706,8 +706,6 @@ static int nn_precond_apply(fx_context *c, int iterpremax, const double *r, doub
 // iterations -- no host round trip per dot product (the first version synchronised 3-6 times per iteration, and so does
 // the reference: hecmw_InnerProduct_R, hecmw_solver_misc.f90:46-70).  Multi-rank: reduce -> in-stream all-reduce -> logic.
 // ---------------------------------------------------------------------------------------------------------------
-struct NnResult { int iter = 0, error = 0; double resid = 0.0; std::vector<double> hist; };
-
 __global__ __launch_bounds__(FX_BLOCK) void k_nn_cg_p(int64_t n, const KrylovState *__restrict__ st, const double *__restrict__ z,
                                                       double *__restrict__ p) {  // hecmw_solver_CG.f90:188-197
   if (st->status != 0) return;
@@ -734,14 +732,6 @@ __global__ __launch_bounds__(FX_BLOCK) void k_nn_cg_xr(int64_t n, const KrylovSt
   if (UPDATE_R) block_sum_store<1>(d, partials, 0);
 }
 
-static int nn_partials(fx_context *c) {  // the partial-sum buffer of the scalar stages (shared with the 3x3 path)
-  if (c->max_partials < 4096 + 8) {
-    dev_free(c->partials);
-    if (dev_alloc(&c->partials, (size_t)(4096 + 8) * 3)) return FX_ERROR_RUNTIME;
-    c->max_partials = 4096 + 8;
-  }
-  return 0;
-}
 static int nn_dot_parts(fx_context *c, const double *x, const double *y, const int32_t *gate, int32_t gate_val, int *np) {
   NnDev *n = nn_of(c);
   const int64_t len = (int64_t)n->ndof * n->nn_internal;  // hecmw_InnerProduct_R: NDOF * nn_internal entries
@@ -811,13 +801,13 @@ static int nn_bicgstab_iteration(fx_context *c, int it, int iterpremax) {  // he
 }
 
 // begin (r0, ||b||), then iterations enqueued in chunks with one poll of the device state per chunk
-static int nn_krylov(fx_context *c, int method, int MAXIT, double TOL, int iterpremax, NnResult *o) {
+static int nn_krylov(fx_context *c, int method, int MAXIT, double TOL, int iterpremax, HostKrylov *o) {
   NnDev *n = nn_of(c);
   const int64_t nlen = (int64_t)n->ndof * n->N;
   const size_t vbytes = (size_t)n->ndof * n->NP * 8;
   double *X = n->X, *B = n->B, *R = n->W[0];
   int np;
-  if (nn_partials(c) || krylov_init_state(c, MAXIT, TOL)) return FX_ERROR_RUNTIME;
+  if (ensure_partials(c) || krylov_init_state(c, MAXIT, TOL)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemsetAsync(n->W[2], 0, vbytes, c->stream));               // P (beta = 0 on the first iteration; keep it finite)
   if (method == 2) HIP_TRY(hipMemsetAsync(n->W[6], 0, vbytes, c->stream));  // V
   if (nn_spmv(c, 1, X, B, R)) return FX_ERROR_RUNTIME;                   // CG :120 / BiCGSTAB :107
@@ -830,7 +820,7 @@ static int nn_krylov(fx_context *c, int method, int MAXIT, double TOL, int iterp
   for (int it = 1; it <= MAXIT; it++) {
     if (method == 1 ? nn_cg_iteration(c, it, iterpremax) : nn_bicgstab_iteration(c, it, iterpremax)) return FX_ERROR_RUNTIME;
     if (it % chunk == 0 || it == MAXIT) {
-      if (int pe = poll_state(c, &s)) return pe;  // FX_DF_RETRY: a block ILU(0) dataflow sweep timed out (nn_solve redoes the attempt)
+      if (int pe = poll_state(c, &s)) return pe;  // FX_DF_RETRY: a block ILU(0) dataflow sweep timed out (OpsNN::attempt redoes it)
       if (s.status != 0) break;
     }
   }
@@ -842,8 +832,6 @@ static int nn_krylov(fx_context *c, int method, int MAXIT, double TOL, int iterp
   if (s.n_hist > 0) HIP_TRY(hipMemcpy(o->hist.data(), c->hist, (size_t)s.n_hist * 8, hipMemcpyDeviceToHost));
   return 0;
 }
-static int nn_cg(fx_context *c, int MAXIT, double TOL, int iterpremax, NnResult *o) { return nn_krylov(c, 1, MAXIT, TOL, iterpremax, o); }
-static int nn_bicgstab(fx_context *c, int MAXIT, double TOL, int iterpremax, NnResult *o) { return nn_krylov(c, 2, MAXIT, TOL, iterpremax, o); }
 
 static int nn_scale_bell(fx_context *c, NnBell &b, int back) {
   NnDev *n = nn_of(c);
@@ -877,7 +865,7 @@ static int nn_scaling(fx_context *c, int back) {
   return 0;
 }
 
-// GMRES(m) and GPBiCG of fx_krylov2_host.h on the generic-block system
+// The generic-block path of GMRES(m) / GPBiCG (fx_krylov2_host.h) and of hecmw_solve_iterative (fistr_hip.hip)
 struct OpsNN {
   fx_context *c;
   NnDev *n() const { return nn_of(c); }
@@ -903,155 +891,96 @@ struct OpsNN {
     HIP_TRY(hipMemsetAsync(d->extra, 0, (size_t)count * len * 8, c->stream));
     return 0;
   }
+
+  // hecmw_solve_iterative
+  // hecmw_precond_BILU_66_setup has no INITIALIZED test (BILU_66.f90:33-126, unlike BILU_44 / BILU_nn :49-57): at NDOF 6 the
+  // reference factors again on every set-up call, whatever the recycle flags say, and with the SIGMA_DIAG of the attempt
+  bool ilu66(const int32_t *I) const { return I[2] == 10 && n()->ndof == 6; }
+  int rhs_norm2(double *b2) const { return nn_dot(c, n()->B, n()->B, b2); }
+  int zero_x() const {
+    HIP_TRY(hipMemsetAsync(n()->X, 0, wbytes(), c->stream));
+    return 0;
+  }
+  void zero_diag(int32_t *flag) const {
+    NnDev *d = n();
+    if (d->N > 0)
+      hipLaunchKernelGGL(k_nn_check_zero_diag, dim3(((int64_t)d->N * d->ndof + 255) / 256), dim3(256), 0, c->stream, d->N, d->ndof,
+                         d->D, flag);
+  }
+  // With SCALING=YES every attempt sets up the preconditioner of the scaled matrix (scale()); block ILU(0) then skips the factor
+  // of the unscaled one here (PRECOND 1-3 keep their set-up: it also validates PRECOND before anything else runs)
+  int setup(const int32_t *I, const double *R, bool asked) const {
+    NnDev *d = n();
+    const int precond = I[2];
+    const double sigma = R[1] < 0.0 ? 1.0 : R[1];
+    if (I[4] <= 0 || (I[6] != 0 && precond == 10 && d->ndof >= 4)) return 0;
+    if (d->precond_valid && !asked && d->sigma == sigma && !ilu66(I) && d->precond_kind == nn_precond_kind(precond)) return 0;
+    return nn_precond_setup(c, precond, sigma, I[33]);
+  }
+  int scale(const int32_t *I, const double *R, double sigma) const {
+    if (nn_scaling(c, 0)) return FX_ERROR_RUNTIME;
+    if (I[4] <= 0) return 0;
+    // every attempt factors with the first SIGMA_DIAG (see the retry rule), BILU_66 with the attempt's
+    if (int e = nn_precond_setup(c, I[2], ilu66(I) ? sigma : (R[1] < 0.0 ? 1.0 : R[1]), I[33], true)) return e;
+    if (n()->precond_kind == 1 && (nn_scale_bell(c, n()->L, 0) || nn_scale_bell(c, n()->U, 0))) return FX_ERROR_RUNTIME;  // built from the caller's values
+    return 0;
+  }
+  int unscale() const {  // the preconditioner belonged to the scaled matrix
+    if (nn_scaling(c, 1)) return FX_ERROR_RUNTIME;
+    n()->precond_valid = false;
+    return 0;
+  }
+  int attempt(const int32_t *I, const double *R, int method, HostKrylov *res) const {
+    NnDev *d = n();
+    const int maxit = I[0], iterpremax = I[4];
+    const double tol = R[0];
+    d->iterpremax = iterpremax;
+    // a block ILU(0) dataflow sweep that times out leaves unusable iterates: the context switches to per-level launches and the
+    // attempt runs again from the X it started with
+    const bool df = iterpremax > 0 && d->precond_kind == 10 && c->df_mode >= 1;
+    if (df) {
+      if (!d->X0 && dev_alloc(&d->X0, (size_t)d->ndof * std::max(d->NP, 1))) return FX_ERROR_RUNTIME;
+      HIP_TRY(hipMemcpyAsync(d->X0, d->X, wbytes(), hipMemcpyDeviceToDevice, c->stream));
+    }
+    int e;
+    for (int redo = 0;; redo++) {
+      *res = HostKrylov();
+      if (method <= 2) {
+        e = nn_krylov(c, method, maxit, tol, iterpremax, res);
+      } else {
+        e = (method == 3) ? gmres_solve_t(*this, maxit, tol, I[5], res) : gpbicg_solve_t(*this, maxit, tol, res);
+        if (df && nn_df_take_error(c)) e = FX_DF_RETRY;  // asked before e: tag values in the vectors cause breakdown codes
+      }
+      if (e != FX_DF_RETRY || !df || redo > 0) break;
+      if (method <= 2) d->ilu_df_fallbacks++;  // poll_state has switched the context already
+      HIP_TRY(hipMemcpyAsync(d->X, d->X0, wbytes(), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return e == FX_DF_RETRY ? FX_ERROR_RUNTIME : e;
+  }
+  int retry(const int32_t *I, double sigma) const {  // BILU_66 factors with the new SIGMA_DIAG (under SCALING, scale() does)
+    return (ilu66(I) && I[6] == 0 && nn_precond_setup(c, I[2], sigma, I[33])) ? FX_ERROR_RUNTIME : 0;
+  }
+  int finish_x() const { return nn_halo(c, n()->X); }
+  int resid2(double *r2) const { return (nn_spmv(c, 1, n()->X, n()->B, n()->W[7]) || nn_dot(c, n()->W[7], n()->W[7], r2)) ? FX_ERROR_RUNTIME : 0; }
+  int fill_info(fx_solve_info *info) const {
+    info->ncolor = n()->precond_kind == 1 ? n()->ncolor : 0;
+    return 0;
+  }
 };
 
-// hecmw_solve for NDOF != 3: host arrays in, host X out (fx_solve forwards here)
+// hecmw_solve for NDOF != 3: host arrays in (fx_solve forwards here, and hands X back)
 static int nn_solve(fx_context *c, const fx_matrix_view *m, const fx_comm_view *cm, int32_t *Iarray, double *Rarray,
                     fx_solve_info *info, double *hist, int32_t hist_len) {
   HIP_TRY(hipSetDevice(c->device));
   if (m->NDOF < 1 || m->NDOF > 6) { g_fx_error = "NDOF must be 1..6"; return FX_ERROR_UNSUPPORTED; }
   c->view_petot = cm ? std::max(1, (int)cm->PETOT) : 1;
   if (require_transport(c, "fx_solve")) return FX_ERROR_RUNTIME;
-  const int maxit = Iarray[0], precond = Iarray[2], method2 = Iarray[7], iterpremax = Iarray[4];
-  int method = Iarray[1];
-  const bool scaling = Iarray[6] != 0;  // SCALING=YES
-  const double t0 = now_s();
-  NnDev *n0 = nn_of(c);
-  const bool values_changed = Iarray[97] >= 1 || Iarray[96] >= 1 || !n0->have_matrix ||
-                              m->D != c->host_D || m->AL != c->host_AL || m->AU != c->host_AU;  // see fx_solve
-  if (nn_upload(c, m, cm, values_changed)) return FX_ERROR_RUNTIME;
-  if (values_changed) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
+  const bool changed = values_changed(c, m, Iarray, nn_of(c)->have_matrix);
+  if (nn_upload(c, m, cm, changed)) return FX_ERROR_RUNTIME;
+  if (changed) { c->host_D = m->D; c->host_AL = m->AL; c->host_AU = m->AU; }
   NnDev *n = nn_of(c);
   n->cur_AL = m->AL; n->cur_AU = m->AU;  // the sweep layouts of a preconditioner (re)built in this call are gathered from these
-  const int nd = n->ndof;
-  int ret = 0;
-  double rhs2 = 0.0;
-  if (nn_dot(c, n->B, n->B, &rhs2)) return FX_ERROR_RUNTIME;  // hecmw_solve_check_zerorhs (:242-278)
-  if (rhs2 == 0.0) { ret = FX_ERROR_ZERO_RHS; HIP_TRY(hipMemsetAsync(n->X, 0, (size_t)nd * n->NP * 8, c->stream)); }
-  {  // hecmw_solve_check_zerodiag (:212-240)
-    int32_t *flag = (int32_t *)(n->scal + 4), hflag = 0;
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
-    if (n->N > 0)
-      hipLaunchKernelGGL(k_nn_check_zero_diag, dim3(((int64_t)n->N * nd + 255) / 256), dim3(256), 0, c->stream, n->N, nd, n->D, flag);
-    HIP_TRY(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (multi_rank(c)) {
-      double f = hflag ? 1.0 : 0.0;
-      HIP_TRY(hipMemcpyAsync(n->scal + 2, &f, 8, hipMemcpyHostToDevice, c->stream));
-      if (allreduce_dev(c, n->scal + 2, 1)) return FX_ERROR_RUNTIME;
-      HIP_TRY(hipMemcpyAsync(&f, n->scal + 2, 8, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      hflag = f > 0.0;
-    }
-    if (hflag && precond < 10 && iterpremax > 0) return FX_ERROR_ZERO_DIAG;
-  }
-  // hecmw_mat_recycle_precond_setting (hecmw_matrix_misc.f90:678-697)
-  if (Iarray[97] >= 1) { Iarray[96] = 1; Iarray[95] = 0; }
-  else if (Iarray[96] > 1) { Iarray[95] = 0; Iarray[96] = 1; }
-  else if (Iarray[96] == 1) {
-    if (Iarray[95] < Iarray[34]) { Iarray[96] = 0; Iarray[95]++; }
-    else Iarray[95] = 0;
-  }
-  const bool auto_sigma = Rarray[1] < 0.0;  // hecmw_solver_Iterative.f90:68-73
-  const double sigma = auto_sigma ? 1.0 : Rarray[1];  // the factors of every attempt (see the retry below)
-  double sigma_attempt = sigma;
-  // with SCALING=YES every attempt sets up the preconditioner of the scaled matrix; block ILU(0) then skips the factor of the
-  // unscaled one here (PRECOND 1-3 keep their set-up: it also validates PRECOND before anything else runs)
-  // hecmw_precond_BILU_66_setup has no INITIALIZED test (BILU_66.f90:33-126, unlike BILU_44 / BILU_nn :49-57): at NDOF 6 the
-  // reference factors again on every set-up call, whatever the recycle flags say, and with the SIGMA_DIAG of the attempt
-  const bool ilu66 = precond == 10 && nd == 6;
-  if (iterpremax > 0 && (!n->precond_valid || Iarray[97] == 1 || Iarray[96] == 1 || n->sigma != sigma || ilu66 ||
-                         n->precond_kind != nn_precond_kind(precond)) && !(scaling && precond == 10 && nd >= 4)) {
-    if (int e = nn_precond_setup(c, precond, sigma, Iarray[33])) return e;
-  }
-  Iarray[97] = 0; Iarray[96] = 0;
-  const double t_setup = now_s() - t0, t1 = now_s();
-  NnResult res;
-  c->attempts.clear();
-  for (;;) {
-    Iarray[80] = 0; Iarray[81] = 0;
-    res = NnResult();
-    int e;
-    n->iterpremax = iterpremax;
-    if (scaling) {  // scale, then build the preconditioner of the scaled matrix (hecmw_solver_CG.f90:104-112)
-      if (nn_scaling(c, 0)) return FX_ERROR_RUNTIME;
-      if (iterpremax > 0) {
-        if (int pe = nn_precond_setup(c, precond, ilu66 ? sigma_attempt : sigma, Iarray[33], true)) return pe;
-        if (n->precond_kind == 1 && (nn_scale_bell(c, n->L, 0) || nn_scale_bell(c, n->U, 0))) return FX_ERROR_RUNTIME;  // built from the caller's values
-      }
-    }
-    if (method < 1 || method > 4) { g_fx_error = "METHOD must be 1 (CG), 2 (BiCGSTAB), 3 (GMRES) or 4 (GPBiCG)"; return FX_ERROR_INCONS_PC; }
-    // a block ILU(0) dataflow sweep that times out leaves unusable iterates: the context switches to per-level launches and the
-    // attempt runs again from the X it started with
-    const bool df = iterpremax > 0 && n->precond_kind == 10 && c->df_mode >= 1;
-    if (df) {
-      if (!n->X0 && dev_alloc(&n->X0, (size_t)nd * std::max(n->NP, 1))) return FX_ERROR_RUNTIME;
-      HIP_TRY(hipMemcpyAsync(n->X0, n->X, (size_t)nd * n->NP * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    for (int df_try = 0;; df_try++) {
-      res = NnResult();
-      if (method == 1) e = nn_cg(c, maxit, Rarray[0], iterpremax, &res);
-      else if (method == 2) e = nn_bicgstab(c, maxit, Rarray[0], iterpremax, &res);
-      else {
-        HostKrylov hk;
-        e = (method == 3) ? gmres_solve_t(OpsNN{c}, maxit, Rarray[0], Iarray[5], &hk) : gpbicg_solve_t(OpsNN{c}, maxit, Rarray[0], &hk);
-        res.iter = hk.iter; res.resid = hk.resid; res.error = hk.error; res.hist = hk.hist;
-        if (df && nn_df_take_error(c)) e = FX_DF_RETRY;  // asked before e: tag values in the vectors cause breakdown codes
-      } 
-      if (e == FX_DF_RETRY && df && df_try == 0) {
-        if (method <= 2) n->ilu_df_fallbacks++;  // poll_state has switched the context already
-        HIP_TRY(hipMemcpyAsync(n->X, n->X0, (size_t)nd * n->NP * 8, hipMemcpyDeviceToDevice, c->stream));
-        continue;
-      }
-      break;
-    }
-    if (e) return e == FX_DF_RETRY ? FX_ERROR_RUNTIME : e;
-    c->attempts.emplace_back();
-    c->attempts.back().method = method;
-    c->attempts.back().sigma_diag = sigma_attempt;
-    c->attempts.back().hist = res.hist;
-    if (scaling) {  // x and b back, matrix restored (hecmw_solver_CG.f90:277); the preconditioner belonged to the scaled matrix
-      if (nn_scaling(c, 1)) return FX_ERROR_RUNTIME;
-      n->precond_valid = false;
-    }
-    if (res.error == FX_ERROR_DIVERGE_PC || res.error == FX_ERROR_DIVERGE_MAT) {  // Iterative.f90:145-156
-      Iarray[81] = 1;
-      // The ILU family's 'Increasing SIGMA_DIAG' retry, as the 3x3 path runs it: the reference's set-up returns early on a retry
-      // (hecmw_precond_BILU_nn.f90:49-57, the flags are already cleared), so every attempt keeps the FIRST SIGMA_DIAG's factors
-      // (NDOF 4, 5; BILU_66 factors again with the attempt's SIGMA_DIAG)
-      // and restarts from the X the failed attempt left.  `sigma_attempt` only decides how many retries there are.
-      if (precond >= 10 && precond < 20 && auto_sigma && sigma_attempt < 2.0) {
-        sigma_attempt += (double)0.1f;  // `SIGMA_DIAG = SIGMA_DIAG + 0.1` with a default-real literal (:147)
-        if (ilu66 && !scaling && nn_precond_setup(c, precond, sigma_attempt, Iarray[33])) return FX_ERROR_RUNTIME;  // BILU_66: see above
-        continue;
-      } else if (method == 1 && method2 > 1) {
-        if (auto_sigma) sigma_attempt = 1.0;  // :152
-        if (ilu66 && !scaling && nn_precond_setup(c, precond, sigma_attempt, Iarray[33])) return FX_ERROR_RUNTIME;
-        method = method2;
-        continue;
-      }
-    }
-    break;
-  }
-  if (nn_halo(c, n->X)) return FX_ERROR_RUNTIME;  // hecmw_update_m_R (hecmw_solver_CG.f90:280)
-  if (res.error > 1) ret = res.error;
-  // hecmw_rel_resid_L2 (hecmw_solver_las.f90:129-158)
-  double r2 = 0.0, b2 = rhs2 == 0.0 ? 1.0 : rhs2;
-  if (nn_spmv(c, 1, n->X, n->B, n->W[7]) || nn_dot(c, n->W[7], n->W[7], &r2)) return FX_ERROR_RUNTIME;
-  const double resid2 = sqrt(r2 / b2);
-  if (resid2 < Rarray[0]) Iarray[80] = 1;
-  HIP_TRY(hipMemcpy(m->X, n->X, (size_t)nd * n->NP * 8, hipMemcpyDeviceToHost));
-  const int nh = std::max(0, std::min((int)hist_len, (int)res.hist.size()));
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->iterations = res.iter; info->method = method; info->precond = precond;
-    info->ncolor = n->precond_kind == 1 ? n->ncolor : 0;
-    info->resid = res.resid; info->rel_resid = resid2;
-    info->time_setup = t_setup; info->time_sol = now_s() - t1;
-    info->n_hist = hist ? nh : 0;
-  }
-  if (hist && nh > 0) memcpy(hist, res.hist.data(), (size_t)nh * 8);
-  return ret;
+  return hecmw_solve_iterative(OpsNN{c}, Iarray, Rarray, info, hist, hist_len);
 }
 
 // hecmw_matvec for NDOF != 3: Y(1:NDOF*N) = A X, the halo part of X is updated
