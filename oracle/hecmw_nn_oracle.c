@@ -4,6 +4,8 @@
  *   hecmw_matvec_nn_inner        hecmw1/src/solver/las/hecmw_solver_las_nn.f90:135-310
  *   hecmw_precond_DIAG_nn_*      hecmw1/src/solver/precond/nn/hecmw_precond_DIAG_nn.f90:27-137
  *   hecmw_precond_SSOR_nn_*      hecmw1/src/solver/precond/nn/hecmw_precond_SSOR_nn.f90:55-213 (setup), :215-420 (apply)
+ *   FORM_ILU0_nn / BILU_nn_apply hecmw1/src/solver/precond/nn/hecmw_precond_BILU_nn.f90:196-333, :90-168 (NDOF = 5; the
+ *                                unrolled FORM_ILU0_44 / _66 and BILU_44 / _66 apply of precond/44, precond/66 for 4 and 6)
  * The reference dispatches NDOF = 1, 2, 4, 6 to hand-unrolled copies (las_11/22/44/66, precond/11/22/44/66) of the
  * same loops -- same LU without pivoting, same sweep order -- so one restatement covers them to rounding; the parity
  * tests pin it against the real reference for NDOF = 1, 2, 4, 5 (the true _nn path) and 6.
@@ -171,5 +173,96 @@ static void ssor_nn_apply(const orc_precond *P, double *ZP) {
       const int32_t iold = F1(P->perm, i);
       for (int d = 0; d < nd; d++) ZP[(size_t)nd * (iold - 1) + d] -= SW[d];
     }
+  }
+}
+
+/* ILU1bNN (BILU_nn.f90:1539-1567 == ILU1b44 / ILU1b66): RHS = Aik * DkINV^-1 * Akj, column by column.  The unrolled copies start
+ * each sum with its first product (ILU1b66 :2222), the generic one with 0.0 + it: the same value, so the unrolled form is kept. */
+static void ilu1b_nn(int nd, double *RHS, const double *DkINV, const double *Aik, const double *Akj) {
+  double X[16];
+  for (int c = 0; c < nd; c++) {
+    for (int r = 0; r < nd; r++) X[r] = Akj[r * nd + c];
+    lusolve_nn(nd, DkINV, X);
+    for (int r = 0; r < nd; r++) {
+      double s = Aik[r * nd] * X[0];
+      for (int q = 1; q < nd; q++) s = s + Aik[r * nd + q] * X[q];
+      RHS[r * nd + c] = s;
+    }
+  }
+}
+
+/* FORM_ILU0_nn, BILU_nn.f90:196-333.  Rows 2..NP in natural order; the LU of the diagonal block of row i (ILU1aNN == lu_nn)
+ * is taken in place once its updates are done.  FORM_ILU0_66 keeps Dlu0 unfactored and takes ILU1a66 of D_k again for every
+ * use and of every row at the end (BILU_66.f90:65-123): the same LU of the same block, so the same bits.  As in the 3x3
+ * restatement only the touched entries of IW1 / IW2 are reset.  Halo columns of U are updated like any other and later
+ * multiply ZP(halo) = 0 in the apply; halo rows are factored too (nothing of rows 1..N depends on them). */
+static void ilu0_nn_setup(orc_precond *P, const orc_matrix *A, double SIGMA_DIAG) {
+  const int nd = P->ndof;
+  const size_t nd2 = (size_t)nd * nd;
+  const int32_t NP = A->NP, NPL = A->indexL[NP], NPU = A->indexU[NP];
+  const int32_t *INL = A->indexL, *INU = A->indexU, *IAL = A->itemL, *IAU = A->itemU;
+  P->Dlu0 = (double *)malloc(nd2 * ((size_t)NP + 1) * sizeof(double));
+  P->ALlu0 = (double *)malloc(nd2 * ((size_t)NPL + 1) * sizeof(double));
+  P->AUlu0 = (double *)malloc(nd2 * ((size_t)NPU + 1) * sizeof(double));
+  memcpy(P->Dlu0, A->D, nd2 * NP * sizeof(double));
+  memcpy(P->ALlu0, A->AL, nd2 * NPL * sizeof(double));
+  memcpy(P->AUlu0, A->AU, nd2 * NPU * sizeof(double));
+  P->inumFI1L = INL; P->inumFI1U = INU; P->FI1L = IAL; P->FI1U = IAU;
+  double *Dlu0 = P->Dlu0, *ALlu0 = P->ALlu0, *AUlu0 = P->AUlu0;
+  int32_t *IW1 = (int32_t *)calloc((size_t)NP + 1, sizeof(int32_t));
+  int32_t *IW2 = (int32_t *)calloc((size_t)NP + 1, sizeof(int32_t));
+  for (int32_t i = 0; i < NP; i++)
+    for (int d = 0; d < nd; d++) Dlu0[nd2 * i + (size_t)(nd + 1) * d] *= SIGMA_DIAG; /* :245-249 */
+  if (NP > 0) lu_nn(nd, &Dlu0[0], 1.0); /* i = 1, :251-257 */
+  for (int32_t i = 2; i <= NP; i++) {
+    for (int32_t k = INL[i - 1] + 1; k <= INL[i]; k++) IW1[F1(IAL, k)] = k;
+    for (int32_t k = INU[i - 1] + 1; k <= INU[i]; k++) IW2[F1(IAU, k)] = k;
+    for (int32_t kk = INL[i - 1] + 1; kk <= INL[i]; kk++) {
+      const int32_t k = F1(IAL, kk);
+      const double *DkINV = &Dlu0[nd2 * (k - 1)];
+      double Aik[36], RHS[36];
+      memcpy(Aik, &ALlu0[nd2 * (kk - 1)], nd2 * sizeof(double));
+      for (int32_t jj = INU[k - 1] + 1; jj <= INU[k]; jj++) {
+        const int32_t j = F1(IAU, jj);
+        if (IW1[j] == 0 && IW2[j] == 0) continue; /* j == i is never listed: the diagonal update below is dead, as in the 3x3 */
+        ilu1b_nn(nd, RHS, DkINV, Aik, &AUlu0[nd2 * (jj - 1)]);
+        double *dst = j == i ? &Dlu0[nd2 * (i - 1)] : j < i ? &ALlu0[nd2 * (IW1[j] - 1)] : &AUlu0[nd2 * (IW2[j] - 1)];
+        for (size_t q = 0; q < nd2; q++) dst[q] = dst[q] - RHS[q];
+      }
+    }
+    lu_nn(nd, &Dlu0[nd2 * (i - 1)], 1.0);
+    for (int32_t k = INL[i - 1] + 1; k <= INL[i]; k++) IW1[F1(IAL, k)] = 0;
+    for (int32_t k = INU[i - 1] + 1; k <= INU[i]; k++) IW2[F1(IAU, k)] = 0;
+  }
+  free(IW1); free(IW2);
+}
+
+/* hecmw_precond_BILU_nn_apply, BILU_nn.f90:90-168 (== BILU_44 / _66 apply): rows 1..N, forward ascending with L in stored
+ * order, backward descending with U in reverse stored order */
+static void ilu_nn_apply(const orc_precond *P, double *WW) {
+  const int nd = P->ndof;
+  const size_t nd2 = (size_t)nd * nd;
+  double SW[16], X[16];
+  for (int32_t i = 1; i <= P->N; i++) {
+    for (int d = 0; d < nd; d++) SW[d] = WW[(size_t)nd * (i - 1) + d];
+    for (int32_t j = P->inumFI1L[i - 1] + 1; j <= P->inumFI1L[i]; j++) {
+      const int32_t k = F1(P->FI1L, j);
+      for (int d = 0; d < nd; d++) X[d] = WW[(size_t)nd * (k - 1) + d];
+      for (int d = 0; d < nd; d++)
+        for (int e = 0; e < nd; e++) SW[d] = SW[d] - P->ALlu0[nd2 * (j - 1) + nd * d + e] * X[e];
+    }
+    lusolve_nn(nd, &P->Dlu0[nd2 * (i - 1)], SW);
+    for (int d = 0; d < nd; d++) WW[(size_t)nd * (i - 1) + d] = SW[d];
+  }
+  for (int32_t i = P->N; i >= 1; i--) {
+    for (int d = 0; d < nd; d++) SW[d] = 0.0;
+    for (int32_t j = P->inumFI1U[i]; j >= P->inumFI1U[i - 1] + 1; j--) {
+      const int32_t k = F1(P->FI1U, j);
+      for (int d = 0; d < nd; d++) X[d] = WW[(size_t)nd * (k - 1) + d];
+      for (int d = 0; d < nd; d++)
+        for (int e = 0; e < nd; e++) SW[d] = SW[d] + P->AUlu0[nd2 * (j - 1) + nd * d + e] * X[e];
+    }
+    lusolve_nn(nd, &P->Dlu0[nd2 * (i - 1)], SW);
+    for (int d = 0; d < nd; d++) WW[(size_t)nd * (i - 1) + d] -= SW[d];
   }
 }

@@ -544,7 +544,7 @@ static void ilu_apply(const orc_precond *P, double *WW) {
 }
 
 /* hecmw_precond_33_setup dispatch, 33/hecmw_precond_33.f90:27-50 */
-#include "hecmw_nn_oracle.c" /* NDOF != 3: matvec, DIAG, SSOR */
+#include "hecmw_nn_oracle.c" /* NDOF != 3: matvec, DIAG, SSOR, block ILU(0) */
 
 orc_precond *orc_precond_setup(const orc_matrix *A, int precond, double sigma_diag, int ncolor_in,
                                int nthreads) {
@@ -554,7 +554,10 @@ orc_precond *orc_precond_setup(const orc_matrix *A, int precond, double sigma_di
     switch (precond) {
       case 1: case 2: P->kind = 1; ssor_nn_setup(P, A, sigma_diag, ncolor_in, nthreads); return P;
       case 3: P->kind = 3; diag_nn_setup(P, A, sigma_diag); return P;
-      default: free(P); return NULL; /* block ILU of the other sizes is not restated */
+      case 10:
+        if (P->ndof >= 4 && P->ndof <= 6) { P->kind = 10; ilu0_nn_setup(P, A, sigma_diag); return P; }
+        free(P); return NULL; /* block ILU(0) of NDOF 1 and 2 is not restated */
+      default: free(P); return NULL;
     }
   }
   switch (precond) {
@@ -594,7 +597,7 @@ void orc_precond_apply(const orc_matrix *A, const orc_comm *c, orc_precond *P, i
     switch (P->kind) {
       case 1: if (P->ndof != 3) ssor_nn_apply(P, ZP); else ssor_apply(P, ZP); break;
       case 3: if (P->ndof != 3) diag_nn_apply(P, ZP); else diag_apply(P, ZP); break;
-      case 10: ilu_apply(P, ZP); break;
+      case 10: if (P->ndof != 3) ilu_nn_apply(P, ZP); else ilu_apply(P, ZP); break;
     }
     for (int32_t i = 0; i < NNDOF; i++) Z[i] = Z[i] + ZP[i]; /* additive Schwarz */
     if (iterPRE == iterPREmax) break;
@@ -845,7 +848,10 @@ int orc_solve_iterative(const orc_matrix *A, const orc_comm *c, const double *B,
     orc_precond *P = NULL;
     if (iterPREmax > 0) {
       if (g_persist) { /* the module-level `save` state of the reference's preconditioners: rebuilt only when the flags ask */
-        if (!g_P || F1(Iarray, 98) == 1 || F1(Iarray, 97) == 1) {
+        /* hecmw_precond_BILU_66_setup (precond/66/hecmw_precond_BILU_66.f90:33-126) keeps no INITIALIZED state: it factors
+         * again on every call, whatever the flags say */
+        const int refactor66 = nd == 6 && PRECOND >= 10 && PRECOND <= 12;
+        if (!g_P || F1(Iarray, 98) == 1 || F1(Iarray, 97) == 1 || refactor66) {
           orc_precond_free(g_P);
           g_P = orc_precond_setup(A, PRECOND, SIGMA_DIAG, NCOLOR_IN, nthreads);
         }

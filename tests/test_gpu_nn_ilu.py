@@ -6,7 +6,7 @@ import pytest
 
 import nn_ilu_ref
 from conftest import load_golden
-from nn_cases import dense, nn_system
+from nn_cases import dense, nn_system, wide_system
 
 pytestmark = pytest.mark.gpu
 
@@ -16,30 +16,6 @@ def to_hip(hip, A, meth=1, pc=10):
                                        NDOF=A.NDOF)
     m.Iarray[0], m.Iarray[1], m.Iarray[2] = 10000, meth, pc
     return m
-
-
-def wide_system(nd, n=160, seed=3):
-    """Random symmetric block profile with some rows of more than 32 blocks (the one-thread-per-row factor kernel)."""
-    from oracle.refrun import BSR
-    rng = np.random.default_rng(seed)
-    low = [set() for _ in range(n)]
-    for i in range(n):
-        for j in rng.choice(n, size=40 if i % 11 == 0 else 5, replace=False):
-            if j != i:
-                low[max(i, j)].add(min(i, j))
-    up = [set() for _ in range(n)]
-    for i in range(n):
-        for j in low[i]:
-            up[j].add(i)
-    itemL = np.array([j + 1 for i in range(n) for j in sorted(low[i])], dtype=np.int32)
-    itemU = np.array([j + 1 for i in range(n) for j in sorted(up[i])], dtype=np.int32)
-    indexL = np.r_[0, np.cumsum([len(s) for s in low])].astype(np.int32)
-    indexU = np.r_[0, np.cumsum([len(s) for s in up])].astype(np.int32)
-    blk = {(i, j): 0.1 * rng.standard_normal((nd, nd)) for i in range(n) for j in low[i]}
-    AL = np.array([blk[(i, j)] for i in range(n) for j in sorted(low[i])])
-    AU = np.array([blk[(j, i)].T for i in range(n) for j in sorted(up[i])])
-    D = np.array([rng.standard_normal((nd, nd)) * 0.1 + (2 + 0.1 * len(low[i]) + 0.1 * len(up[i])) * np.eye(nd) for i in range(n)])
-    return BSR(n, n, indexL, itemL, indexU, itemU, D.ravel(), AL.ravel(), AU.ravel(), rng.standard_normal(nd * n), NDOF=nd)
 
 
 def expected_z(A, k=0):

@@ -5,61 +5,9 @@ GPU against the CPU oracle for the 3x3 path (all preconditioners) and the generi
 import numpy as np
 import pytest
 
+from nn_cases import random_system
+
 pytestmark = pytest.mark.gpu
-
-
-def random_system(nd, N, n_halo, seed, hub=True):
-    """hub: True = one hub row of up to 60 off-diagonal blocks; a sequence of sizes = one hub row per entry."""
-    from oracle.refrun import BSR
-    rng = np.random.default_rng(seed)
-    NP = N + n_halo
-    edges = set()
-    live = np.arange(N)
-    iso = set(rng.choice(N, 5, replace=False).tolist())
-    live = np.array([i for i in live if i not in iso])
-    for _ in range(3 * N):
-        i, j = rng.choice(live, 2, replace=False)
-        edges.add((min(i, j), max(i, j)))
-    sizes = (60,) if hub is True else tuple(hub or ())
-    for k, size in enumerate(sizes):
-        h = int(live[(k + 1) * len(live) // (len(sizes) + 1)])
-        for j in rng.choice(live, min(size, len(live) - 1), replace=False):
-            if j != h:
-                edges.add((min(h, int(j)), max(h, int(j))))
-    for k in range(n_halo):                     # each halo node hangs on two internal rows
-        for i in rng.choice(live, 2, replace=False):
-            edges.add((int(i), N + k))
-    low = [[] for _ in range(NP)]
-    up = [[] for _ in range(NP)]
-    for i, j in edges:
-        up[i].append(j)
-        if j < N:
-            low[j].append(i)
-    indexL, indexU = np.zeros(NP + 1, dtype=np.int32), np.zeros(NP + 1, dtype=np.int32)
-    itemL, itemU = [], []
-    for i in range(NP):
-        low[i].sort(); up[i].sort()
-        itemL += [c + 1 for c in low[i]]
-        itemU += [c + 1 for c in up[i]]
-        indexL[i + 1], indexU[i + 1] = len(itemL), len(itemU)
-    posL = {(i, c): indexL[i] + k for i in range(NP) for k, c in enumerate(low[i])}
-    posU = {(i, c): indexU[i] + k for i in range(NP) for k, c in enumerate(up[i])}
-    D = np.tile(0.05 * np.eye(nd), (NP, 1, 1))
-    AL = np.zeros((max(len(itemL), 1), nd, nd))
-    AU = np.zeros((max(len(itemU), 1), nd, nd))
-    for i, j in sorted(edges):
-        G = rng.standard_normal((nd, nd))
-        P = G @ G.T / nd + 0.1 * np.eye(nd)
-        D[i] += P
-        AU[posU[(i, j)]] = -P
-        if j < N:
-            D[j] += P
-            AL[posL[(j, i)]] = -P
-    B = rng.standard_normal(nd * NP)
-    B[nd * N:] = 0.0
-    A = BSR(N, NP, indexL, np.array(itemL, dtype=np.int32), indexU, np.array(itemU, dtype=np.int32), D.ravel(),
-            AL[:len(itemL)].ravel(), AU[:len(itemU)].ravel(), B, NDOF=nd)
-    return A
 
 
 def to_hip(hip, A):

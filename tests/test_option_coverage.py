@@ -11,14 +11,14 @@ EXEMPT = {
     "FX_ARENA_TRIES": "value arena verification: test_arena_walk_keeps_the_answers_bit_identical",
     "FX_ARENA_MAX_MB": "value arena cap: test_value_arena_places_reuses_and_falls_back",
     "FX_ARENA_THRESHOLD_MB": "value arena threshold: test_arena_walk_keeps_the_answers_bit_identical",
-    "FX_BFS_DEVICE_MIN": "device level ordering: test_device_level_ordering_*",
+    "FX_BFS_DEVICE_MIN": "device level ordering: test_device_level_ordering_*, test_gpu_nn_shapes.py::test_device_ordering_equals_host_ordering",
     "FX_BFS_BATCH": "device level ordering: test_device_level_ordering_disconnected_graph_takes_host_walk",
-    "FX_MC_DEVICE_MIN": "device multicolouring: test_device_level_ordering_*",
+    "FX_MC_DEVICE_MIN": "device multicolouring: test_device_level_ordering_*, test_gpu_nn_shapes.py::test_device_ordering_equals_host_ordering",
     "FX_MC_BATCH": "device multicolouring: test_device_level_ordering_equals_host_ordering",
     "FX_VAL2_POW2": "allocation size of value arrays of 1 GiB or more outside the arena: placement only, no kernel or data change",
     "FX_GRAPH": "graph capture of the Krylov loop: test_graph_replay_is_bit_identical",
     "FX_OVERLAP": "halo exchange overlap of decomposed systems: test_gpu_distributed",
-    "FX_DF_GRID": "dataflow grid clamp: test_dataflow_grid_is_clamped_to_the_co_resident_bound, test_dataflow_sweeps_equal_launch_per_level_sweeps_bitwise",
+    "FX_DF_GRID": "dataflow grid clamp: test_dataflow_grid_is_clamped_to_the_co_resident_bound, test_dataflow_sweeps_equal_launch_per_level_sweeps_bitwise, test_gpu_nn_shapes.py::test_ilu_sweep_forms_bitwise",
     "FX_MARCH": "plane march: test_march_*",
     "FX_MARCH_CHUNK": "plane march: test_march_*",
     "FX_MARCH_WAVES": "plane march: test_march_*",
