@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "fx_assemble.h"
+#include "fx_assemble_tet.h"
 #include "fx_kernels.h"
 #include "fx_nonlinear.h"
 

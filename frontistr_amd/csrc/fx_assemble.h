@@ -95,15 +95,18 @@ __device__ __forceinline__ int32_t item_search(const int32_t *item, int32_t lo, 
 }
 
 // Position of every (row node a, column node b) block of every element in AL / AU, found once per (profile, mesh) so that the
-// assembly kernels do not repeat 56 binary searches per element in every Newton iteration: pos[64 * elem + 8 * a + b]
-// (-1: not in the profile; the diagonal entries a == b are unused).
+// assembly kernels do not repeat the binary searches per element in every Newton iteration: pos[NN^2 * elem + NN * a + b]
+// (-1: not in the profile; the diagonal entries a == b are unused).  NN nodes per element: 8 (361), 4 (341), 10 (342); thread t
+// handles block (a, b) of element elem, t = NN^2 elem + NN a + b (NN = 8: the shifts the hexahedron's kernels always had).
+template <int NN>
 __global__ void k_scatter_map(int32_t n_elem, const int32_t *__restrict__ conn, const int32_t *__restrict__ indexL,
                               const int32_t *__restrict__ itemL, const int32_t *__restrict__ indexU,
                               const int32_t *__restrict__ itemU, int32_t *__restrict__ pos) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)64 * n_elem) return;
-  const int32_t elem = (int32_t)(t >> 6), a = (int)(t >> 3) & 7, b = (int)t & 7;
-  const int32_t inod = conn[(size_t)8 * elem + a], jnod = conn[(size_t)8 * elem + b];
+  if (t >= (int64_t)(NN * NN) * n_elem) return;
+  const int32_t elem = NN == 8 ? (int32_t)(t >> 6) : (int32_t)(t / (NN * NN)), a = NN == 8 ? (int)(t >> 3) & 7 : (int)(t / NN % NN),
+                b = NN == 8 ? (int)t & 7 : (int)(t % NN);
+  const int32_t inod = conn[(size_t)NN * elem + a], jnod = conn[(size_t)NN * elem + b];
   int32_t k = 0;
   if (jnod < inod) k = item_search(itemL, indexL[inod - 1], indexL[inod], jnod);
   else if (jnod > inod) k = item_search(itemU, indexU[inod - 1], indexU[inod], jnod);
@@ -116,25 +119,29 @@ __global__ void k_scatter_map(int32_t n_elem, const int32_t *__restrict__ conn, 
 // 30 of the contribution's map entry (the diagonal's otherwise unused entry too) says "this one is the first".
 #define FXA_FIRST_BIT 0x40000000
 #define FXA_NO_COLOR 0x7F7F7F7F  // what hipMemset(0x7F) leaves: above every colour
+template <int NN>
 __global__ void k_scatter_first_min(int32_t n_elem, const int32_t *__restrict__ conn, const int32_t *__restrict__ pos,
                                     const int32_t *__restrict__ elem_color, int32_t *__restrict__ minD, int32_t *__restrict__ minL,
                                     int32_t *__restrict__ minU) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)64 * n_elem) return;
-  const int32_t elem = (int32_t)(t >> 6), a = (int)(t >> 3) & 7, b = (int)t & 7;
-  const int32_t inod = conn[(size_t)8 * elem + a], jnod = conn[(size_t)8 * elem + b], k = pos[t], col = elem_color[elem];
+  if (t >= (int64_t)(NN * NN) * n_elem) return;
+  const int32_t elem = NN == 8 ? (int32_t)(t >> 6) : (int32_t)(t / (NN * NN)), a = NN == 8 ? (int)(t >> 3) & 7 : (int)(t / NN % NN),
+                b = NN == 8 ? (int)t & 7 : (int)(t % NN);
+  const int32_t inod = conn[(size_t)NN * elem + a], jnod = conn[(size_t)NN * elem + b], k = pos[t], col = elem_color[elem];
   if (k < 0) return;
   if (inod == jnod) atomicMin(minD + (inod - 1), col);
   else if (jnod < inod) atomicMin(minL + k, col);
   else atomicMin(minU + k, col);
 }
+template <int NN>
 __global__ void k_scatter_first_flag(int32_t n_elem, const int32_t *__restrict__ conn, int32_t *__restrict__ pos,
                                      const int32_t *__restrict__ elem_color, const int32_t *__restrict__ minD,
                                      const int32_t *__restrict__ minL, const int32_t *__restrict__ minU) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)64 * n_elem) return;
-  const int32_t elem = (int32_t)(t >> 6), a = (int)(t >> 3) & 7, b = (int)t & 7;
-  const int32_t inod = conn[(size_t)8 * elem + a], jnod = conn[(size_t)8 * elem + b], k = pos[t], col = elem_color[elem];
+  if (t >= (int64_t)(NN * NN) * n_elem) return;
+  const int32_t elem = NN == 8 ? (int32_t)(t >> 6) : (int32_t)(t / (NN * NN)), a = NN == 8 ? (int)(t >> 3) & 7 : (int)(t / NN % NN),
+                b = NN == 8 ? (int)t & 7 : (int)(t % NN);
+  const int32_t inod = conn[(size_t)NN * elem + a], jnod = conn[(size_t)NN * elem + b], k = pos[t], col = elem_color[elem];
   if (k < 0) return;
   const int32_t m = inod == jnod ? minD[inod - 1] : (jnod < inod ? minL[k] : minU[k]);
   if (m == col) pos[t] = k | FXA_FIRST_BIT;

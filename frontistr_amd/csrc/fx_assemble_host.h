@@ -169,13 +169,17 @@ static void elem_colors_free(ElemColors &ec) {
   dev_free(ec.dup);
   ec = ElemColors();
 }
-// the position map of k_scatter_map for the resident profile and the device connectivity d_conn (FX_ASM_MAP=0: search every time)
-static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, bool with_first = false) {
+// the position map of k_scatter_map for the resident profile and the device connectivity d_conn of nn-node elements (8, 4 or 10;
+// FX_ASM_MAP=0: search every time)
+#define FX_NN_DISPATCH(nn, F) ((nn) == 4 ? F<4> : ((nn) == 10 ? F<10> : F<8>))
+static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, bool with_first = false,
+                              int nn = 8) {
   static const bool off = getenv("FX_ASM_MAP") && atoi(getenv("FX_ASM_MAP")) == 0;
   if (off || ec.pos || ec.offsets.empty()) return 0;
-  if (dev_alloc(&ec.pos, (size_t)64 * n_elem)) { (void)hipGetLastError(); ec.pos = nullptr; return 0; }  // no memory: keep searching
+  const int64_t nmap = (int64_t)nn * nn * n_elem;
+  if (dev_alloc(&ec.pos, (size_t)nmap)) { (void)hipGetLastError(); ec.pos = nullptr; return 0; }  // no memory: keep searching
   const DevCSR &A = c->A;
-  hipLaunchKernelGGL(k_scatter_map, dim3((unsigned)(((int64_t)64 * n_elem + 255) / 256)), dim3(256), 0, c->stream, n_elem, d_conn,
+  hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_map), dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, c->stream, n_elem, d_conn,
                      A.indexL, A.itemL, A.indexU, A.itemU, ec.pos);
   HIP_TRY(hipGetLastError());
   // first-write flags (FX_ASM_FIRST=0: off): which contribution to a block comes first in the order of the colour launches
@@ -200,10 +204,11 @@ static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, con
     HIP_TRY(hipMemsetAsync(minL, 0x7F, (size_t)std::max(A.NPL, 1) * 4, c->stream));
     HIP_TRY(hipMemsetAsync(minU, 0x7F, (size_t)std::max(A.NPU, 1) * 4, c->stream));
     HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-    const dim3 g((unsigned)(((int64_t)64 * n_elem + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_scatter_first_min, g, b, 0, c->stream, n_elem, d_conn, (const int32_t *)ec.pos, (const int32_t *)ecol, minD, minL, minU);
-    hipLaunchKernelGGL(k_scatter_first_flag, g, b, 0, c->stream, n_elem, d_conn, ec.pos, (const int32_t *)ecol, (const int32_t *)minD,
-                       (const int32_t *)minL, (const int32_t *)minU);
+    const dim3 g((unsigned)((nmap + 255) / 256)), b(256);
+    hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_min), g, b, 0, c->stream, n_elem, d_conn, (const int32_t *)ec.pos,
+                       (const int32_t *)ecol, minD, minL, minU);
+    hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_flag), g, b, 0, c->stream, n_elem, d_conn, ec.pos, (const int32_t *)ecol,
+                       (const int32_t *)minD, (const int32_t *)minL, (const int32_t *)minU);
     hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NP, (const int32_t *)minD, cnt);
     if (A.NPL > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPL, (const int32_t *)minL, cnt);
     if (A.NPU > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPU, (const int32_t *)minU, cnt);
@@ -217,9 +222,9 @@ static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, con
 }
 // Moves the elements that name a node twice out of the colour lists (order, off) into their own list (dups, dup_off), colour by
 // colour, each list keeping the colour order; an empty dup_off: there are none.  k_add_elem_blocks adds them after the colours.
-static bool names_a_node_twice(const int32_t *en) {
-  for (int x = 0; x < 8; x++)
-    for (int y = x + 1; y < 8; y++)
+static bool names_a_node_twice(const int32_t *en, int nn = 8) {
+  for (int x = 0; x < nn; x++)
+    for (int y = x + 1; y < nn; y++)
       if (en[x] == en[y]) return true;
   return false;
 }
@@ -239,11 +244,13 @@ static void split_collapsed(const int32_t *conn, std::vector<int32_t> &order, st
   off.swap(koff);
   if (dups.empty()) dup_off.clear();
 }
-static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *conn, int32_t NP) {
+// nn nodes per element of type etype (361: 8; 341: 4; 342: 10).  The colouring and the map are cached per (connectivity, type).
+static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *conn, int32_t NP, int nn = 8,
+                              int32_t etype = 361) {
   static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
   if (force_atomic || n_elem < 1) { elem_colors_free(ec); return 0; }
   // checksum of the connectivity: per-chunk FNV-1a, chunks combined in order
-  const int64_t nw = (int64_t)8 * n_elem;
+  const int64_t nw = (int64_t)nn * n_elem;
   const int nchunk = 64;
   uint64_t part[nchunk];
   bool bad[nchunk], dup[nchunk];
@@ -255,10 +262,10 @@ static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, con
         h = (h ^ (uint32_t)conn[i]) * 1099511628211ull;
         oob |= (conn[i] < 1 || conn[i] > NP);
       }
-      bool dp = false;  // an element that names a node twice (a collapsed hexahedron): two of its 64 blocks coincide
+      bool dp = false;  // an element that names a node twice (a collapsed hexahedron): two of its nn^2 blocks coincide
       for (int64_t e = (int64_t)n_elem * q / nchunk; e < (int64_t)n_elem * (q + 1) / nchunk; e++)
-        for (int x = 0; x < 8; x++)
-          for (int y = x + 1; y < 8; y++) dp |= (conn[8 * e + x] == conn[8 * e + y]);
+        for (int x = 0; x < nn; x++)
+          for (int y = x + 1; y < nn; y++) dp |= (conn[nn * e + x] == conn[nn * e + y]);
       part[q] = h; bad[q] = oob; dup[q] = dp;
     }
   });
@@ -267,19 +274,20 @@ static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, con
     if (bad[q]) { g_fx_error = "element connectivity: node id out of range"; return FX_ERROR_RUNTIME; }
     key = (key ^ part[q]) * 1099511628211ull;
   }
-  if (ec.order && ec.n_elem == n_elem && ec.key == key && !ec.offsets.empty()) return 0;
+  if (ec.order && ec.n_elem == n_elem && ec.key == key && ec.etype == etype && !ec.offsets.empty()) return 0;
   elem_colors_free(ec);
   std::vector<int32_t> order, off, dups, dup_off;
-  if (!fxo::color_elements(n_elem, 8, conn, NP, order, off)) return 0;  // a node in more than 64 elements: atomics
+  if (!fxo::color_elements(n_elem, nn, conn, NP, order, off)) return 0;  // a node in more than 64 elements: atomics
   ec.dup_nodes = false;
   for (int q = 0; q < nchunk; q++) ec.dup_nodes |= dup[q];
+  if (ec.dup_nodes && nn != 8) { g_fx_error = "element connectivity: a tetrahedron names a node twice"; return FX_ERROR_RUNTIME; }
   if (ec.dup_nodes) split_collapsed(conn, order, off, dups, dup_off);
   if (dev_alloc(&ec.order, std::max<size_t>(order.size(), 1)) || (!dups.empty() && dev_alloc(&ec.dup, dups.size())))
     return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpyAsync(ec.order, order.data(), order.size() * 4, hipMemcpyHostToDevice, c->stream));
   if (!dups.empty()) HIP_TRY(hipMemcpyAsync(ec.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  ec.n_elem = n_elem; ec.key = key; ec.offsets = off; ec.dup_off = dup_off;
+  ec.n_elem = n_elem; ec.key = key; ec.etype = etype; ec.offsets = off; ec.dup_off = dup_off;
   return 0;
 }
 
@@ -316,26 +324,91 @@ static void launch_assemble(fx_context *c, int32_t n_elem, const double *coord, 
                      mat_tab, (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
 }
 
+// nodes per element of the types the linear device assembly knows; 0: none of them
+static int c3_nodes(int32_t etype) { return etype == 361 ? 8 : (etype == 341 ? 4 : (etype == 342 ? 10 : 0)); }
+
+// A tetrahedron that names a node twice has zero volume (the reference stops in getJacobian): refused, never assembled.
+// One parallel pass with the node-id range check; the lowest offending element is named.
+static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int nn) {
+  int32_t first_bad = INT32_MAX, first_dup = INT32_MAX;  // 0-based elements
+  parallel_for(mesh->n_elem, [&](int64_t a, int64_t b) {
+    int32_t bad = INT32_MAX, dup = INT32_MAX;
+    for (int64_t e = a; e < b && bad == INT32_MAX && dup == INT32_MAX; e++) {
+      const int32_t *en = mesh->conn + (size_t)nn * e;
+      for (int x = 0; x < nn; x++)
+        if (en[x] < 1 || en[x] > mesh->n_node) bad = (int32_t)e;
+      if (bad == INT32_MAX && names_a_node_twice(en, nn)) dup = (int32_t)e;
+    }
+    __atomic_fetch_min(&first_bad, bad, __ATOMIC_RELAXED);
+    __atomic_fetch_min(&first_dup, dup, __ATOMIC_RELAXED);
+  });
+  static thread_local char msg[160];
+  if (first_bad != INT32_MAX) {
+    snprintf(msg, sizeof msg, "%s: node id out of range (element %d)", who, (int)first_bad + 1);
+    g_fx_error = msg;
+    return FX_ERROR_RUNTIME;
+  }
+  if (first_dup != INT32_MAX) {
+    snprintf(msg, sizeof msg, "%s: element %d names a node twice (a tetrahedron of zero volume)", who, (int)first_dup + 1);
+    g_fx_error = msg;
+    return FX_ERROR_RUNTIME;
+  }
+  return 0;
+}
+
+template <int ETYPE>
+static void launch_assemble_tet(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
+                                double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
+                                const ElemColors *ec) {
+  const DevCSR &A = c->A;
+  constexpr int EPB = FXT_EPB(ETYPE);
+  if (ec && !ec->offsets.empty() && !Kout) {
+    for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
+      const int32_t e0 = ec->offsets[k], e1 = ec->offsets[k + 1];
+      if (e1 > e0)
+        hipLaunchKernelGGL((k_assemble_tet<ETYPE>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, e1, coord, conn, D11,
+                           D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
+                           (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
+    }
+    return;
+  }
+  hipLaunchKernelGGL((k_assemble_tet<ETYPE>), dim3((n_elem + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, n_elem, coord, conn, D11, D12,
+                     D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
+                     (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
+}
+
+// etype 361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8; 341 / 342 through k_assemble_tet (elemopt unused)
 static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int32_t n_mat, const double *Es,
                                 const double *nus, const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
-                                const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
+                                const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble,
+                                int32_t etype = 361) {
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->have_profile) { g_fx_error = "fx_assemble_c3d8: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
-  if (mesh->n_node != c->A.NP) { g_fx_error = "fx_assemble_c3d8: mesh/profile size mismatch"; return FX_ERROR_RUNTIME; }
-  if (elemopt < 1 || elemopt > 3) { g_fx_error = "fx_assemble_c3d8: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)"; return FX_ERROR_UNSUPPORTED; }
+  const int nn = c3_nodes(etype);
+  const char *who = etype == 361 ? "fx_assemble_c3d8" : "fx_assemble_c3";
+  static thread_local char msg[200];
+  auto fail = [&](const char *what, int code) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    g_fx_error = msg;
+    return code;
+  };
+  if (!c->have_profile) return fail("upload the profile first (fx_upload FX_UP_PROFILE)", FX_ERROR_RUNTIME);
+  if (mesh->n_node != c->A.NP) return fail("mesh/profile size mismatch", FX_ERROR_RUNTIME);
+  if (etype == 361 && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
+  if (nn == 0) return fail("element type not supported on the device (341, 342; 361 through fx_assemble_c3d8)", FX_ERROR_UNSUPPORTED);
+  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;  // (361: its checks stay in the colouring)
   DevCSR &A = c->A;
   DevScratch tmp;
   double *d_coord = nullptr, *d_bcv = nullptr, *d_val = nullptr;
   int32_t *d_conn = nullptr, *d_err = nullptr, *d_node = nullptr, *d_dof = nullptr;
   uint8_t *d_flag = nullptr;
-  if (tmp.alloc(&d_coord, (size_t)3 * mesh->n_node) || tmp.alloc(&d_conn, (size_t)8 * mesh->n_elem) || tmp.alloc(&d_err, 1))
+  if (tmp.alloc(&d_coord, (size_t)3 * mesh->n_node) || tmp.alloc(&d_conn, (size_t)nn * mesh->n_elem) || tmp.alloc(&d_err, 1))
     return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpyAsync(d_coord, mesh->coord, (size_t)3 * mesh->n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)8 * mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)nn * mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-  if (ensure_elem_colors(c, c->asm_colors, mesh->n_elem, mesh->conn, mesh->n_node) ||
-      ensure_scatter_map(c, c->asm_colors, mesh->n_elem, d_conn, true))
-    return FX_ERROR_RUNTIME;  // both cached per (profile, mesh)
+  if (ensure_elem_colors(c, c->asm_colors, mesh->n_elem, mesh->conn, mesh->n_node, nn, etype) ||
+      ensure_scatter_map(c, c->asm_colors, mesh->n_elem, d_conn, true, nn))
+    return FX_ERROR_RUNTIME;  // both cached per (profile, mesh, element type)
   double D11 = 0.0, D12 = 0.0, D44 = 0.0;
   int32_t *d_emat = nullptr;
   double *d_mtab = nullptr;
@@ -343,7 +416,10 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
     std::vector<double> tab((size_t)3 * n_mat);
     for (int32_t k = 0; k < n_mat; k++) elastic_constants(Es[k], nus[k], tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]);
     for (int32_t e = 0; e < mesh->n_elem; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_assemble_c3d8_sections: material id out of range"; return FX_ERROR_RUNTIME; }
+      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) {
+        g_fx_error = etype == 361 ? "fx_assemble_c3d8_sections: material id out of range" : "fx_assemble_c3: material id out of range";
+        return FX_ERROR_RUNTIME;
+      }
     if (tmp.alloc(&d_emat, (size_t)mesh->n_elem) || tmp.alloc(&d_mtab, tab.size())) return FX_ERROR_RUNTIME;
     HIP_TRY(hipMemcpyAsync(d_emat, elem_mat, (size_t)mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_mtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -360,7 +436,9 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
     HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
     HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
   }
-  if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
+  if (etype == 341) launch_assemble_tet<341>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
+  else if (etype == 342) launch_assemble_tet<342>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
+  else if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   HIP_TRY(hipGetLastError());
@@ -371,7 +449,7 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
         tmp.alloc(&d_dof, (size_t)n_bc) || tmp.alloc(&d_val, (size_t)n_bc))
       return FX_ERROR_RUNTIME;
     for (int32_t k = 0; k < n_bc; k++)
-      if (bc_node[k] < 1 || bc_node[k] > A.NP) { g_fx_error = "fx_assemble_c3d8: BC node id out of range"; return FX_ERROR_RUNTIME; }
+      if (bc_node[k] < 1 || bc_node[k] > A.NP) return fail("BC node id out of range", FX_ERROR_RUNTIME);
     HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
     HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
     HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
@@ -440,5 +518,46 @@ extern "C" int fx_element_stiffness_c3d8(fx_context *c, int elemopt, const doubl
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(stiff, d_k, 576 * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- tetrahedra (TYPE=341, 342): fx_assemble_c3, fx_element_stiffness_c3 ------------------------------------------------
+extern "C" int fx_assemble_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
+                              const double *nu, const int32_t *elem_mat, const double *load, int32_t n_bc, const int32_t *bc_node,
+                              const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
+  if (!c || !mesh) { g_fx_error = "fx_assemble_c3: null argument"; return FX_ERROR_RUNTIME; }
+  if (etype != 341 && etype != 342) {
+    g_fx_error = "fx_assemble_c3: element type not supported on the device (341, 342; 361 through fx_assemble_c3d8)";
+    return FX_ERROR_UNSUPPORTED;
+  }
+  if (n_mat < 1 || !E || !nu) { g_fx_error = "fx_assemble_c3: materials missing"; return FX_ERROR_RUNTIME; }
+  if (n_mat > 1 && !elem_mat) { g_fx_error = "fx_assemble_c3: several materials need elem_mat"; return FX_ERROR_RUNTIME; }
+  if (!elem_mat)
+    return assemble_c3d8_common(c, mesh, E[0], nu[0], 0, nullptr, nullptr, nullptr, 0, load, n_bc, bc_node, bc_dof, bc_val,
+                                ms_assemble, etype);
+  return assemble_c3d8_common(c, mesh, 0.0, 0.0, n_mat, E, nu, elem_mat, 0, load, n_bc, bc_node, bc_dof, bc_val, ms_assemble, etype);
+}
+
+extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const double *ecoord, double E, double nu, double *stiff) {
+  if (!c || !ecoord || !stiff) { g_fx_error = "fx_element_stiffness_c3: null argument"; return FX_ERROR_RUNTIME; }
+  if (etype != 341 && etype != 342) { g_fx_error = "fx_element_stiffness_c3: etype must be 341 or 342"; return FX_ERROR_UNSUPPORTED; }
+  HIP_TRY(hipSetDevice(c->device));
+  const int nn = c3_nodes(etype), w = 3 * nn;
+  DevScratch tmp;
+  double *d_coord = nullptr, *d_k = nullptr;
+  int32_t *d_conn = nullptr, *d_err = nullptr;
+  if (tmp.alloc(&d_coord, (size_t)w) || tmp.alloc(&d_conn, (size_t)nn) || tmp.alloc(&d_k, (size_t)w * w) || tmp.alloc(&d_err, 1))
+    return FX_ERROR_RUNTIME;
+  const int32_t conn[10] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
+  HIP_TRY(hipMemcpy(d_coord, ecoord, (size_t)w * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_conn, conn, (size_t)nn * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_err, 0, 4));
+  double D11, D12, D44;
+  elastic_constants(E, nu, D11, D12, D44);
+  if (etype == 341) launch_assemble_tet<341>(c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
+  else launch_assemble_tet<342>(c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(stiff, d_k, (size_t)w * w * 8, hipMemcpyDeviceToHost));
   return 0;
 }

@@ -173,9 +173,10 @@ struct NlMat {
 struct ElemColors {
   int32_t n_elem = 0;
   uint64_t key = 0;                 // checksum of the connectivity the colouring belongs to
+  int32_t etype = 361;              // element type of that connectivity (361, 341, 342): a map of one type is never used for another
   int32_t *order = nullptr;         // device: element ids, colour by colour
   std::vector<int32_t> offsets;     // host: first position of each colour (+ end); empty = not coloured (atomics)
-  int32_t *pos = nullptr;           // device: 64 per element, position of block (a, b) in AL / AU (k_scatter_map), or null
+  int32_t *pos = nullptr;           // device: nn^2 per element, position of block (a, b) in AL / AU (k_scatter_map), or null
   bool dup_nodes = false;           // an element names a node twice: two of its blocks coincide, no first-write flags
   int32_t *dup = nullptr;           // device: those elements (collapsed hexahedra), colour by colour; they are not in `order`
   std::vector<int32_t> dup_off;     // host: first position of each colour in `dup` (+ end); empty = none

@@ -275,26 +275,43 @@ extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
 // materials (E, nu), elem_mat 1-based per element (NULL with one material); elemopt 1 IC, 2 B-bar, 3 FI; disp = total
 // displacement unode + dunode (3 * n_node, host).  Out: *strain, *stress = pinned host arrays owned by the library, valid until
 // the next call ([n_elem][8][6], the reference's gausses(1:8)%strain(1:6) / %stress(1:6)); qforce (3 * n_node, host, caller's).
-extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
-                                     const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
-                                     const double **stress, double *qforce, float *ms_kernel) {
+// etype 361 (elemopt 1..3, 8 quadrature points) through k_update_c3d8_linear; 341 / 342 (1 / 4 points) through k_update_tet.
+// Results: [n_elem][nq][6] in the pinned staging.
+static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
+                                const double *nu, const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
+                                const double **stress, double *qforce, float *ms_kernel) {
   HIP_TRY(hipSetDevice(c->device));
-  if (!mesh || !E || !nu || !disp || n_mat < 1) { g_fx_error = "fx_update_c3d8_linear: null argument"; return FX_ERROR_RUNTIME; }
-  if (elemopt < 1 || elemopt > 3) { g_fx_error = "fx_update_c3d8_linear: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)"; return FX_ERROR_UNSUPPORTED; }
+  const bool hex = etype == 361;
+  const char *who = hex ? "fx_update_c3d8_linear" : "fx_update_c3_linear";
+  static thread_local char msg[200];
+  auto fail = [&](const char *what, int code) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    g_fx_error = msg;
+    return code;
+  };
+  if (!mesh || !E || !nu || !disp || n_mat < 1) return fail("null argument", FX_ERROR_RUNTIME);
+  if (hex && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
+  if (!hex && etype != 341 && etype != 342) return fail("element type not supported on the device (341, 342; 361 through fx_update_c3d8_linear)", FX_ERROR_UNSUPPORTED);
   const int32_t ne = mesh->n_elem, nn = mesh->n_node;
-  if (ne < 1 || nn < 1) { g_fx_error = "fx_update_c3d8_linear: empty mesh"; return FX_ERROR_RUNTIME; }
-  for (int64_t k = 0; k < (int64_t)8 * ne; k++)
-    if (mesh->conn[k] < 1 || mesh->conn[k] > nn) { g_fx_error = "fx_update_c3d8_linear: node id out of range"; return FX_ERROR_RUNTIME; }
+  const int enn = c3_nodes(etype), nq = hex ? 8 : (etype == 341 ? 1 : 4);
+  const size_t per_elem = (size_t)6 * nq;  // doubles of strain (and of stress) per element
+  if (ne < 1 || nn < 1) return fail("empty mesh", FX_ERROR_RUNTIME);
+  if (hex) {
+    for (int64_t k = 0; k < (int64_t)enn * ne; k++)
+      if (mesh->conn[k] < 1 || mesh->conn[k] > nn) return fail("node id out of range", FX_ERROR_RUNTIME);
+  } else if (refuse_degenerate_tets(who, mesh, enn)) {
+    return FX_ERROR_RUNTIME;
+  }
   PhaseTimer pt("update linear");
   DevScratch tmp;
   double *d_coord = nullptr, *d_disp = nullptr, *d_strain = nullptr, *d_stress = nullptr, *d_q = nullptr, *d_mtab = nullptr;
   int32_t *d_conn = nullptr, *d_emat = nullptr, *d_err = nullptr;
   if (tmp.alloc(&d_coord, (size_t)3 * nn) || tmp.alloc(&d_disp, (size_t)3 * nn) || tmp.alloc(&d_q, (size_t)3 * nn) ||
-      tmp.alloc(&d_conn, (size_t)8 * ne) || tmp.alloc(&d_strain, (size_t)48 * ne) || tmp.alloc(&d_stress, (size_t)48 * ne) ||
+      tmp.alloc(&d_conn, (size_t)enn * ne) || tmp.alloc(&d_strain, per_elem * ne) || tmp.alloc(&d_stress, per_elem * ne) ||
       tmp.alloc(&d_err, 1))
     return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpyAsync(d_coord, mesh->coord, (size_t)3 * nn * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)8 * ne * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)enn * ne * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_disp, disp, (size_t)3 * nn * 8, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_q, 0, (size_t)3 * nn * 8, c->stream));
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
@@ -302,9 +319,9 @@ extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, in
   std::vector<double> tab((size_t)3 * n_mat);
   for (int32_t k = 0; k < n_mat; k++) elastic_constants(E[k], nu[k], tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]);
   if (n_mat > 1 || elem_mat) {
-    if (!elem_mat) { g_fx_error = "fx_update_c3d8_linear: several materials need elem_mat"; return FX_ERROR_RUNTIME; }
+    if (!elem_mat) return fail("several materials need elem_mat", FX_ERROR_RUNTIME);
     for (int32_t e = 0; e < ne; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_update_c3d8_linear: material id out of range"; return FX_ERROR_RUNTIME; }
+      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) return fail("material id out of range", FX_ERROR_RUNTIME);
     if (tmp.alloc(&d_emat, (size_t)ne) || tmp.alloc(&d_mtab, tab.size())) return FX_ERROR_RUNTIME;
     HIP_TRY(hipMemcpyAsync(d_emat, elem_mat, (size_t)ne * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_mtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -314,9 +331,9 @@ extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, in
   if (pt.on) HIP_TRY(hipStreamSynchronize(c->stream));
   pt.lap("device buffers + uploads");
   upd_stage_wait();
-  if (g_upd_stage.make_err || g_upd_stage.cap < (size_t)48 * ne) {
+  if (g_upd_stage.make_err || g_upd_stage.cap < per_elem * ne) {
     g_upd_stage.make_err = 0;
-    if (upd_stage_make(c->device, (size_t)48 * ne)) { g_fx_error = "fx_update_c3d8_linear: cannot pin the host staging"; (void)hipGetLastError(); return FX_ERROR_RUNTIME; }
+    if (upd_stage_make(c->device, per_elem * ne)) { (void)hipGetLastError(); return fail("cannot pin the host staging", FX_ERROR_RUNTIME); }
   }
   pt.lap("pinned staging");
   const dim3 grid((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), blk(FXU_BS);
@@ -324,15 +341,22 @@ extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, in
 #define FXU_LAUNCH(EO)                                                                                                       \
   hipLaunchKernelGGL((k_update_c3d8_linear<EO>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, \
                      d_disp, d_strain, d_stress, d_q, d_err)
-  if (elemopt == 1) FXU_LAUNCH(1);
+  const dim3 tgrid((unsigned)(((int64_t)nq * ne + FXU_TET_BS - 1) / FXU_TET_BS)), tblk(FXU_TET_BS);
+  if (etype == 341)
+    hipLaunchKernelGGL((k_update_tet<341>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                       d_strain, d_stress, d_q);
+  else if (etype == 342)
+    hipLaunchKernelGGL((k_update_tet<342>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                       d_strain, d_stress, d_q);
+  else if (elemopt == 1) FXU_LAUNCH(1);
   else if (elemopt == 2) FXU_LAUNCH(2);
   else FXU_LAUNCH(3);
 #undef FXU_LAUNCH
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.strain, d_strain, (size_t)48 * ne * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.stress, d_stress, (size_t)48 * ne * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(g_upd_stage.strain, d_strain, per_elem * ne * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(g_upd_stage.stress, d_stress, per_elem * ne * 8, hipMemcpyDeviceToHost, c->stream));
   if (qforce) HIP_TRY(hipMemcpyAsync(qforce, d_q, (size_t)3 * nn * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -344,4 +368,22 @@ extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, in
   if (strain) *strain = g_upd_stage.strain;
   if (stress) *stress = g_upd_stage.stress;
   return 0;
+}
+
+extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
+                                     const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
+                                     const double **stress, double *qforce, float *ms_kernel) {
+  return update_linear_common(c, mesh, 361, n_mat, E, nu, elem_mat, elemopt, disp, strain, stress, qforce, ms_kernel);
+}
+
+// The same for a group of tetrahedra (etype 341 or 342; UPDATE_C3): [n_elem][nq][6] with nq = 1 (341) or 4 (342).
+extern "C" int fx_update_c3_linear(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
+                                   const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
+                                   const double **stress, double *qforce, float *ms_kernel) {
+  if (!c) { g_fx_error = "fx_update_c3_linear: null argument"; return FX_ERROR_RUNTIME; }
+  if (etype != 341 && etype != 342) {
+    g_fx_error = "fx_update_c3_linear: element type not supported on the device (341, 342; 361 through fx_update_c3d8_linear)";
+    return FX_ERROR_UNSUPPORTED;
+  }
+  return update_linear_common(c, mesh, etype, n_mat, E, nu, elem_mat, 3, disp, strain, stress, qforce, ms_kernel);
 }

@@ -164,6 +164,7 @@ class hecmwST_local_mesh:
         self.export_item = np.zeros(0, dtype=np.int32)
         self.node = None            # 3*n_node coordinates
         self.elem_node_item = None  # flattened connectivity, 1-based
+        self.nn_elem = 8            # nodes per element of elem_node_item (8: TYPE=361, 4: 341, 10: 342)
         self.n_elem = 0
 
     def comm_view(self):
@@ -435,6 +436,58 @@ class SolverContext:
         _chk(lib().fx_element_stiffness_c3d8(self.h, int(elemopt), _ptr(ec), C.c_double(E), C.c_double(nu), _ptr(k)))
         return k
 
+    def assemble_c3(self, coord, conn, etype, E, nu, load=None, bc=None, elem_mat=None):
+        """fstr_StiffMatrix + fstr_AddBC on the device for tetrahedra (fx_assemble_c3): etype 341 (conn (n_elem, 4)) or 342
+        (conn (n_elem, 10), FrontISTR's node order).  E, nu scalars, or per-material arrays with elem_mat (1-based per
+        element).  Returns the kernel milliseconds."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        conn = np.ascontiguousarray(conn, dtype=np.int32)
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
+        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
+        if bc is None:
+            bn = np.zeros(0, dtype=np.int32); bd = np.zeros(0, dtype=np.int32); bv = np.zeros(0)
+        else:
+            bn = np.ascontiguousarray(bc[0], dtype=np.int32)
+            bd = np.ascontiguousarray(bc[1], dtype=np.int32)
+            bv = np.ascontiguousarray(bc[2], dtype=np.float64)
+        load = None if load is None else np.ascontiguousarray(load, dtype=np.float64)
+        ms = C.c_float(0)
+        _chk(lib().fx_assemble_c3(self.h, C.byref(mv), int(etype), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), _ptr(load),
+                                  int(bn.size), _ptr(bn), _ptr(bd), _ptr(bv), C.byref(ms)))
+        return ms.value
+
+    def update_c3_linear(self, coord, conn, etype, E, nu, disp, elem_mat=None):
+        """fstr_UpdateNewton of a linear static analysis of tetrahedra on the device (fx_update_c3_linear): strain, stress
+        (n_elem, nq, 6) with nq = 1 (341) or 4 (342), QFORCE (3 * n_node) from the total displacement.  Returns (strain,
+        stress, qforce, kernel ms)."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        conn = np.ascontiguousarray(conn, dtype=np.int32)
+        disp = np.ascontiguousarray(disp, dtype=np.float64)
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
+        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
+        ps, pt = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        qf = np.zeros(3 * coord.shape[0])
+        ms = C.c_float(0)
+        _chk(lib().fx_update_c3_linear(self.h, C.byref(mv), int(etype), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), _ptr(disp),
+                                       C.byref(ps), C.byref(pt), _ptr(qf), C.byref(ms)))
+        nq = 1 if int(etype) == 341 else 4
+        n = 6 * nq * conn.shape[0]
+        strain = np.ctypeslib.as_array(ps, shape=(n,)).reshape(-1, nq, 6).copy()    # the library's pinned staging: copy out
+        stress = np.ctypeslib.as_array(pt, shape=(n,)).reshape(-1, nq, 6).copy()
+        return strain, stress, qf, ms.value
+
+    def element_stiffness_c3(self, etype, ecoord, E, nu):
+        """One tetrahedron's (3 nn, 3 nn) stiffness through the device kernel (fx_element_stiffness_c3)."""
+        nn = {341: 4, 342: 10}.get(int(etype), 4)
+        ec = np.ascontiguousarray(ecoord, dtype=np.float64).reshape(nn, 3)
+        k = np.zeros((3 * nn, 3 * nn))
+        _chk(lib().fx_element_stiffness_c3(self.h, int(etype), _ptr(ec), C.c_double(E), C.c_double(nu), _ptr(k)))
+        return k
+
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * 128).from_buffer_copy(bytes(unique_id))
         _chk(lib().fx_comm_init(self.h, buf, rank, nranks))
@@ -477,15 +530,17 @@ def _ctx(ctx):
 
 
 def hecmw_mat_con(hecMESH, hecMAT):
-    """CRS block profile from hecMESH%elem_node_item (TYPE=361: 8 nodes per element)."""
-    conn = np.ascontiguousarray(hecMESH.elem_node_item, dtype=np.int32).reshape(-1, 8)
+    """CRS block profile from hecMESH%elem_node_item: hecMESH.nn_elem nodes per element when the mesh sets it (4 at TYPE=341,
+    10 at 342), else 8 (TYPE=361)."""
+    nn = int(getattr(hecMESH, "nn_elem", 8))
+    conn = np.ascontiguousarray(hecMESH.elem_node_item, dtype=np.int32).reshape(-1, nn)
     NP = hecMESH.n_node
     indexL = np.zeros(NP + 1, dtype=np.int32)
     indexU = np.zeros(NP + 1, dtype=np.int32)
-    _chk(lib().fx_mat_con(NP, conn.shape[0], 8, _ptr(conn), _ptr(indexL), _ptr(indexU), None, None))
+    _chk(lib().fx_mat_con(NP, conn.shape[0], nn, _ptr(conn), _ptr(indexL), _ptr(indexU), None, None))
     itemL = np.zeros(max(int(indexL[NP]), 1), dtype=np.int32)
     itemU = np.zeros(max(int(indexU[NP]), 1), dtype=np.int32)
-    _chk(lib().fx_mat_con(NP, conn.shape[0], 8, _ptr(conn), _ptr(indexL), _ptr(indexU), _ptr(itemL), _ptr(itemU)))
+    _chk(lib().fx_mat_con(NP, conn.shape[0], nn, _ptr(conn), _ptr(indexL), _ptr(indexU), _ptr(itemL), _ptr(itemU)))
     hecMAT.N, hecMAT.NP = hecMESH.nn_internal, NP
     hecMAT.indexL, hecMAT.indexU = indexL, indexU
     hecMAT.itemL, hecMAT.itemU = itemL[:indexL[NP]], itemU[:indexU[NP]]       # exact-size arrays (views when nothing is cut)

@@ -181,3 +181,63 @@ def color_elements(conn, n_node):
         for v in nodes:
             used[v] |= np.uint64(1) << np.uint64(c)
     return col
+
+
+# Kuhn split of a hexahedron into 6 tetrahedra: every tetrahedron runs from corner (0,0,0) to corner (1,1,1) of the cube along
+# one permutation of the axes.  All cubes use the same diagonal, so neighbouring faces are split the same way (the mesh is
+# conforming).  Positions in CubeMesh's connectivity (bottom face counter-clockwise, then top); each tetrahedron is ordered for
+# a positive volume.
+_KUHN = ((0, 1, 2, 6), (0, 5, 1, 6), (0, 2, 3, 6), (0, 3, 7, 6), (0, 4, 5, 6), (0, 7, 4, 6))
+# mid-edge nodes of the 10-node tetrahedron (HEC-MW TYPE=342, FrontISTR order): 5=(1,2), 6=(2,3), 7=(3,1), 8=(1,4), 9=(2,4), 10=(3,4)
+TET10_EDGES = ((0, 1), (1, 2), (2, 0), (0, 3), (1, 3), (2, 3))
+
+
+class TetMesh:
+    """The n^3 cube of CubeMesh with every hexahedron split into 6 tetrahedra (Kuhn split, conforming): TYPE=341 (4 nodes) or,
+    with one node added at the middle of every edge, TYPE=342 (10 nodes, FrontISTR's node order).  The vertices keep CubeMesh's
+    numbering; the mid-edge nodes follow, in the order of their edges sorted by (lower, higher) vertex id.  ``skew`` moves the
+    interior vertices as CubeMesh does; ``curve`` then moves the interior mid-edge nodes off their edges (curved 342 elements).
+    Boundary conditions and load as CubeMesh: the z=0 face clamped, unit x-load on every node of the z=n face."""
+
+    def __init__(self, n, etype=342, spacing=1.0, skew=0.0, curve=0.0):
+        if etype not in (341, 342):
+            raise ValueError("etype must be 341 or 342")
+        hexes = CubeMesh(n, spacing=spacing, skew=skew)
+        self.n, self.etype = int(n), int(etype)
+        tets = np.concatenate([hexes.conn[:, list(t)] for t in _KUHN], axis=1).reshape(-1, 4)  # hex by hex, 6 each
+        coord = hexes.coord
+        if etype == 342:
+            pairs = np.stack([tets[:, list(e)] for e in TET10_EDGES], axis=1)        # (n_tet, 6, 2)
+            key = np.sort(pairs, axis=2).reshape(-1, 2)
+            edges, inverse = np.unique(key, axis=0, return_inverse=True)
+            mid = 0.5 * (coord[edges[:, 0] - 1] + coord[edges[:, 1] - 1])
+            if curve:
+                eid = np.arange(edges.shape[0], dtype=np.float64)
+                lo, hi = 0.0, self.n * spacing
+                inside = np.all((mid > lo + 1e-9 * spacing) & (mid < hi - 1e-9 * spacing), axis=1)
+                d = np.stack([np.sin(0.9 * eid + 0.3), np.sin(1.7 * eid + 1.1), np.sin(2.3 * eid + 0.5)], axis=1)
+                mid[inside] += curve * spacing * d[inside]
+            tets = np.concatenate([tets, hexes.n_node + 1 + inverse.reshape(-1, 6)], axis=1)
+            coord = np.concatenate([coord, mid])
+        self.coord = np.ascontiguousarray(coord)
+        self.conn = np.ascontiguousarray(tets.astype(np.int32))
+        self.n_node, self.n_elem = self.coord.shape[0], self.conn.shape[0]
+        z = self.coord[:, 2]
+        self.bottom_nodes = (1 + np.flatnonzero(z == 0.0)).astype(np.int32)
+        self.top_nodes = (1 + np.flatnonzero(z == self.n * spacing)).astype(np.int32)
+
+    @property
+    def ndof(self):
+        return 3 * self.n_node
+
+    def dirichlet(self):
+        """(node, dof, value) triplets: z=0 face clamped."""
+        node = np.repeat(self.bottom_nodes, 3).astype(np.int32)
+        dof = np.tile(np.array([1, 2, 3], dtype=np.int32), self.bottom_nodes.size)
+        return node, dof, np.zeros(node.size, dtype=np.float64)
+
+    def load(self):
+        """1.0 in x on every node of the z=n face."""
+        b = np.zeros(3 * self.n_node, dtype=np.float64)
+        b[3 * (self.top_nodes - 1)] = 1.0
+        return b

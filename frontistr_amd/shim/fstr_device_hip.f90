@@ -28,6 +28,7 @@ module fstr_device_hip
   logical, save :: lin_decided = .false., lin_eligible = .false., lin_ready = .false.
   type(c_ptr), save :: the_ctx_saved = c_null_ptr
   integer(c_int), save :: lin_elemopt = 0
+  integer(c_int32_t), save :: lin_etype = 361      ! 361, or the tetrahedra 341 / 342 (fx_assemble_c3 / fx_update_c3_linear)
   real(c_double), allocatable, target, save :: lin_E(:), lin_nu(:)
   integer(c_int32_t), allocatable, target, save :: lin_emat(:)
   integer(c_int32_t), save :: n_elem = 0
@@ -78,7 +79,9 @@ contains
     if (fstrPR%solution_type /= kstSTATIC .or. .not. fstrPR%nlgeom) return
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return                       ! the solve must run on the device too: same predicate as hecmw_solve (method, preconditioner, no MPC / contact)
     if (hecMESH%n_elem_type /= 1) return
-    if (hecMESH%elem_type_item(1) /= 361) return
+    lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
+    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return
+    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed tet meshes: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
@@ -110,13 +113,16 @@ contains
   !> Linear static analysis (`!SOLUTION, TYPE=STATIC`, small strain) of TYPE=361 elements with isotropic ELASTIC materials: the
   !> element loop of fstr_StiffMatrix runs on the device -- STF_C3D8IC (the default of 361), STF_C3D8Bbar or STF_C3, whichever
   !> `!SECTION ... ELEMOPT361` selects, the same for every section -- and the matrix stays there for hecmw_solve; fstr_UpdateNewton
-  !> (strains, stresses, QFORCE from the solution vector) remains the reference's routine, it never reads the matrix.
+  !> (strains, stresses, QFORCE from the solution vector) runs there too (fsd_update_newton_linear).  A mesh of tetrahedra only,
+  !> TYPE=341 or 342 (STF_C3 / UPDATE_C3, fstr_StiffMatrix.f90:134-144, fstr_Update.f90:182-189), is covered the same way under
+  !> the same conditions, ELEMOPT361 aside; a decomposed tet mesh (PETOT > 1) keeps the host loops.
   logical function fsd_eligible_linear(hecMESH, hecMAT, fstrSOLID)
     type(hecmwST_local_mesh), intent(in) :: hecMESH
     type(hecmwST_matrix), intent(in) :: hecMAT
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
-    integer :: elen, estat, i, icel, cid, opt
+    integer :: elen, estat, i, icel, cid, opt, nn
+    character(len=3) :: tname
     if (lin_decided) then
       fsd_eligible_linear = lin_eligible
       return
@@ -132,7 +138,9 @@ contains
     if (fstrPR%solution_type /= kstSTATIC .or. fstrPR%nlgeom) return
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return
     if (hecMESH%n_elem_type /= 1) return
-    if (hecMESH%elem_type_item(1) /= 361) return
+    lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
+    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return
+    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed tet meshes: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return      ! thermal strains enter the element routine
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
@@ -143,17 +151,22 @@ contains
     opt = -1
     do i = 1, hecMESH%section%n_sect
       if (opt == -1) opt = fstrSOLID%sections(i)%elemopt361
-      if (fstrSOLID%sections(i)%elemopt361 /= opt) return
+      if (lin_etype == 361 .and. fstrSOLID%sections(i)%elemopt361 /= opt) return
       if (hecMESH%section%sect_orien_ID(i) > 0) return
     enddo
-    select case (opt)
-      case (kel361IC);   lin_elemopt = 1
-      case (kel361BBAR); lin_elemopt = 2
-      case (kel361FI);   lin_elemopt = 3
-      case default; return
-    end select
+    if (lin_etype == 361) then       ! ELEMOPT361 selects the 361 formulation only
+      select case (opt)
+        case (kel361IC);   lin_elemopt = 1
+        case (kel361BBAR); lin_elemopt = 2
+        case (kel361FI);   lin_elemopt = 3
+        case default; return
+      end select
+    endif
+    nn = 8
+    if (lin_etype == 341) nn = 4
+    if (lin_etype == 342) nn = 10
     do icel = 1, hecMESH%n_elem
-      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= 8) return
+      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
       cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
       if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
     enddo
@@ -165,7 +178,8 @@ contains
     enddo
     lin_eligible = .true.
     fsd_eligible_linear = .true.
-    if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly on the device (linear static, TYPE=361); '// &
+    write(tname, '(i3)') lin_etype
+    if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly on the device (linear static, TYPE='//tname//'); '// &
       'HECMW_GPU_ASSEMBLY=0 keeps it on the host'
   end function fsd_eligible_linear
 
@@ -359,9 +373,15 @@ contains
       if (.not. lin_ready) call fsd_init_linear(hecMESH, hecMAT, fstrSOLID)
       mesh%n_node = hecMESH%n_node; mesh%n_elem = hecMESH%n_elem
       mesh%coord = c_loc(hecMESH%node(1)); mesh%conn = c_loc(hecMESH%elem_node_item(1))
-      ierr = fx_assemble_c3d8_sections(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, lin_elemopt, &
-                                       c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
-      if (ierr /= 0) call fsd_fail('fx_assemble_c3d8_sections')
+      if (lin_etype == 361) then
+        ierr = fx_assemble_c3d8_sections(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, &
+                                         lin_elemopt, c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
+        if (ierr /= 0) call fsd_fail('fx_assemble_c3d8_sections')
+      else
+        ierr = fx_assemble_c3(fxb_context(hecMESH), mesh, lin_etype, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, &
+                              c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
+        if (ierr /= 0) call fsd_fail('fx_assemble_c3')
+      endif
       call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
       if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '0')) &    ! the stress update follows the solve: pin its staging meanwhile
         ierr = fx_update_c3d8_linear_prepare(fxb_context(hecMESH), int(hecMESH%n_elem, c_int32_t))
@@ -419,7 +439,7 @@ contains
     real(c_double), pointer :: s6(:,:,:), t6(:,:,:)
     real(c_double), allocatable :: tot(:)
     character(len=8) :: env
-    integer :: elen, estat, icel, g
+    integer :: elen, estat, icel, g, nq
     real(kind=kreal) :: t0
     fsd_update_newton_linear = .false.
     call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
@@ -429,17 +449,26 @@ contains
     mesh%n_node = hecMESH%n_node; mesh%n_elem = hecMESH%n_elem
     mesh%coord = c_loc(hecMESH%node(1)); mesh%conn = c_loc(hecMESH%elem_node_item(1))
     t0 = hecmw_Wtime()
-    ierr = fx_update_c3d8_linear(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, lin_elemopt, tot, &
-                                 ps, pt, fstrSOLID%QFORCE, ms)
-    if (ierr /= 0) call fsd_fail('fx_update_c3d8_linear')
+    nq = 8
+    if (lin_etype == 361) then
+      ierr = fx_update_c3d8_linear(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, lin_elemopt, &
+                                   tot, ps, pt, fstrSOLID%QFORCE, ms)
+      if (ierr /= 0) call fsd_fail('fx_update_c3d8_linear')
+    else                             ! tetrahedra: UPDATE_C3 at 1 (341) or 4 (342) quadrature points
+      nq = 4
+      if (lin_etype == 341) nq = 1
+      ierr = fx_update_c3_linear(fxb_context(hecMESH), mesh, lin_etype, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, &
+                                 tot, ps, pt, fstrSOLID%QFORCE, ms)
+      if (ierr /= 0) call fsd_fail('fx_update_c3_linear')
+    endif
     deallocate(tot)
     call fsd_report('  of which the library call (uploads, kernel, strain / stress / QFORCE back)', hecmw_Wtime() - t0)
     call fsd_report('  of which the element kernel alone', real(ms, kreal) * 1.d-3)
-    call c_f_pointer(ps, s6, [6, 8, hecMESH%n_elem])
-    call c_f_pointer(pt, t6, [6, 8, hecMESH%n_elem])
+    call c_f_pointer(ps, s6, [6, nq, hecMESH%n_elem])
+    call c_f_pointer(pt, t6, [6, nq, hecMESH%n_elem])
     !$omp parallel do default(shared) private(icel, g)
     do icel = 1, hecMESH%n_elem
-      do g = 1, 8
+      do g = 1, nq
         fstrSOLID%elements(icel)%gausses(g)%strain(1:6) = s6(1:6, g, icel)
         fstrSOLID%elements(icel)%gausses(g)%stress(1:6) = t6(1:6, g, icel)
       enddo

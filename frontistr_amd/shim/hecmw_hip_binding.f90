@@ -22,7 +22,8 @@ module hecmw_hip_binding
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
   public :: fx_mesh_view, fx_material_view, fx_nl_state_view
   public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
-            fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot
+            fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
+            fx_assemble_c3, fx_update_c3_linear
   public :: fxb_values_owner, fxb_values_addr
   public :: fxb_matrix_on_device, fxb_defer_bc, fxb_solve_device_matrix, FX_UP_PROFILE
   public :: fxb_context, fxb_views, fxb_ensure_transport, fxb_error_text, fxb_on_gpu_path, fx_get_stats
@@ -129,6 +130,32 @@ module hecmw_hip_binding
       real(c_double), intent(inout) :: qforce(*)
       real(c_float), intent(out) :: ms
     end function fx_update_c3d8_linear
+    integer(c_int) function fx_assemble_c3(ctx, mesh, etype, n_mat, E, nu, elem_mat, load, n_bc, bc_node, bc_dof, bc_val, ms) &
+        bind(C, name='fx_assemble_c3')
+      import :: c_int, c_ptr, c_int32_t, c_double, c_float, fx_mesh_view
+      type(c_ptr), value :: ctx
+      type(fx_mesh_view) :: mesh
+      integer(c_int32_t), value :: etype, n_mat
+      real(c_double) :: E(*), nu(*)
+      integer(c_int32_t) :: elem_mat(*)
+      type(c_ptr), value :: load                 ! NULL: B is not touched
+      integer(c_int32_t), value :: n_bc
+      type(c_ptr), value :: bc_node, bc_dof, bc_val
+      real(c_float) :: ms
+    end function fx_assemble_c3
+    integer(c_int) function fx_update_c3_linear(ctx, mesh, etype, n_mat, E, nu, elem_mat, disp, strain, stress, qforce, ms) &
+        bind(C, name='fx_update_c3_linear')
+      import :: c_ptr, c_int, c_int32_t, c_double, c_float, fx_mesh_view
+      type(c_ptr), value :: ctx
+      type(fx_mesh_view), intent(in) :: mesh
+      integer(c_int32_t), value :: etype, n_mat
+      real(c_double), intent(in) :: E(*), nu(*)
+      integer(c_int32_t), intent(in) :: elem_mat(*)
+      real(c_double), intent(in) :: disp(*)
+      type(c_ptr) :: strain, stress
+      real(c_double) :: qforce(*)
+      real(c_float) :: ms
+    end function fx_update_c3_linear
     integer(c_int) function fx_update_c3d8_linear_prepare(ctx, n_elem) bind(C, name='fx_update_c3d8_linear_prepare')
       import :: c_ptr, c_int, c_int32_t
       type(c_ptr), value :: ctx

@@ -1,5 +1,9 @@
 """Device assembly (fstr_StiffMatrix + fstr_AddBC) on the n^3-element cube: ms per call for ELEMOPT361 = IC / B-bar / FI.
-FX_ASM_ATOMIC=1 selects the single-launch atomic scatter instead of the coloured one.  Usage: python scripts/bench_assembly.py [n]"""
+FX_ASM_ATOMIC=1 selects the single-launch atomic scatter instead of the coloured one.  Usage: python scripts/bench_assembly.py [n]
+
+--etype 341|342: the same cube split into tetrahedra (TetMesh; 6 per hexahedron, at 342 with mid-edge nodes): ms per call of
+fx_assemble_c3 (three warm calls), the algorithmic bytes of one call (matrix values written once, position map, connectivity
+and coordinates read once) and the bandwidth they imply.  Usage: python scripts/bench_assembly.py --etype 342 [n]"""
 import json
 import os
 import sys
@@ -10,7 +14,36 @@ if os.environ.get("FX_LIBPATH"):
     hip.LIBPATH = os.environ["FX_LIBPATH"]      # timing experiments: a library built with -DFXA_EXP_*
 from frontistr_amd.mesh import CubeMesh          # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 149
+from frontistr_amd.mesh import TetMesh           # noqa: E402
+
+args = sys.argv[1:]
+etype = None
+if "--etype" in args:
+    k = args.index("--etype")
+    etype = int(args[k + 1])
+    del args[k:k + 2]
+if etype is not None:
+    n = int(args[0]) if args else 74
+    mesh = TetMesh(n, etype=etype)
+    nn = mesh.conn.shape[1]
+    hm = hip.hecmwST_local_mesh(n_node=mesh.n_node)
+    hm.nn_elem = nn
+    hm.elem_node_item = mesh.conn.ravel()
+    m = hip.hecmw_mat_con(hm, hip.hecmwST_matrix())
+    ctx = hip.SolverContext()
+    ctx.upload(m, hm, what=hip.FX_UP_PROFILE)
+    load, bc = mesh.load(), mesh.dirichlet()
+    ms = [ctx.assemble_c3(mesh.coord, mesh.conn, etype, 210000.0, 0.3, load=load, bc=bc) for _ in range(3)]
+    nbytes = (72 * (m.NP + m.NPL + m.NPU)                  # D / AL / AU written once
+              + 4 * nn * nn * mesh.n_elem                  # position map
+              + 4 * nn * mesh.n_elem + 24 * mesh.n_node)   # connectivity, coordinates
+    out = {"etype": etype, "n_elem": int(mesh.n_elem), "dof": 3 * mesh.n_node,
+           "scatter": "atomic" if os.environ.get("FX_ASM_ATOMIC", "0") not in ("", "0") else "coloured",
+           "ms": [round(v, 2) for v in ms], "algorithmic_GB": round(nbytes / 1e9, 3),
+           "GBps": round(nbytes / 1e6 / min(ms), 1), "fraction_of_8TBps": round(nbytes / 1e6 / min(ms) / 8000.0, 3)}
+    print(json.dumps(out))
+    sys.exit(0)
+n = int(args[0]) if args else 149
 mesh = CubeMesh(n)
 hm = hip.hecmwST_local_mesh(n_node=mesh.n_node)
 hm.elem_node_item = mesh.conn.ravel()

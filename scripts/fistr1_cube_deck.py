@@ -3,7 +3,10 @@
 face pulled by 0.5 % in z with a little shear, multilinear Mises plasticity of tutorial/05_plastic_cylinder (necking.cnt), updated
 Lagrange (NLSTATIC default), SUBSTEPS sub-steps, CG + SSOR (or what --solver says) with TIMELOG.  Writes <dir>/cube.msh, cube.cnt,
 hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to time fistr1_hip end to end: device assembly
-(default) against HECMW_GPU_ASSEMBLY=0 (scripts/r3/fistr1_big.sh).  usage: fistr1_cube_deck.py DIR N [SUBSTEPS] [METHOD] [PRECOND] [STRAIN]"""
+(default) against HECMW_GPU_ASSEMBLY=0 (scripts/r3/fistr1_big.sh).  usage: fistr1_cube_deck.py DIR N [SUBSTEPS] [METHOD] [PRECOND] [STRAIN]
+--etype 341|342 (with --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
+mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --two-sections (with --linear): the second half of the elements
+forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33)."""
 import os
 import sys
 
@@ -15,6 +18,16 @@ if linear:
 form361 = None                       # --form361 FI|BBAR|IC: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's (IC)
 if "--form361" in sys.argv:
     k = sys.argv.index("--form361"); form361 = sys.argv[k + 1]; del sys.argv[k:k + 2]
+etype = 361                          # --etype 341|342: tetrahedra (linear decks only)
+if "--etype" in sys.argv:
+    k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
+    if etype not in (341, 342) or not linear:
+        sys.exit("--etype takes 341 or 342, with --linear")
+two = "--two-sections" in sys.argv
+if two:
+    sys.argv.remove("--two-sections")
+    if not linear:
+        sys.exit("--two-sections needs --linear")
 d, n = sys.argv[1], int(sys.argv[2])
 nsub = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 method = sys.argv[4] if len(sys.argv) > 4 else "CG"
@@ -28,14 +41,34 @@ xyz = np.stack([i.ravel(), j.ravel(), k.ravel()], axis=1).astype(float)
 ek, ej, ei = np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij")
 n0 = (1 + ei + m * (ej + m * ek)).ravel()
 conn = np.stack([n0, n0 + 1, n0 + 1 + m, n0 + m, n0 + m * m, n0 + 1 + m * m, n0 + 1 + m + m * m, n0 + m + m * m], axis=1)
+if etype != 361:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from frontistr_amd.mesh import TetMesh
+    tm = TetMesh(n, etype=etype)
+    nid, xyz, conn = np.arange(1, tm.n_node + 1), tm.coord, tm.conn
+    if etype == 342:   # the mesh file lists the mid-edge nodes as (2,3), (3,1), (1,2), (1,4), (2,4), (3,4); fistr1 reorders them on input
+        conn = conn[:, [0, 1, 2, 3, 5, 6, 4, 7, 8, 9]]
 with open(os.path.join(d, "cube.msh"), "w") as fh:
     fh.write("!HEADER\n synthetic cube, frontistr_amd scripts/fistr1_cube_deck.py\n!NODE\n")
-    np.savetxt(fh, np.column_stack([nid, xyz]), fmt="%d,%.1f,%.1f,%.1f")
-    fh.write("!ELEMENT,TYPE=361,EGRP=E1\n")
-    np.savetxt(fh, np.column_stack([np.arange(1, conn.shape[0] + 1), conn]), fmt="%d", delimiter=",")
+    np.savetxt(fh, np.column_stack([nid, xyz]), fmt="%d,%.1f,%.1f,%.1f" if etype == 361 else "%d,%.2f,%.2f,%.2f")
+    eid = np.arange(1, conn.shape[0] + 1)
+    half = conn.shape[0] // 2 if two else conn.shape[0]
+    fh.write("!ELEMENT,TYPE=%d,EGRP=E1\n" % etype)
+    np.savetxt(fh, np.column_stack([eid[:half], conn[:half]]), fmt="%d", delimiter=",")
+    if two:
+        fh.write("!ELEMENT,TYPE=%d,EGRP=E2\n" % etype)
+        np.savetxt(fh, np.column_stack([eid[half:], conn[half:]]), fmt="%d", delimiter=",")
     fh.write("!MATERIAL,NAME=MAT1,ITEM=1\n!ITEM=1,SUBITEM=2\n 206900.0,0.29\n!SECTION,TYPE=SOLID,EGRP=E1,MATERIAL=MAT1\n")
-    fh.write("!NGROUP, NGRP=FIX, GENERATE\n 1,%d,1\n" % (m * m))
-    fh.write("!NGROUP, NGRP=TOP, GENERATE\n %d,%d,1\n!END\n" % (m * m * n + 1, m * m * m))
+    if two:
+        fh.write("!MATERIAL,NAME=MAT2,ITEM=1\n!ITEM=1,SUBITEM=2\n 70000.0,0.33\n!SECTION,TYPE=SOLID,EGRP=E2,MATERIAL=MAT2\n")
+    if etype == 361:
+        fh.write("!NGROUP, NGRP=FIX, GENERATE\n 1,%d,1\n" % (m * m))
+        fh.write("!NGROUP, NGRP=TOP, GENERATE\n %d,%d,1\n!END\n" % (m * m * n + 1, m * m * m))
+    else:
+        for name, ids in (("FIX", tm.bottom_nodes), ("TOP", tm.top_nodes)):
+            fh.write("!NGROUP, NGRP=%s\n" % name)
+            np.savetxt(fh, ids.reshape(-1, 1), fmt=" %d")
+        fh.write("!END\n")
 if linear:
     with open(os.path.join(d, "cube.cnt"), "w") as fh:
         fh.write("""!VERSION
@@ -49,12 +82,13 @@ if linear:
 !MATERIAL, NAME=MAT1
 !ELASTIC
  210000.0, 0.3
-%s!RESTART, FREQUENCY=100000
+%s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  10000, 1
  1.0e-8, 1.0, 0.0
 !END
-""" % ("!SECTION, SECNUM=1, FORM361=%s\n" % form361 if form361 else "", method, precond))
+""" % ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" if two else "",
+       "!SECTION, SECNUM=1, FORM361=%s\n" % form361 if form361 else "", method, precond))
 with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
     if not linear:
       fh.write("""!VERSION
@@ -87,4 +121,4 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
-print("wrote", d, "nodes", m ** 3, "dof", 3 * m ** 3, "elements", n ** 3)
+print("wrote", d, "nodes", nid.size, "dof", 3 * nid.size, "elements", conn.shape[0])
