@@ -356,6 +356,11 @@ extern "C" int fx_create(int device, fx_context **out) {
     occ(2, k_tri_dataflow<8, 1, true>, 512); occ(2, k_tri_dataflow<8, 0, true>, 512); occ(2, k_tri_dataflow<8, 1, false>, 512); occ(2, k_tri_dataflow<8, 0, false>, 512);
     (void)hipGetLastError();
     for (int k = 0; k < 3; k++) c->df_grid_max[k] = std::max(1, c->n_cu * std::max(1, std::min(pc[k], 8)));
+    int pe[2] = {1, 1};
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pe[0], k_eis_backward_df<4>, 256, 0) != hipSuccess) pe[0] = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pe[1], k_eis_forward_df<4>, 256, 0) != hipSuccess) pe[1] = 1;
+    (void)hipGetLastError();
+    for (int k = 0; k < 2; k++) c->eis_df_grid_max[k] = std::max(1, c->n_cu * std::max(1, std::min(pe[k], EIS_DF_MAX_PER_CU)));
     int pm[4] = {1, 1, 1, 1};
     auto occm = [&](int k, auto kernel, int threads) {
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pm[k], kernel, threads, 0) != hipSuccess) pm[k] = 1;
@@ -2130,6 +2135,31 @@ static int eis_begin(fx_context *c) {  // after the standard begin (r0 = b - A x
   HIP_TRY(hipMemsetAsync(c->W[3], 0, (size_t)c->wlen * 8, c->stream));
   return eis_refresh_t(c, nullptr);
 }
+// The latency-bound tail of the fused Eisenstat sweeps (k_eis_*_df): the longest run of colours at the
+// end of the colour order with at most EIS_TAIL_GRIDS x G slices each, G the co-resident grid of the dataflow kernels.  Only where it
+// is exact and safe: FX_DATAFLOW >= 1, one rank (a one-rank retry inside a collective solve is not safe), the fused backward sweep,
+// one workgroup per slice (eis_grid 0: the partial of every slice sits where OP_CG_C1 expects it), every tail colour a split launch.
+// Returns the first tail colour (ncolor: no tail) and the grids of the backward and forward tail launches.
+static int eis_tail(fx_context *c, int *grid) {
+  const SsorDev &S = c->ssor;
+  grid[0] = grid[1] = 0;
+  if (c->df_mode < 1 || multi_rank(c) || c->nranks > 1 || halo_active(c) || !c->eis_fuse || c->eis_grid > 0 || S.ncolor <= 0)
+    return S.ncolor;
+  int gk[2];
+  for (int k = 0; k < 2; k++) gk[k] = c->df_grid > 0 ? std::min(c->df_grid, c->eis_df_grid_max[k]) : c->eis_df_grid_max[k];
+  const int g = std::min(gk[0], gk[1]);
+  int c0 = S.ncolor;
+  while (c0 > 0) {
+    const int nsl = S.color_slice[c0] - S.color_slice[c0 - 1];
+    if (nsl > EIS_TAIL_GRIDS * g || nsl > c->split_max_slices) break;
+    c0--;
+  }
+  const int nt = S.color_slice[S.ncolor] - S.color_slice[c0];
+  if (nt <= 0) return S.ncolor;
+  for (int k = 0; k < 2; k++) grid[k] = std::min(gk[k], nt);
+  return c0;
+}
+
 static int eis_cg_iteration(fx_context *c, int it) {
   SsorDev &S = c->ssor;
   const int32_t ns = c->ord.nslots;
@@ -2143,10 +2173,24 @@ static int eis_cg_iteration(fx_context *c, int it) {
   // (already done by the previous iteration's OP_RESID_RHO stage unless t was refreshed since)
   if (!c->eis_rho_done && scalar_stage<OP_CG_RHO>(c, ugrid, 0, RECOMPUTE, part_rho)) return FX_ERROR_RUNTIME;
   c->eis_rho_done = false;
+  int tgrid[2];
+  const int tc0 = eis_tail(c, tgrid);  // colours [tc0, ncolor): one dataflow launch per half sweep
+  const int ts0 = S.color_slice[tc0], ts1 = S.color_slice[S.ncolor];
+  c->eis_tail_color0 = tc0; c->eis_tail_slices = ts1 - ts0; c->eis_tail_grid = tgrid[0];
+  if (tc0 < S.ncolor) {  // tags into the tail ranges of p and v (nothing reads them before the sweeps that produce them)
+    const int64_t n16 = (int64_t)(ts1 - ts0) * 64 * 3 * 8 / 16;
+    hipLaunchKernelGGL(k_eis_tag, dim3(grid_for(n16, 256, 2048)), dim3(256), 0, c->stream, n16, (fx_u4 *)(P + (size_t)3 * 64 * ts0),
+                       (fx_u4 *)(V + (size_t)3 * 64 * ts0), gate_status(c));
+  }
   if (c->eis_fuse) {  // p = (D~+U)^-1 ph with ph = D~ t + beta ph formed by each row's own lane on the way (k_eis_backward)
     ClockScope cs(c, 1);
     const int spb = c->ssor_bs / 64;
-    for (int col = S.ncolor - 1; col >= 0; col--) {
+    if (tc0 < S.ncolor) {
+      hipLaunchKernelGGL((k_eis_backward_df<4>), dim3(tgrid[0]), dim3(256), 0, c->stream, ts0, ts1, S.U.pair_ptr, S.U.val2, S.U.col2, S.alu,
+                         c->st, DT, PH, P, gate_status(c), c->df_err, c->dbg_df_fail ? 1 : 0);
+      c->eis_tail_launches++;
+    }
+    for (int col = tc0 - 1; col >= 0; col--) {
       const int s0 = S.color_slice[col], s1 = S.color_slice[col + 1];
       if (s1 <= s0) continue;
       if (s1 - s0 <= c->split_max_slices)
@@ -2177,7 +2221,7 @@ static int eis_cg_iteration(fx_context *c, int it) {
     ClockScope cs(c, 0);
     const int spb = c->ssor_bs / 64;
     int off = 0;
-    for (int col = 0; col < S.ncolor; col++) {
+    for (int col = 0; col < tc0; col++) {
       const int s0 = S.color_slice[col], s1 = S.color_slice[col + 1];
       if (s1 <= s0) continue;
       int g = (s1 - s0 + spb - 1) / spb;
@@ -2192,6 +2236,12 @@ static int eis_cg_iteration(fx_context *c, int it) {
         hipLaunchKernelGGL((k_eis_forward<256>), dim3(g), dim3(256), 0, c->stream, s0, s1, S.L.pair_ptr, S.L.val2, S.L.col2, S.alu,
                            esc, PH, P, V, WH, Q, c->partials, off, gate_status(c), HP);
       off += g;
+    }
+    if (tc0 < S.ncolor) {  // the tail: one partial per slice, where the launch per colour puts it
+      hipLaunchKernelGGL((k_eis_forward_df<4>), dim3(tgrid[1]), dim3(256), 0, c->stream, ts0, ts1, S.L.pair_ptr, S.L.val2, S.L.col2, S.alu,
+                         esc, PH, P, V, WH, Q, c->partials, off, gate_status(c), c->df_err, c->dbg_df_fail ? 1 : 0);
+      c->eis_tail_launches++;
+      off += ts1 - ts0;
     }
     HIP_TRY(hipGetLastError());
     if (off > c->max_partials) { g_fx_error = "eisenstat: partial-sum buffer too small"; return FX_ERROR_RUNTIME; }
@@ -3073,6 +3123,14 @@ extern "C" int fx_get_stats(fx_context *c, int64_t out[16]) {
   out[13] = c->M.n_wg_interior; out[14] = c->M.n_wg_boundary;  // SpMV workgroups overlapped with / ordered after the halo exchange
   out[15] = (c->eis_active ? 1 : 0) | (c->precond_kind == 11 ? 2 : 0) | ((int64_t)(c->df_mode & 3) << 2) | ((int64_t)std::min(c->df_fallbacks, 255) << 8) |
            ((int64_t)c->df_grid_last << 16);   // bit 0: the last Krylov loop ran in Eisenstat's form; bit 1: PRECOND = 1 runs as the natural-order SSOR
+  return 0;
+}
+
+// The dataflow tail of the Eisenstat sweeps (k_eis_*_df): out[0] first tail colour of the last iteration (ncolor: none), [1] its
+// slices, [2] workgroups of its backward launch, [3] tail launches enqueued or captured by this context, [4] colours, [5] the co-resident grid.
+extern "C" int fx_eis_tail_stats(fx_context *c, int64_t out[6]) {
+  out[0] = c->eis_tail_color0; out[1] = c->eis_tail_slices; out[2] = c->eis_tail_grid; out[3] = c->eis_tail_launches;
+  out[4] = c->ssor.ncolor; out[5] = std::min(c->eis_df_grid_max[0], c->eis_df_grid_max[1]);
   return 0;
 }
 

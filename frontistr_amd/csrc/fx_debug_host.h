@@ -281,3 +281,22 @@ extern "C" int fx_debug_march_rounds(fx_context *c, int32_t chunk, double *out, 
   }
   return 0;
 }
+
+// The multicolour SSOR layout, colour by colour (scripts/r5/eis_colour_table.py): slice range of every colour and the block
+// positions (64 rows each, padding included) of its strictly-lower and strictly-upper rows.  out holds 3 * (ncolor + 1) values:
+// color_slice[0..ncolor], then L.pair_ptr and U.pair_ptr at those slices.  Returns ncolor through *ncolor (0: no SSOR set up).
+extern "C" int fx_debug_ssor_colours(fx_context *c, int64_t *out, int32_t cap, int32_t *ncolor) {
+  const SsorDev &S = c->ssor;
+  *ncolor = S.ncolor;
+  if (S.ncolor <= 0 || !S.L.pair_ptr || !S.U.pair_ptr) { *ncolor = 0; return 0; }
+  if (cap < 3 * (S.ncolor + 1)) { g_fx_error = "fx_debug_ssor_colours: buffer too small"; return FX_ERROR_RUNTIME; }
+  for (int k = 0; k <= S.ncolor; k++) {
+    int32_t l = 0, u = 0;
+    HIP_TRY(hipMemcpy(&l, S.L.pair_ptr + S.color_slice[k], 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&u, S.U.pair_ptr + S.color_slice[k], 4, hipMemcpyDeviceToHost));
+    out[k] = S.color_slice[k];
+    out[S.ncolor + 1 + k] = l;
+    out[2 * (S.ncolor + 1) + k] = u;
+  }
+  return 0;
+}

@@ -137,6 +137,12 @@ struct DiagDev {
 
 // Scalars of the Krylov loops, resident on the device; the host only polls `status`.
 #define FX_DF_RETRY (-77)  // internal: a dataflow sweep timed out, the context switched to df_mode 0, redo the work
+// The dataflow tail of the Eisenstat sweeps (eis_tail, fistr_hip.hip): a colour of at most EIS_TAIL_GRIDS x G slices is latency-bound,
+// G = the smaller co-resident grid of k_eis_*_df (at most EIS_DF_MAX_PER_CU workgroups per CU).  At 10.1 M DOF on 256 CUs the big
+// colours have 5,274 slices and the others at most 1,456 (profiles/r05_eis_colour_times_before.txt): any G from 364 to 1,318 separates
+// them, and G is 768 there (3 forward workgroups per CU); EIS_DF_MAX_PER_CU keeps G at or below 1,024 on such a device.
+#define EIS_TAIL_GRIDS 4
+#define EIS_DF_MAX_PER_CU 4
 #define FX_ST_PAUSED 2  // KrylovState::status: waiting for the host to enqueue the true-residual check (hecmw_solver_CG.f90:259-266)
 struct KrylovState {
   double rho, rho1, beta, c1, alpha, omega, c2, cg0, cg1, dnrm2, bnrm2, resid, tol;
@@ -325,7 +331,8 @@ struct fx_context {
   int split_max_slices = 1 << 30;
   int split_wps = 0;
   // Dataflow triangular sweeps (k_tri_dataflow): one persistent launch per apply, rows synchronised through
-  // sentinel-tagged data instead of one launch per colour / level.  FX_DATAFLOW=0 off, 1 (default) ILU(0) levels,
+  // sentinel-tagged data instead of one launch per colour / level.  FX_DATAFLOW=0 off, 1 (default) ILU(0) levels and the
+  // latency-bound tail colours of the fused Eisenstat sweeps (k_eis_*_df, eis_tail),
   // 2 also the multicolour SSOR (measured slower than the colour launches: 1.59-1.71 against 1.50 ms per apply -- the big
   // colours are bandwidth-bound and a few hundred workgroups with one slice each in flight do not saturate HBM).
   // FX_DF_GRID workgroups (default: one per two CUs), FX_DF_WPS waves per slice (2, 4, 8), FX_DF_POLL 0 = every poll
@@ -377,6 +384,11 @@ struct fx_context {
   int eis_grid = 0;  // FX_EIS_GRID: most workgroups of one colour launch of the wave-split Eisenstat sweeps (a workgroup then walks slices b, b + grid, ...); 0 = one workgroup per slice
   bool dbg_onecolor = false; // measurement only (FX_DEBUG_ONECOLOR): the half sweeps as one launch each, dependencies ignored
   bool eis_fuse = true;      // direction update fused into the backward sweep (FX_EIS_FUSE=0: k_cg_update_p + the plain sweep)
+  // The latency-bound tail of the fused Eisenstat sweeps as one dataflow launch per half sweep (k_eis_backward_df / k_eis_forward_df,
+  // FX_DATAFLOW >= 1, one rank): the run of colours at the end of the colour order with at most EIS_TAIL_GRIDS x grid slices each.
+  int eis_df_grid_max[2] = {128, 128};  // co-resident workgroups of k_eis_backward_df<4> / k_eis_forward_df<4> (occupancy query at fx_create)
+  int eis_tail_color0 = 0, eis_tail_slices = 0, eis_tail_grid = 0;  // the tail of the last iteration: first colour, slices, workgroups
+  int64_t eis_tail_launches = 0;        // dataflow tail launches enqueued (or captured) by this context
   int64_t values_epoch = 0;  // counts the refreshes of the SpMV layout's values
   bool layout_device = true;        // BELL source maps built by k_bell_count / k_bell_map (FX_LAYOUT_DEVICE=0: host threads)
   int32_t mc_batch = 32;            // rounds of the device multicolouring between two looks at the queue length by the host (FX_MC_BATCH)

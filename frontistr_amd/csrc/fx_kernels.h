@@ -500,6 +500,20 @@ __global__ __launch_bounds__(64 * WPS) void k_ssor_color_split(int32_t slice0, i
   if (!FWD && partials) block_sum_store<1, 64 * WPS>(d, partials, 0, blockIdx.x);
 }
 
+// Hand-off words of the dataflow sweeps (k_tri_dataflow, k_eis_*_df; see "Dataflow triangular sweeps" below).
+#define FX_DF_SENTINEL (-1LL)          // 0xFFFFFFFFFFFFFFFF: a NaN pattern no arithmetic instruction produces
+#define FX_DF_TIMEOUT_TICKS 200000000ull  // 2 s of the 100 MHz constant clock
+
+__device__ __forceinline__ double df_load(const double *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+typedef unsigned int fx_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void df_store(double *p, double v) {
+  if (__double_as_longlong(v) == FX_DF_SENTINEL) v = __longlong_as_double(0x7FF8000000000000LL);  // keep the tag unique
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+
 // ------------------------------------------------------------------------
 // Eisenstat's form of CG + multicolour SSOR (opt-in; fx_context::eisenstat).  Per iteration, with ph = (D~+U) p carried
 // instead of p:   ph = D~ t + beta ph                      (k_cg_update_p on (dt, ph))
@@ -570,8 +584,35 @@ __device__ __forceinline__ void bell_row_sweep_dual(int h0, int h1, const double
   }
 }
 
-// the row's own part of the forward Eisenstat sweep, from the two block sums sv = (L v)_i, sp = (L p)_i; returns ph_i . w_i
+// the row's own part of the forward Eisenstat sweep, from the two block sums sv = (L v)_i, sp = (L p)_i and the row's own operands
+// (diagonal factor u, p, ph); returns ph_i . w_i.  PUB: v is published with df_store (the dataflow tail, k_eis_forward_df).
 // esc = (SIGMA_DIAG - 1) / SIGMA_DIAG: (D~ - D) p = esc * diag(D~) p (SIGMA_DIAG scales the three scalar diagonal entries only).
+template <bool PUB>
+__device__ __forceinline__ double eis_forward_finish_own(size_t o, const double (&u)[9], double p0, double p1, double p2,
+                                                         double h0v, double h1v, double h2v, const double (&sv)[3],
+                                                         const double (&sp)[3], double esc, double *v, double *__restrict__ w,
+                                                         double *__restrict__ q, const double *__restrict__ hp) {
+  const double pd = h0v, pe = h1v, pf = h2v;  // ph itself (the dot product p.q = ph.w uses it without the halo term)
+  if (hp) {  // subdomain: A = (D~+L) + (D~+U) + (D - 2D~) + H with H the halo columns; H p enters g and q alike
+    h0v += hp[o]; h1v += hp[o + 1]; h2v += hp[o + 2];
+  }
+  double Tp0, Tp1, Tp2, d0, d1, d2;   // D~ p and diag(D~) from the factors
+  lumul33_dev(u, p0, p1, p2, Tp0, Tp1, Tp2, d0, d1, d2);
+  const double e0 = esc * d0 * p0, e1 = esc * d1 * p1, e2 = esc * d2 * p2;  // (D~ - D) p
+  // g = ph + H p + (D - 2 D~) p = ph + H p - D~ p - (D~ - D) p ;  v = D~^-1 (g - L v)
+  double x1 = h0v - Tp0 - e0 - sv[0], x2 = h1v - Tp1 - e1 - sv[1], x3 = h2v - Tp2 - e2 - sv[2];
+  lusolve33_dev(u, x1, x2, x3);
+  if (PUB) {
+    df_store(v + o, x1); df_store(v + o + 1, x2); df_store(v + o + 2, x3);
+  } else {
+    v[o] = x1; v[o + 1] = x2; v[o + 2] = x3;
+  }
+  const double w0 = p0 + x1, w1 = p1 + x2, w2 = p2 + x3;
+  w[o] = w0; w[o + 1] = w1; w[o + 2] = w2;
+  // q = A p = ph + H p + L p + (D - D~) p
+  q[o] = h0v + sp[0] - e0; q[o + 1] = h1v + sp[1] - e1; q[o + 2] = h2v + sp[2] - e2;
+  return pd * w0 + pe * w1 + pf * w2;
+}
 __device__ __forceinline__ double eis_forward_finish(int slice, int lane, const double (&sv)[3], const double (&sp)[3],
                                                      const double *__restrict__ alu, double esc,
                                                      const double *__restrict__ ph, const double *__restrict__ p,
@@ -582,24 +623,9 @@ __device__ __forceinline__ double eis_forward_finish(int slice, int lane, const 
   const size_t base = (size_t)slice * 576 + lane;
 #pragma unroll
   for (int e = 0; e < 9; e++) u[e] = alu[base + (size_t)e * 64];
-  const double p0 = p[(size_t)3 * slot], p1 = p[(size_t)3 * slot + 1], p2 = p[(size_t)3 * slot + 2];
-  double h0v = ph[(size_t)3 * slot], h1v = ph[(size_t)3 * slot + 1], h2v = ph[(size_t)3 * slot + 2];
-  const double pd = h0v, pe = h1v, pf = h2v;  // ph itself (the dot product p.q = ph.w uses it without the halo term)
-  if (hp) {  // subdomain: A = (D~+L) + (D~+U) + (D - 2D~) + H with H the halo columns; H p enters g and q alike
-    h0v += hp[(size_t)3 * slot]; h1v += hp[(size_t)3 * slot + 1]; h2v += hp[(size_t)3 * slot + 2];
-  }
-  double Tp0, Tp1, Tp2, d0, d1, d2;   // D~ p and diag(D~) from the factors
-  lumul33_dev(u, p0, p1, p2, Tp0, Tp1, Tp2, d0, d1, d2);
-  const double e0 = esc * d0 * p0, e1 = esc * d1 * p1, e2 = esc * d2 * p2;  // (D~ - D) p
-  // g = ph + H p + (D - 2 D~) p = ph + H p - D~ p - (D~ - D) p ;  v = D~^-1 (g - L v)
-  double x1 = h0v - Tp0 - e0 - sv[0], x2 = h1v - Tp1 - e1 - sv[1], x3 = h2v - Tp2 - e2 - sv[2];
-  lusolve33_dev(u, x1, x2, x3);
-  v[(size_t)3 * slot] = x1; v[(size_t)3 * slot + 1] = x2; v[(size_t)3 * slot + 2] = x3;
-  const double w0 = p0 + x1, w1 = p1 + x2, w2 = p2 + x3;
-  w[(size_t)3 * slot] = w0; w[(size_t)3 * slot + 1] = w1; w[(size_t)3 * slot + 2] = w2;
-  // q = A p = ph + H p + L p + (D - D~) p
-  q[(size_t)3 * slot] = h0v + sp[0] - e0; q[(size_t)3 * slot + 1] = h1v + sp[1] - e1; q[(size_t)3 * slot + 2] = h2v + sp[2] - e2;
-  return pd * w0 + pe * w1 + pf * w2;
+  const size_t o = (size_t)3 * slot;
+  const double p0 = p[o], p1 = p[o + 1], p2 = p[o + 2];
+  return eis_forward_finish_own<false>(o, u, p0, p1, p2, ph[o], ph[o + 1], ph[o + 2], sv, sp, esc, v, w, q, hp);
 }
 
 template <int BS>
@@ -727,6 +753,27 @@ __global__ __launch_bounds__(BS) void k_eis_backward(int32_t slice0, int32_t sli
   eis_backward_finish(slice, lane, s0, s1, s2, alu, st, dt, ph, p);
 }
 
+// the wave-split kernels' finish from the row's preloaded operands (diagonal factor fu, dt, old ph); PUB: p is published with
+// df_store (the dataflow tail, k_eis_backward_df)
+template <bool PUB>
+__device__ __forceinline__ void eis_backward_finish_own(size_t o, const double (&fu)[9], const double (&fd)[3], const double (&fp)[3],
+                                                        double s0, double s1, double s2, const KrylovState *__restrict__ st,
+                                                        double *__restrict__ ph, double *p) {
+  double g0 = fd[0], g1 = fd[1], g2 = fd[2];
+  if (st->iter != 1) {
+    const double beta = st->beta;
+    g0 = g0 + beta * fp[0]; g1 = g1 + beta * fp[1]; g2 = g2 + beta * fp[2];
+  }
+  ph[o] = g0; ph[o + 1] = g1; ph[o + 2] = g2;
+  double x1 = g0 - s0, x2 = g1 - s1, x3 = g2 - s2;
+  lusolve33_dev(fu, x1, x2, x3);
+  if (PUB) {
+    df_store(p + o, x1); df_store(p + o + 1, x2); df_store(p + o + 2, x3);
+  } else {
+    p[o] = x1; p[o + 1] = x2; p[o + 2] = x3;
+  }
+}
+
 template <int WPS>
 __global__ __launch_bounds__(64 * WPS) void k_eis_backward_split(int32_t slice0, int32_t slice1, const int32_t *__restrict__ pair_ptr,
                                                                  const double *__restrict__ val2, const int *__restrict__ col2,
@@ -777,18 +824,7 @@ __global__ __launch_bounds__(64 * WPS) void k_eis_backward_split(int32_t slice0,
       s0 = part[0][0][lane]; s1 = part[0][1][lane]; s2 = part[0][2][lane];
 #pragma unroll
       for (int k = 1; k < WPS; k++) { s0 += part[k][0][lane]; s1 += part[k][1][lane]; s2 += part[k][2][lane]; }
-      {
-        const size_t o = (size_t)3 * (slice * 64 + lane);
-        double g0 = fd[0], g1 = fd[1], g2 = fd[2];
-        if (st->iter != 1) {
-          const double beta = st->beta;
-          g0 = g0 + beta * fp[0]; g1 = g1 + beta * fp[1]; g2 = g2 + beta * fp[2];
-        }
-        ph[o] = g0; ph[o + 1] = g1; ph[o + 2] = g2;
-        double x1 = g0 - s0, x2 = g1 - s1, x3 = g2 - s2;
-        lusolve33_dev(fu, x1, x2, x3);
-        p[o] = x1; p[o + 1] = x2; p[o + 2] = x3;
-      }
+      eis_backward_finish_own<false>((size_t)3 * (slice * 64 + lane), fu, fd, fp, s0, s1, s2, st, ph, p);
     }
     if (slice + (int)gridDim.x < slice1) __syncthreads();
   }
@@ -861,6 +897,233 @@ __global__ __launch_bounds__(FX_BLOCK) void k_eis_update(int32_t nslots, const K
 }
 
 // ------------------------------------------------------------------------
+// The latency-bound tail of the Eisenstat sweeps as ONE dataflow launch per half sweep.  The colours
+// at the end of the colour order with few slices each (fx_context: eis_tail) form one slot range [tail0, nslots); the big colours
+// keep their launches.  The backward sweep runs the tail first (colours descending), the forward sweep last (ascending).  Inside the
+// launch the data is the flag, as in k_tri_dataflow: the swept vector's tail range (p backward, v forward) holds FX_DF_SENTINEL
+// (k_eis_tag), a row publishes its entries with df_store, and a gathered entry of the tail range is re-read with agent-scope loads
+// until it is not the sentinel.  Entries below tail0 (v of the big colours) and p in the forward sweep are final: plain loads.
+// Workgroup b takes tail slices b, b + G, ... in the sweep's order; a slice only waits for slices earlier in that order, so the
+// first unfinished slice can always run -- provided all G workgroups are resident (G <= the occupancy bound, eis_df_grid_max).
+// Per row: the same operands in the same order as k_eis_*_split<WPS> (pairs i = w, w + WPS, ... of wave w, the odd block by wave
+// np % WPS, the LDS sum in wave order, the same finish): bit-identical to the launch per colour.
+// ------------------------------------------------------------------------
+// Gather x at the NB block columns `col` of one lane: an entry at or above tail0 waits until it is not the sentinel (bounded as
+// df_gather); a padding block (col == self) contributes 0 whatever its slot holds.  PLAIN: no entry is produced in this launch.
+template <int NB>
+__device__ __forceinline__ void eis_df_gather(const double *x, const int (&col)[NB], int self, int tail0, double (&g)[3 * NB],
+                                              int32_t *__restrict__ err, bool &dead) {
+  bool miss[3 * NB];
+  bool any = false;
+#pragma unroll
+  for (int b = 0; b < NB; b++) {
+    const bool tag = col[b] >= tail0 && col[b] != self;
+    const double *xa = x + (size_t)3 * col[b];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      g[3 * b + k] = tag ? df_load(xa + k) : xa[k];
+      miss[3 * b + k] = tag && __double_as_longlong(g[3 * b + k]) == FX_DF_SENTINEL;
+      any |= miss[3 * b + k];
+    }
+    if (col[b] == self) { g[3 * b] = 0.0; g[3 * b + 1] = 0.0; g[3 * b + 2] = 0.0; }
+  }
+  if (!__any(any) || dead) return;  // a wave that has given up takes what is there: the launch drains without waiting
+  unsigned long long t0 = 0;
+  for (unsigned spins = 1;; spins++) {
+    any = false;
+    double v[3 * NB];
+#pragma unroll
+    for (int e = 0; e < 3 * NB; e++) v[e] = df_load(x + (size_t)3 * (miss[e] ? col[e / 3] : 0) + (e % 3));
+#pragma unroll
+    for (int e = 0; e < 3 * NB; e++) {
+      if (miss[e]) {
+        g[e] = v[e];
+        miss[e] = __double_as_longlong(v[e]) == FX_DF_SENTINEL;
+        any |= miss[e];
+      }
+    }
+    if (!__any(any)) return;
+    if ((spins & 255u) == 0u) {  // bounded: give up after FX_DF_TIMEOUT_TICKS, or as soon as somebody else has
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+      if (t0 == 0) t0 = now;
+      const int e = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (e != 0 || now - t0 > FX_DF_TIMEOUT_TICKS) {
+        if (e == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        dead = true;
+        return;
+      }
+    }
+  }
+}
+
+// Tag fill of the two tail ranges (p and v, n16 16-byte words each) before an iteration's sweeps: write-through stores as k_df_fill,
+// gated like the sweeps so that a parked loop leaves the vectors alone.
+__global__ __launch_bounds__(256) void k_eis_tag(int64_t n16, fx_u4 *__restrict__ a, fx_u4 *__restrict__ b, const int32_t *__restrict__ gate) {
+  if (gate && *gate != 0) return;
+  const fx_u4 tag = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(a + i), "v"(tag) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(b + i), "v"(tag) : "memory");
+  }
+}
+
+// Co-resident workgroups of 4 waves per CU the compiler is held to: 3 for both (137 / 160 VGPRs, no spill; 768 workgroups on 256
+// CUs).  Same-process pairs at 10.1 M DOF, ms per iteration saved by the tail against FX_DATAFLOW=0: backward 3 0.050-0.053, backward
+// 4 (128 VGPRs, 52 bytes of spill) 0.042; forward 4 without the preloaded own operands (128 VGPRs) 0.044-0.053.
+#define EIS_DF_BLOCKS_BWD 3
+#define EIS_DF_BLOCKS_FWD 3
+
+// backward tail: slices [s0, s1) descending; p = (D~+U)^-1 ph with ph = dt + beta ph on the way (k_eis_backward_split)
+template <int WPS>
+__global__ __launch_bounds__(64 * WPS, EIS_DF_BLOCKS_BWD) void k_eis_backward_df(int32_t s0, int32_t s1, const int32_t *__restrict__ pair_ptr,
+                                                              const double *__restrict__ val2, const int *__restrict__ col2,
+                                                              const double *__restrict__ alu, const KrylovState *__restrict__ st,
+                                                              const double *__restrict__ dt, double *__restrict__ ph, double *p,
+                                                              const int32_t *__restrict__ gate, int32_t *__restrict__ err, int fail) {
+  if (gate && *gate != 0) return;
+  if (fail) {  // test hook (FX_DEBUG_DF_FAIL): a launch whose bounded wait ran out at once -- nothing usable written, err raised
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  __shared__ double part[2][WPS][3][64];  // double-buffered: one workgroup barrier per slice
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tail0 = s0 * 64;
+  bool dead = false;
+  int buf = 0;
+  for (int slice = s1 - 1 - (int)blockIdx.x; slice >= s0; slice -= gridDim.x, buf ^= 1) {
+    const int h0 = pair_ptr[slice], h1 = pair_ptr[slice + 1];
+    const int np = (h1 - h0) >> 1, self = slice * 64 + lane;
+    double s0v = 0.0, s1v = 0.0, s2v = 0.0;
+    double fu[9], fd[3], fp[3];
+    if (w == 0) {  // the finishing wave's own operands: in flight before the first wait
+      const size_t o = (size_t)3 * self, base = (size_t)slice * 576 + lane;
+#pragma unroll
+      for (int e = 0; e < 9; e++) fu[e] = alu[base + (size_t)e * 64];
+#pragma unroll
+      for (int k = 0; k < 3; k++) { fd[k] = dt[o + k]; fp[k] = ph[o + k]; }
+    }
+    const double2 *vbase = (const double2 *)(val2 + (size_t)h0 * 576) + lane;
+    const int2 *cbase = (const int2 *)(col2 + (size_t)h0 * 64) + lane;
+    // the column ids of the wave's next pair are loaded before this pair waits: its blocks and gathers then need no round trip first
+    auto pair = [&](int i, int2 cc) {
+      double2 a[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) a[e] = ld_stream(vbase + (size_t)i * 576 + e * 64);
+      const int cols[2] = {cc.x, cc.y};
+      double x[6];
+      eis_df_gather<2>(p, cols, self, tail0, x, err, dead);
+      bell_pair_fma(a, x, s0v, s1v, s2v);
+    };
+    int2 cn = w < np ? ld_stream(cbase + (size_t)w * 64) : make_int2(0, 0);
+    for (int i = w; i < np; i += WPS) {
+      const int2 cc = cn;
+      if (i + WPS < np) cn = ld_stream(cbase + (size_t)(i + WPS) * 64);
+      pair(i, cc);
+    }
+    if (((h1 - h0) & 1) && w == (np % WPS)) {  // the odd last block of the slice, stored alone
+      const double *vt = val2 + (size_t)(h0 + 2 * np) * 576 + lane;
+      const int cols[1] = {ld_stream(col2 + (size_t)(h0 + 2 * np) * 64 + lane)};
+      double a[9], x[3];
+#pragma unroll
+      for (int e = 0; e < 9; e++) a[e] = ld_stream(vt + e * 64);
+      eis_df_gather<1>(p, cols, self, tail0, x, err, dead);
+      bell_single_fma(a, x, s0v, s1v, s2v);
+    }
+    part[buf][w][0][lane] = s0v; part[buf][w][1][lane] = s1v; part[buf][w][2][lane] = s2v;
+    __syncthreads();
+    if (w == 0) {
+      s0v = part[buf][0][0][lane]; s1v = part[buf][0][1][lane]; s2v = part[buf][0][2][lane];
+#pragma unroll
+      for (int k = 1; k < WPS; k++) { s0v += part[buf][k][0][lane]; s1v += part[buf][k][1][lane]; s2v += part[buf][k][2][lane]; }
+      eis_backward_finish_own<true>((size_t)3 * self, fu, fd, fp, s0v, s1v, s2v, st, ph, p);
+    }
+  }
+}
+
+// forward tail: slices [s0, s1) ascending; v, w, q and the partial of ph.w of every slice at partials[part0 + slice - s0] (where
+// k_eis_forward_split with one workgroup per slice puts it: OP_CG_C1 sums the same numbers in the same order)
+template <int WPS>
+__global__ __launch_bounds__(64 * WPS, EIS_DF_BLOCKS_FWD) void k_eis_forward_df(int32_t s0, int32_t s1, const int32_t *__restrict__ pair_ptr,
+                                                             const double *__restrict__ val2, const int *__restrict__ col2,
+                                                             const double *__restrict__ alu, double esc,
+                                                             const double *__restrict__ ph, const double *__restrict__ p, double *v,
+                                                             double *__restrict__ w, double *__restrict__ q,
+                                                             double *__restrict__ partials, int32_t part0,
+                                                             const int32_t *__restrict__ gate, int32_t *__restrict__ err, int fail) {
+  if (gate && *gate != 0) return;
+  if (fail) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  __shared__ double part[2][WPS][6][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, tail0 = s0 * 64;
+  bool dead = false;
+  int buf = 0;
+  for (int slice = s0 + (int)blockIdx.x; slice < s1; slice += gridDim.x, buf ^= 1) {
+    const int h0 = pair_ptr[slice], h1 = pair_ptr[slice + 1];
+    const int np = (h1 - h0) >> 1, self = slice * 64 + lane;
+    const size_t o = (size_t)3 * self;
+    double u[9], op[3], oh[3];
+    if (wv == 0) {  // the finishing wave's own operands: in flight before the first wait
+      const size_t base = (size_t)slice * 576 + lane;
+#pragma unroll
+      for (int e = 0; e < 9; e++) u[e] = alu[base + (size_t)e * 64];
+#pragma unroll
+      for (int k = 0; k < 3; k++) { op[k] = p[o + k]; oh[k] = ph[o + k]; }
+    }
+    double sv[3] = {0.0, 0.0, 0.0}, sp[3] = {0.0, 0.0, 0.0};
+    const double2 *vbase = (const double2 *)(val2 + (size_t)h0 * 576) + lane;
+    const int2 *cbase = (const int2 *)(col2 + (size_t)h0 * 64) + lane;
+    auto pair = [&](int i, int2 cc) {  // as in k_eis_backward_df: the next pair's column ids in flight before this pair waits
+      double2 a[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) a[e] = ld_stream(vbase + (size_t)i * 576 + e * 64);
+      double gp[6];
+#pragma unroll
+      for (int k = 0; k < 3; k++) { gp[k] = p[(size_t)3 * cc.x + k]; gp[3 + k] = p[(size_t)3 * cc.y + k]; }
+      const int cols[2] = {cc.x, cc.y};
+      double gv[6];
+      eis_df_gather<2>(v, cols, self, tail0, gv, err, dead);
+      bell_pair_fma(a, gv, sv[0], sv[1], sv[2]);
+      bell_pair_fma(a, gp, sp[0], sp[1], sp[2]);
+    };
+    int2 cn = wv < np ? ld_stream(cbase + (size_t)wv * 64) : make_int2(0, 0);
+    for (int i = wv; i < np; i += WPS) {
+      const int2 cc = cn;
+      if (i + WPS < np) cn = ld_stream(cbase + (size_t)(i + WPS) * 64);
+      pair(i, cc);
+    }
+    if (((h1 - h0) & 1) && wv == (np % WPS)) {
+      const double *vt = val2 + (size_t)(h0 + 2 * np) * 576 + lane;
+      const int cc = ld_stream(col2 + (size_t)(h0 + 2 * np) * 64 + lane);
+      double a[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) a[e] = ld_stream(vt + e * 64);
+      const double ap[3] = {p[(size_t)3 * cc], p[(size_t)3 * cc + 1], p[(size_t)3 * cc + 2]};
+      const int cols[1] = {cc};
+      double av[3];
+      eis_df_gather<1>(v, cols, self, tail0, av, err, dead);
+      bell_single_fma(a, av, sv[0], sv[1], sv[2]);
+      bell_single_fma(a, ap, sp[0], sp[1], sp[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { part[buf][wv][k][lane] = sv[k]; part[buf][wv][3 + k][lane] = sp[k]; }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) { sv[k] = part[buf][0][k][lane]; sp[k] = part[buf][0][3 + k][lane]; }
+#pragma unroll
+      for (int j = 1; j < WPS; j++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) { sv[k] += part[buf][j][k][lane]; sp[k] += part[buf][j][3 + k][lane]; }
+      double dsum = 0.0;
+      dsum += eis_forward_finish_own<true>(o, u, op[0], op[1], op[2], oh[0], oh[1], oh[2], sv, sp, esc, v, w, q, nullptr);
+      dsum = wave_sum(dsum);
+      if (lane == 0) partials[part0 + (slice - s0)] = dsum;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------
 // Dataflow triangular sweeps: ONE persistent launch per preconditioner apply instead of one launch per colour / per
 // ILU(0) dependency level (1,044 levels x 2 half sweeps at 10M DOF; each level is ~50 slices, i.e. a few microseconds
 // of dependent latency and almost no bandwidth).  There is no grid barrier either: the DATA is the flag.  Both sweep
@@ -879,20 +1142,8 @@ __global__ __launch_bounds__(FX_BLOCK) void k_eis_update(int32_t nslots, const K
 // sweep can always run -- provided all G workgroups are resident (G <= CUs here).
 // Every spin is bounded by wall-clock time; a timeout raises *err (the host turns it into a runtime failure).
 // ------------------------------------------------------------------------
-#define FX_DF_SENTINEL (-1LL)          // 0xFFFFFFFFFFFFFFFF: a NaN pattern no arithmetic instruction produces
-#define FX_DF_TIMEOUT_TICKS 200000000ull  // 2 s of the 100 MHz constant clock
-
-__device__ __forceinline__ double df_load(const double *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void df_store(double *p, double v) {
-  if (__double_as_longlong(v) == FX_DF_SENTINEL) v = __longlong_as_double(0x7FF8000000000000LL);  // keep the tag unique
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Tag fill of the sweep vectors before a launch, with the same agent-scope write-through stores the hand-off itself uses
 // (a plain memset's lines can survive, stale, in another XCD's L2: per-XCD L2s are only kept coherent for sc1 traffic).
-typedef unsigned int fx_u4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void k_df_fill(int64_t n16, fx_u4 *__restrict__ a, fx_u4 *__restrict__ b) {
   const fx_u4 tag = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {

@@ -307,6 +307,14 @@ class SolverContext:
         st["eisenstat"] = v & 1
         return st
 
+    def eis_tail_stats(self):
+        """The dataflow tail of the Eisenstat sweeps (fx_eis_tail_stats): first tail colour of the last iteration (== ncolor: none),
+        its slices, workgroups of the backward tail launch, tail launches enqueued or captured so far, colours, co-resident grid."""
+        out = (C.c_int64 * 6)()
+        _chk(lib().fx_eis_tail_stats(self.h, out))
+        keys = ("color0", "slices", "grid", "launches", "ncolor", "grid_max")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
     def krylov_begin(self, hecMAT):
         _chk(lib().fx_krylov_begin(self.h, _ptr(hecMAT.Iarray), _ptr(hecMAT.Rarray)))
 

@@ -163,6 +163,12 @@ int fx_precond_apply_host(fx_context *ctx, const double *r, double *z);   /* z =
  * SpMV workgroups overlapped with the halo exchange (interior), ordered after it (boundary) | [15] bit 0: the last Krylov
  * loop ran in Eisenstat's form (the default for CG + multicolour SSOR, FX_EISENSTAT=0 opts out); bit 1: the ILU(0) sweeps are chain sweeps (FX_DATAFLOW=3) */
 int fx_get_stats(fx_context *ctx, int64_t out[16]);
+/* The dataflow tail of the Eisenstat sweeps (FX_DATAFLOW >= 1, one rank, CG + multicolour SSOR in Eisenstat's form): the colours at
+ * the end of the colour order with at most 4 x G slices each, G the co-resident grid of the tail kernels, run as ONE launch per half
+ * sweep instead of one per colour; bit-identical to FX_DATAFLOW=0.  out[0] first tail colour of the last iteration (== ncolor: no
+ * tail), [1] its slices, [2] workgroups of the backward tail launch, [3] tail launches enqueued or captured by this context,
+ * [4] colours, [5] G.  A tail launch that times out raises the same fallback as the other dataflow sweeps (df_fallbacks). */
+int fx_eis_tail_stats(fx_context *ctx, int64_t out[6]);
 /* Where the value arrays of the sliced layouts live: out[0] bytes of the context's value arena (one large allocation taken when the
  * size of a large system first becomes known, before anything else of it: 0 = none), [1] bytes in use, [2] arrays placed in it,
  * [3..5] 1 if the value array of the SpMV layout / the lower / the upper sweep layout lies in it, [6] bytes of the SpMV layout's

@@ -1,5 +1,5 @@
 """Same-context A/B at 10.1M DOF: ONE context (same data, same placement), the knobs flipped on it with fx_set_option between
-timings.  usage: python scripts/r3/ab_opts.py [--eis] [--method M --precond P] "K=V,K=V" "K=V" ...   ("default" is always first)"""
+timings.  usage: [AB_REPS=3] python scripts/r3/ab_opts.py [--eis] [--method M --precond P] "K=V,K=V" "K=V" ...   ("default" is always first)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 args = sys.argv[1:]
@@ -46,9 +46,9 @@ def it_ms(steps=40):
     it, status, resid = ctx.krylov_steps(steps)
     ctx.synchronize()
     return 1e3 * (time.perf_counter() - t0) / steps, resid
-for rep in range(3):
+for rep in range(int(os.environ.get("AB_REPS", "3"))):
     for v in variants:
         apply(v)
         ms, resid = it_ms()
-        print("rep %d  %-50s precond_apply %.4f ms  iteration %.4f ms  (resid %.3e, eisenstat=%d)"
-              % (rep, v, ctx.precond_apply_ms(10), ms, resid, ctx.stats()["eisenstat"]), flush=True)
+        print("rep %d  %-50s precond_apply %.4f ms  iteration %.4f ms  (resid %.3e, eisenstat=%d, df_fallbacks=%d)"
+              % (rep, v, ctx.precond_apply_ms(10), ms, resid, ctx.stats()["eisenstat"], ctx.stats()["df_fallbacks"]), flush=True)
