@@ -14,6 +14,7 @@
 
 #include "fx_assemble.h"
 #include "fx_assemble_tet.h"
+#include "fx_assemble_c3.h"
 #include "fx_kernels.h"
 #include "fx_nonlinear.h"
 

@@ -169,9 +169,10 @@ static void elem_colors_free(ElemColors &ec) {
   dev_free(ec.dup);
   ec = ElemColors();
 }
-// the position map of k_scatter_map for the resident profile and the device connectivity d_conn of nn-node elements (8, 4 or 10;
-// FX_ASM_MAP=0: search every time)
-#define FX_NN_DISPATCH(nn, F) ((nn) == 4 ? F<4> : ((nn) == 10 ? F<10> : F<8>))
+// the position map of k_scatter_map for the resident profile and the device connectivity d_conn of nn-node elements (8, 4, 10,
+// 6, 15 or 20; FX_ASM_MAP=0: search every time)
+#define FX_NN_DISPATCH(nn, F) \
+  ((nn) == 4 ? F<4> : ((nn) == 10 ? F<10> : ((nn) == 6 ? F<6> : ((nn) == 15 ? F<15> : ((nn) == 20 ? F<20> : F<8>)))))
 static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, bool with_first = false,
                               int nn = 8) {
   static const bool off = getenv("FX_ASM_MAP") && atoi(getenv("FX_ASM_MAP")) == 0;
@@ -244,7 +245,7 @@ static void split_collapsed(const int32_t *conn, std::vector<int32_t> &order, st
   off.swap(koff);
   if (dups.empty()) dup_off.clear();
 }
-// nn nodes per element of type etype (361: 8; 341: 4; 342: 10).  The colouring and the map are cached per (connectivity, type).
+// nn nodes per element of type etype (361: 8; 341: 4; 342: 10; 351: 6; 352: 15; 362: 20).  The colouring and the map are cached per (connectivity, type).
 static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *conn, int32_t NP, int nn = 8,
                               int32_t etype = 361) {
   static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
@@ -280,7 +281,7 @@ static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, con
   if (!fxo::color_elements(n_elem, nn, conn, NP, order, off)) return 0;  // a node in more than 64 elements: atomics
   ec.dup_nodes = false;
   for (int q = 0; q < nchunk; q++) ec.dup_nodes |= dup[q];
-  if (ec.dup_nodes && nn != 8) { g_fx_error = "element connectivity: a tetrahedron names a node twice"; return FX_ERROR_RUNTIME; }
+  if (ec.dup_nodes && nn != 8) { g_fx_error = "element connectivity: an element names a node twice"; return FX_ERROR_RUNTIME; }
   if (ec.dup_nodes) split_collapsed(conn, order, off, dups, dup_off);
   if (dev_alloc(&ec.order, std::max<size_t>(order.size(), 1)) || (!dups.empty() && dev_alloc(&ec.dup, dups.size())))
     return FX_ERROR_RUNTIME;
@@ -325,9 +326,36 @@ static void launch_assemble(fx_context *c, int32_t n_elem, const double *coord, 
 }
 
 // nodes per element of the types the linear device assembly knows; 0: none of them
-static int c3_nodes(int32_t etype) { return etype == 361 ? 8 : (etype == 341 ? 4 : (etype == 342 ? 10 : 0)); }
+static int c3_nodes(int32_t etype) {
+  switch (etype) {
+    case 361: return 8;
+    case 341: return 4;
+    case 342: return 10;
+    case 351: return 6;
+    case 352: return 15;
+    case 362: return 20;
+    default: return 0;
+  }
+}
+// the types of fx_assemble_c3 / fx_update_c3_linear / fx_element_stiffness_c3: what STF_C3 / UPDATE_C3 serve (361 has its own entries)
+static bool c3_linear_type(int32_t etype) { return etype != 361 && c3_nodes(etype) != 0; }
+// quadrature points per element (NumOfQuadPoints, element.f90:415-447)
+static int c3_points(int32_t etype) {
+  switch (etype) {
+    case 361: return 8;
+    case 341: return 1;
+    case 342: return 4;
+    case 351: return 2;
+    case 352: return 9;
+    case 362: return 27;
+    default: return 0;
+  }
+}
+#define FX_C3_UNSUPPORTED "element type not supported on the device (341, 342, 351, 352, 362; 361 through "
 
-// A tetrahedron that names a node twice has zero volume (the reference stops in getJacobian): refused, never assembled.
+
+// A tetrahedron, wedge or 20-node hexahedron that names a node twice is degenerate (the reference stops in getJacobian or
+// assembles a singular element): refused, never assembled.
 // One parallel pass with the node-id range check; the lowest offending element is named.
 static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int nn) {
   int32_t first_bad = INT32_MAX, first_dup = INT32_MAX;  // 0-based elements
@@ -349,7 +377,7 @@ static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int
     return FX_ERROR_RUNTIME;
   }
   if (first_dup != INT32_MAX) {
-    snprintf(msg, sizeof msg, "%s: element %d names a node twice (a tetrahedron of zero volume)", who, (int)first_dup + 1);
+    snprintf(msg, sizeof msg, "%s: element %d names a node twice (a degenerate element)", who, (int)first_dup + 1);
     g_fx_error = msg;
     return FX_ERROR_RUNTIME;
   }
@@ -377,7 +405,41 @@ static void launch_assemble_tet(fx_context *c, int32_t n_elem, const double *coo
                      (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
 }
 
-// etype 361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8; 341 / 342 through k_assemble_tet (elemopt unused)
+template <int ETYPE>
+static void launch_assemble_c3(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
+                               double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
+                               const ElemColors *ec) {
+  const DevCSR &A = c->A;
+  constexpr int EPB = FXC_EPB(ETYPE);
+  if (ec && !ec->offsets.empty() && !Kout) {
+    for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
+      const int32_t e0 = ec->offsets[k], e1 = ec->offsets[k + 1];
+      if (e1 > e0)
+        hipLaunchKernelGGL((k_assemble_c3<ETYPE>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXC_BS), 0, c->stream, e1, coord, conn, D11,
+                           D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
+                           (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
+    }
+    return;
+  }
+  hipLaunchKernelGGL((k_assemble_c3<ETYPE>), dim3((n_elem + EPB - 1) / EPB), dim3(FXC_BS), 0, c->stream, n_elem, coord, conn, D11, D12,
+                     D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
+                     (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
+}
+// 341 / 342 through k_assemble_tet, 351 / 352 / 362 through k_assemble_c3; false: not one of them
+static bool launch_assemble_c3_type(int32_t etype, fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11,
+                                    double D12, double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
+                                    const ElemColors *ec) {
+  switch (etype) {
+    case 341: launch_assemble_tet<341>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
+    case 342: launch_assemble_tet<342>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
+    case 351: launch_assemble_c3<351>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
+    case 352: launch_assemble_c3<352>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
+    case 362: launch_assemble_c3<362>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
+    default: return false;
+  }
+}
+
+// etype 361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8; the other types as launch_assemble_c3_type (elemopt unused)
 static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int32_t n_mat, const double *Es,
                                 const double *nus, const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
                                 const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble,
@@ -394,7 +456,7 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   if (!c->have_profile) return fail("upload the profile first (fx_upload FX_UP_PROFILE)", FX_ERROR_RUNTIME);
   if (mesh->n_node != c->A.NP) return fail("mesh/profile size mismatch", FX_ERROR_RUNTIME);
   if (etype == 361 && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
-  if (nn == 0) return fail("element type not supported on the device (341, 342; 361 through fx_assemble_c3d8)", FX_ERROR_UNSUPPORTED);
+  if (nn == 0) return fail(FX_C3_UNSUPPORTED "fx_assemble_c3d8)", FX_ERROR_UNSUPPORTED);
   if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;  // (361: its checks stay in the colouring)
   DevCSR &A = c->A;
   DevScratch tmp;
@@ -436,9 +498,8 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
     HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
     HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
   }
-  if (etype == 341) launch_assemble_tet<341>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
-  else if (etype == 342) launch_assemble_tet<342>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors);
-  else if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
+  if (launch_assemble_c3_type(etype, c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors)) {
+  } else if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   HIP_TRY(hipGetLastError());
@@ -521,13 +582,13 @@ extern "C" int fx_element_stiffness_c3d8(fx_context *c, int elemopt, const doubl
   return 0;
 }
 
-// ---- tetrahedra (TYPE=341, 342): fx_assemble_c3, fx_element_stiffness_c3 ------------------------------------------------
+// ---- tetrahedra, wedges, 20-node hexahedra (TYPE=341, 342, 351, 352, 362): fx_assemble_c3, fx_element_stiffness_c3 ------------------------------------------------
 extern "C" int fx_assemble_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                               const double *nu, const int32_t *elem_mat, const double *load, int32_t n_bc, const int32_t *bc_node,
                               const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
   if (!c || !mesh) { g_fx_error = "fx_assemble_c3: null argument"; return FX_ERROR_RUNTIME; }
-  if (etype != 341 && etype != 342) {
-    g_fx_error = "fx_assemble_c3: element type not supported on the device (341, 342; 361 through fx_assemble_c3d8)";
+  if (!c3_linear_type(etype)) {
+    g_fx_error = "fx_assemble_c3: " FX_C3_UNSUPPORTED "fx_assemble_c3d8)";
     return FX_ERROR_UNSUPPORTED;
   }
   if (n_mat < 1 || !E || !nu) { g_fx_error = "fx_assemble_c3: materials missing"; return FX_ERROR_RUNTIME; }
@@ -540,7 +601,7 @@ extern "C" int fx_assemble_c3(fx_context *c, const fx_mesh_view *mesh, int32_t e
 
 extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const double *ecoord, double E, double nu, double *stiff) {
   if (!c || !ecoord || !stiff) { g_fx_error = "fx_element_stiffness_c3: null argument"; return FX_ERROR_RUNTIME; }
-  if (etype != 341 && etype != 342) { g_fx_error = "fx_element_stiffness_c3: etype must be 341 or 342"; return FX_ERROR_UNSUPPORTED; }
+  if (!c3_linear_type(etype)) { g_fx_error = "fx_element_stiffness_c3: etype must be 341, 342, 351, 352 or 362"; return FX_ERROR_UNSUPPORTED; }
   HIP_TRY(hipSetDevice(c->device));
   const int nn = c3_nodes(etype), w = 3 * nn;
   DevScratch tmp;
@@ -548,14 +609,13 @@ extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const doubl
   int32_t *d_conn = nullptr, *d_err = nullptr;
   if (tmp.alloc(&d_coord, (size_t)w) || tmp.alloc(&d_conn, (size_t)nn) || tmp.alloc(&d_k, (size_t)w * w) || tmp.alloc(&d_err, 1))
     return FX_ERROR_RUNTIME;
-  const int32_t conn[10] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
+  const int32_t conn[20] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20};
   HIP_TRY(hipMemcpy(d_coord, ecoord, (size_t)w * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_conn, conn, (size_t)nn * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(d_err, 0, 4));
   double D11, D12, D44;
   elastic_constants(E, nu, D11, D12, D44);
-  if (etype == 341) launch_assemble_tet<341>(c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
-  else launch_assemble_tet<342>(c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
+  (void)launch_assemble_c3_type(etype, c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(stiff, d_k, (size_t)w * w * 8, hipMemcpyDeviceToHost));

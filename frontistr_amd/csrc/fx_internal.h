@@ -179,7 +179,7 @@ struct NlMat {
 struct ElemColors {
   int32_t n_elem = 0;
   uint64_t key = 0;                 // checksum of the connectivity the colouring belongs to
-  int32_t etype = 361;              // element type of that connectivity (361, 341, 342): a map of one type is never used for another
+  int32_t etype = 361;              // element type of that connectivity (361, 341, 342, 351, 352, 362): a map of one type is never used for another
   int32_t *order = nullptr;         // device: element ids, colour by colour
   std::vector<int32_t> offsets;     // host: first position of each colour (+ end); empty = not coloured (atomics)
   int32_t *pos = nullptr;           // device: nn^2 per element, position of block (a, b) in AL / AU (k_scatter_map), or null

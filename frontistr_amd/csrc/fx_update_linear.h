@@ -275,7 +275,8 @@ extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
 // materials (E, nu), elem_mat 1-based per element (NULL with one material); elemopt 1 IC, 2 B-bar, 3 FI; disp = total
 // displacement unode + dunode (3 * n_node, host).  Out: *strain, *stress = pinned host arrays owned by the library, valid until
 // the next call ([n_elem][8][6], the reference's gausses(1:8)%strain(1:6) / %stress(1:6)); qforce (3 * n_node, host, caller's).
-// etype 361 (elemopt 1..3, 8 quadrature points) through k_update_c3d8_linear; 341 / 342 (1 / 4 points) through k_update_tet.
+// etype 361 (elemopt 1..3, 8 quadrature points) through k_update_c3d8_linear; 341 / 342 (1 / 4 points) through k_update_tet;
+// 351 / 352 / 362 (2 / 9 / 27 points) through k_update_c3.
 // Results: [n_elem][nq][6] in the pinned staging.
 static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                                 const double *nu, const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
@@ -291,9 +292,9 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   };
   if (!mesh || !E || !nu || !disp || n_mat < 1) return fail("null argument", FX_ERROR_RUNTIME);
   if (hex && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
-  if (!hex && etype != 341 && etype != 342) return fail("element type not supported on the device (341, 342; 361 through fx_update_c3d8_linear)", FX_ERROR_UNSUPPORTED);
+  if (!hex && !c3_linear_type(etype)) return fail(FX_C3_UNSUPPORTED "fx_update_c3d8_linear)", FX_ERROR_UNSUPPORTED);
   const int32_t ne = mesh->n_elem, nn = mesh->n_node;
-  const int enn = c3_nodes(etype), nq = hex ? 8 : (etype == 341 ? 1 : 4);
+  const int enn = c3_nodes(etype), nq = c3_points(etype);
   const size_t per_elem = (size_t)6 * nq;  // doubles of strain (and of stress) per element
   if (ne < 1 || nn < 1) return fail("empty mesh", FX_ERROR_RUNTIME);
   if (hex) {
@@ -348,6 +349,13 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   else if (etype == 342)
     hipLaunchKernelGGL((k_update_tet<342>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
                        d_strain, d_stress, d_q);
+#define FXU_C3_LAUNCH(ET)                                                                                                      \
+  hipLaunchKernelGGL((k_update_c3<ET>), dim3((unsigned)((ne + FXC_UEPB(ET) - 1) / FXC_UEPB(ET))), dim3(FXC_BS), 0, c->stream, ne, \
+                     d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q)
+  else if (etype == 351) FXU_C3_LAUNCH(351);
+  else if (etype == 352) FXU_C3_LAUNCH(352);
+  else if (etype == 362) FXU_C3_LAUNCH(362);
+#undef FXU_C3_LAUNCH
   else if (elemopt == 1) FXU_LAUNCH(1);
   else if (elemopt == 2) FXU_LAUNCH(2);
   else FXU_LAUNCH(3);
@@ -376,13 +384,14 @@ extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, in
   return update_linear_common(c, mesh, 361, n_mat, E, nu, elem_mat, elemopt, disp, strain, stress, qforce, ms_kernel);
 }
 
-// The same for a group of tetrahedra (etype 341 or 342; UPDATE_C3): [n_elem][nq][6] with nq = 1 (341) or 4 (342).
+// The same for a group of tetrahedra, wedges or 20-node hexahedra (etype 341, 342, 351, 352 or 362; UPDATE_C3): [n_elem][nq][6]
+// with nq = 1, 4, 2, 9, 27.
 extern "C" int fx_update_c3_linear(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                                    const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
                                    const double **stress, double *qforce, float *ms_kernel) {
   if (!c) { g_fx_error = "fx_update_c3_linear: null argument"; return FX_ERROR_RUNTIME; }
-  if (etype != 341 && etype != 342) {
-    g_fx_error = "fx_update_c3_linear: element type not supported on the device (341, 342; 361 through fx_update_c3d8_linear)";
+  if (!c3_linear_type(etype)) {
+    g_fx_error = "fx_update_c3_linear: " FX_C3_UNSUPPORTED "fx_update_c3d8_linear)";
     return FX_ERROR_UNSUPPORTED;
   }
   return update_linear_common(c, mesh, etype, n_mat, E, nu, elem_mat, 3, disp, strain, stress, qforce, ms_kernel);

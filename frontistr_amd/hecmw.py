@@ -164,7 +164,7 @@ class hecmwST_local_mesh:
         self.export_item = np.zeros(0, dtype=np.int32)
         self.node = None            # 3*n_node coordinates
         self.elem_node_item = None  # flattened connectivity, 1-based
-        self.nn_elem = 8            # nodes per element of elem_node_item (8: TYPE=361, 4: 341, 10: 342)
+        self.nn_elem = 8            # nodes per element of elem_node_item (8: TYPE=361, 4: 341, 10: 342, 6: 351, 15: 352, 20: 362)
         self.n_elem = 0
 
     def comm_view(self):
@@ -173,6 +173,10 @@ class hecmwST_local_mesh:
                       _ptr(self.export_index), _ptr(self.export_item))
         v._keep = self
         return v
+
+
+_C3_NODES = {341: 4, 342: 10, 351: 6, 352: 15, 362: 20}      # nodes and quadrature points of the types of fx_assemble_c3
+_C3_POINTS = {341: 1, 342: 4, 351: 2, 352: 9, 362: 27}
 
 
 class SolverContext:
@@ -445,9 +449,9 @@ class SolverContext:
         return k
 
     def assemble_c3(self, coord, conn, etype, E, nu, load=None, bc=None, elem_mat=None):
-        """fstr_StiffMatrix + fstr_AddBC on the device for tetrahedra (fx_assemble_c3): etype 341 (conn (n_elem, 4)) or 342
-        (conn (n_elem, 10), FrontISTR's node order).  E, nu scalars, or per-material arrays with elem_mat (1-based per
-        element).  Returns the kernel milliseconds."""
+        """fstr_StiffMatrix + fstr_AddBC on the device for the elements of STF_C3 (fx_assemble_c3): etype 341 (conn (n_elem, 4)),
+        342 (n_elem, 10), 351 (n_elem, 6), 352 (n_elem, 15) or 362 (n_elem, 20), FrontISTR's node order.  E, nu scalars, or
+        per-material arrays with elem_mat (1-based per element).  Returns the kernel milliseconds."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
         Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
@@ -467,9 +471,9 @@ class SolverContext:
         return ms.value
 
     def update_c3_linear(self, coord, conn, etype, E, nu, disp, elem_mat=None):
-        """fstr_UpdateNewton of a linear static analysis of tetrahedra on the device (fx_update_c3_linear): strain, stress
-        (n_elem, nq, 6) with nq = 1 (341) or 4 (342), QFORCE (3 * n_node) from the total displacement.  Returns (strain,
-        stress, qforce, kernel ms)."""
+        """fstr_UpdateNewton of a linear static analysis on the device for the elements of UPDATE_C3 (fx_update_c3_linear):
+        strain, stress (n_elem, nq, 6) with nq = 1 (341), 4 (342), 2 (351), 9 (352) or 27 (362), QFORCE (3 * n_node) from the
+        total displacement.  Returns (strain, stress, qforce, kernel ms)."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
         disp = np.ascontiguousarray(disp, dtype=np.float64)
@@ -482,15 +486,16 @@ class SolverContext:
         ms = C.c_float(0)
         _chk(lib().fx_update_c3_linear(self.h, C.byref(mv), int(etype), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), _ptr(disp),
                                        C.byref(ps), C.byref(pt), _ptr(qf), C.byref(ms)))
-        nq = 1 if int(etype) == 341 else 4
+        nq = _C3_POINTS.get(int(etype), 1)
         n = 6 * nq * conn.shape[0]
         strain = np.ctypeslib.as_array(ps, shape=(n,)).reshape(-1, nq, 6).copy()    # the library's pinned staging: copy out
         stress = np.ctypeslib.as_array(pt, shape=(n,)).reshape(-1, nq, 6).copy()
         return strain, stress, qf, ms.value
 
     def element_stiffness_c3(self, etype, ecoord, E, nu):
-        """One tetrahedron's (3 nn, 3 nn) stiffness through the device kernel (fx_element_stiffness_c3)."""
-        nn = {341: 4, 342: 10}.get(int(etype), 4)
+        """One element's (3 nn, 3 nn) stiffness through the device kernel (fx_element_stiffness_c3): etype 341, 342, 351, 352
+        or 362."""
+        nn = _C3_NODES.get(int(etype), 4)
         ec = np.ascontiguousarray(ecoord, dtype=np.float64).reshape(nn, 3)
         k = np.zeros((3 * nn, 3 * nn))
         _chk(lib().fx_element_stiffness_c3(self.h, int(etype), _ptr(ec), C.c_double(E), C.c_double(nu), _ptr(k)))
@@ -539,7 +544,7 @@ def _ctx(ctx):
 
 def hecmw_mat_con(hecMESH, hecMAT):
     """CRS block profile from hecMESH%elem_node_item: hecMESH.nn_elem nodes per element when the mesh sets it (4 at TYPE=341,
-    10 at 342), else 8 (TYPE=361)."""
+    10 at 342, 6 at 351, 15 at 352, 20 at 362), else 8 (TYPE=361)."""
     nn = int(getattr(hecMESH, "nn_elem", 8))
     conn = np.ascontiguousarray(hecMESH.elem_node_item, dtype=np.int32).reshape(-1, nn)
     NP = hecMESH.n_node

@@ -241,3 +241,101 @@ class TetMesh:
         b = np.zeros(3 * self.n_node, dtype=np.float64)
         b[3 * (self.top_nodes - 1)] = 1.0
         return b
+
+
+# Wedges and the 20-node hexahedron (HEC-MW TYPE=351, 352, 362; FrontISTR's node order).  A hexahedron of CubeMesh (bottom
+# face counter-clockwise 0-3, top face 4-7) splits along the diagonal 0-2 of its bottom and top faces into two prisms, each
+# listed bottom triangle (counter-clockwise seen from above) then top triangle; every cube uses the same diagonal and the
+# vertical faces stay whole, so the mesh is conforming.
+_PRISMS = ((0, 1, 2, 4, 5, 6), (0, 2, 3, 4, 6, 7))
+# mid-edge nodes of the 15-node prism: 7-9 bottom triangle (1,2), (2,3), (3,1); 10-12 top triangle (4,5), (5,6), (6,4); 13-15
+# the vertical edges (1,4), (2,5), (3,6)
+PRISM15_EDGES = ((0, 1), (1, 2), (2, 0), (3, 4), (4, 5), (5, 3), (0, 3), (1, 4), (2, 5))
+# mid-edge nodes of the 20-node hexahedron: 9-12 bottom face (1,2), (2,3), (3,4), (4,1); 13-16 top face (5,6), (6,7), (7,8),
+# (8,5); 17-20 the vertical edges (1,5), (2,6), (3,7), (4,8)
+HEX20_EDGES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7))
+C3_NODES = {341: 4, 342: 10, 351: 6, 352: 15, 361: 8, 362: 20}
+C3_POINTS = {341: 1, 342: 4, 351: 2, 352: 9, 361: 8, 362: 27}          # NumOfQuadPoints
+C3_EDGES = {342: TET10_EDGES, 352: PRISM15_EDGES, 362: HEX20_EDGES}
+
+
+def _add_midedge_nodes(coord, conn, edges, curve, lo, hi, spacing):
+    """One node at the middle of every edge of the first-order elements ``conn``: appended after the vertices in the order of
+    the edges sorted by (lower, higher) vertex id; ``curve`` moves the interior ones off their edges."""
+    pairs = np.stack([conn[:, list(e)] for e in edges], axis=1)
+    key = np.sort(pairs, axis=2).reshape(-1, 2)
+    uniq, inverse = np.unique(key, axis=0, return_inverse=True)
+    mid = 0.5 * (coord[uniq[:, 0] - 1] + coord[uniq[:, 1] - 1])
+    if curve:
+        eid = np.arange(uniq.shape[0], dtype=np.float64)
+        inside = np.all((mid > lo + 1e-9 * spacing) & (mid < hi - 1e-9 * spacing), axis=1)
+        d = np.stack([np.sin(0.9 * eid + 0.3), np.sin(1.7 * eid + 1.1), np.sin(2.3 * eid + 0.5)], axis=1)
+        mid[inside] += curve * spacing * d[inside]
+    conn = np.concatenate([conn, coord.shape[0] + 1 + inverse.reshape(-1, len(edges))], axis=1)
+    return np.concatenate([coord, mid]), conn
+
+
+class _CubeOfSolids:
+    """Common part of WedgeMesh and Hex20Mesh: boundary sets by coordinate, the clamp and the load of CubeMesh."""
+
+    def _finish(self, coord, conn, n, spacing):
+        self.coord = np.ascontiguousarray(coord)
+        self.conn = np.ascontiguousarray(conn.astype(np.int32))
+        self.n_node, self.n_elem = self.coord.shape[0], self.conn.shape[0]
+        z = self.coord[:, 2]
+        self.bottom_nodes = (1 + np.flatnonzero(z == 0.0)).astype(np.int32)
+        self.top_nodes = (1 + np.flatnonzero(z == n * spacing)).astype(np.int32)
+
+    @property
+    def ndof(self):
+        return 3 * self.n_node
+
+    def dirichlet(self):
+        """(node, dof, value) triplets: z=0 face clamped."""
+        node = np.repeat(self.bottom_nodes, 3).astype(np.int32)
+        dof = np.tile(np.array([1, 2, 3], dtype=np.int32), self.bottom_nodes.size)
+        return node, dof, np.zeros(node.size, dtype=np.float64)
+
+    def load(self):
+        """1.0 in x on every node of the z=n face."""
+        b = np.zeros(3 * self.n_node, dtype=np.float64)
+        b[3 * (self.top_nodes - 1)] = 1.0
+        return b
+
+
+class WedgeMesh(_CubeOfSolids):
+    """The n^3 cube of CubeMesh with every hexahedron split into 2 prisms: TYPE=351 (6 nodes) or, with one node added at the
+    middle of every edge, TYPE=352 (15 nodes).  Vertex numbering, ``skew``, ``curve``, boundary conditions and load as
+    TetMesh."""
+
+    def __init__(self, n, etype=352, spacing=1.0, skew=0.0, curve=0.0):
+        if etype not in (351, 352):
+            raise ValueError("etype must be 351 or 352")
+        hexes = CubeMesh(n, spacing=spacing, skew=skew)
+        self.n, self.etype = int(n), int(etype)
+        conn = np.concatenate([hexes.conn[:, list(p)] for p in _PRISMS], axis=1).reshape(-1, 6)   # hex by hex, 2 each
+        coord = hexes.coord
+        if etype == 352:
+            coord, conn = _add_midedge_nodes(coord, conn, PRISM15_EDGES, curve, 0.0, self.n * spacing, spacing)
+        self._finish(coord, conn, self.n, spacing)
+
+
+class Hex20Mesh(_CubeOfSolids):
+    """The n^3 cube of CubeMesh as TYPE=362 elements: one node added at the middle of every edge (20 nodes per element)."""
+
+    def __init__(self, n, spacing=1.0, skew=0.0, curve=0.0):
+        hexes = CubeMesh(n, spacing=spacing, skew=skew)
+        self.n, self.etype = int(n), 362
+        coord, conn = _add_midedge_nodes(hexes.coord, hexes.conn, HEX20_EDGES, curve, 0.0, self.n * spacing, spacing)
+        self._finish(coord, conn, self.n, spacing)
+
+
+def solid_mesh(n, etype, **kw):
+    """The cube of n^3 cells as elements of ``etype``: 341 / 342 TetMesh, 351 / 352 WedgeMesh, 362 Hex20Mesh."""
+    if etype in (341, 342):
+        return TetMesh(n, etype=etype, **kw)
+    if etype in (351, 352):
+        return WedgeMesh(n, etype=etype, **kw)
+    if etype == 362:
+        return Hex20Mesh(n, **kw)
+    raise ValueError("etype must be 341, 342, 351, 352 or 362")

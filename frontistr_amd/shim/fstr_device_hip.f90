@@ -28,7 +28,7 @@ module fstr_device_hip
   logical, save :: lin_decided = .false., lin_eligible = .false., lin_ready = .false.
   type(c_ptr), save :: the_ctx_saved = c_null_ptr
   integer(c_int), save :: lin_elemopt = 0
-  integer(c_int32_t), save :: lin_etype = 361      ! 361, or the tetrahedra 341 / 342 (fx_assemble_c3 / fx_update_c3_linear)
+  integer(c_int32_t), save :: lin_etype = 361      ! 361, or a type of STF_C3: 341 / 342 / 351 / 352 / 362 (fx_assemble_c3 / fx_update_c3_linear)
   real(c_double), allocatable, target, save :: lin_E(:), lin_nu(:)
   integer(c_int32_t), allocatable, target, save :: lin_emat(:)
   integer(c_int32_t), save :: n_elem = 0
@@ -80,8 +80,8 @@ contains
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return                       ! the solve must run on the device too: same predicate as hecmw_solve (method, preconditioner, no MPC / contact)
     if (hecMESH%n_elem_type /= 1) return
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
-    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return
-    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed tet meshes: not yet on the device
+    if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return
+    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
@@ -110,12 +110,54 @@ contains
       'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
   end function fsd_eligible
 
+  !> Where fstr_UpdateNewton of an eligible linear static deck runs.  HECMW_GPU_UPDATE=0: the host, =1: the device.  Unset: the
+  !> device for 361, 341 and 342; the host for 351, 352 and 362, whose device update was measured slower than the reference's
+  !> loop on 16 threads at a million elements (the copy of 2 x 6 x nq doubles per element back into gausses(:) outweighs the
+  !> kernel; DESIGN.md section 4), so these types opt in.
+  logical function lin_update_on_device()
+    character(len=8) :: env
+    integer :: elen, estat
+    call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
+    if (estat == 0 .and. elen > 0) then
+      lin_update_on_device = env(1:1) /= '0'
+    else
+      lin_update_on_device = .not. (lin_etype == 351 .or. lin_etype == 352 .or. lin_etype == 362)
+    endif
+  end function lin_update_on_device
+
+  !> Nodes per element of the types STF_C3 / UPDATE_C3 serve on the device beside 361; 0: not one of them.
+  pure integer function c3_type_nodes(etype)
+    integer(c_int32_t), intent(in) :: etype
+    select case (etype)
+      case (341); c3_type_nodes = 4
+      case (342); c3_type_nodes = 10
+      case (351); c3_type_nodes = 6
+      case (352); c3_type_nodes = 15
+      case (362); c3_type_nodes = 20
+      case default; c3_type_nodes = 0
+    end select
+  end function c3_type_nodes
+
+  !> Their quadrature points per element (NumOfQuadPoints).
+  pure integer function c3_type_points(etype)
+    integer(c_int32_t), intent(in) :: etype
+    select case (etype)
+      case (341); c3_type_points = 1
+      case (342); c3_type_points = 4
+      case (351); c3_type_points = 2
+      case (352); c3_type_points = 9
+      case (362); c3_type_points = 27
+      case default; c3_type_points = 0
+    end select
+  end function c3_type_points
+
   !> Linear static analysis (`!SOLUTION, TYPE=STATIC`, small strain) of TYPE=361 elements with isotropic ELASTIC materials: the
   !> element loop of fstr_StiffMatrix runs on the device -- STF_C3D8IC (the default of 361), STF_C3D8Bbar or STF_C3, whichever
   !> `!SECTION ... ELEMOPT361` selects, the same for every section -- and the matrix stays there for hecmw_solve; fstr_UpdateNewton
   !> (strains, stresses, QFORCE from the solution vector) runs there too (fsd_update_newton_linear).  A mesh of tetrahedra only,
-  !> TYPE=341 or 342 (STF_C3 / UPDATE_C3, fstr_StiffMatrix.f90:134-144, fstr_Update.f90:182-189), is covered the same way under
-  !> the same conditions, ELEMOPT361 aside; a decomposed tet mesh (PETOT > 1) keeps the host loops.
+  !> TYPE=341 or 342, of wedges only, TYPE=351 or 352, or of 20-node hexahedra only, TYPE=362 (STF_C3 / UPDATE_C3,
+  !> fstr_StiffMatrix.f90:134-144, fstr_Update.f90:182-189), is covered the same way under
+  !> the same conditions, ELEMOPT361 aside; a decomposed mesh of these types (PETOT > 1) and a mesh of several types keep the host loops.
   logical function fsd_eligible_linear(hecMESH, hecMAT, fstrSOLID)
     type(hecmwST_local_mesh), intent(in) :: hecMESH
     type(hecmwST_matrix), intent(in) :: hecMAT
@@ -139,8 +181,8 @@ contains
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return
     if (hecMESH%n_elem_type /= 1) return
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
-    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return
-    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed tet meshes: not yet on the device
+    if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return
+    if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return      ! thermal strains enter the element routine
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
@@ -163,8 +205,7 @@ contains
       end select
     endif
     nn = 8
-    if (lin_etype == 341) nn = 4
-    if (lin_etype == 342) nn = 10
+    if (lin_etype /= 361) nn = c3_type_nodes(lin_etype)
     do icel = 1, hecMESH%n_elem
       if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
       cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
@@ -366,6 +407,7 @@ contains
     type(fx_mesh_view) :: mesh
     character(len=8) :: env
     integer :: elen, estat
+    integer(kind=8) :: units
     fsd_stiffness = .false.
     fxb_matrix_on_device = .false.
     if (.not. fsd_eligible(hecMESH, hecMAT, fstrSOLID)) then
@@ -382,9 +424,11 @@ contains
                               c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
         if (ierr /= 0) call fsd_fail('fx_assemble_c3')
       endif
-      call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
-      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '0')) &    ! the stress update follows the solve: pin its staging meanwhile
-        ierr = fx_update_c3d8_linear_prepare(fxb_context(hecMESH), int(hecMESH%n_elem, c_int32_t))
+      if (lin_update_on_device()) then    ! the stress update follows the solve: pin its staging meanwhile (48 doubles per element unit)
+        units = int(hecMESH%n_elem, 8)
+        if (lin_etype /= 361) units = max(units, (units * 6 * c3_type_points(lin_etype) + 47) / 48)    ! 9 and 27 points need more
+        ierr = fx_update_c3d8_linear_prepare(fxb_context(hecMESH), int(units, c_int32_t))
+      endif
       fxb_matrix_on_device = .true.
       fsd_stiffness = .true.
       return
@@ -442,8 +486,7 @@ contains
     integer :: elen, estat, icel, g, nq
     real(kind=kreal) :: t0
     fsd_update_newton_linear = .false.
-    call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
-    if (estat == 0 .and. elen > 0 .and. env(1:1) == '0') return
+    if (.not. lin_update_on_device()) return
     allocate(tot(3*hecMESH%n_node))
     tot(:) = fstrSOLID%unode(1:3*hecMESH%n_node) + fstrSOLID%dunode(1:3*hecMESH%n_node)
     mesh%n_node = hecMESH%n_node; mesh%n_elem = hecMESH%n_elem
@@ -454,9 +497,8 @@ contains
       ierr = fx_update_c3d8_linear(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, lin_elemopt, &
                                    tot, ps, pt, fstrSOLID%QFORCE, ms)
       if (ierr /= 0) call fsd_fail('fx_update_c3d8_linear')
-    else                             ! tetrahedra: UPDATE_C3 at 1 (341) or 4 (342) quadrature points
-      nq = 4
-      if (lin_etype == 341) nq = 1
+    else                             ! UPDATE_C3 at the type's quadrature points: 1 (341), 4 (342), 2 (351), 9 (352), 27 (362)
+      nq = c3_type_points(lin_etype)
       ierr = fx_update_c3_linear(fxb_context(hecMESH), mesh, lin_etype, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, &
                                  tot, ps, pt, fstrSOLID%QFORCE, ms)
       if (ierr /= 0) call fsd_fail('fx_update_c3_linear')

@@ -244,7 +244,7 @@ int fx_color_elements(int32_t NP, int32_t n_elem, int32_t nn, const int32_t *con
 typedef struct fx_mesh_view {
   int32_t n_node, n_elem;
   const double *coord;  /* 3*n_node, hecMESH%node */
-  const int32_t *conn;  /* nn*n_elem (8 at 361, 4 at 341, 10 at 342), 1-based, hecMESH%elem_node_item */
+  const int32_t *conn;  /* nn*n_elem (8 at 361, 4 at 341, 10 at 342, 6 at 351, 15 at 352, 20 at 362), 1-based, hecMESH%elem_node_item */
 } fx_mesh_view;
 int fx_assemble_c3d8(fx_context *ctx, const fx_mesh_view *mesh, double E, double nu, int elemopt,
                      const double *load, int32_t n_bc, const int32_t *bc_node,
@@ -270,22 +270,24 @@ int fx_update_c3d8_linear_prepare(fx_context *ctx, int32_t n_elem);
 int fx_element_stiffness_c3d8(fx_context *ctx, int elemopt, const double *ecoord, double E, double nu,
                               double *stiff);
 
-/* Tetrahedra: fstr_StiffMatrix + hecmw_mat_ass_bc for one group of TYPE=341 (4 nodes, 1 quadrature point) or TYPE=342
- * (10 nodes, FrontISTR's node order, 4 points) elements, STF_C3 (static_LIB_3d.f90:47-205) per element, small strain,
- * isotropic ELASTIC; element stiffness and the coloured scatter run on the device into the resident D/AL/AU as for
- * fx_assemble_c3d8.  mesh->conn holds 4 (341) or 10 (342) node ids per element.  n_mat materials (E[m-1], nu[m-1]); elem_mat
- * (1-based per element) may be NULL with one material.  A tetrahedron that names a node twice (zero volume) is refused
+/* Tetrahedra, wedges and 20-node hexahedra: fstr_StiffMatrix + hecmw_mat_ass_bc for one group of elements of one of the
+ * types that fstr_StiffMatrix.f90:134-144 sends through STF_C3 (static_LIB_3d.f90:47-205), FrontISTR's node order:
+ *   TYPE=341  4 nodes,  1 quadrature point      TYPE=351  6 nodes,  2 points      TYPE=362  20 nodes, 27 points
+ *   TYPE=342 10 nodes,  4 points                TYPE=352 15 nodes,  9 points
+ * small strain, isotropic ELASTIC; element stiffness and the coloured scatter run on the device into the resident D/AL/AU
+ * as for fx_assemble_c3d8.  mesh->conn holds that many node ids per element.  n_mat materials (E[m-1], nu[m-1]); elem_mat
+ * (1-based per element) may be NULL with one material.  An element that names a node twice (degenerate) is refused
  * (FX_ERROR_RUNTIME, nothing assembled); any other etype: FX_ERROR_UNSUPPORTED. */
 int fx_assemble_c3(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                    const double *nu, const int32_t *elem_mat, const double *load, int32_t n_bc,
                    const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble);
-/* fstr_UpdateNewton of a linear static analysis for one TYPE=341 / 342 group: UPDATE_C3 (static_LIB_3d.f90:516-837), small
- * strain.  As fx_update_c3d8_linear, with *strain, *stress [n_elem][nq][6] (nq = 1 at 341, 4 at 342) in the library's pinned
- * staging, valid until the next call. */
+/* fstr_UpdateNewton of a linear static analysis for one group of the same types: UPDATE_C3 (static_LIB_3d.f90:516-837), small
+ * strain.  As fx_update_c3d8_linear, with *strain, *stress [n_elem][nq][6] (nq = the type's quadrature points: 1, 4, 2, 9,
+ * 27) in the library's pinned staging, valid until the next call. */
 int fx_update_c3_linear(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                         const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
                         const double **stress, double *qforce, float *ms_kernel);
-/* One tetrahedron's stiffness through the device kernel (tests): ecoord nn x 3, stiff (3 nn) x (3 nn) row-major. */
+/* One element's stiffness through the device kernel (tests), etype as above: ecoord nn x 3, stiff (3 nn) x (3 nn) row-major. */
 int fx_element_stiffness_c3(fx_context *ctx, int32_t etype, const double *ecoord, double E, double nu, double *stiff);
 
 /* ---- nonlinear static loop: the steps of fstr_Newton either side of the solve -------------

@@ -3,7 +3,11 @@ FX_ASM_ATOMIC=1 selects the single-launch atomic scatter instead of the coloured
 
 --etype 341|342: the same cube split into tetrahedra (TetMesh; 6 per hexahedron, at 342 with mid-edge nodes): ms per call of
 fx_assemble_c3 (three warm calls), the algorithmic bytes of one call (matrix values written once, position map, connectivity
-and coordinates read once) and the bandwidth they imply.  Usage: python scripts/bench_assembly.py --etype 342 [n]"""
+and coordinates read once) and the bandwidth they imply.  Usage: python scripts/bench_assembly.py --etype 342 [n]
+--etype 351|352|362: the cube split into wedges (WedgeMesh, 2 per hexahedron) or as 20-node hexahedra (Hex20Mesh), the same
+figures; n defaults to the smallest cube with a million elements.  --update adds ms per fx_update_c3_linear kernel (three
+calls, displacement = a smooth field) and the bytes it must move (strain and stress written, connectivity, coordinates and
+displacement read)."""
 import json
 import os
 import sys
@@ -14,17 +18,20 @@ if os.environ.get("FX_LIBPATH"):
     hip.LIBPATH = os.environ["FX_LIBPATH"]      # timing experiments: a library built with -DFXA_EXP_*
 from frontistr_amd.mesh import CubeMesh          # noqa: E402
 
-from frontistr_amd.mesh import TetMesh           # noqa: E402
+from frontistr_amd.mesh import solid_mesh        # noqa: E402
 
 args = sys.argv[1:]
+with_update = "--update" in args
+if with_update:
+    args.remove("--update")
 etype = None
 if "--etype" in args:
     k = args.index("--etype")
     etype = int(args[k + 1])
     del args[k:k + 2]
 if etype is not None:
-    n = int(args[0]) if args else 74
-    mesh = TetMesh(n, etype=etype)
+    n = int(args[0]) if args else {341: 74, 342: 74, 351: 80, 352: 80, 362: 100}[etype]
+    mesh = solid_mesh(n, etype)
     nn = mesh.conn.shape[1]
     hm = hip.hecmwST_local_mesh(n_node=mesh.n_node)
     hm.nn_elem = nn
@@ -41,6 +48,14 @@ if etype is not None:
            "scatter": "atomic" if os.environ.get("FX_ASM_ATOMIC", "0") not in ("", "0") else "coloured",
            "ms": [round(v, 2) for v in ms], "algorithmic_GB": round(nbytes / 1e9, 3),
            "GBps": round(nbytes / 1e6 / min(ms), 1), "fraction_of_8TBps": round(nbytes / 1e6 / min(ms) / 8000.0, 3)}
+    if with_update:
+        import numpy as np
+        from frontistr_amd.mesh import C3_POINTS
+        u = 1e-3 * np.sin(mesh.coord @ np.array([[0.3, 0.1, 0.2], [0.2, 0.4, 0.1], [0.1, 0.2, 0.5]])).ravel()
+        ums = [ctx.update_c3_linear(mesh.coord, mesh.conn, etype, 210000.0, 0.3, u)[3] for _ in range(3)]
+        ub = 2 * 48 * C3_POINTS[etype] * mesh.n_elem + 4 * nn * mesh.n_elem + 2 * 24 * mesh.n_node + 24 * mesh.n_node
+        out.update({"update_ms": [round(v, 2) for v in ums], "update_algorithmic_GB": round(ub / 1e9, 3),
+                    "update_GBps": round(ub / 1e6 / min(ums), 1)})
     print(json.dumps(out))
     sys.exit(0)
 n = int(args[0]) if args else 149

@@ -5,7 +5,8 @@ Lagrange (NLSTATIC default), SUBSTEPS sub-steps, CG + SSOR (or what --solver say
 hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to time fistr1_hip end to end: device assembly
 (default) against HECMW_GPU_ASSEMBLY=0 (scripts/r3/fistr1_big.sh).  usage: fistr1_cube_deck.py DIR N [SUBSTEPS] [METHOD] [PRECOND] [STRAIN]
 --etype 341|342 (with --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
-mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --two-sections (with --linear): the second half of the elements
+mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with --linear): the cube split into wedges
+(WedgeMesh, 2 per hexahedron; 352 with mid-edge nodes) or as 20-node hexahedra (Hex20Mesh).  --two-sections (with --linear): the second half of the elements
 forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33)."""
 import os
 import sys
@@ -18,11 +19,11 @@ if linear:
 form361 = None                       # --form361 FI|BBAR|IC: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's (IC)
 if "--form361" in sys.argv:
     k = sys.argv.index("--form361"); form361 = sys.argv[k + 1]; del sys.argv[k:k + 2]
-etype = 361                          # --etype 341|342: tetrahedra (linear decks only)
+etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra (linear decks only)
 if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
-    if etype not in (341, 342) or not linear:
-        sys.exit("--etype takes 341 or 342, with --linear")
+    if etype not in (341, 342, 351, 352, 362) or not linear:
+        sys.exit("--etype takes 341, 342, 351, 352 or 362, with --linear")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
@@ -43,11 +44,13 @@ n0 = (1 + ei + m * (ej + m * ek)).ravel()
 conn = np.stack([n0, n0 + 1, n0 + 1 + m, n0 + m, n0 + m * m, n0 + 1 + m * m, n0 + 1 + m + m * m, n0 + m + m * m], axis=1)
 if etype != 361:
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-    from frontistr_amd.mesh import TetMesh
-    tm = TetMesh(n, etype=etype)
+    from frontistr_amd.mesh import solid_mesh
+    tm = solid_mesh(n, etype)
     nid, xyz, conn = np.arange(1, tm.n_node + 1), tm.coord, tm.conn
     if etype == 342:   # the mesh file lists the mid-edge nodes as (2,3), (3,1), (1,2), (1,4), (2,4), (3,4); fistr1 reorders them on input
         conn = conn[:, [0, 1, 2, 3, 5, 6, 4, 7, 8, 9]]
+    if etype == 352:   # likewise: the file's triangle mid-edge nodes are (2,3), (3,1), (1,2) and (5,6), (6,4), (4,5); 362 is read as written
+        conn = conn[:, [0, 1, 2, 3, 4, 5, 7, 8, 6, 10, 11, 9, 12, 13, 14]]
 with open(os.path.join(d, "cube.msh"), "w") as fh:
     fh.write("!HEADER\n synthetic cube, frontistr_amd scripts/fistr1_cube_deck.py\n!NODE\n")
     np.savetxt(fh, np.column_stack([nid, xyz]), fmt="%d,%.1f,%.1f,%.1f" if etype == 361 else "%d,%.2f,%.2f,%.2f")
