@@ -443,6 +443,10 @@ static void bell_free(Bell &b) {
 static void nl_free(fx_context *c);  // fx_nonlinear_host.h
 static void nn_free(fx_context *c);  // fx_nn_host.h
 static void graphs_destroy(fx_context *c);
+static void asm_groups_free(fx_context *c) {  // the groups' maps belong to the profile too
+  for (ElemColors &ec : c->asm_groups.ec) { dev_free(ec.order); dev_free(ec.pos); dev_free(ec.dup); }
+  c->asm_groups = AsmGroups();
+}
 static void free_matrix(fx_context *c) {
   DevCSR &A = c->A;
   dev_free(A.indexL); dev_free(A.itemL); dev_free(A.indexU); dev_free(A.itemU);
@@ -460,6 +464,7 @@ static void free_matrix(fx_context *c) {
   c->have_profile = c->have_values = c->bell_valid = false;
   dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos); dev_free(c->asm_colors.dup);  // the scatter map belongs to the profile
   c->asm_colors = ElemColors();
+  asm_groups_free(c);
 }
 
 static void free_precond(fx_context *c) {
@@ -3148,5 +3153,6 @@ extern "C" int fx_get_ssor_ordering(fx_context *c, int32_t *perm, int32_t *color
 
 #include "fx_assemble_host.h"
 #include "fx_update_linear.h"
+#include "fx_assemble_groups.h"
 #include "fx_nonlinear_host.h"
 #include "fx_debug_host.h"

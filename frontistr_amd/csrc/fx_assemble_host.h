@@ -439,6 +439,44 @@ static bool launch_assemble_c3_type(int32_t etype, fx_context *c, int32_t n_elem
   }
 }
 
+// `load` (or zero) becomes B, then hecmw_mat_ass_bc (hecmw_mat_ass.f90:292) for the listed dofs: once per assembly, after the last
+// element group.  The temporaries live in the caller's scratch until its synchronize.
+static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const double *load, int32_t n_bc, const int32_t *bc_node,
+                       const int32_t *bc_dof, const double *bc_val) {
+  DevCSR &A = c->A;
+  double *d_bcv = nullptr, *d_val = nullptr;
+  int32_t *d_node = nullptr, *d_dof = nullptr;
+  uint8_t *d_flag = nullptr;
+  static thread_local char msg[200];
+  auto fail = [&](const char *what, int code) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    g_fx_error = msg;
+    return code;
+  };
+  if (load) HIP_TRY(hipMemcpyAsync(A.B, load, (size_t)3 * A.NP * 8, hipMemcpyHostToDevice, c->stream));
+  else HIP_TRY(hipMemsetAsync(A.B, 0, (size_t)3 * A.NP * 8, c->stream));
+  if (n_bc > 0) {
+    if (tmp.alloc(&d_flag, (size_t)3 * A.NP) || tmp.alloc(&d_bcv, (size_t)3 * A.NP) || tmp.alloc(&d_node, (size_t)n_bc) ||
+        tmp.alloc(&d_dof, (size_t)n_bc) || tmp.alloc(&d_val, (size_t)n_bc))
+      return FX_ERROR_RUNTIME;
+    for (int32_t k = 0; k < n_bc; k++)
+      if (bc_node[k] < 1 || bc_node[k] > A.NP) return fail("BC node id out of range", FX_ERROR_RUNTIME);
+    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
+    HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_dof, bc_dof, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_val, bc_val, (size_t)n_bc * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, d_node, d_dof, d_val, d_flag, d_bcv);
+    const dim3 g((A.NP + 255) / 256);
+    hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
+                       A.B, d_flag, d_bcv);
+    hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
+                       A.B, d_flag, d_bcv);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
 // etype 361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8; the other types as launch_assemble_c3_type (elemopt unused)
 static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int32_t n_mat, const double *Es,
                                 const double *nus, const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
@@ -460,9 +498,8 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;  // (361: its checks stay in the colouring)
   DevCSR &A = c->A;
   DevScratch tmp;
-  double *d_coord = nullptr, *d_bcv = nullptr, *d_val = nullptr;
-  int32_t *d_conn = nullptr, *d_err = nullptr, *d_node = nullptr, *d_dof = nullptr;
-  uint8_t *d_flag = nullptr;
+  double *d_coord = nullptr;
+  int32_t *d_conn = nullptr, *d_err = nullptr;
   if (tmp.alloc(&d_coord, (size_t)3 * mesh->n_node) || tmp.alloc(&d_conn, (size_t)nn * mesh->n_elem) || tmp.alloc(&d_err, 1))
     return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpyAsync(d_coord, mesh->coord, (size_t)3 * mesh->n_node * 8, hipMemcpyHostToDevice, c->stream));
@@ -503,27 +540,7 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   HIP_TRY(hipGetLastError());
-  if (load) HIP_TRY(hipMemcpyAsync(A.B, load, (size_t)3 * A.NP * 8, hipMemcpyHostToDevice, c->stream));
-  else HIP_TRY(hipMemsetAsync(A.B, 0, (size_t)3 * A.NP * 8, c->stream));
-  if (n_bc > 0) {
-    if (tmp.alloc(&d_flag, (size_t)3 * A.NP) || tmp.alloc(&d_bcv, (size_t)3 * A.NP) || tmp.alloc(&d_node, (size_t)n_bc) ||
-        tmp.alloc(&d_dof, (size_t)n_bc) || tmp.alloc(&d_val, (size_t)n_bc))
-      return FX_ERROR_RUNTIME;
-    for (int32_t k = 0; k < n_bc; k++)
-      if (bc_node[k] < 1 || bc_node[k] > A.NP) return fail("BC node id out of range", FX_ERROR_RUNTIME);
-    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
-    HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_dof, bc_dof, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_val, bc_val, (size_t)n_bc * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, d_node, d_dof, d_val, d_flag, d_bcv);
-    const dim3 g((A.NP + 255) / 256);
-    hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                       A.B, d_flag, d_bcv);
-    hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                       A.B, d_flag, d_bcv);
-    HIP_TRY(hipGetLastError());
-  }
+  if (int rc = load_and_bc(c, tmp, who, load, n_bc, bc_node, bc_dof, bc_val)) return rc;
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;  // the streaming (BELL) layouts re-gather these values on next use (ensure_solver)
   HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));

@@ -190,6 +190,14 @@ struct ElemColors {
                                     // the coloured scatter stores the first contribution to a block and the matrix is not cleared first
 };
 
+// fx_assemble_groups with more than one group: one ElemColors per group (by position in the call), and the first-write flags of
+// their maps in the launch order of ALL groups (group after group, colour after colour).
+struct AsmGroups {
+  std::vector<ElemColors> ec;
+  uint64_t flag_sig = 0;     // checksum of the (key, etype, n_elem) sequence the maps' first-write flags were made for; 0 = none
+  bool first_write = false;  // the maps carry those flags and every block of the profile is covered: no clearing
+};
+
 struct NlDev {
   bool ready = false;
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
@@ -458,6 +466,7 @@ struct fx_context {
   hipEvent_t ev_packed = nullptr, ev_halo = nullptr;
   NlDev nl;
   ElemColors asm_colors;  // fx_assemble_c3d8
+  AsmGroups asm_groups;   // fx_assemble_groups (several groups)
   void *nn = nullptr;  // NnDev (fx_nn_host.h): systems with NDOF != 3
   const void *host_D = nullptr, *host_AL = nullptr, *host_AU = nullptr;  // the caller's arrays of the last value upload (fx_solve)
   // timing

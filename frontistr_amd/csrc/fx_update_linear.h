@@ -271,6 +271,35 @@ extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
   return 0;
 }
 
+// One group's update kernel: 361 (elemopt 1..3) k_update_c3d8_linear, 341 / 342 k_update_tet, 351 / 352 / 362 k_update_c3.
+static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
+                                 double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
+                                 const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err) {
+  const int nq = c3_points(etype);
+  const dim3 grid((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), blk(FXU_BS);
+#define FXU_LAUNCH(EO)                                                                                                       \
+  hipLaunchKernelGGL((k_update_c3d8_linear<EO>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, \
+                     d_disp, d_strain, d_stress, d_q, d_err)
+  const dim3 tgrid((unsigned)(((int64_t)nq * ne + FXU_TET_BS - 1) / FXU_TET_BS)), tblk(FXU_TET_BS);
+  if (etype == 341)
+    hipLaunchKernelGGL((k_update_tet<341>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                       d_strain, d_stress, d_q);
+  else if (etype == 342)
+    hipLaunchKernelGGL((k_update_tet<342>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                       d_strain, d_stress, d_q);
+#define FXU_C3_LAUNCH(ET)                                                                                                      \
+  hipLaunchKernelGGL((k_update_c3<ET>), dim3((unsigned)((ne + FXC_UEPB(ET) - 1) / FXC_UEPB(ET))), dim3(FXC_BS), 0, c->stream, ne, \
+                     d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q)
+  else if (etype == 351) FXU_C3_LAUNCH(351);
+  else if (etype == 352) FXU_C3_LAUNCH(352);
+  else if (etype == 362) FXU_C3_LAUNCH(362);
+#undef FXU_C3_LAUNCH
+  else if (elemopt == 1) FXU_LAUNCH(1);
+  else if (elemopt == 2) FXU_LAUNCH(2);
+  else FXU_LAUNCH(3);
+#undef FXU_LAUNCH
+}
+
 // fstr_UpdateNewton of a linear static analysis (see the header of this file).  mesh: coordinates + connectivity (host); n_mat
 // materials (E, nu), elem_mat 1-based per element (NULL with one material); elemopt 1 IC, 2 B-bar, 3 FI; disp = total
 // displacement unode + dunode (3 * n_node, host).  Out: *strain, *stress = pinned host arrays owned by the library, valid until
@@ -337,29 +366,8 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
     if (upd_stage_make(c->device, per_elem * ne)) { (void)hipGetLastError(); return fail("cannot pin the host staging", FX_ERROR_RUNTIME); }
   }
   pt.lap("pinned staging");
-  const dim3 grid((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), blk(FXU_BS);
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-#define FXU_LAUNCH(EO)                                                                                                       \
-  hipLaunchKernelGGL((k_update_c3d8_linear<EO>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, \
-                     d_disp, d_strain, d_stress, d_q, d_err)
-  const dim3 tgrid((unsigned)(((int64_t)nq * ne + FXU_TET_BS - 1) / FXU_TET_BS)), tblk(FXU_TET_BS);
-  if (etype == 341)
-    hipLaunchKernelGGL((k_update_tet<341>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
-                       d_strain, d_stress, d_q);
-  else if (etype == 342)
-    hipLaunchKernelGGL((k_update_tet<342>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
-                       d_strain, d_stress, d_q);
-#define FXU_C3_LAUNCH(ET)                                                                                                      \
-  hipLaunchKernelGGL((k_update_c3<ET>), dim3((unsigned)((ne + FXC_UEPB(ET) - 1) / FXC_UEPB(ET))), dim3(FXC_BS), 0, c->stream, ne, \
-                     d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q)
-  else if (etype == 351) FXU_C3_LAUNCH(351);
-  else if (etype == 352) FXU_C3_LAUNCH(352);
-  else if (etype == 362) FXU_C3_LAUNCH(362);
-#undef FXU_C3_LAUNCH
-  else if (elemopt == 1) FXU_LAUNCH(1);
-  else if (elemopt == 2) FXU_LAUNCH(2);
-  else FXU_LAUNCH(3);
-#undef FXU_LAUNCH
+  launch_update_linear(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;

@@ -66,6 +66,11 @@ class _MeshView(C.Structure):
     _fields_ = [("n_node", C.c_int32), ("n_elem", C.c_int32), ("coord", C.c_void_p), ("conn", C.c_void_p)]
 
 
+class _ElemGroup(C.Structure):      # fx_elem_group
+    _fields_ = [("etype", C.c_int32), ("elemopt", C.c_int32), ("n_elem", C.c_int32), ("conn", C.c_void_p),
+                ("elem_mat", C.c_void_p)]
+
+
 def lib():
     """Load libfistr_hip.so (built by `make -C frontistr_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -501,6 +506,69 @@ class SolverContext:
         _chk(lib().fx_element_stiffness_c3(self.h, int(etype), _ptr(ec), C.c_double(E), C.c_double(nu), _ptr(k)))
         return k
 
+    @staticmethod
+    def _group_table(groups):
+        """fx_elem_group[] of [(etype, conn, elemopt, elem_mat)] (elemopt and elem_mat may be left out); the arrays are kept
+        alive by the second return value."""
+        keep, tab = [], (_ElemGroup * max(len(groups), 1))()
+        for g, grp in enumerate(groups):
+            etype, conn = int(grp[0]), np.ascontiguousarray(grp[1], dtype=np.int32)
+            elemopt = int(grp[2]) if len(grp) > 2 and grp[2] is not None else 1
+            em = None if len(grp) < 4 or grp[3] is None else np.ascontiguousarray(grp[3], dtype=np.int32)
+            nn = 8 if etype == 361 else _C3_NODES.get(etype, 0)
+            n_elem = conn.size // nn if nn else (conn.shape[0] if conn.ndim == 2 else 0)
+            keep += [conn, em]
+            tab[g] = _ElemGroup(etype, elemopt, n_elem, _ptr(conn), _ptr(em))
+        return tab, keep
+
+    def assemble_groups(self, coord, groups, E, nu, load=None, bc=None):
+        """fstr_StiffMatrix + fstr_AddBC on the device for a mesh of several solid element types (fx_assemble_groups):
+        ``groups`` = [(etype, conn, elemopt, elem_mat)], etype 361 (elemopt 1 IC, 2 B-bar, 3 FI), 341, 342, 351, 352 or 362,
+        all into the one resident matrix; E, nu scalars, or per-material arrays with every group's elem_mat (1-based).
+        Returns the kernel milliseconds."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
+        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        tab, keep = self._group_table(groups)
+        if bc is None:
+            bn = np.zeros(0, dtype=np.int32); bd = np.zeros(0, dtype=np.int32); bv = np.zeros(0)
+        else:
+            bn = np.ascontiguousarray(bc[0], dtype=np.int32)
+            bd = np.ascontiguousarray(bc[1], dtype=np.int32)
+            bv = np.ascontiguousarray(bc[2], dtype=np.float64)
+        load = None if load is None else np.ascontiguousarray(load, dtype=np.float64)
+        ms = C.c_float(0)
+        _chk(lib().fx_assemble_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, int(Es.size), _ptr(Es), _ptr(nus),
+                                      _ptr(load), int(bn.size), _ptr(bn), _ptr(bd), _ptr(bv), C.byref(ms)))
+        del keep
+        return ms.value
+
+    def update_groups_linear(self, coord, groups, E, nu, disp):
+        """fstr_UpdateNewton of a linear static analysis on the device for the same groups (fx_update_groups_linear).
+        Returns ([strain per group (n_elem, nq, 6)], [stress per group], qforce (3 * n_node) summed over the groups, kernel ms)."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        disp = np.ascontiguousarray(disp, dtype=np.float64)
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
+        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        tab, keep = self._group_table(groups)
+        ng = len(groups)
+        ps, pt = (C.POINTER(C.c_double) * max(ng, 1))(), (C.POINTER(C.c_double) * max(ng, 1))()
+        qf = np.zeros(3 * coord.shape[0])
+        ms = C.c_float(0)
+        _chk(lib().fx_update_groups_linear(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es), _ptr(nus),
+                                           _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
+        strain, stress = [], []
+        for g in range(ng):
+            nq = 8 if tab[g].etype == 361 else _C3_POINTS[tab[g].etype]
+            n = 6 * nq * tab[g].n_elem
+            if n == 0:
+                strain.append(np.zeros((0, nq, 6))); stress.append(np.zeros((0, nq, 6)))
+                continue
+            strain.append(np.ctypeslib.as_array(ps[g], shape=(n,)).reshape(-1, nq, 6).copy())   # pinned staging: copy out
+            stress.append(np.ctypeslib.as_array(pt[g], shape=(n,)).reshape(-1, nq, 6).copy())
+        del keep
+        return strain, stress, qf, ms.value
+
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * 128).from_buffer_copy(bytes(unique_id))
         _chk(lib().fx_comm_init(self.h, buf, rank, nranks))
@@ -557,6 +625,38 @@ def hecmw_mat_con(hecMESH, hecMAT):
     hecMAT.N, hecMAT.NP = hecMESH.nn_internal, NP
     hecMAT.indexL, hecMAT.indexU = indexL, indexU
     hecMAT.itemL, hecMAT.itemU = itemL[:indexL[NP]], itemU[:indexU[NP]]       # exact-size arrays (views when nothing is cut)
+    hecMAT.NPL, hecMAT.NPU = int(indexL[NP]), int(indexU[NP])
+    hecMAT.B = np.zeros(3 * NP)
+    hecMAT.X = np.zeros(3 * NP)
+    return hecMAT
+
+
+def hecmw_mat_con_groups(hecMESH, hecMAT, groups):
+    """hecmw_mat_con for a mesh of several element types: the CRS block profile of the union of the groups' elements
+    (``groups`` = [(etype, conn, ...)], conn (n_elem, nn) 1-based).  Host only (numpy): the node pairs of the elements, made
+    unique slice by slice and then together."""
+    NP = int(hecMESH.n_node)
+    parts = []
+    for grp in groups:
+        conn = np.asarray(grp[1], dtype=np.int64)
+        if conn.size == 0:
+            continue
+        nn = conn.shape[1]
+        step = max(1, (1 << 24) // (nn * nn))
+        for a in range(0, conn.shape[0], step):          # in slices: nn^2 pairs per element
+            c = conn[a:a + step] - 1
+            parts.append(np.unique((c[:, :, None] * NP + c[:, None, :]).ravel()))
+    keys = np.unique(np.concatenate(parts)) if parts else np.zeros(0, dtype=np.int64)
+    row, col = keys // NP, keys % NP
+    lower, upper = col < row, col > row
+    indexL = np.zeros(NP + 1, dtype=np.int32)
+    indexU = np.zeros(NP + 1, dtype=np.int32)
+    indexL[1:] = np.cumsum(np.bincount(row[lower], minlength=NP))
+    indexU[1:] = np.cumsum(np.bincount(row[upper], minlength=NP))
+    hecMAT.N, hecMAT.NP = hecMESH.nn_internal, NP
+    hecMAT.indexL, hecMAT.indexU = indexL, indexU
+    hecMAT.itemL = np.ascontiguousarray(col[lower] + 1, dtype=np.int32)      # keys are sorted by (row, col)
+    hecMAT.itemU = np.ascontiguousarray(col[upper] + 1, dtype=np.int32)
     hecMAT.NPL, hecMAT.NPU = int(indexL[NP]), int(indexU[NP])
     hecMAT.B = np.zeros(3 * NP)
     hecMAT.X = np.zeros(3 * NP)

@@ -339,3 +339,132 @@ def solid_mesh(n, etype, **kw):
     if etype == 362:
         return Hex20Mesh(n, **kw)
     raise ValueError("etype must be 341, 342, 351, 352 or 362")
+
+
+# A hexahedron of CubeMesh split into 2 prisms whose axis runs along x: the triangles lie in the x = const faces, cut along the
+# diagonal from their (low y, low z) corner to their (high y, high z) corner -- the diagonal the Kuhn split puts on that face --
+# each listed x = low triangle (counter-clockwise seen from +x) then x = high triangle.  The y and z faces stay whole.
+_PRISMS_X = ((0, 3, 7, 1, 2, 6), (0, 7, 4, 1, 6, 5))
+
+
+def _add_midedge_nodes_groups(coord, conns, edge_tables, curve, lo, hi, spacing):
+    """_add_midedge_nodes for several first-order connectivities at once: one node per edge of the whole mesh, shared by
+    every element (of whatever type) that holds the edge; numbered after the vertices in the order of the edges sorted by
+    (lower, higher) vertex id."""
+    keys = [np.sort(np.stack([c[:, list(e)] for e in edges], axis=1), axis=2).reshape(-1, 2)
+            for c, edges in zip(conns, edge_tables)]
+    uniq, inverse = np.unique(np.concatenate(keys), axis=0, return_inverse=True)
+    inverse = inverse.ravel()
+    mid = 0.5 * (coord[uniq[:, 0] - 1] + coord[uniq[:, 1] - 1])
+    if curve:
+        eid = np.arange(uniq.shape[0], dtype=np.float64)
+        inside = np.all((mid > lo + 1e-9 * spacing) & (mid < hi - 1e-9 * spacing), axis=1)
+        d = np.stack([np.sin(0.9 * eid + 0.3), np.sin(1.7 * eid + 1.1), np.sin(2.3 * eid + 0.5)], axis=1)
+        mid[inside] += curve * spacing * d[inside]
+    out, at = [], 0
+    for c, edges, k in zip(conns, edge_tables, keys):
+        out.append(np.concatenate([c, coord.shape[0] + 1 + inverse[at:at + k.shape[0]].reshape(-1, len(edges))], axis=1))
+        at += k.shape[0]
+    return np.concatenate([coord, mid]), out
+
+
+class MixedMesh(_CubeOfSolids):
+    """A conforming cube of three solid element types: the pattern of the reference's examples/static/refine/hexpritet sample,
+    extruded along y.  The n^3 cells of CubeMesh (n >= 2) are split at h = n // 2 in x and z.  Looking at the (x, z) plane:
+
+        low x,  low z   hexahedra                                        TYPE=361 (order 1) / 362 (order 2)
+        high x, low z   2 wedges per cell, axis along z (_PRISMS)        TYPE=351 / 352
+        low x,  high z  2 wedges per cell, axis along x (_PRISMS_X)      TYPE=351 / 352
+        high x, high z  6 tetrahedra per cell (Kuhn split)               TYPE=341 / 342
+
+    The hexahedra meet both wedge quadrants in whole quadrilaterals; the tetrahedra meet the z-axis wedges in the z = h
+    triangles and the x-axis wedges in the x = h triangles, both cut along the diagonal the Kuhn split uses.  ``order=2`` adds
+    one node at the middle of every edge of the mesh, shared across the types.  ``groups``: [(etype, conn, elemopt, elem_mat)]
+    in mesh order (hexahedra, wedges -- the z-axis quadrant first --, tetrahedra), the argument of
+    SolverContext.assemble_groups; ``elem_offsets``: first element of each group (+ end) in that order.  ``skew``, ``curve``,
+    boundary conditions and load as the single-type builders."""
+
+    def __init__(self, n, order=1, spacing=1.0, skew=0.0, curve=0.0):
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        if n < 2:
+            raise ValueError("n must be >= 2")
+        hexes = CubeMesh(n, spacing=spacing, skew=skew)
+        self.n, self.order = int(n), int(order)
+        h = self.n // 2
+        ek, ej, ei = np.meshgrid(np.arange(self.n), np.arange(self.n), np.arange(self.n), indexing="ij")
+        ei, ek = ei.ravel(), ek.ravel()
+        cells = hexes.conn
+        hex_c = cells[(ei < h) & (ek < h)]
+        wz = np.concatenate([cells[(ei >= h) & (ek < h)][:, list(p)] for p in _PRISMS], axis=1).reshape(-1, 6)
+        wx = np.concatenate([cells[(ei < h) & (ek >= h)][:, list(p)] for p in _PRISMS_X], axis=1).reshape(-1, 6)
+        tet = np.concatenate([cells[(ei >= h) & (ek >= h)][:, list(t)] for t in _KUHN], axis=1).reshape(-1, 4)
+        conns = [hex_c, np.concatenate([wz, wx]), tet]
+        coord = hexes.coord
+        self.etypes = (361, 351, 341) if order == 1 else (362, 352, 342)
+        if order == 2:
+            coord, conns = _add_midedge_nodes_groups(coord, conns, (HEX20_EDGES, PRISM15_EDGES, TET10_EDGES), curve, 0.0,
+                                                     self.n * spacing, spacing)
+        self.conns = [np.ascontiguousarray(c.astype(np.int32)) for c in conns]
+        self.coord = np.ascontiguousarray(coord)
+        self.n_node = self.coord.shape[0]
+        self.elem_offsets = np.concatenate([[0], np.cumsum([c.shape[0] for c in self.conns])]).astype(np.int64)
+        self.n_elem = int(self.elem_offsets[-1])
+        z = self.coord[:, 2]
+        self.bottom_nodes = (1 + np.flatnonzero(z == 0.0)).astype(np.int32)
+        self.top_nodes = (1 + np.flatnonzero(z == self.n * spacing)).astype(np.int32)
+
+    def groups_with(self, elemopt=1, elem_mat=None):
+        """The groups with ``elemopt`` for the 361 group and the per-element material ids ``elem_mat`` (1-based, mesh order)
+        cut into the groups."""
+        o = self.elem_offsets
+        return [(et, c, elemopt, None if elem_mat is None else np.ascontiguousarray(elem_mat[o[g]:o[g + 1]], dtype=np.int32))
+                for g, (et, c) in enumerate(zip(self.etypes, self.conns))]
+
+    @property
+    def groups(self):
+        return self.groups_with()
+
+
+class RenumberedGroups:
+    """A mesh of element groups (MixedMesh) with its node ids permuted at random and the elements of every group shuffled
+    within the group (np.random.default_rng(seed)); what RenumberedMesh is to the single-type builders."""
+
+    def __init__(self, mesh, seed):
+        rng = np.random.default_rng(seed)
+        self.base = mesh
+        self.n_node, self.n_elem = mesh.n_node, mesh.n_elem
+        self.etypes, self.elem_offsets = mesh.etypes, mesh.elem_offsets
+        self.new_of_old = (1 + rng.permutation(self.n_node)).astype(np.int32)
+        old_of_new = np.empty(self.n_node, dtype=np.int64)
+        old_of_new[self.new_of_old - 1] = np.arange(self.n_node)
+        self.coord = np.ascontiguousarray(mesh.coord[old_of_new])
+        self.elem_orders = [rng.permutation(c.shape[0]) for c in mesh.conns]     # per group: new element -> old element
+        self.conns = [np.ascontiguousarray(self.new_of_old[c[o] - 1].astype(np.int32)) for c, o in zip(mesh.conns, self.elem_orders)]
+        self.bottom_nodes = self.new_of_old[mesh.bottom_nodes - 1]
+        self.top_nodes = self.new_of_old[mesh.top_nodes - 1]
+
+    ndof = property(lambda self: 3 * self.n_node)
+    groups = property(lambda self: self.groups_with())
+
+    def groups_with(self, elemopt=1, elem_mat=None):
+        """``elem_mat`` in the BASE mesh's element order; it follows the shuffled elements."""
+        o = self.elem_offsets
+        return [(et, c, elemopt, None if elem_mat is None else
+                 np.ascontiguousarray(np.asarray(elem_mat)[o[g]:o[g + 1]][self.elem_orders[g]], dtype=np.int32))
+                for g, (et, c) in enumerate(zip(self.etypes, self.conns))]
+
+    def dirichlet(self):
+        node, dof, val = self.base.dirichlet()
+        return self.new_of_old[node - 1].astype(np.int32), dof, val
+
+    def load(self):
+        f = self.base.load()
+        out = np.empty_like(f)
+        out.reshape(-1, 3)[self.new_of_old - 1] = f.reshape(-1, 3)
+        return out
+
+
+def renumber_groups(mesh, seed):
+    """renumber() for a mesh of element groups."""
+    return RenumberedGroups(mesh, seed)

@@ -31,6 +31,8 @@ module fstr_device_hip
   integer(c_int32_t), save :: lin_etype = 361      ! 361, or a type of STF_C3: 341 / 342 / 351 / 352 / 362 (fx_assemble_c3 / fx_update_c3_linear)
   real(c_double), allocatable, target, save :: lin_E(:), lin_nu(:)
   integer(c_int32_t), allocatable, target, save :: lin_emat(:)
+  logical, save :: lin_mixed = .false.             ! several element types: fx_assemble_groups / fx_update_groups_linear
+  type(fx_elem_group), allocatable, save :: lin_groups(:)    ! hecMESH%elem_type_index / elem_type_item as the library takes them
   integer(c_int32_t), save :: n_elem = 0
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
   real(c_double), allocatable, target, save :: b6(:,:,:), b1(:,:), b6b(:,:,:)
@@ -120,6 +122,8 @@ contains
     call get_environment_variable('HECMW_GPU_UPDATE', env, elen, estat)
     if (estat == 0 .and. elen > 0) then
       lin_update_on_device = env(1:1) /= '0'
+    else if (lin_mixed) then
+      lin_update_on_device = .false.      ! a mesh of several types: the host unless asked for (DESIGN.md section 4, "mixed meshes")
     else
       lin_update_on_device = .not. (lin_etype == 351 .or. lin_etype == 352 .or. lin_etype == 362)
     endif
@@ -157,14 +161,19 @@ contains
   !> (strains, stresses, QFORCE from the solution vector) runs there too (fsd_update_newton_linear).  A mesh of tetrahedra only,
   !> TYPE=341 or 342, of wedges only, TYPE=351 or 352, or of 20-node hexahedra only, TYPE=362 (STF_C3 / UPDATE_C3,
   !> fstr_StiffMatrix.f90:134-144, fstr_Update.f90:182-189), is covered the same way under
-  !> the same conditions, ELEMOPT361 aside; a decomposed mesh of these types (PETOT > 1) and a mesh of several types keep the host loops.
+  !> the same conditions, ELEMOPT361 aside; a decomposed mesh of these types (PETOT > 1) keeps the host loops.  A mesh of several
+  !> of the six types (hecMESH%n_elem_type > 1, one rank) is covered through fx_assemble_groups, one group per entry of
+  !> elem_type_item; any other type in the mesh (371, beams, shells, link elements) keeps the host loops.
   logical function fsd_eligible_linear(hecMESH, hecMAT, fstrSOLID)
     type(hecmwST_local_mesh), intent(in) :: hecMESH
     type(hecmwST_matrix), intent(in) :: hecMAT
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
-    integer :: elen, estat, i, icel, cid, opt, nn
+    integer :: elen, estat, i, icel, cid, opt, nn, itype
+    integer(c_int32_t) :: et
     character(len=3) :: tname
+    character(len=64) :: tnames
+    logical :: has361
     if (lin_decided) then
       fsd_eligible_linear = lin_eligible
       return
@@ -179,9 +188,17 @@ contains
     if (hecMAT%NDOF /= 3 .or. hecMESH%n_dof /= 3) return
     if (fstrPR%solution_type /= kstSTATIC .or. fstrPR%nlgeom) return
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return
-    if (hecMESH%n_elem_type /= 1) return
+    if (hecMESH%n_elem_type < 1) return
+    lin_mixed = hecMESH%n_elem_type > 1
+    if (lin_mixed .and. hecMESH%PETOT > 1) return               ! decomposed mixed meshes: not yet on the device
+    if (lin_mixed .and. hecMESH%n_elem_type > 16) return        ! (the report line names every type)
+    has361 = .false.
+    do itype = 1, hecMESH%n_elem_type
+      et = int(hecMESH%elem_type_item(itype), c_int32_t)
+      if (et /= 361 .and. c3_type_nodes(et) == 0) return
+      if (et == 361) has361 = .true.
+    enddo
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
-    if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return
     if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return      ! thermal strains enter the element routine
@@ -193,10 +210,10 @@ contains
     opt = -1
     do i = 1, hecMESH%section%n_sect
       if (opt == -1) opt = fstrSOLID%sections(i)%elemopt361
-      if (lin_etype == 361 .and. fstrSOLID%sections(i)%elemopt361 /= opt) return
+      if (has361 .and. fstrSOLID%sections(i)%elemopt361 /= opt) return
       if (hecMESH%section%sect_orien_ID(i) > 0) return
     enddo
-    if (lin_etype == 361) then       ! ELEMOPT361 selects the 361 formulation only
+    if (has361) then                 ! ELEMOPT361 selects the 361 formulation only
       select case (opt)
         case (kel361IC);   lin_elemopt = 1
         case (kel361BBAR); lin_elemopt = 2
@@ -204,13 +221,17 @@ contains
         case default; return
       end select
     endif
-    nn = 8
-    if (lin_etype /= 361) nn = c3_type_nodes(lin_etype)
-    do icel = 1, hecMESH%n_elem
-      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
-      cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
-      if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
+    do itype = 1, hecMESH%n_elem_type      ! the node count per element, checked per type range
+      et = int(hecMESH%elem_type_item(itype), c_int32_t)
+      nn = 8
+      if (et /= 361) nn = c3_type_nodes(et)
+      do icel = hecMESH%elem_type_index(itype-1) + 1, hecMESH%elem_type_index(itype)
+        if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
+        cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
+        if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
+      enddo
     enddo
+    if (hecMESH%elem_type_index(hecMESH%n_elem_type) /= hecMESH%n_elem) return
     do i = 1, size(fstrSOLID%materials)
       if (fstrSOLID%materials(i)%mtype == -1) cycle
       if (fstrSOLID%materials(i)%mtype /= ELASTIC) return
@@ -220,7 +241,12 @@ contains
     lin_eligible = .true.
     fsd_eligible_linear = .true.
     write(tname, '(i3)') lin_etype
-    if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly on the device (linear static, TYPE='//tname//'); '// &
+    tnames = tname
+    do itype = 2, hecMESH%n_elem_type      ! a mixed mesh: the types in mesh order, TYPE=361+351+341
+      write(tname, '(i3)') hecMESH%elem_type_item(itype)
+      tnames = trim(tnames)//'+'//tname
+    enddo
+    if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly on the device (linear static, TYPE='//trim(tnames)//'); '// &
       'HECMW_GPU_ASSEMBLY=0 keeps it on the host'
   end function fsd_eligible_linear
 
@@ -232,7 +258,7 @@ contains
     type(fx_matrix_view) :: mv
     type(fx_comm_view) :: cv
     integer(c_int) :: ierr
-    integer :: i, icel, nmat
+    integer :: i, icel, nmat, itype, first
     ctx = fxb_context(hecMESH)
     call fxb_ensure_transport(hecMESH, 3)
     call fxb_views(hecMESH, hecMAT, mv, cv)
@@ -251,6 +277,22 @@ contains
     do icel = 1, hecMESH%n_elem
       lin_emat(icel) = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
     enddo
+    if (lin_mixed) then     ! elem_node_item holds the elements type by type: a group is a pointer into it (and into lin_emat)
+      if (allocated(lin_groups)) deallocate(lin_groups)
+      allocate(lin_groups(hecMESH%n_elem_type))
+      do itype = 1, hecMESH%n_elem_type
+        first = hecMESH%elem_type_index(itype-1) + 1
+        lin_groups(itype)%etype = int(hecMESH%elem_type_item(itype), c_int32_t)
+        lin_groups(itype)%elemopt = max(lin_elemopt, 1)
+        lin_groups(itype)%n_elem = int(hecMESH%elem_type_index(itype) - hecMESH%elem_type_index(itype-1), c_int32_t)
+        lin_groups(itype)%conn = c_null_ptr
+        lin_groups(itype)%elem_mat = c_null_ptr
+        if (lin_groups(itype)%n_elem > 0) then
+          lin_groups(itype)%conn = c_loc(hecMESH%elem_node_item(hecMESH%elem_node_index(first-1) + 1))
+          lin_groups(itype)%elem_mat = c_loc(lin_emat(first))
+        endif
+      enddo
+    endif
     lin_ready = .true.
   end subroutine fsd_init_linear
 
@@ -415,7 +457,12 @@ contains
       if (.not. lin_ready) call fsd_init_linear(hecMESH, hecMAT, fstrSOLID)
       mesh%n_node = hecMESH%n_node; mesh%n_elem = hecMESH%n_elem
       mesh%coord = c_loc(hecMESH%node(1)); mesh%conn = c_loc(hecMESH%elem_node_item(1))
-      if (lin_etype == 361) then
+      if (lin_mixed) then
+        ierr = fx_assemble_groups(fxb_context(hecMESH), int(hecMESH%n_node, c_int32_t), hecMESH%node, &
+                                  int(size(lin_groups), c_int32_t), lin_groups, int(size(lin_E), c_int32_t), lin_E, lin_nu, &
+                                  c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
+        if (ierr /= 0) call fsd_fail('fx_assemble_groups')
+      else if (lin_etype == 361) then
         ierr = fx_assemble_c3d8_sections(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, &
                                          lin_elemopt, c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
         if (ierr /= 0) call fsd_fail('fx_assemble_c3d8_sections')
@@ -424,7 +471,9 @@ contains
                               c_null_ptr, 0_c_int32_t, c_null_ptr, c_null_ptr, c_null_ptr, ms)
         if (ierr /= 0) call fsd_fail('fx_assemble_c3')
       endif
-      if (lin_update_on_device()) then    ! the stress update follows the solve: pin its staging meanwhile (48 doubles per element unit)
+      if (lin_mixed) then
+        if (lin_update_on_device()) ierr = fx_update_groups_linear_prepare(fxb_context(hecMESH), int(size(lin_groups), c_int32_t), lin_groups)
+      else if (lin_update_on_device()) then    ! the stress update follows the solve: pin its staging meanwhile (48 doubles per element unit)
         units = int(hecMESH%n_elem, 8)
         if (lin_etype /= 361) units = max(units, (units * 6 * c3_type_points(lin_etype) + 47) / 48)    ! 9 and 27 points need more
         ierr = fx_update_c3d8_linear_prepare(fxb_context(hecMESH), int(units, c_int32_t))
@@ -483,8 +532,9 @@ contains
     real(c_double), pointer :: s6(:,:,:), t6(:,:,:)
     real(c_double), allocatable :: tot(:)
     character(len=8) :: env
-    integer :: elen, estat, icel, g, nq
+    integer :: elen, estat, icel, g, nq, itype, first
     real(kind=kreal) :: t0
+    type(c_ptr), allocatable :: gps(:), gpt(:)
     fsd_update_newton_linear = .false.
     if (.not. lin_update_on_device()) return
     allocate(tot(3*hecMESH%n_node))
@@ -493,6 +543,36 @@ contains
     mesh%coord = c_loc(hecMESH%node(1)); mesh%conn = c_loc(hecMESH%elem_node_item(1))
     t0 = hecmw_Wtime()
     nq = 8
+    if (lin_mixed) then              ! every group's results come back in its own (6, nq, n_elem) block of the staging
+      allocate(gps(size(lin_groups)), gpt(size(lin_groups)))
+      ierr = fx_update_groups_linear(fxb_context(hecMESH), int(hecMESH%n_node, c_int32_t), hecMESH%node, &
+                                     int(size(lin_groups), c_int32_t), lin_groups, int(size(lin_E), c_int32_t), lin_E, lin_nu, &
+                                     tot, gps, gpt, fstrSOLID%QFORCE, ms)
+      if (ierr /= 0) call fsd_fail('fx_update_groups_linear')
+      deallocate(tot)
+      call fsd_report('  of which the library call (uploads, kernel, strain / stress / QFORCE back)', hecmw_Wtime() - t0)
+      call fsd_report('  of which the element kernel alone', real(ms, kreal) * 1.d-3)
+      do itype = 1, size(lin_groups)
+        if (lin_groups(itype)%n_elem < 1) cycle
+        nq = 8
+        if (lin_groups(itype)%etype /= 361) nq = c3_type_points(lin_groups(itype)%etype)
+        first = hecMESH%elem_type_index(itype-1)
+        call c_f_pointer(gps(itype), s6, [6, nq, int(lin_groups(itype)%n_elem)])
+        call c_f_pointer(gpt(itype), t6, [6, nq, int(lin_groups(itype)%n_elem)])
+        !$omp parallel do default(shared) private(icel, g)
+        do icel = 1, lin_groups(itype)%n_elem
+          do g = 1, nq
+            fstrSOLID%elements(first + icel)%gausses(g)%strain(1:6) = s6(1:6, g, icel)
+            fstrSOLID%elements(first + icel)%gausses(g)%stress(1:6) = t6(1:6, g, icel)
+          enddo
+        enddo
+        !$omp end parallel do
+      enddo
+      deallocate(gps, gpt)
+      call hecmw_update_3_R(hecMESH, fstrSOLID%QFORCE, hecMESH%n_node)
+      fsd_update_newton_linear = .true.
+      return
+    endif
     if (lin_etype == 361) then
       ierr = fx_update_c3d8_linear(fxb_context(hecMESH), mesh, int(size(lin_E), c_int32_t), lin_E, lin_nu, lin_emat, lin_elemopt, &
                                    tot, ps, pt, fstrSOLID%QFORCE, ms)

@@ -20,10 +20,10 @@ module hecmw_hip_binding
   public :: fx_matrix_view, fx_comm_view, fx_solve_info
   public :: fx_solve, fx_matvec, fx_last_error, fx_solve_attempts, fx_solve_attempt_history
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
-  public :: fx_mesh_view, fx_material_view, fx_nl_state_view
+  public :: fx_mesh_view, fx_material_view, fx_nl_state_view, fx_elem_group
   public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
             fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
-            fx_assemble_c3, fx_update_c3_linear
+            fx_assemble_c3, fx_update_c3_linear, fx_assemble_groups, fx_update_groups_linear, fx_update_groups_linear_prepare
   public :: fxb_values_owner, fxb_values_addr
   public :: fxb_matrix_on_device, fxb_defer_bc, fxb_solve_device_matrix, FX_UP_PROFILE
   public :: fxb_context, fxb_views, fxb_ensure_transport, fxb_error_text, fxb_on_gpu_path, fx_get_stats
@@ -43,6 +43,11 @@ module hecmw_hip_binding
     integer(c_int32_t) :: n_node, n_elem
     type(c_ptr) :: coord, conn
   end type fx_mesh_view
+
+  type, bind(C) :: fx_elem_group               ! one entry of fstr_StiffMatrix's loop over hecMESH%elem_type_item
+    integer(c_int32_t) :: etype, elemopt, n_elem
+    type(c_ptr) :: conn, elem_mat
+  end type fx_elem_group
 
   type, bind(C) :: fx_material_view
     real(c_double) :: E, nu
@@ -156,6 +161,37 @@ module hecmw_hip_binding
       real(c_double) :: qforce(*)
       real(c_float) :: ms
     end function fx_update_c3_linear
+    integer(c_int) function fx_assemble_groups(ctx, n_node, coord, n_group, groups, n_mat, E, nu, load, n_bc, bc_node, bc_dof, &
+        bc_val, ms) bind(C, name='fx_assemble_groups')
+      import :: c_int, c_ptr, c_int32_t, c_double, c_float, fx_elem_group
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: n_node, n_group, n_mat
+      real(c_double), intent(in) :: coord(*)
+      type(fx_elem_group), intent(in) :: groups(*)
+      real(c_double), intent(in) :: E(*), nu(*)
+      type(c_ptr), value :: load                 ! NULL: B is zero
+      integer(c_int32_t), value :: n_bc
+      type(c_ptr), value :: bc_node, bc_dof, bc_val
+      real(c_float) :: ms
+    end function fx_assemble_groups
+    integer(c_int) function fx_update_groups_linear(ctx, n_node, coord, n_group, groups, n_mat, E, nu, disp, strain, stress, &
+        qforce, ms) bind(C, name='fx_update_groups_linear')
+      import :: c_int, c_ptr, c_int32_t, c_double, c_float, fx_elem_group
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: n_node, n_group, n_mat
+      real(c_double), intent(in) :: coord(*)
+      type(fx_elem_group), intent(in) :: groups(*)
+      real(c_double), intent(in) :: E(*), nu(*), disp(*)
+      type(c_ptr) :: strain(*), stress(*)        ! n_group pointers each: (6, nq, n_elem) of the group in the library's pinned staging
+      real(c_double) :: qforce(*)
+      real(c_float) :: ms
+    end function fx_update_groups_linear
+    integer(c_int) function fx_update_groups_linear_prepare(ctx, n_group, groups) bind(C, name='fx_update_groups_linear_prepare')
+      import :: c_int, c_ptr, c_int32_t, fx_elem_group
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: n_group
+      type(fx_elem_group), intent(in) :: groups(*)
+    end function fx_update_groups_linear_prepare
     integer(c_int) function fx_update_c3d8_linear_prepare(ctx, n_elem) bind(C, name='fx_update_c3d8_linear_prepare')
       import :: c_ptr, c_int, c_int32_t
       type(c_ptr), value :: ctx

@@ -290,6 +290,35 @@ int fx_update_c3_linear(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype
 /* One element's stiffness through the device kernel (tests), etype as above: ecoord nn x 3, stiff (3 nn) x (3 nn) row-major. */
 int fx_element_stiffness_c3(fx_context *ctx, int32_t etype, const double *ecoord, double E, double nu, double *stiff);
 
+/* A mesh of several solid element types: fstr_StiffMatrix's loop over itype (fstr_StiffMatrix.f90:43-212) restated.
+ * hecMESH%elem_node_item holds the elements type by type (elem_type_index / elem_type_item), so a group is a pointer into it
+ * and its element count; nothing is copied or re-sorted by the caller.  A type may appear in several groups, and 361 groups
+ * may differ in elemopt. */
+typedef struct fx_elem_group {
+  int32_t etype;           /* 361, 341, 342, 351, 352, 362 */
+  int32_t elemopt;         /* 361 only: 1 IC, 2 B-bar, 3 FI; ignored otherwise */
+  int32_t n_elem;
+  const int32_t *conn;     /* nn(etype) * n_elem, 1-based */
+  const int32_t *elem_mat; /* 1-based per element, may be NULL with one material */
+} fx_elem_group;
+/* All groups into the one resident matrix: cleared (or first-written) once, group after group in the order given, each group
+ * colour by colour (no atomics, bitwise reproducible); `load` and the boundary conditions once after the last group
+ * (hecmw_mat_ass_bc, matrix/hecmw_mat_ass.f90:292).  The colouring and the position map are kept per group and re-used by the
+ * next call with the same groups.  With ONE group the result is bit for bit that of fx_assemble_c3d8_sections / fx_assemble_c3.
+ * An unknown etype in any group: FX_ERROR_UNSUPPORTED; n_group < 1, missing materials, a material or node id out of range, a
+ * degenerate element of a type other than 361 (named with its group and element): FX_ERROR_RUNTIME.  Nothing is assembled then. */
+int fx_assemble_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                       int32_t n_mat, const double *E, const double *nu, const double *load, int32_t n_bc,
+                       const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble);
+/* fstr_UpdateNewton's element loop (fstr_Update.f90:73-264) over the same groups.  strain[g], stress[g] (n_group pointers each,
+ * the caller's arrays of pointers): group g's [n_elem][nq(etype)][6] in the library's pinned staging, valid until the next
+ * call; qforce (3*n_node, may be NULL) summed over all groups. */
+int fx_update_groups_linear(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                            int32_t n_mat, const double *E, const double *nu, const double *disp, const double **strain,
+                            const double **stress, double *qforce, float *ms_kernel);
+/* As fx_update_c3d8_linear_prepare, for the staging that fx_update_groups_linear needs for these groups (conn is not read). */
+int fx_update_groups_linear_prepare(fx_context *ctx, int32_t n_group, const fx_elem_group *groups);
+
 /* ---- nonlinear static loop: the steps of fstr_Newton either side of the solve -------------
  * (fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29-167).  One TYPE=361 group with the
  * B-bar formulation (the reference's default for NLSTATIC, fstr_setup.f90:366-368) and one

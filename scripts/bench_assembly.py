@@ -7,7 +7,11 @@ and coordinates read once) and the bandwidth they imply.  Usage: python scripts/
 --etype 351|352|362: the cube split into wedges (WedgeMesh, 2 per hexahedron) or as 20-node hexahedra (Hex20Mesh), the same
 figures; n defaults to the smallest cube with a million elements.  --update adds ms per fx_update_c3_linear kernel (three
 calls, displacement = a smooth field) and the bytes it must move (strain and stress written, connectivity, coordinates and
-displacement read)."""
+displacement read).
+--mixed 1|2: the cube as a mesh of three types (MixedMesh: 361 + 351 + 341, or 362 + 352 + 342), n defaults to 72 (1.03 M
+elements): ms per fx_assemble_groups call (three warm calls after the first, which colours and maps) and, beside it, the three
+single-type assemblies of the same element sets through fx_assemble_c3d8 / fx_assemble_c3, each into the profile of its own
+elements, and their sum; the colour launches of the mixed call."""
 import json
 import os
 import sys
@@ -29,6 +33,47 @@ if "--etype" in args:
     k = args.index("--etype")
     etype = int(args[k + 1])
     del args[k:k + 2]
+mixed = 0
+if "--mixed" in args:
+    k = args.index("--mixed")
+    mixed = int(args[k + 1])
+    del args[k:k + 2]
+if mixed:
+    import numpy as np
+    from frontistr_amd.mesh import MixedMesh
+    n = int(args[0]) if args else 72
+    mesh = MixedMesh(n, order=mixed)
+    groups = mesh.groups
+    hm = hip.hecmwST_local_mesh(n_node=mesh.n_node)
+    m = hip.hecmw_mat_con_groups(hm, hip.hecmwST_matrix(), groups)
+    ctx = hip.SolverContext()
+    ctx.upload(m, hm, what=hip.FX_UP_PROFILE)
+    load, bc = mesh.load(), mesh.dirichlet()
+    first = ctx.assemble_groups(mesh.coord, groups, 210000.0, 0.3, load=load, bc=bc)
+    ms = [ctx.assemble_groups(mesh.coord, groups, 210000.0, 0.3, load=load, bc=bc) for _ in range(3)]
+    ctx.close()
+    out = {"mixed": mixed, "n": n, "types": list(mesh.etypes), "n_elem": [int(c.shape[0]) for c in mesh.conns], "dof": 3 * mesh.n_node,
+           "blocks": int(m.NP + m.NPL + m.NPU), "colouring": "per group, groups one after another",
+           "scatter": "atomic" if os.environ.get("FX_ASM_ATOMIC", "0") not in ("", "0") else "coloured",
+           "first_call_ms": round(first, 2), "ms": [round(v, 2) for v in ms], "spread_ms": round(max(ms) - min(ms), 2)}
+    single = {}
+    for et, conn, _, _ in groups:              # the same elements alone, through the single-type entry point, in their own profile
+        hs = hip.hecmwST_local_mesh(n_node=mesh.n_node)
+        hs.nn_elem = conn.shape[1]
+        hs.elem_node_item = conn.ravel()
+        ms1 = hip.hecmw_mat_con(hs, hip.hecmwST_matrix())
+        c1 = hip.SolverContext()
+        c1.upload(ms1, hs, what=hip.FX_UP_PROFILE)
+        if et == 361:
+            t = [c1.assemble_c3d8(mesh.coord, conn, 210000.0, 0.3, elemopt=1, load=load, bc=bc) for _ in range(4)][1:]
+        else:
+            t = [c1.assemble_c3(mesh.coord, conn, et, 210000.0, 0.3, load=load, bc=bc) for _ in range(4)][1:]
+        c1.close()
+        single[str(et)] = [round(v, 2) for v in t]
+    out["single_type_ms"] = single
+    out["single_type_sum_ms"] = [round(sum(single[k][i] for k in single), 2) for i in range(3)]
+    print(json.dumps(out))
+    sys.exit(0)
 if etype is not None:
     n = int(args[0]) if args else {341: 74, 342: 74, 351: 80, 352: 80, 362: 100}[etype]
     mesh = solid_mesh(n, etype)

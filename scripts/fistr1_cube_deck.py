@@ -7,7 +7,9 @@ hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to 
 --etype 341|342 (with --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
 mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with --linear): the cube split into wedges
 (WedgeMesh, 2 per hexahedron; 352 with mid-edge nodes) or as 20-node hexahedra (Hex20Mesh).  --two-sections (with --linear): the second half of the elements
-forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33)."""
+forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33).  --mixed 1|2 (with --linear): the cube as a mesh of
+three element types (frontistr_amd.mesh.MixedMesh: 361 + 351 + 341, or 362 + 352 + 342 with shared mid-edge nodes), one !ELEMENT
+card per type in mesh order; with --two-sections the second half of the elements in that order is EGRP=E2."""
 import os
 import sys
 
@@ -24,6 +26,11 @@ if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
     if etype not in (341, 342, 351, 352, 362) or not linear:
         sys.exit("--etype takes 341, 342, 351, 352 or 362, with --linear")
+mixed = 0                            # --mixed 1|2: hexahedra + wedges + tetrahedra of that order (linear decks only)
+if "--mixed" in sys.argv:
+    k = sys.argv.index("--mixed"); mixed = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
+    if mixed not in (1, 2) or not linear or etype != 361:
+        sys.exit("--mixed takes 1 or 2, with --linear and without --etype")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
@@ -51,20 +58,34 @@ if etype != 361:
         conn = conn[:, [0, 1, 2, 3, 5, 6, 4, 7, 8, 9]]
     if etype == 352:   # likewise: the file's triangle mid-edge nodes are (2,3), (3,1), (1,2) and (5,6), (6,4), (4,5); 362 is read as written
         conn = conn[:, [0, 1, 2, 3, 4, 5, 7, 8, 6, 10, 11, 9, 12, 13, 14]]
+FILE_ORDER = {342: [0, 1, 2, 3, 5, 6, 4, 7, 8, 9], 352: [0, 1, 2, 3, 4, 5, 7, 8, 6, 10, 11, 9, 12, 13, 14]}   # as above
+blocks = [(etype, conn)]             # (type, connectivity in the file's node order) per !ELEMENT type, in mesh order
+if mixed:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from frontistr_amd.mesh import MixedMesh
+    tm = MixedMesh(n, order=mixed)
+    nid, xyz = np.arange(1, tm.n_node + 1), tm.coord
+    blocks = [(et, c[:, FILE_ORDER[et]] if et in FILE_ORDER else c) for et, c in zip(tm.etypes, tm.conns)]
+n_elem_all = sum(c.shape[0] for _, c in blocks)
 with open(os.path.join(d, "cube.msh"), "w") as fh:
     fh.write("!HEADER\n synthetic cube, frontistr_amd scripts/fistr1_cube_deck.py\n!NODE\n")
-    np.savetxt(fh, np.column_stack([nid, xyz]), fmt="%d,%.1f,%.1f,%.1f" if etype == 361 else "%d,%.2f,%.2f,%.2f")
-    eid = np.arange(1, conn.shape[0] + 1)
-    half = conn.shape[0] // 2 if two else conn.shape[0]
-    fh.write("!ELEMENT,TYPE=%d,EGRP=E1\n" % etype)
-    np.savetxt(fh, np.column_stack([eid[:half], conn[:half]]), fmt="%d", delimiter=",")
-    if two:
-        fh.write("!ELEMENT,TYPE=%d,EGRP=E2\n" % etype)
-        np.savetxt(fh, np.column_stack([eid[half:], conn[half:]]), fmt="%d", delimiter=",")
+    np.savetxt(fh, np.column_stack([nid, xyz]), fmt="%d,%.1f,%.1f,%.1f" if etype == 361 and not mixed else "%d,%.2f,%.2f,%.2f")
+    half = n_elem_all // 2 if two else n_elem_all
+    first = 0                        # elements before this block
+    for btype, bconn in blocks:
+        eid = np.arange(first + 1, first + bconn.shape[0] + 1)
+        cut = min(max(half - first, 0), bconn.shape[0])
+        if cut > 0:
+            fh.write("!ELEMENT,TYPE=%d,EGRP=E1\n" % btype)
+            np.savetxt(fh, np.column_stack([eid[:cut], bconn[:cut]]), fmt="%d", delimiter=",")
+        if cut < bconn.shape[0]:
+            fh.write("!ELEMENT,TYPE=%d,EGRP=E2\n" % btype)
+            np.savetxt(fh, np.column_stack([eid[cut:], bconn[cut:]]), fmt="%d", delimiter=",")
+        first += bconn.shape[0]
     fh.write("!MATERIAL,NAME=MAT1,ITEM=1\n!ITEM=1,SUBITEM=2\n 206900.0,0.29\n!SECTION,TYPE=SOLID,EGRP=E1,MATERIAL=MAT1\n")
     if two:
         fh.write("!MATERIAL,NAME=MAT2,ITEM=1\n!ITEM=1,SUBITEM=2\n 70000.0,0.33\n!SECTION,TYPE=SOLID,EGRP=E2,MATERIAL=MAT2\n")
-    if etype == 361:
+    if etype == 361 and not mixed:
         fh.write("!NGROUP, NGRP=FIX, GENERATE\n 1,%d,1\n" % (m * m))
         fh.write("!NGROUP, NGRP=TOP, GENERATE\n %d,%d,1\n!END\n" % (m * m * n + 1, m * m * m))
     else:
@@ -124,4 +145,4 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
-print("wrote", d, "nodes", nid.size, "dof", 3 * nid.size, "elements", conn.shape[0])
+print("wrote", d, "nodes", nid.size, "dof", 3 * nid.size, "elements", n_elem_all)
