@@ -200,6 +200,8 @@ struct AsmGroups {
 
 struct NlDev {
   bool ready = false;
+  int32_t etype = 361;                // element type of the context: 361 (B-bar, fx_nl_init) or 341 / 342 (fx_nl_init_c3)
+  int nn = 8, nq = 8;                 // its nodes and quadrature points per element
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
   std::vector<int32_t> grp_off[3];    // per NLGEOM flag (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG): positions of its colours in order (+ end)
   std::vector<int32_t> dup_off[3];    // per NLGEOM flag: its collapsed elements' colours in colors.dup (+ end); empty = none

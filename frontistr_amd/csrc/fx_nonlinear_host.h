@@ -29,32 +29,35 @@ static int nl_check_material(const fx_material_view *mat) {
 }
 
 static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                          const int32_t *elem_mat) {
+                          const int32_t *elem_mat, int32_t etype = 361) {
   HIP_TRY(hipSetDevice(c->device));
+  const int nn = c3_nodes(etype), nq = c3_points(etype);
   if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
   if (mesh->n_node != c->A.NP) { g_fx_error = "fx_nl_init: mesh/profile size mismatch"; return FX_ERROR_RUNTIME; }
   if (n_mat < 1 || !mats || (n_mat > 1 && !elem_mat)) { g_fx_error = "fx_nl_init: materials missing"; return FX_ERROR_RUNTIME; }
   for (int32_t k = 0; k < n_mat; k++)
     if (int e = nl_check_material(&mats[k])) return e;
   if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
-  for (int64_t k = 0; k < (int64_t)8 * mesh->n_elem; k++)
+  for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
     if (mesh->conn[k] < 1 || mesh->conn[k] > mesh->n_node) { g_fx_error = "fx_nl_init: node id out of range"; return FX_ERROR_RUNTIME; }
   if (n_mat > 1)
     for (int32_t e = 0; e < mesh->n_elem; e++)
       if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
+  if (etype != 361 && refuse_degenerate_tets("fx_nl_init_c3", mesh, nn)) return FX_ERROR_RUNTIME;
   nl_free(c);
   NlDev &n = c->nl;
   n.n_elem = mesh->n_elem;
   n.n_mat = n_mat;
-  const size_t np3 = (size_t)3 * c->A.NP, npt = (size_t)8 * mesh->n_elem;
-  if (dev_alloc(&n.coord, np3) || dev_alloc(&n.conn, npt) || dev_alloc(&n.stress, 6 * npt) || dev_alloc(&n.strain, 6 * npt) ||
+  n.etype = etype; n.nn = nn; n.nq = nq;
+  const size_t np3 = (size_t)3 * c->A.NP, npt = (size_t)nq * mesh->n_elem, ncn = (size_t)nn * mesh->n_elem;
+  if (dev_alloc(&n.coord, np3) || dev_alloc(&n.conn, ncn) || dev_alloc(&n.stress, 6 * npt) || dev_alloc(&n.strain, 6 * npt) ||
       dev_alloc(&n.stress_bak, 6 * npt) || dev_alloc(&n.strain_bak, 6 * npt) || dev_alloc(&n.plstrain, npt) ||
       dev_alloc(&n.fstat, npt) || dev_alloc(&n.istat, npt) || dev_alloc(&n.unode, np3) || dev_alloc(&n.dunode, np3) ||
       dev_alloc(&n.qforce, np3) || dev_alloc(&n.GL, np3) || dev_alloc(&n.bc_flag, np3) || dev_alloc(&n.bc_val, np3) ||
       dev_alloc(&n.err, 1))
     return FX_ERROR_RUNTIME;
   HIP_TRY(hipMemcpyAsync(n.coord, mesh->coord, np3 * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(n.conn, mesh->conn, npt * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(n.conn, mesh->conn, ncn * 4, hipMemcpyHostToDevice, c->stream));
   // materials: one NlMat per section, hardening tables on the device
   n.h_mats.resize((size_t)n_mat);
   for (int32_t k = 0; k < n_mat; k++) {
@@ -81,7 +84,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   {
     static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
     std::vector<int32_t> order, off;
-    const bool coloured = !force_atomic && fxo::color_elements(mesh->n_elem, 8, mesh->conn, mesh->n_node, order, off);
+    const bool coloured = !force_atomic && fxo::color_elements(mesh->n_elem, nn, mesh->conn, mesh->n_node, order, off);
     if (!coloured) {
       order.resize((size_t)mesh->n_elem);
       for (int32_t e = 0; e < mesh->n_elem; e++) order[e] = e;
@@ -101,7 +104,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
         for (int32_t q = off[k]; q < off[k + 1]; q++) {
           const int32_t e = order[q];
           const int flag = n.h_mats[n_mat > 1 ? elem_mat[e] - 1 : 0].nlgeom;
-          if (flag == g) (coloured && names_a_node_twice(mesh->conn + (size_t)8 * e) ? dups : grouped).push_back(e);
+          if (flag == g) (coloured && names_a_node_twice(mesh->conn + (size_t)nn * e, nn) ? dups : grouped).push_back(e);
         }
         doff.push_back((int32_t)dups.size());
         if (grouped.size() > before || any) {
@@ -119,8 +122,17 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     if (n.n_dup > 0) HIP_TRY(hipMemcpyAsync(n.colors.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // grouped and dups are host temporaries
     n.colors.n_elem = mesh->n_elem;
+    n.colors.etype = etype;
     n.colors.offsets = {0, mesh->n_elem};       // marks the lists as built (ensure_scatter_map)
-    if (ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn)) return FX_ERROR_RUNTIME;
+    if (etype != 361 && coloured) {
+      // tetrahedra: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
+      // of all the launches are the `colours` the flags are made for (no tetrahedron is in colors.dup: they were refused above)
+      n.colors.offsets.assign(1, 0);
+      for (int g = 0; g < 3; g++)
+        for (size_t k = 1; k < n.grp_off[g].size(); k++)
+          if (n.grp_off[g][k] > n.colors.offsets.back()) n.colors.offsets.push_back(n.grp_off[g][k]);
+    }
+    if (ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn, etype != 361 && coloured, nn)) return FX_ERROR_RUNTIME;
   }
   for (double *p : {n.stress, n.strain, n.stress_bak, n.strain_bak}) HIP_TRY(hipMemsetAsync(p, 0, 6 * npt * 8, c->stream));
   for (double *p : {n.plstrain, n.fstat}) HIP_TRY(hipMemsetAsync(p, 0, npt * 8, c->stream));
@@ -144,9 +156,62 @@ extern "C" int fx_nl_init_sections(fx_context *c, const fx_mesh_view *mesh, int3
   return nl_init_common(c, mesh, n_mat, mats, elem_mat);
 }
 
+// The same context for a mesh of tetrahedra, etype 341 or 342 (STF_C3 / UPDATE_C3, fx_nonlinear_tet.h): n_mat materials,
+// elem_mat[e] in 1..n_mat (may be NULL with one material).  Every other fx_nl_* entry point works on either context.
+extern "C" int fx_nl_init_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const fx_material_view *mats,
+                             const int32_t *elem_mat) {
+  if (etype != 341 && etype != 342) {
+    g_fx_error = "fx_nl_init_c3: the nonlinear loop covers TYPE=341 and 342 (361 through fx_nl_init / fx_nl_init_sections)";
+    return FX_ERROR_UNSUPPORTED;
+  }
+  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype);
+}
+
 #define NL_READY(name)                                                                              \
   HIP_TRY(hipSetDevice(c->device));                                                                 \
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }
+
+template <int ETYPE, int G>
+static void nl_launch_stiffness_tet_group(fx_context *c, double *Kout) {
+  NlDev &n = c->nl;
+  const DevCSR &A = c->A;
+  const std::vector<int32_t> &off = n.grp_off[G];
+  constexpr int EPB = FXT_EPB(ETYPE);
+  const bool one_range = Kout || n.scatter_atomic;  // element matrices out, or atomics: the group's colours in one launch
+  for (size_t k = 0; k + 1 < off.size(); k++) {
+    const int32_t e0 = one_range ? off.front() : off[k], e1 = one_range ? off.back() : off[k + 1];
+    if (e1 > e0)
+      hipLaunchKernelGGL((k_nl_stiffness_tet<ETYPE, G>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, e1, n.coord, n.conn,
+                         n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL,
+                         A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos,
+                         n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+    if (one_range) break;
+  }
+}
+template <int ETYPE, int G>
+static void nl_launch_update_tet_group(fx_context *c, double *qf_out) {
+  NlDev &n = c->nl;
+  const std::vector<int32_t> &off = n.grp_off[G];
+  if (off.empty() || off.back() <= off.front()) return;
+  const int32_t e0 = off.front(), e1 = off.back();
+  const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;  // as nl_launch_update_group
+  const int64_t lanes = (int64_t)(e1 - e0) * TetEl<ETYPE>::NQ;
+  hipLaunchKernelGGL((k_nl_update_tet<ETYPE, G>), dim3((unsigned)((lanes + FXU_TET_BS - 1) / FXU_TET_BS)), dim3(FXU_TET_BS), 0, c->stream,
+                     e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat,
+                     n.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+}
+template <int ETYPE>
+static void nl_launch_tet(fx_context *c, double *Kout, double *qf_out, bool update) {
+  if (update) {
+    nl_launch_update_tet_group<ETYPE, 0>(c, qf_out);
+    nl_launch_update_tet_group<ETYPE, 1>(c, qf_out);
+    nl_launch_update_tet_group<ETYPE, 2>(c, qf_out);
+  } else {
+    nl_launch_stiffness_tet_group<ETYPE, 0>(c, Kout);
+    nl_launch_stiffness_tet_group<ETYPE, 1>(c, Kout);
+    nl_launch_stiffness_tet_group<ETYPE, 2>(c, Kout);
+  }
+}
 
 template <int G>
 static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k) {
@@ -180,6 +245,8 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
                          A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
 static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
+  if (c->nl.etype == 341) { nl_launch_tet<341>(c, Kout, nullptr, false); return 0; }
+  if (c->nl.etype == 342) { nl_launch_tet<342>(c, Kout, nullptr, false); return 0; }
   DevScratch tmp;
   double *dup_k = nullptr;
   if (!Kout && c->nl.n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * c->nl.n_dup)) return FX_ERROR_RUNTIME;
@@ -210,6 +277,8 @@ static void nl_launch_update_group(fx_context *c, double *qf_out) {
                        (const int32_t *)n.emat);
 }
 static void nl_launch_update(fx_context *c, double *qf_out) {
+  if (c->nl.etype == 341) { nl_launch_tet<341>(c, nullptr, qf_out, true); return; }
+  if (c->nl.etype == 342) { nl_launch_tet<342>(c, nullptr, qf_out, true); return; }
   nl_launch_update_group<0>(c, qf_out);
   nl_launch_update_group<1>(c, qf_out);
   nl_launch_update_group<2>(c, qf_out);
@@ -227,9 +296,11 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
     if (bc_node[k] < 1 || bc_node[k] > A.NP) { g_fx_error = "fx_nl_stiffness: BC node id out of range"; return FX_ERROR_RUNTIME; }
   HIP_TRY(hipMemsetAsync(n.err, 0, 4, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));  // hecmw_mat_clear
-  HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
-  HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
+  if (!(n.colors.first_write && n.colors.pos && !n.scatter_atomic)) {  // first-write scatter (tetrahedra): every block is stored before it is added to
+    HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));  // hecmw_mat_clear
+    HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
+  }
   if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(n.bc_flag, 0, (size_t)3 * A.NP, c->stream));
@@ -312,7 +383,7 @@ extern "C" int fx_nl_update(fx_context *c, double out[4], float *ms_update) {
   nl_launch_update(c, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  if (n.mat.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45)
+  for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45); the flag is the process's, whichever section set it
   if (nl_halo_natural(c, n.qforce)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, n.GL, n.qforce, n.bc_flag, c->A.B);
   HIP_TRY(hipGetLastError());
@@ -396,10 +467,14 @@ extern "C" int fx_mat_ass_bc(fx_context *c, int32_t n_bc, const int32_t *bc_node
 extern "C" int fx_nl_commit(fx_context *c) {
   NL_READY("fx_nl_commit");
   NlDev &n = c->nl;
-  const int64_t np3 = (int64_t)3 * c->A.NP, npt = (int64_t)8 * n.n_elem;
+  const int64_t np3 = (int64_t)3 * c->A.NP, npt = (int64_t)n.nq * n.n_elem;
   hipLaunchKernelGGL(k_axpy_plain, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, 1.0, n.dunode, n.unode);
-  hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.mat.plastic, n.fstat, n.plstrain, n.stress,
-                     n.strain, n.stress_bak, n.strain_bak, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  if (n.etype == 361)
+    hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.mat.plastic, n.fstat, n.plstrain, n.stress,
+                       n.strain, n.stress_bak, n.strain_bak, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  else
+    hipLaunchKernelGGL(k_nl_commit_c3, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.nq, n.mat.plastic, n.fstat, n.plstrain,
+                       n.stress, n.strain, n.stress_bak, n.strain_bak, (const NlMat *)n.mats, (const int32_t *)n.emat);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -412,7 +487,7 @@ extern "C" int fx_nl_commit(fx_context *c) {
 extern "C" int fx_nl_snapshot(fx_context *c, int load) {
   NL_READY("fx_nl_snapshot");
   NlDev &n = c->nl;
-  const size_t npt = (size_t)8 * n.n_elem;
+  const size_t npt = (size_t)n.nq * n.n_elem;
   if (!n.bk_stress) {
     if (load) { g_fx_error = "fx_nl_snapshot: nothing was saved"; return FX_ERROR_RUNTIME; }
     if (dev_alloc(&n.bk_stress, 6 * npt) || dev_alloc(&n.bk_strain, 6 * npt) || dev_alloc(&n.bk_stress_bak, 6 * npt) ||
@@ -435,7 +510,7 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
 
 static int nl_copy_state(fx_context *c, const fx_nl_state_view *s, bool to_device) {
   NlDev &n = c->nl;
-  const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)8 * n.n_elem;
+  const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)n.nq * n.n_elem;
   struct { void *h; void *d; size_t bytes; } f[] = {
       {s->stress, n.stress, 6 * npt * 8}, {s->strain, n.strain, 6 * npt * 8}, {s->stress_bak, n.stress_bak, 6 * npt * 8},
       {s->strain_bak, n.strain_bak, 6 * npt * 8}, {s->plstrain, n.plstrain, npt * 8}, {s->fstat, n.fstat, npt * 8},
@@ -466,10 +541,11 @@ extern "C" int fx_nl_element_tangents(fx_context *c, double *ke) {
   NlDev &n = c->nl;
   DevScratch tmp;
   double *d = nullptr;
-  if (tmp.alloc(&d, (size_t)576 * n.n_elem)) return FX_ERROR_RUNTIME;
+  const size_t nk = (size_t)(3 * n.nn) * (3 * n.nn) * n.n_elem;
+  if (tmp.alloc(&d, nk)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, d)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(ke, d, (size_t)576 * n.n_elem * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(ke, d, nk * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -478,11 +554,12 @@ extern "C" int fx_nl_element_update(fx_context *c, double *qf) {
   NlDev &n = c->nl;
   DevScratch tmp;
   double *d = nullptr;
-  if (tmp.alloc(&d, (size_t)24 * n.n_elem)) return FX_ERROR_RUNTIME;
+  const size_t nqf = (size_t)3 * n.nn * n.n_elem;
+  if (tmp.alloc(&d, nqf)) return FX_ERROR_RUNTIME;
   nl_launch_update(c, d);
   HIP_TRY(hipGetLastError());
-  if (n.mat.plastic) n.latch = 1;
-  HIP_TRY(hipMemcpyAsync(qf, d, (size_t)24 * n.n_elem * 8, hipMemcpyDeviceToHost, c->stream));
+  for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;
+  HIP_TRY(hipMemcpyAsync(qf, d, nqf * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

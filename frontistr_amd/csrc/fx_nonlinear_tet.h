@@ -1,0 +1,383 @@
+// Nonlinear (total / updated Lagrange, Mises elastoplastic) path of the tetrahedra TYPE=341 and TYPE=342: STF_C3
+// (static_LIB_3d.f90:47-205) with `u` present and UPDATE_C3 (:516-837) without temperatures, as fstr_StiffMatrix.f90:134-144 and
+// fstr_Update.f90:182-189 call them inside fstr_Newton.  The element data (shape functions, quadrature, Jacobian) is that of
+// fx_assemble_tet.h, the material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening) that of fx_nonlinear.h.
+//
+// k_nl_stiffness_tet keeps the lane mapping of k_assemble_tet: the element matrix is symmetric in all three branches (D is held
+// as 21 entries, the initial-stress term is symmetric), so one lane owns one upper block a <= b (10 lanes at 341, 55 at 342) and
+// stores it at (a, b) and, transposed, at (b, a).  What is new against the linear kernel is data per quadrature point: the
+// material matrix (21 doubles: it differs between plastic points), the stress (6) and, for TOTALLAG, the displacement gradient
+// (9).  The lanes 0..NQ-1 of an element compute them with the Jacobian and stage them in LDS beside the inverse Jacobian,
+// weight * determinant and global derivatives; the block lanes read them from there.
+//
+// k_nl_update_tet: one lane per quadrature point, as k_update_tet.  The internal force is summed over the element's lanes with
+// xor shuffles and added to QFORCE with fp64 atomics.
+//
+// UPDATE_C3's UPDATELAG branch computes `dstress = real( matmul(D, dstrain) )` (:718): REAL() of a double-precision argument
+// without KIND is default real, so the reference rounds the stress increment to single precision before it adds it to the
+// stress of the last converged sub-step (Update_C3D8Bbar has no real() there).  fx_real_default() restates that.
+#pragma once
+#include "fx_assemble_tet.h"
+#include "fx_nonlinear.h"
+
+__device__ __forceinline__ double fx_real_default(double x) { return (double)(float)x; }
+
+// global derivatives of node n at a point whose inverse Jacobian is inv (row-major 3x3): getGlobalDeriv, element.f90:693-744
+template <int ETYPE>
+__device__ __forceinline__ void tet_node_gderiv(int n, double xi, double et, double ze, const double *inv, double *g) {
+  double d[3];
+  tet_shape_deriv<ETYPE>(n, xi, et, ze, d);
+#pragma unroll
+  for (int j = 0; j < 3; j++) g[j] = d[0] * inv[j] + d[1] * inv[3 + j] + d[2] * inv[6 + j];
+}
+
+// Arguments as k_nl_stiffness.  Positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one
+// colour, scattered with plain read-modify-writes (a block whose first-write flag is set in pos_map is stored, not added to).
+// Kout: element matrices out ((3 NN)^2 each, row-major, by element id), no scatter.
+template <int ETYPE, int NLGEOM>
+__global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, const double *__restrict__ coord,
+                                                            const int32_t *__restrict__ conn, const double *__restrict__ unode,
+                                                            const double *__restrict__ dunode, NlMat m, int latch,
+                                                            const double *__restrict__ stress, const double *__restrict__ fstat,
+                                                            const int32_t *__restrict__ istat, const int32_t *__restrict__ indexL,
+                                                            const int32_t *__restrict__ itemL, const int32_t *__restrict__ indexU,
+                                                            const int32_t *__restrict__ itemU, double *__restrict__ D,
+                                                            double *__restrict__ AL, double *__restrict__ AU,
+                                                            double *__restrict__ Kout, int32_t *__restrict__ err,
+                                                            const int32_t *__restrict__ elem_list, int32_t e0,
+                                                            const int32_t *__restrict__ pos_map, int atomic,
+                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+  constexpr int NN = TetEl<ETYPE>::NN, NQ = TetEl<ETYPE>::NQ, EPB = FXT_EPB(ETYPE), LPE = FXT_LPE(ETYPE);
+  constexpr int NB = FXT_NB(ETYPE);
+  constexpr int NF = NLGEOM == 1 ? 9 : 1, NS = NLGEOM != 0 ? 6 : 1;
+  __shared__ double Jsh[EPB][NQ][10];     // per quadrature point: inverse Jacobian (row-major), weight * determinant
+  __shared__ double Gsh[EPB][NQ][NN][3];  // global derivatives of every node at every point
+  __shared__ double Dsh[EPB][NQ][21];     // material matrix (MatlMatrix, minus GEOMAT_C3 for UPDATELAG), upper triangle
+  __shared__ double Ssh[EPB][NQ][NS];     // stress (initial-stress term)
+  __shared__ double Fsh[EPB][NQ][NF];     // gdispderiv = u . gderiv (TOTALLAG)
+  const int wave = threadIdx.x >> 6, wl = threadIdx.x & 63;
+  const int el = wave * TetEl<ETYPE>::EPW + wl / LPE, k = wl % LPE;
+  const int32_t epos = e0 + blockIdx.x * EPB + el;
+  const bool active = wl < TetEl<ETYPE>::EPW * LPE && epos < n_elem;
+  const int32_t elem = !active ? 0 : (elem_list ? elem_list[epos] : epos);
+  if (active && k < NQ) {
+    if (mats) m = mats[emat[elem] - 1];
+    double ec[NN][3], ut[NN][3];
+#pragma unroll
+    for (int j = 0; j < NN; j++) {
+      const int32_t nd = conn[(size_t)NN * elem + j];
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const size_t o = (size_t)3 * (nd - 1) + d;
+        ec[j][d] = coord[o];
+        if (NLGEOM != 0) {
+          ut[j][d] = unode[o] + dunode[o];
+          if (NLGEOM == 2) ec[j][d] += ut[j][d];  // elem = ecoord + u (:91)
+        }
+      }
+    }
+    double det, inv[3][3], xi, et, ze, w;
+    tet_jacobian<ETYPE>(ec, k, det, inv);
+    tet_gauss<ETYPE>(k, xi, et, ze, w);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) Jsh[el][k][3 * i + j] = inv[i][j];
+    Jsh[el][k][9] = w * det;  // wg = getWeight * det
+    const size_t gp = (size_t)NQ * elem + k;
+    double S[6], Dm[21];
+#pragma unroll
+    for (int i = 0; i < 6; i++) S[i] = stress[gp * 6 + i];
+    nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+#pragma unroll
+    for (int i = 0; i < 21; i++) Dsh[el][k][i] = Dm[i];
+    if (NLGEOM != 0) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) Ssh[el][k][i % NS] = S[i];
+    }
+    if (NLGEOM == 1) {  // gdispderiv = matmul(u, gderiv) (:136)
+      double F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int a = 0; a < NN; a++) {
+        double g[3];
+        tet_node_gderiv<ETYPE>(a, xi, et, ze, &inv[0][0], g);
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+#pragma unroll
+          for (int d = 0; d < 3; d++) F[3 * c + d] += ut[a][c] * g[d];
+      }
+#pragma unroll
+      for (int i = 0; i < 9; i++) Fsh[el][k][i % NF] = F[i];
+    }
+  }
+  __syncthreads();
+  if (active && k < NQ * NN) {
+    const int q = k / NN, n = k % NN;
+    double xi, et, ze, w;
+    tet_gauss<ETYPE>(q, xi, et, ze, w);
+    tet_node_gderiv<ETYPE>(n, xi, et, ze, Jsh[el][q], Gsh[el][q][n]);
+  }
+  __syncthreads();
+  if (!active || k >= NB) return;
+  int a, b;
+  upper_block<NN>(k, a, b);
+  const int32_t inod = conn[(size_t)NN * elem + a], jnod = conn[(size_t)NN * elem + b];
+  auto block_ptr = [&](int ra, int rb, int32_t rnod, int32_t cnod, bool &first) -> double * {  // hecmw_mat_add_node
+    const int32_t raw = pos_map ? pos_map[(size_t)(NN * NN) * elem + NN * ra + rb] : 0;
+    first = pos_map && raw >= 0 && (raw & FXA_FIRST_BIT);
+    if (rnod == cnod) return D + (size_t)9 * (rnod - 1);
+    if (cnod < rnod) {
+      const int32_t p = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemL, indexL[rnod - 1], indexL[rnod], cnod);
+      return p < 0 ? nullptr : AL + (size_t)9 * p;
+    }
+    const int32_t p = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemU, indexU[rnod - 1], indexU[rnod], cnod);
+    return p < 0 ? nullptr : AU + (size_t)9 * p;
+  };
+  double *dst = nullptr, *dstT = nullptr;
+  double old[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oldT[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (!Kout) {  // destinations and old values first: the reads' latency runs under the arithmetic
+    bool first = false, firstT = false;
+    dst = block_ptr(a, b, inod, jnod, first);
+    if (a != b) dstT = block_ptr(b, a, jnod, inod, firstT);
+    if (!dst || (a != b && !dstT)) { if (err) atomicExch(err, 2); return; }
+    if (!atomic && !first) {
+#pragma unroll
+      for (int e = 0; e < 9; e++) old[e] = dst[e];
+    }
+    if (!atomic && a != b && !firstT) {
+#pragma unroll
+      for (int e = 0; e < 9; e++) oldT[e] = dstT[e];
+    }
+  }
+  double K[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const double h0[3] = {0.0, 0.0, 0.0};
+    const double *ga = Gsh[el][q][a], *gb = Gsh[el][q][b], *Dl = Dsh[el][q];
+    const double w = Jsh[el][q][9];
+    double F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (NLGEOM == 1) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) F[i] = Fsh[el][q][i % NF];
+    }
+    double Ba[6][3], Bb[6][3], DB[6][3];
+    nl_node_B<NLGEOM>(ga, h0, F, Ba);  // BL0 (+ BL1 for TOTALLAG, :120-162)
+    nl_node_B<NLGEOM>(gb, h0, F, Bb);
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < 6; p++) s += Dl[sym21(r, p)] * Bb[p][j];
+        DB[r][j] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < 6; p++) s += Ba[p][i] * DB[p][j];
+        K[3 * i + j] += s * w;
+      }
+    if (NLGEOM != 0) {  // initial-stress matrix BN^T S BN (:170-199): (grad N_a . S grad N_b) on the diagonal of the block
+      const double *Sl = Ssh[el][q];
+      const double sb0 = Sl[0 % NS] * gb[0] + Sl[3 % NS] * gb[1] + Sl[5 % NS] * gb[2];
+      const double sb1 = Sl[3 % NS] * gb[0] + Sl[1 % NS] * gb[1] + Sl[4 % NS] * gb[2];
+      const double sb2 = Sl[5 % NS] * gb[0] + Sl[4 % NS] * gb[1] + Sl[2 % NS] * gb[2];
+      const double geo = (ga[0] * sb0 + ga[1] * sb1 + ga[2] * sb2) * w;
+      K[0] += geo; K[4] += geo; K[8] += geo;
+    }
+  }
+  if (Kout) {
+    constexpr int W = 3 * NN;
+    const size_t ko = (size_t)elem * W * W;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        Kout[ko + (size_t)(3 * a + i) * W + 3 * b + j] = K[3 * i + j];
+        if (a != b) Kout[ko + (size_t)(3 * b + j) * W + 3 * a + i] = K[3 * i + j];
+      }
+    return;
+  }
+  if (!atomic) {
+#pragma unroll
+    for (int e = 0; e < 9; e++) dst[e] = old[e] + K[e];
+    if (a != b) {
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) dstT[3 * j + i] = oldT[3 * j + i] + K[3 * i + j];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; e++) unsafeAtomicAdd(dst + e, K[e]);
+    if (a != b) {
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) unsafeAtomicAdd(dstT + 3 * j + i, K[3 * i + j]);
+    }
+  }
+}
+
+// Node coordinates of the configuration x + (u + alpha du) the derivatives are taken in, and the Jacobian of point g there.
+// alpha = 0.5: `(0.5 ddu + u) + ecoord` (:563), alpha = 1: `(ddu + u) + ecoord` (:564); UPDATELAG only, else the initial coordinates.
+template <int ETYPE, int NLGEOM>
+__device__ __forceinline__ void nl_tet_config_jacobian(const int32_t (&nod)[TetEl<ETYPE>::NN], const double *__restrict__ coord,
+                                                       const double *__restrict__ unode, const double *__restrict__ dunode, double alpha,
+                                                       int g, double &det, double (&inv)[3][3]) {
+  constexpr int NN = TetEl<ETYPE>::NN;
+  double ec[NN][3];
+#pragma unroll
+  for (int j = 0; j < NN; j++)
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const size_t o = (size_t)3 * (nod[j] - 1) + d;
+      ec[j][d] = coord[o];
+      if (NLGEOM == 2) ec[j][d] = (alpha * dunode[o] + unode[o]) + coord[o];
+    }
+  tet_jacobian<ETYPE>(ec, g, det, inv);
+}
+
+// UPDATE_C3 + scatter of the internal force.  Arguments as k_nl_update; state arrays [elem][NQ][.]; qf_out (tests): per-element
+// qf[3 NN] instead of the scatter.
+template <int ETYPE, int NLGEOM>
+__global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, const double *__restrict__ coord,
+                                                             const int32_t *__restrict__ conn, const double *__restrict__ unode,
+                                                             const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
+                                                             double *__restrict__ strain, const double *__restrict__ stress_bak,
+                                                             const double *__restrict__ strain_bak, const double *__restrict__ plstrain,
+                                                             double *__restrict__ fstat, int32_t *__restrict__ istat,
+                                                             double *__restrict__ qforce, double *__restrict__ qf_out,
+                                                             const int32_t *__restrict__ elem_list, int32_t e0,
+                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+  constexpr int NN = TetEl<ETYPE>::NN, NQ = TetEl<ETYPE>::NQ;
+  const int64_t t = (int64_t)blockIdx.x * FXU_TET_BS + threadIdx.x;
+  const int g = (int)(t % NQ);
+  int64_t epos = e0 + t / NQ;
+  const bool active = epos < n_elem;
+  if (!active) epos = n_elem - 1;  // idle lanes shadow the last element's geometry (uniform shuffles); they read no state and write nothing
+  const int32_t elem = elem_list ? elem_list[epos] : (int32_t)epos;
+  if (mats) m = mats[emat[elem] - 1];
+  int32_t nod[NN];
+#pragma unroll
+  for (int j = 0; j < NN; j++) nod[j] = conn[(size_t)NN * elem + j];
+  double det, inv[3][3], xi, et, ze, w;
+  tet_gauss<ETYPE>(g, xi, et, ze, w);
+  nl_tet_config_jacobian<ETYPE, NLGEOM>(nod, coord, unode, dunode, 0.5, g, det, inv);
+  // gdispderiv = matmul(totaldisp, gderiv) (:646); totaldisp = u + ddu, or ddu for UPDATELAG (:561-566)
+  double gu[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+  for (int a = 0; a < NN; a++) {
+    double gd[3];
+    tet_node_gderiv<ETYPE>(a, xi, et, ze, &inv[0][0], gd);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const size_t o = (size_t)3 * (nod[a] - 1) + i;
+      const double td = NLGEOM == 2 ? dunode[o] : unode[o] + dunode[o];
+#pragma unroll
+      for (int j = 0; j < 3; j++) gu[i][j] += td * gd[j];
+    }
+  }
+  double de[6] = {gu[0][0], gu[1][1], gu[2][2], gu[0][1] + gu[1][0], gu[1][2] + gu[2][1], gu[2][0] + gu[0][2]};
+  if (NLGEOM == 1) {  // Green-Lagrange strain (:671-679)
+#pragma unroll
+    for (int c = 0; c < 3; c++) de[c] += 0.5 * (gu[0][c] * gu[0][c] + gu[1][c] * gu[1][c] + gu[2][c] * gu[2][c]);
+    de[3] += gu[0][0] * gu[0][1] + gu[1][0] * gu[1][1] + gu[2][0] * gu[2][1];
+    de[4] += gu[0][1] * gu[0][2] + gu[1][1] * gu[1][2] + gu[2][1] * gu[2][2];
+    de[5] += gu[0][0] * gu[0][2] + gu[1][0] * gu[1][2] + gu[2][0] * gu[2][2];
+  }
+  // MatlMatrix with isEp: the elastic matrix (the call itself sets the latch for an elastoplastic material)
+  const double D11 = m.E * (1.0 - m.nu) / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
+  const double D12 = m.E * m.nu / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
+  const double D44 = m.E / (1.0 + m.nu) * 0.5;
+  const double ds[6] = {D11 * de[0] + D12 * de[1] + D12 * de[2], D12 * de[0] + D11 * de[1] + D12 * de[2],
+                        D12 * de[0] + D12 * de[1] + D11 * de[2], D44 * de[3], D44 * de[4], D44 * de[5]};
+  const size_t gp = (size_t)NQ * elem + g;
+  double sg[6], eg[6];
+  if (NLGEOM == 2) {  // :702-732
+    double sb[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { sb[i] = active ? stress_bak[gp * 6 + i] : 0.0; eg[i] = (active ? strain_bak[gp * 6 + i] : 0.0) + de[i]; }
+    const double r01 = 0.5 * (gu[0][1] - gu[1][0]), r12 = 0.5 * (gu[1][2] - gu[2][1]), r02 = 0.5 * (gu[0][2] - gu[2][0]);
+    const double rot[3][3] = {{0.0, r01, r02}, {-r01, 0.0, r12}, {-r02, -r12, 0.0}};
+    const double Sb[3][3] = {{sb[0], sb[3], sb[5]}, {sb[3], sb[1], sb[4]}, {sb[5], sb[4], sb[2]}};
+    double dum[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double p = 0.0, q = 0.0;
+#pragma unroll
+        for (int l = 0; l < 3; l++) { p += rot[i][l] * Sb[l][j]; q += Sb[i][l] * rot[l][j]; }
+        dum[i][j] = p - q;
+      }
+    sg[0] = sb[0] + fx_real_default(ds[0]) + dum[0][0];
+    sg[1] = sb[1] + fx_real_default(ds[1]) + dum[1][1];
+    sg[2] = sb[2] + fx_real_default(ds[2]) + dum[2][2];
+    sg[3] = sb[3] + fx_real_default(ds[3]) + dum[0][1];
+    sg[4] = sb[4] + fx_real_default(ds[4]) + dum[1][2];
+    sg[5] = sb[5] + fx_real_default(ds[5]) + dum[2][0];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
+  }
+  if (m.plastic) {
+    int32_t ist = active ? istat[gp] : 0;      // idle lanes read no state another workgroup may be writing
+    double fs = active ? fstat[gp] : 0.0;
+    nl_backward_euler(m, sg, active ? plstrain[gp] : 0.0, ist, fs);
+    if (active) { istat[gp] = ist; fstat[gp] = fs; }
+  }
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) { stress[gp * 6 + i] = sg[i]; strain[gp * 6 + i] = eg[i]; }
+  }
+  // ---- internal force of this point (:767-833): UPDATELAG takes the derivatives and the determinant at the end configuration
+  double F[9];
+#pragma unroll
+  for (int c = 0; c < 3; c++)
+#pragma unroll
+    for (int d = 0; d < 3; d++) F[3 * c + d] = gu[c][d];
+  if (NLGEOM == 2) nl_tet_config_jacobian<ETYPE, NLGEOM>(nod, coord, unode, dunode, 1.0, g, det, inv);
+  const double wg = w * det;
+#pragma unroll
+  for (int a = 0; a < NN; a++) {
+    const double h0[3] = {0.0, 0.0, 0.0};
+    double gd[3], B[6][3], o[3];
+    tet_node_gderiv<ETYPE>(a, xi, et, ze, &inv[0][0], gd);
+    nl_node_B<NLGEOM>(gd, h0, F, B);
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      double s = 0.0;
+#pragma unroll
+      for (int p = 0; p < 6; p++) s += sg[p] * B[p][d];
+      o[d] = s * wg;
+#pragma unroll
+      for (int sft = 1; sft < NQ; sft <<= 1) o[d] += __shfl_xor(o[d], sft, 64);
+    }
+    if (active && a % NQ == g) {
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        if (qf_out) qf_out[(size_t)elem * (3 * NN) + 3 * a + d] = o[d];
+        else unsafeAtomicAdd(qforce + (size_t)3 * (nod[a] - 1) + d, o[d]);
+      }
+    }
+  }
+}
+
+// fstr_UpdateState for nq points per element: as k_nl_commit, the element of point i is i / nq
+__global__ void k_nl_commit_c3(int64_t npt, int nq, int plastic, const double *__restrict__ fstat, double *__restrict__ plstrain,
+                               const double *__restrict__ stress, const double *__restrict__ strain, double *__restrict__ stress_bak,
+                               double *__restrict__ strain_bak, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 6 * npt; i += (int64_t)gridDim.x * blockDim.x) {
+    stress_bak[i] = stress[i];
+    strain_bak[i] = strain[i];
+    if (i < npt) {
+      const int pl = mats ? mats[emat[i / nq] - 1].plastic : plastic;
+      if (pl) plstrain[i] = fstat[i];
+    }
+  }
+}

@@ -13,8 +13,9 @@
     fstr_Newton          fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
 
-for one TYPE=361 B-bar group with one isotropic (Mises elastoplastic or elastic) material per section.  Everything is
-resident on the GPU; there is NO CPU fallback.
+for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342 (fstr_solid(..., etype=341 | 342): STF_C3 / UPDATE_C3),
+with one isotropic (Mises elastoplastic or elastic) material per section.  Everything is resident on the GPU; there is NO CPU
+fallback.
 """
 import ctypes as C
 
@@ -63,15 +64,29 @@ class tMaterial:
 class fstr_solid:
     """The resident nonlinear state of one context (created by fx_nl_init)."""
 
-    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None):
+    NODES = {361: 8, 341: 4, 342: 10}     # nodes per element
+    POINTS = {361: 8, 341: 1, 342: 4}     # quadrature points per element (NumOfQuadPoints)
+
+    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361):
         """material: one tMaterial, or a list of them with elem_mat (1-based material id per element = the section's
-        material, hecMESH%section_ID -> fstrSOLID%materials)."""
+        material, hecMESH%section_ID -> fstrSOLID%materials).  etype: 361 (B-bar), or 341 / 342 (fx_nl_init_c3)."""
         self.ctx = ctx
+        self.etype = int(etype)
+        self.nn, self.nq = self.NODES.get(self.etype, 0), self.POINTS.get(self.etype, 0)
         self.coord = np.ascontiguousarray(hecMESH_coord, dtype=np.float64)
         self.conn = np.ascontiguousarray(hecMESH_conn, dtype=np.int32)
         self.material = material
         self.n_node, self.n_elem = self.coord.shape[0], self.conn.shape[0]
         mv = hecmw._MeshView(self.n_node, self.n_elem, _ptr(self.coord), _ptr(self.conn))
+        if self.etype != 361:
+            mats = list(material) if isinstance(material, (list, tuple)) else [material]
+            views = [m.view() for m in mats]
+            arr = (_MaterialView * len(views))(*views)
+            self.elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+            if len(views) > 1 and (self.elem_mat is None or self.elem_mat.shape != (self.n_elem,)):
+                raise ValueError("elem_mat: one material id per element")
+            _chk(lib().fx_nl_init_c3(ctx.h, C.byref(mv), self.etype, len(views), arr, _ptr(self.elem_mat)))
+            return
         if isinstance(material, (list, tuple)):
             views = [m.view() for m in material]
             arr = (_MaterialView * len(views))(*views)
@@ -86,9 +101,9 @@ class fstr_solid:
     # ---- state transfer (tests, restart, output)
     def get_state(self, names=("stress", "strain", "stress_bak", "strain_bak", "plstrain", "fstat", "istat",
                                "unode", "dunode", "qforce")):
-        ne, nn = self.n_elem, self.n_node
-        shapes = {"stress": (ne, 8, 6), "strain": (ne, 8, 6), "stress_bak": (ne, 8, 6), "strain_bak": (ne, 8, 6),
-                  "plstrain": (ne, 8), "fstat": (ne, 8), "istat": (ne, 8), "unode": (3 * nn,), "dunode": (3 * nn,),
+        ne, nn, q = self.n_elem, self.n_node, self.nq
+        shapes = {"stress": (ne, q, 6), "strain": (ne, q, 6), "stress_bak": (ne, q, 6), "strain_bak": (ne, q, 6),
+                  "plstrain": (ne, q), "fstat": (ne, q), "istat": (ne, q), "unode": (3 * nn,), "dunode": (3 * nn,),
                   "qforce": (3 * nn,)}
         out = {k: np.zeros(shapes[k], dtype=np.int32 if k == "istat" else np.float64) for k in names}
         v = _StateView(*[_ptr(out.get(k)) for k in shapes], 0)
@@ -106,12 +121,12 @@ class fstr_solid:
         _chk(lib().fx_nl_set_state(self.ctx.h, C.byref(v)))
 
     def element_tangents(self):
-        ke = np.zeros((self.n_elem, 24, 24))
+        ke = np.zeros((self.n_elem, 3 * self.nn, 3 * self.nn))
         _chk(lib().fx_nl_element_tangents(self.ctx.h, _ptr(ke)))
         return ke
 
     def element_update(self):
-        qf = np.zeros((self.n_elem, 24))
+        qf = np.zeros((self.n_elem, 3 * self.nn))
         _chk(lib().fx_nl_element_update(self.ctx.h, _ptr(qf)))
         return qf
 

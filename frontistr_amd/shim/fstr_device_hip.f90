@@ -8,9 +8,12 @@
 !>   fstr_UpdateNewton -> fx_nl_update_at (dunode up, QFORCE down)
 !>   fstr_UpdateState  -> fx_nl_commit + the quadrature-point history down (once per sub-step: results, restart)
 !> Taken only for what the device kernels cover -- static analysis with NLGEOM, every element TYPE=361 with the B-bar formulation,
-!> isotropic ELASTIC or Mises-elastoplastic materials with isotropic hardening, no temperature / contact / MPC / spring / local
-!> coordinate system / cutback; anything else runs the reference's own routines (kept, renamed, in the same binary).
-!> HECMW_GPU_ASSEMBLY=0 keeps the reference's element loops on the host for every deck.
+!> or (on one process) every element a tetrahedron TYPE=341 or every element TYPE=342, isotropic ELASTIC or Mises-elastoplastic
+!> materials with isotropic hardening, no temperature / contact / MPC / spring / local coordinate system; fixed or automatic
+!> increments (a cutback rolls the device's history back too, fsd_cutback); anything else runs the reference's own routines (kept,
+!> renamed, in the same binary).
+!> HECMW_GPU_ASSEMBLY=0 keeps the reference's element loops on the host for every deck; the tetrahedra are taken only with
+!> HECMW_GPU_NL_TET=1 (opt-in until their end-to-end time against the host loops is on record).
 module fstr_device_hip
   use iso_c_binding
   use hecmw
@@ -34,6 +37,8 @@ module fstr_device_hip
   logical, save :: lin_mixed = .false.             ! several element types: fx_assemble_groups / fx_update_groups_linear
   type(fx_elem_group), allocatable, save :: lin_groups(:)    ! hecMESH%elem_type_index / elem_type_item as the library takes them
   integer(c_int32_t), save :: n_elem = 0
+  integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or 341 / 342 (STF_C3 / UPDATE_C3, fx_nl_init_c3)
+  integer, save :: nl_nq = 8                       ! its quadrature points per element
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
   real(c_double), allocatable, target, save :: b6(:,:,:), b1(:,:), b6b(:,:,:)
   integer(c_int32_t), allocatable, target, save :: bi(:,:)
@@ -65,7 +70,8 @@ contains
     type(hecmwST_matrix), intent(in) :: hecMAT
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
-    integer :: elen, estat, i, icel, cid
+    character(len=3) :: tname
+    integer :: elen, estat, i, icel, cid, nn
     if (decided) then
       fsd_eligible = eligible
       return
@@ -82,8 +88,14 @@ contains
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return                       ! the solve must run on the device too: same predicate as hecmw_solve (method, preconditioner, no MPC / contact)
     if (hecMESH%n_elem_type /= 1) return
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
-    if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return
+    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return   ! the nonlinear kernels: 361 B-bar and the tetrahedra
     if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
+    if (lin_etype /= 361) then      ! tetrahedra opt in: no end-to-end timing against the host loops has been recorded yet (DESIGN.md section 4)
+      call get_environment_variable('HECMW_GPU_NL_TET', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+    endif
+    nn = 8
+    if (lin_etype /= 361) nn = c3_type_nodes(lin_etype)
     if (hecMESH%mpc%n_mpc > 0) return
     if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
@@ -95,11 +107,11 @@ contains
     !  host's, shim/fstr_Cutback_hip.f90 -> fsd_cutback.  A run continued from a restart file: the history read from the file is what
     !  fsd_init pushes to the device at the first fstr_StiffMatrix, after fstr_read_restart, fstr_solve_NLGEOM.f90:70-76.)
     do i = 1, hecMESH%section%n_sect
-      if (fstrSOLID%sections(i)%elemopt361 /= kel361BBAR) return
+      if (lin_etype == 361 .and. fstrSOLID%sections(i)%elemopt361 /= kel361BBAR) return
       if (hecMESH%section%sect_orien_ID(i) > 0) return
     enddo
     do icel = 1, hecMESH%n_elem
-      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= 8) return
+      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
       cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
       if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
     enddo
@@ -108,6 +120,15 @@ contains
     enddo
     eligible = .true.
     fsd_eligible = .true.
+    nl_etype = lin_etype
+    nl_nq = 8
+    if (nl_etype /= 361) nl_nq = c3_type_points(nl_etype)
+    if (nl_etype /= 361) then
+      write(tname, '(i3)') nl_etype
+      if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//tname//'); '// &
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+      return
+    endif
     if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
       'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
   end function fsd_eligible
@@ -376,11 +397,16 @@ contains
     do icel = 1, n_elem
       emat(icel) = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
     enddo
-    ierr = fx_nl_init_sections(ctx, mesh, int(nmat, c_int32_t), mats, emat)
-    if (ierr /= 0) call fsd_fail('fx_nl_init_sections')
+    if (nl_etype == 361) then
+      ierr = fx_nl_init_sections(ctx, mesh, int(nmat, c_int32_t), mats, emat)
+      if (ierr /= 0) call fsd_fail('fx_nl_init_sections')
+    else
+      ierr = fx_nl_init_c3(ctx, mesh, nl_etype, int(nmat, c_int32_t), mats, emat)
+      if (ierr /= 0) call fsd_fail('fx_nl_init_c3')
+    endif
     deallocate(mats, emat)
     if (allocated(b6)) deallocate(b6, b6b, b1, bi)
-    allocate(b6(6, 8, n_elem), b6b(6, 8, n_elem), b1(8, n_elem), bi(8, n_elem))
+    allocate(b6(6, nl_nq, n_elem), b6b(6, nl_nq, n_elem), b1(nl_nq, n_elem), bi(nl_nq, n_elem))
     call fsd_push_state(ctx, fstrSOLID)
     ready = .true.
     the_ctx_saved = ctx
@@ -417,10 +443,10 @@ contains
     integer(c_int) :: ierr
     integer :: icel, g
     real(c_double), allocatable, target :: s6(:,:,:), sb6(:,:,:), e6b(:,:,:), pl(:,:), fs(:,:)
-    allocate(s6(6, 8, n_elem), sb6(6, 8, n_elem), e6b(6, 8, n_elem), pl(8, n_elem), fs(8, n_elem))
+    allocate(s6(6, nl_nq, n_elem), sb6(6, nl_nq, n_elem), e6b(6, nl_nq, n_elem), pl(nl_nq, n_elem), fs(nl_nq, n_elem))
     bi = 0; fs = 0.d0
     do icel = 1, n_elem
-      do g = 1, 8
+      do g = 1, nl_nq
         b6(:, g, icel)  = fstrSOLID%elements(icel)%gausses(g)%strain
         s6(:, g, icel)  = fstrSOLID%elements(icel)%gausses(g)%stress
         e6b(:, g, icel) = fstrSOLID%elements(icel)%gausses(g)%strain_bak
@@ -615,7 +641,7 @@ contains
     ctx = fxb_context(hecMESH)
     ierr = fx_nl_commit(ctx)      ! unode += dunode is the host's (fstr_Newton :156-158); the device does the same on its copy
     if (ierr /= 0) call fsd_fail('fx_nl_commit')
-    allocate(s6(6, 8, n_elem), pl(8, n_elem), fs(8, n_elem))
+    allocate(s6(6, nl_nq, n_elem), pl(nl_nq, n_elem), fs(nl_nq, n_elem))
     sv%stress = c_loc(s6(1,1,1)); sv%strain = c_loc(b6(1,1,1)); sv%stress_bak = c_null_ptr; sv%strain_bak = c_null_ptr
     sv%plstrain = c_loc(pl(1,1)); sv%fstat = c_loc(fs(1,1)); sv%istat = c_loc(bi(1,1))
     sv%unode = c_null_ptr; sv%dunode = c_null_ptr; sv%qforce = c_null_ptr
@@ -623,7 +649,7 @@ contains
     ierr = fx_nl_get_state(ctx, sv)
     if (ierr /= 0) call fsd_fail('fx_nl_get_state')
     do icel = 1, n_elem
-      do g = 1, 8
+      do g = 1, nl_nq
         fstrSOLID%elements(icel)%gausses(g)%strain = b6(:, g, icel)
         fstrSOLID%elements(icel)%gausses(g)%stress = s6(:, g, icel)
         fstrSOLID%elements(icel)%gausses(g)%strain_bak = b6(:, g, icel)     ! fstr_UpdateState :338-339

@@ -335,9 +335,9 @@ typedef struct fx_material_view { /* tMaterial after fstr_ctrl_get_ELASTICITY/_P
   const double *tab;    /* ntab rows (yield stress, plastic strain) */
 } fx_material_view;
 typedef struct fx_nl_state_view { /* host arrays, any may be NULL (skipped).  tGaussStatus members (mechgauss.f90:13-22) */
-  double *stress, *strain, *stress_bak, *strain_bak; /* n_elem*8*6 */
-  double *plstrain, *fstat;                           /* n_elem*8: plstrain, fstatus(1) */
-  int32_t *istat;                                     /* n_elem*8: istatus(1) */
+  double *stress, *strain, *stress_bak, *strain_bak; /* n_elem*nq*6 (nq = 8 at 361) */
+  double *plstrain, *fstat;                           /* n_elem*nq: plstrain, fstatus(1) */
+  int32_t *istat;                                     /* n_elem*nq: istatus(1) */
   double *unode, *dunode, *qforce;                    /* 3*NP: fstrSOLID%unode, %dunode, %QFORCE */
   int32_t latch; /* MatlMatrix's saved flag (calMatMatrix.f90:39); set_state: <0 leaves it */
 } fx_nl_state_view;
@@ -348,6 +348,13 @@ int fx_nl_init(fx_context *ctx, const fx_mesh_view *mesh, const fx_material_view
  * tMaterial).  The materials may carry different NLGEOM flags (an ELASTIC TOTALLAG part next to a PLASTIC UPDATELAG part). */
 int fx_nl_init_sections(fx_context *ctx, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
                         const int32_t *elem_mat);
+/* The same context for a mesh of tetrahedra: etype 341 (4 nodes, 1 quadrature point) or 342 (10 nodes, 4 points), STF_C3 /
+ * UPDATE_C3 (static_LIB_3d.f90:47-205, :516-837) in their INFINITE / TOTALLAG / UPDATELAG branches.  elem_mat may be NULL with
+ * n_mat == 1.  Another etype: FX_ERROR_UNSUPPORTED; a tetrahedron that names a node twice: FX_ERROR_RUNTIME.  Every fx_nl_* entry
+ * point below works on either context; the per-point arrays hold nq(etype) points per element ([elem][point][.]), the element
+ * outputs (3 nn)^2 and 3 nn doubles per element. */
+int fx_nl_init_c3(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const fx_material_view *mats,
+                  const int32_t *elem_mat);
 /* fstr_Newton :63-68 + fstr_ass_load: dunode = 0, GL (3*NP, may be NULL), B = GL - QFORCE. */
 int fx_nl_begin_substep(fx_context *ctx, const double *GL);
 /* fstr_StiffMatrix (fstr_StiffMatrix.f90:18-212) + fstr_AddBC (fstr_AddBC.f90:17-190) with the
@@ -379,7 +386,7 @@ int fx_nl_commit(fx_context *ctx);
 int fx_nl_snapshot(fx_context *ctx, int load);
 int fx_nl_get_state(fx_context *ctx, fx_nl_state_view *s);
 int fx_nl_set_state(fx_context *ctx, const fx_nl_state_view *s);
-/* element-level outputs of the two kernels, no scatter (tests): ke n_elem*24*24, qf n_elem*24 */
+/* element-level outputs of the two kernels, no scatter (tests): ke n_elem*(3 nn)^2, qf n_elem*3 nn (nn = 8 at 361) */
 int fx_nl_element_tangents(fx_context *ctx, double *ke);
 int fx_nl_element_update(fx_context *ctx, double *qf);
 /* One substep of fstr_Newton around fx_solve_resident.  log: 7 doubles per Newton iteration

@@ -4,12 +4,17 @@ face pulled by 0.5 % in z with a little shear, multilinear Mises plasticity of t
 Lagrange (NLSTATIC default), SUBSTEPS sub-steps, CG + SSOR (or what --solver says) with TIMELOG.  Writes <dir>/cube.msh, cube.cnt,
 hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to time fistr1_hip end to end: device assembly
 (default) against HECMW_GPU_ASSEMBLY=0 (scripts/r3/fistr1_big.sh).  usage: fistr1_cube_deck.py DIR N [SUBSTEPS] [METHOD] [PRECOND] [STRAIN]
---etype 341|342 (with --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
+--etype 341|342 (with or without --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
 mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with --linear): the cube split into wedges
 (WedgeMesh, 2 per hexahedron; 352 with mid-edge nodes) or as 20-node hexahedra (Hex20Mesh).  --two-sections (with --linear): the second half of the elements
 forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33).  --mixed 1|2 (with --linear): the cube as a mesh of
 three element types (frontistr_amd.mesh.MixedMesh: 361 + 351 + 341, or 362 + 352 + 342 with shared mid-edge nodes), one !ELEMENT
-card per type in mesh order; with --two-sections the second half of the elements in that order is EGRP=E2."""
+card per type in mesh order; with --two-sections the second half of the elements in that order is EGRP=E2.
+NLSTATIC decks of tetrahedra (--etype 341|342 without --linear) take two more options:
+  --nl-material multilinear|bilinear|elastic_tl|elastic_ul   MAT1: Mises MULTILINEAR (default) or BILINEAR, both updated Lagrange;
+                                                             ELASTIC total Lagrange; `!ELASTIC, CAUCHY`, updated Lagrange.
+  --two-sections                                             the second half of the elements is MAT2, ELASTIC 70000 / 0.33, TOTAL
+                                                             Lagrange: next to an updated-Lagrange MAT1 the deck mixes the two flags."""
 import os
 import sys
 
@@ -21,11 +26,11 @@ if linear:
 form361 = None                       # --form361 FI|BBAR|IC: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's (IC)
 if "--form361" in sys.argv:
     k = sys.argv.index("--form361"); form361 = sys.argv[k + 1]; del sys.argv[k:k + 2]
-etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra (linear decks only)
+etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra (351 / 352 / 362: linear decks only)
 if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
-    if etype not in (341, 342, 351, 352, 362) or not linear:
-        sys.exit("--etype takes 341, 342, 351, 352 or 362, with --linear")
+    if etype not in (341, 342, 351, 352, 362) or (not linear and etype not in (341, 342)):
+        sys.exit("--etype takes 341 or 342, or with --linear 351, 352 or 362")
 mixed = 0                            # --mixed 1|2: hexahedra + wedges + tetrahedra of that order (linear decks only)
 if "--mixed" in sys.argv:
     k = sys.argv.index("--mixed"); mixed = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
@@ -34,8 +39,13 @@ if "--mixed" in sys.argv:
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear:
-        sys.exit("--two-sections needs --linear")
+    if not linear and etype not in (341, 342):
+        sys.exit("--two-sections needs --linear, or --etype 341|342")
+nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
+if "--nl-material" in sys.argv:
+    k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
+    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul"):
+        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl or elastic_ul, without --linear")
 d, n = sys.argv[1], int(sys.argv[2])
 nsub = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 method = sys.argv[4] if len(sys.argv) > 4 else "CG"
@@ -113,6 +123,24 @@ if linear:
 !END
 """ % ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" if two else "",
        "!SECTION, SECNUM=1, FORM361=%s\n" % form361 if form361 else "", method, precond))
+# MAT1 of the NLSTATIC deck.  multilinear / bilinear: Mises, updated Lagrange (the default of !PLASTIC); elastic_tl: total Lagrange
+# (the default of !ELASTIC under NLSTATIC); elastic_ul: `!ELASTIC, CAUCHY`, updated Lagrange.  --two-sections: MAT2 is ELASTIC (total Lagrange).
+NL_MATERIALS = {
+    "multilinear": """!ELASTIC
+ 206900.0, 0.29
+!PLASTIC, YIELD=MISES, HARDEN=MULTILINEAR
+ 450.0, 0.0
+ 608.0, 0.05
+ 679.0, 0.1
+ 732.0, 0.2
+ 752.0, 0.3
+ 766.0, 0.4
+ 780.0, 0.5
+""",
+    "bilinear": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MISES, HARDEN=BILINEAR\n 450.0, 2000.0\n",
+    "elastic_tl": "!ELASTIC\n 206900.0, 0.29\n",
+    "elastic_ul": "!ELASTIC, CAUCHY\n 206900.0, 0.29\n",
+}
 with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
     if not linear:
       fh.write("""!VERSION
@@ -126,22 +154,13 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
 !STEP, SUBSTEPS=%d, CONVERG=1.0e-3
  BOUNDARY, 1
 !MATERIAL, NAME=MAT1
-!ELASTIC
- 206900.0, 0.29
-!PLASTIC, YIELD=MISES, HARDEN=MULTILINEAR
- 450.0, 0.0
- 608.0, 0.05
- 679.0, 0.1
- 732.0, 0.2
- 752.0, 0.3
- 766.0, 0.4
- 780.0, 0.5
-!RESTART, FREQUENCY=100000
+%s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  5000, 1
  1.0e-8, 1.0, 0.0
 !END
-""" % (strain * n, 0.2 * strain * n, nsub, method, precond))
+""" % (strain * n, 0.2 * strain * n, nsub, NL_MATERIALS[nlmat],
+       "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" if two else "", method, precond))
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
