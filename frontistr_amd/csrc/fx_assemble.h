@@ -17,6 +17,7 @@
 // `!$omp atomic` for the same purpose).
 #pragma once
 #include "fx_internal.h"
+#include "fx_c3_element.h"
 
 #define FXA_BLOCK 256
 #define FXA_LPE(EO) 8                               // lanes per element: lane a owns the 3-row block of node a
@@ -52,18 +53,7 @@ __device__ __forceinline__ void hex8_global_deriv(const double (&ec)[8][3], doub
       for (int a = 0; a < 8; a++) s += ec[a][i] * dN[a][j];
       J[i][j] = s;
     }
-  det = J[0][0] * J[1][1] * J[2][2] + J[1][0] * J[2][1] * J[0][2] + J[2][0] * J[0][1] * J[1][2] -
-        J[2][0] * J[1][1] * J[0][2] - J[1][0] * J[0][1] * J[2][2] - J[0][0] * J[2][1] * J[1][2];
-  const double dum = 1.0 / det;
-  inv[0][0] = dum * (J[1][1] * J[2][2] - J[2][1] * J[1][2]);
-  inv[0][1] = dum * (-J[0][1] * J[2][2] + J[2][1] * J[0][2]);
-  inv[0][2] = dum * (J[0][1] * J[1][2] - J[1][1] * J[0][2]);
-  inv[1][0] = dum * (-J[1][0] * J[2][2] + J[2][0] * J[1][2]);
-  inv[1][1] = dum * (J[0][0] * J[2][2] - J[2][0] * J[0][2]);
-  inv[1][2] = dum * (-J[0][0] * J[1][2] + J[1][0] * J[0][2]);
-  inv[2][0] = dum * (J[1][0] * J[2][1] - J[2][0] * J[1][1]);
-  inv[2][1] = dum * (-J[0][0] * J[2][1] + J[2][0] * J[0][1]);
-  inv[2][2] = dum * (J[0][0] * J[1][1] - J[1][0] * J[0][1]);
+  invert3(J, det, inv);
 #pragma unroll
   for (int a = 0; a < 8; a++)
 #pragma unroll
@@ -146,12 +136,114 @@ __global__ void k_scatter_first_flag(int32_t n_elem, const int32_t *__restrict__
   const int32_t m = inod == jnod ? minD[inod - 1] : (jnod < inod ? minL[k] : minU[k]);
   if (m == col) pos[t] = k | FXA_FIRST_BIT;
 }
+// the colour of every element of a coloured list: ecol[order[p]] = base + (the colour k with off[k] <= p < off[k + 1]); empty
+// colours have off[k] == off[k + 1]
+__global__ void k_elem_colors(int32_t n, const int32_t *__restrict__ order, const int32_t *__restrict__ off, int32_t ncolor,
+                              int32_t base, int32_t *__restrict__ ecol) {
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n) return;
+  int lo = 0, hi = ncolor;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= p) lo = mid;
+    else hi = mid;
+  }
+  ecol[order[p]] = base + lo;
+}
 // blocks that no element contributes to (a profile wider than the mesh's): they would keep stale values without the clearing
 __global__ void k_count_uncovered(int64_t n, const int32_t *__restrict__ m, unsigned long long *__restrict__ count) {
   unsigned long long c = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) c += (m[i] == FXA_NO_COLOR);
   if (c) atomicAdd(count, c);
 }
+
+// ---- symmetric-block scatter of the stiffness kernels ---------------------------------------------------------------------
+// The resident block CRS matrix and the position map of the launch (null: binary searches, no first-write flags).
+struct ScatterDest {
+  const int32_t *indexL, *itemL, *indexU, *itemU;
+  double *D, *AL, *AU;
+  const int32_t *pos_map;
+};
+// One 3x3 block K_ab of a symmetric element matrix of NN nodes on its way into the matrix: stored at (a, b) and -- `twin` -- its
+// transpose at (b, a).  prepare() runs BEFORE the block's arithmetic: it finds the destinations and, for the coloured scatter
+// (`rmw`: plain read-modify-write), requests their old values, so that the reads' latency runs under the arithmetic; a
+// contribution whose first-write flag is set is stored, not added, and reads nothing.  commit() runs after it.
+template <int NN>
+struct BlockScatter {
+  int a, b;
+  bool twin, rmw;
+  double *dst = nullptr, *dstT = nullptr;
+  double old[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oldT[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+
+  // hecmw_mat_add_node (hecmw_mat_ass.f90:72-134): block (row node rnod, column node cnod) = block (ra, rb) of element elem
+  static __device__ __forceinline__ double *block_ptr(const ScatterDest &A, int32_t elem, int ra, int rb, int32_t rnod, int32_t cnod,
+                                                      bool &first) {
+    const int32_t raw = A.pos_map ? A.pos_map[(size_t)(NN * NN) * elem + NN * ra + rb] : 0;
+    first = A.pos_map && raw >= 0 && (raw & FXA_FIRST_BIT);  // k_scatter_first_flag: no earlier colour launch touches this block
+    if (rnod == cnod) return A.D + (size_t)9 * (rnod - 1);
+    if (cnod < rnod) {
+      const int32_t p = A.pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(A.itemL, A.indexL[rnod - 1], A.indexL[rnod], cnod);
+      return p < 0 ? nullptr : A.AL + (size_t)9 * p;
+    }
+    const int32_t p = A.pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(A.itemU, A.indexU[rnod - 1], A.indexU[rnod], cnod);
+    return p < 0 ? nullptr : A.AU + (size_t)9 * p;
+  }
+  // en: the element's NN node ids.  to_kout: element matrices out, nothing to find.  false: a block is not in the profile (*err = 2)
+  __device__ __forceinline__ bool prepare(const ScatterDest &A, bool to_kout, const int32_t *__restrict__ en, int32_t elem, int a_, int b_,
+                                          bool twin_, bool rmw_, int32_t *__restrict__ err) {
+    a = a_; b = b_; twin = twin_; rmw = rmw_;
+    if (to_kout) return true;
+    const int32_t inod = en[a], jnod = en[b];
+    bool first = false, firstT = false;
+    dst = block_ptr(A, elem, a, b, inod, jnod, first);
+    if (twin) dstT = block_ptr(A, elem, b, a, jnod, inod, firstT);
+    if (!dst || (twin && !dstT)) { if (err) atomicExch(err, 2); return false; }
+    if (rmw && !first) {
+#pragma unroll
+      for (int e = 0; e < 9; e++) old[e] = dst[e];
+    }
+    if (rmw && twin && !firstT) {
+#pragma unroll
+      for (int e = 0; e < 9; e++) oldT[e] = dstT[e];
+    }
+    return true;
+  }
+  // Kout (the pointer prepare()'s to_kout was made from, so that the compiler sees one condition): the element matrix
+  // ((3 NN)^2, row-major) at Kout + ko instead of the scatter
+  __device__ __forceinline__ void commit(const double (&K)[9], double *__restrict__ Kout, size_t ko) const {
+    if (Kout) {
+      double *Kel = Kout + ko;
+      constexpr int W = 3 * NN;
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          Kel[(size_t)(3 * a + i) * W + 3 * b + j] = K[3 * i + j];
+          if (twin) Kel[(size_t)(3 * b + j) * W + 3 * a + i] = K[3 * i + j];
+        }
+      return;
+    }
+    if (rmw) {
+#pragma unroll
+      for (int e = 0; e < 9; e++) dst[e] = old[e] + K[e];
+      if (twin) {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+          for (int j = 0; j < 3; j++) dstT[3 * j + i] = oldT[3 * j + i] + K[3 * i + j];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 9; e++) unsafeAtomicAdd(dst + e, K[e]);
+      if (twin) {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+          for (int j = 0; j < 3; j++) unsafeAtomicAdd(dstT + 3 * j + i, K[3 * i + j]);
+      }
+    }
+  }
+};
 
 // Elements that name a node twice (collapsed hexahedra) are left out of the coloured launches: two of their 64 blocks are one block
 // of the matrix, and the lanes of k_assemble_c3d8 / k_nl_stiffness that share it would read-modify-write it at the same time.  Their
@@ -411,49 +503,14 @@ __global__ __launch_bounds__(FXA_BS(ELEMOPT)) void k_assemble_c3d8(int32_t n_ele
   // of the 64, and scatters each off-diagonal one twice, as it stands into row a and transposed into row b.  4.5 strips per lane
   // instead of 8; the transposed copies differ from separately accumulated ones in the last bit at most (sums of the same products in the
   // same order, transposed), far inside the 1e-12 of the parity tests.  No other element of the launch touches these rows (colouring).
-  const int32_t inod = conn[(size_t)8 * elem + a];
-  auto block_ptr = [&](int ra, int rb, int32_t rnod, int32_t cnod, bool &first) -> double * {  // hecmw_mat_add_node, hecmw_mat_ass.f90:72-134
-    const int32_t raw = pos_map ? pos_map[(size_t)64 * elem + 8 * ra + rb] : 0;
-    first = pos_map && raw >= 0 && (raw & FXA_FIRST_BIT);  // k_scatter_first_flag: no earlier colour launch touches this block
-    if (rnod == cnod) return D + (size_t)9 * (rnod - 1);
-    if (cnod < rnod) {
-      const int32_t k = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemL, indexL[rnod - 1], indexL[rnod], cnod);
-      return k < 0 ? nullptr : AL + (size_t)9 * k;
-    }
-    const int32_t k = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemU, indexU[rnod - 1], indexU[rnod], cnod);
-    return k < 0 ? nullptr : AU + (size_t)9 * k;
-  };
+  const ScatterDest A = {indexL, itemL, indexU, itemU, D, AL, AU, pos_map};
 #pragma unroll 1
   for (int st = 0; st < 5; st++) {
     if (st == 4 && a >= 4) break;
     const int b = (a + st) & 7;
-    // the destination blocks of this strip and -- coloured scatter: plain read-modify-write -- their old values, requested BEFORE the
-    // strip's arithmetic: the reads' latency runs under ~500 flops instead of after them
-    double *dst = nullptr, *dstT = nullptr;
-    double old[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oldT[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (!Kout) {
-      const int32_t jnod = conn[(size_t)8 * elem + b];
-      bool first = false, firstT = false;
-      dst = block_ptr(a, b, inod, jnod, first);
-      if (st > 0) dstT = block_ptr(b, a, jnod, inod, firstT);
-      if (!dst || (st > 0 && !dstT)) { if (err) atomicExch(err, 2); continue; }
-#ifndef FXA_EXP_NOSCATTER
-      if (elem_list && !first) {  // the first contribution to a block is stored, not added: nothing to read
-#pragma unroll
-        for (int e = 0; e < 9; e++) old[e] = dst[e];
-      }
-      if (elem_list && !firstT) {
-        if (st > 0) {
-#pragma unroll
-          for (int e = 0; e < 9; e++) oldT[e] = dstT[e];
-        }
-      }
-#endif
-    }
+    BlockScatter<8> sc;  // destinations and old values BEFORE the strip's arithmetic: the reads' latency runs under ~500 flops
+    if (!sc.prepare(A, Kout != nullptr, conn + (size_t)8 * elem, elem, a, b, st > 0, elem_list != nullptr, err)) continue;
     double K[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#ifdef FXA_EXP_NOCOMPUTE  // timing experiment: the scatter alone
-    K[0] = 1e-3 * (double)(a + b);
-#else
 #pragma unroll 1
     for (int LX = 0; LX < 8; LX++) {
       double Ba[6][3], Bb[6][3];
@@ -461,7 +518,6 @@ __global__ __launch_bounds__(FXA_BS(ELEMOPT)) void k_assemble_c3d8(int32_t n_ele
       node_B_at(b, LX, Bb);
       btdb_accumulate(Ba, Bb, D11, D12, D44, Jsh[el][LX][9], K);
     }
-#endif
     if (IC) {  // condense (3dIC.f90:206-209)
 #pragma unroll
       for (int i = 0; i < 3; i++)
@@ -473,40 +529,8 @@ __global__ __launch_bounds__(FXA_BS(ELEMOPT)) void k_assemble_c3d8(int32_t n_ele
           K[3 * i + j] -= sm;
         }
     }
-    if (Kout) {  // by element id; with an element list (the collapsed elements, k_add_elem_blocks) by position in the list
-      const size_t ko = (size_t)(elem_list ? epos : elem) * 576;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          Kout[ko + (size_t)(3 * a + i) * 24 + 3 * b + j] = K[3 * i + j];
-          if (st > 0) Kout[ko + (size_t)(3 * b + j) * 24 + 3 * a + i] = K[3 * i + j];
-        }
-      continue;
-    }
-#ifdef FXA_EXP_NOSCATTER  // timing experiment: the arithmetic alone (one word written so that nothing is optimised away)
-    if (K[0] + K[4] + K[8] == 1.2345e300) dst[0] = K[0];
-    continue;
-#endif
-    if (elem_list) {
-#pragma unroll
-      for (int e = 0; e < 9; e++) dst[e] = old[e] + K[e];
-      if (st > 0) {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) dstT[3 * j + i] = oldT[3 * j + i] + K[3 * i + j];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 9; e++) unsafeAtomicAdd(dst + e, K[e]);
-      if (st > 0) {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) unsafeAtomicAdd(dstT + 3 * j + i, K[3 * i + j]);
-      }
-    }
+    // element matrices by element id; with an element list (the collapsed elements, k_add_elem_blocks) by position in the list
+    sc.commit(K, Kout, (size_t)(elem_list ? epos : elem) * 576);
   }
 }
 

@@ -5,29 +5,9 @@
 // Scatter: every group keeps its own colouring (ElemColors, as the single-type calls) and the groups run one after another,
 // colour after colour, on one stream: no two elements of a launch share a node, launches are ordered, so there are no atomics and
 // the sums are bitwise reproducible.  The first-write flags (fx_assemble.h) must know the first contribution to a block in the
-// launch order of ALL groups: each element gets the global colour "colours of the groups before its own + its colour"
-// (k_group_elem_colors), k_scatter_first_min runs over every group's map into one set of per-block minima, then
-// k_scatter_first_flag over every group's map.  A block that no element of the first group touches is then stored by the first
-// later group that does, and the matrix needs no clearing.
+// launch order of ALL groups: build_first_write (fx_assemble_host.h) takes every group's map.  A block that no element of the
+// first group touches is then stored by the first later group that does, and the matrix needs no clearing.
 #pragma once
-#include <cstdarg>
-
-struct ColourOffsets {
-  int32_t off[66];  // offsets[0 .. ncolor] of one group's ElemColors (at most 64 colours, fx_order.cpp)
-};
-// ecol[order[p]] = base + (the colour whose range holds position p)
-__global__ void k_group_elem_colors(int32_t n, const int32_t *__restrict__ order, ColourOffsets co, int32_t ncolor, int32_t base,
-                                    int32_t *__restrict__ ecol) {
-  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (p >= n) return;
-  int lo = 0, hi = ncolor;  // the colour k with off[k] <= p < off[k + 1] (empty colours have off[k] == off[k + 1])
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (co.off[mid] <= p) lo = mid;
-    else hi = mid;
-  }
-  ecol[order[p]] = base + lo;
-}
 
 static uint64_t fnv_mix(uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; }
 
@@ -35,110 +15,50 @@ static uint64_t fnv_mix(uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211
 // d_conn[g]: group g's connectivity on the device.
 static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group *groups, const std::vector<const int32_t *> &d_conn) {
   AsmGroups &ag = c->asm_groups;
-  const DevCSR &A = c->A;
   uint64_t sig = 1469598103934665603ull;
-  bool have_all = true, flaggable = true;
+  bool have_all = true;
   for (int32_t g = 0; g < n_group; g++) {
     const ElemColors &ec = ag.ec[g];
     if (groups[g].n_elem < 1) continue;
     sig = fnv_mix(fnv_mix(fnv_mix(sig, ec.key), (uint64_t)ec.etype), (uint64_t)ec.n_elem);
     have_all &= ec.pos != nullptr;
-    flaggable &= !ec.offsets.empty() && !ec.dup_nodes;  // atomics (not coloured) or collapsed hexahedra in a group: no flags anywhere
   }
   sig = fnv_mix(sig, (uint64_t)n_group) | 1;
   if (have_all && ag.flag_sig == sig) return 0;
   ag.flag_sig = 0;
   ag.first_write = false;
+  std::vector<FirstWriteGroup> fw;
   for (int32_t g = 0; g < n_group; g++) {  // maps made for another set of groups may carry that set's flags: made again, without
     dev_free(ag.ec[g].pos);
     ag.ec[g].first_write = false;
     if (groups[g].n_elem < 1) continue;
-    if (ensure_scatter_map(c, ag.ec[g], groups[g].n_elem, d_conn[g], false, c3_nodes(groups[g].etype))) return FX_ERROR_RUNTIME;
-    flaggable &= ag.ec[g].pos != nullptr;  // FX_ASM_MAP=0, or no memory
+    if (ensure_scatter_map(c, ag.ec[g], groups[g].n_elem, d_conn[g], groups[g].etype)) return FX_ERROR_RUNTIME;
+    fw.push_back({&ag.ec[g], d_conn[g]});
   }
-  static const bool no_first = getenv("FX_ASM_FIRST") && atoi(getenv("FX_ASM_FIRST")) == 0;
-  if (flaggable && !no_first) {
-    DevScratch tmp;
-    int32_t *minD = nullptr, *minL = nullptr, *minU = nullptr;
-    unsigned long long *cnt = nullptr;
-    std::vector<int32_t *> ecol((size_t)n_group, nullptr);
-    bool mem = !(tmp.alloc(&minD, (size_t)A.NP) || tmp.alloc(&minL, (size_t)std::max(A.NPL, 1)) ||
-                 tmp.alloc(&minU, (size_t)std::max(A.NPU, 1)) || tmp.alloc(&cnt, 1));
-    for (int32_t g = 0; g < n_group && mem; g++)
-      if (groups[g].n_elem > 0) mem = !tmp.alloc(&ecol[g], (size_t)groups[g].n_elem);
-    if (!mem) { (void)hipGetLastError(); ag.flag_sig = sig; return 0; }  // no memory for the temporaries: read-modify-write, cleared matrix
-    HIP_TRY(hipMemsetAsync(minD, 0x7F, (size_t)A.NP * 4, c->stream));  // FXA_NO_COLOR
-    HIP_TRY(hipMemsetAsync(minL, 0x7F, (size_t)std::max(A.NPL, 1) * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(minU, 0x7F, (size_t)std::max(A.NPU, 1) * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-    const dim3 b(256);
-    int32_t base = 0;
-    for (int32_t g = 0; g < n_group; g++) {
-      const ElemColors &ec = ag.ec[g];
-      const int32_t ne = groups[g].n_elem;
-      if (ne < 1) continue;
-      const int nn = c3_nodes(groups[g].etype), ncolor = (int)ec.offsets.size() - 1;
-      ColourOffsets co;
-      for (int k = 0; k < 66; k++) co.off[k] = ec.offsets[std::min<size_t>((size_t)k, ec.offsets.size() - 1)];
-      hipLaunchKernelGGL(k_group_elem_colors, dim3((unsigned)((ne + 255) / 256)), b, 0, c->stream, ne, (const int32_t *)ec.order, co,
-                         ncolor, base, ecol[g]);
-      const dim3 gr((unsigned)(((int64_t)nn * nn * ne + 255) / 256));
-      hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_min), gr, b, 0, c->stream, ne, d_conn[g], (const int32_t *)ec.pos,
-                         (const int32_t *)ecol[g], minD, minL, minU);
-      base += ncolor;
-    }
-    for (int32_t g = 0; g < n_group; g++) {
-      const ElemColors &ec = ag.ec[g];
-      const int32_t ne = groups[g].n_elem;
-      if (ne < 1) continue;
-      const int nn = c3_nodes(groups[g].etype);
-      const dim3 gr((unsigned)(((int64_t)nn * nn * ne + 255) / 256));
-      hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_flag), gr, b, 0, c->stream, ne, d_conn[g], ec.pos, (const int32_t *)ecol[g],
-                         (const int32_t *)minD, (const int32_t *)minL, (const int32_t *)minU);
-    }
-    hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NP, (const int32_t *)minD, cnt);
-    if (A.NPL > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPL, (const int32_t *)minL, cnt);
-    if (A.NPU > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPU, (const int32_t *)minU, cnt);
-    unsigned long long uncovered = 1;
-    HIP_TRY(hipMemcpyAsync(&uncovered, cnt, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
-    ag.first_write = (uncovered == 0);  // a block nobody writes would keep what it held: then the matrix is cleared (flagged stores onto zeros are the adds)
-    for (int32_t g = 0; g < n_group; g++) ag.ec[g].first_write = ag.first_write;
-  }
+  // atomics (not coloured), collapsed hexahedra or no map (FX_ASM_MAP=0, no memory) in a group: no flags anywhere
+  if (build_first_write(c, fw, &ag.first_write)) return FX_ERROR_RUNTIME;
   ag.flag_sig = sig;
   return 0;
-}
-
-static thread_local char g_groups_msg[240];
-static int groups_fail(const char *who, int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  const int n = snprintf(g_groups_msg, sizeof g_groups_msg, "%s: ", who);
-  vsnprintf(g_groups_msg + n, sizeof g_groups_msg - (size_t)n, fmt, ap);
-  va_end(ap);
-  g_fx_error = g_groups_msg;
-  return code;
 }
 
 // What both entry points refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
 // material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
 static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                         int32_t n_mat, const double *E, const double *nu) {
-  if (n_group < 1 || !groups) return groups_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
+  if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
   for (int32_t g = 0; g < n_group; g++) {
     if (c3_nodes(groups[g].etype) == 0)
-      return groups_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)",
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)",
                          (int)g + 1, (int)groups[g].etype);
     if (groups[g].etype == 361 && (groups[g].elemopt < 1 || groups[g].elemopt > 3))
-      return groups_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
   }
-  if (n_node < 1 || !coord) return groups_fail(who, FX_ERROR_RUNTIME, "empty mesh");
-  if (n_mat < 1 || !E || !nu) return groups_fail(who, FX_ERROR_RUNTIME, "materials missing");
+  if (n_node < 1 || !coord) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  if (n_mat < 1 || !E || !nu) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
-    if (G.n_elem < 0 || (G.n_elem > 0 && !G.conn)) return groups_fail(who, FX_ERROR_RUNTIME, "group %d: connectivity missing", (int)g + 1);
-    if (n_mat > 1 && G.n_elem > 0 && !G.elem_mat) return groups_fail(who, FX_ERROR_RUNTIME, "group %d: several materials need elem_mat", (int)g + 1);
+    if (G.n_elem < 0 || (G.n_elem > 0 && !G.conn)) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: connectivity missing", (int)g + 1);
+    if (n_mat > 1 && G.n_elem > 0 && !G.elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: several materials need elem_mat", (int)g + 1);
     const int nn = c3_nodes(G.etype);
     int32_t bad_mat = INT32_MAX, bad_node = INT32_MAX, dup = INT32_MAX;  // lowest offending element (0-based) of each kind
     parallel_for(G.n_elem, [&](int64_t a, int64_t b) {
@@ -154,10 +74,10 @@ static int check_groups(const char *who, int32_t n_node, const double *coord, in
       __atomic_fetch_min(&bad_node, bn, __ATOMIC_RELAXED);
       __atomic_fetch_min(&dup, dp, __ATOMIC_RELAXED);
     });
-    if (bad_mat != INT32_MAX) return groups_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: material id out of range", (int)g + 1, (int)bad_mat + 1);
-    if (bad_node != INT32_MAX) return groups_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: node id out of range", (int)g + 1, (int)bad_node + 1);
+    if (bad_mat != INT32_MAX) return fx_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: material id out of range", (int)g + 1, (int)bad_mat + 1);
+    if (bad_node != INT32_MAX) return fx_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: node id out of range", (int)g + 1, (int)bad_node + 1);
     if (dup != INT32_MAX)
-      return groups_fail(who, FX_ERROR_RUNTIME, "group %d (TYPE=%d), element %d names a node twice (a degenerate element)", (int)g + 1,
+      return fx_fail(who, FX_ERROR_RUNTIME, "group %d (TYPE=%d), element %d names a node twice (a degenerate element)", (int)g + 1,
                          (int)G.etype, (int)dup + 1);
   }
   return 0;
@@ -214,9 +134,8 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
                                 ms_assemble, G.etype);
   }
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->have_profile) return groups_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
-  if (n_node != c->A.NP) return groups_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
-  DevCSR &A = c->A;
+  if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
+  if (n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
   AsmGroups &ag = c->asm_groups;
   DevScratch tmp;
   GroupUploads up;
@@ -239,20 +158,12 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
   for (int32_t g = 0; g < n_group; g++)
     if (!ag.ec[g].dup_off.empty() && tmp.alloc(&d_dupk[g], (size_t)576 * ag.ec[g].dup_off.back())) return FX_ERROR_RUNTIME;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  if (!ag.first_write) {  // hecmw_mat_clear (fstr_StiffMatrix.f90:40), once
-    HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
-  }
+  if (!ag.first_write && mat_clear(c)) return FX_ERROR_RUNTIME;  // once
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
     if (G.n_elem < 1) continue;
-    const ElemColors *ec = &ag.ec[g];
-    const double *mt = up.emat[g] ? up.mtab : nullptr;
-    if (launch_assemble_c3_type(G.etype, c, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, nullptr, d_err, up.emat[g], mt, ec)) {
-    } else if (G.elemopt == 1) launch_assemble<1>(c, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, nullptr, d_err, up.emat[g], mt, ec, d_dupk[g]);
-    else if (G.elemopt == 2) launch_assemble<2>(c, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, nullptr, d_err, up.emat[g], mt, ec, d_dupk[g]);
-    else launch_assemble<3>(c, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, nullptr, d_err, up.emat[g], mt, ec, d_dupk[g]);
+    launch_assemble(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, nullptr, d_err, up.emat[g],
+                    up.emat[g] ? up.mtab : nullptr, &ag.ec[g], d_dupk[g]);
   }
   HIP_TRY(hipGetLastError());
   if (int rc = load_and_bc(c, tmp, who, load, n_bc, bc_node, bc_dof, bc_val)) return rc;
@@ -263,8 +174,7 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_assemble) *ms_assemble = ms;
-  if (herr == 1) { g_fx_error = "PIVOT ERROR in the incompatible-mode condensation (calInverse)"; return FX_ERROR_RUNTIME; }
-  if (herr == 2) { g_fx_error = "###ERROR### : cannot find connectivity (element not covered by the profile)"; return FX_ERROR_RUNTIME; }
+  if (int rc = assembly_error(herr)) return rc;
   c->have_values = true;
   c->bell_valid = false;
   return 0;
@@ -302,7 +212,7 @@ extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const doub
   }
   HIP_TRY(hipSetDevice(c->device));
   const size_t total = groups_stage_doubles(n_group, groups);
-  if (total == 0) return groups_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  if (total == 0) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
   DevScratch tmp;
   GroupUploads up;
   double *d_coord = nullptr, *d_disp = nullptr, *d_q = nullptr, *d_strain = nullptr, *d_stress = nullptr;
@@ -318,7 +228,7 @@ extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const doub
   upd_stage_wait();
   if (g_upd_stage.make_err || g_upd_stage.cap < total) {
     g_upd_stage.make_err = 0;
-    if (upd_stage_make(c->device, total)) { (void)hipGetLastError(); return groups_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
+    if (upd_stage_make(c->device, total)) { (void)hipGetLastError(); return fx_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
   }
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   size_t at = 0;  // group g's results start at `at` doubles, in the device arrays and in the staging

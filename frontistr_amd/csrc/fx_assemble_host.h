@@ -1,5 +1,6 @@
 // Host entry points of the assembly side (included at the end of fistr_hip.hip).
 #pragma once
+#include <cstdarg>
 
 // hecmw_mat_con (hecmw_mat_con.f90:23-268): CRS block profile from element connectivity.
 // Node -> element incidence by counting sort (host threads, relaxed atomic counters: the order of a node's elements does
@@ -154,13 +155,6 @@ extern "C" int fx_color_elements(int32_t NP, int32_t n_elem, int32_t nn, const i
   return 0;
 }
 
-static void elastic_constants(double E, double nu, double &D11, double &D12, double &D44) {
-  // calElasticMatrix, 3-D case (ElasticLinear.f90:43-55)
-  D11 = E * (1.0 - nu) / (1.0 - 2.0 * nu) / (1.0 + nu);
-  D12 = E * nu / (1.0 - 2.0 * nu) / (1.0 + nu);
-  D44 = E / (1.0 + nu) * 0.5;
-}
-
 // Colour the elements of a mesh once (fx_order.cpp: color_elements) and keep the grouped element list on the device; the
 // stiffness kernels then scatter colour by colour without atomics.  FX_ASM_ATOMIC=1 keeps the single-launch atomic scatter.
 static void elem_colors_free(ElemColors &ec) {
@@ -169,57 +163,157 @@ static void elem_colors_free(ElemColors &ec) {
   dev_free(ec.dup);
   ec = ElemColors();
 }
-// the position map of k_scatter_map for the resident profile and the device connectivity d_conn of nn-node elements (8, 4, 10,
-// 6, 15 or 20; FX_ASM_MAP=0: search every time)
-#define FX_NN_DISPATCH(nn, F) \
-  ((nn) == 4 ? F<4> : ((nn) == 10 ? F<10> : ((nn) == 6 ? F<6> : ((nn) == 15 ? F<15> : ((nn) == 20 ? F<20> : F<8>)))))
-static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, bool with_first = false,
-                              int nn = 8) {
+// f(C3Tag<ETYPE>()) for the element type given at run time: the five STF_C3 types (with_c3_type), or those and 361
+// (with_solid_type).  false: not one of them, f is not called.
+template <int ETYPE>
+struct C3Tag {
+  static constexpr int value = ETYPE;
+};
+template <class F>
+static bool with_c3_type(int32_t etype, F &&f) {
+  switch (etype) {
+    case 341: f(C3Tag<341>()); return true;
+    case 342: f(C3Tag<342>()); return true;
+    case 351: f(C3Tag<351>()); return true;
+    case 352: f(C3Tag<352>()); return true;
+    case 362: f(C3Tag<362>()); return true;
+    default: return false;
+  }
+}
+template <class F>
+static bool with_solid_type(int32_t etype, F &&f) {
+  if (etype != 361) return with_c3_type(etype, f);
+  f(C3Tag<361>());
+  return true;
+}
+// nodes and quadrature points per element of the types the device knows (C3_TABLE); 0: none of them
+static int c3_nodes(int32_t etype) { return c3_facts(etype).nn; }
+static int c3_points(int32_t etype) { return c3_facts(etype).nq; }
+// the types of fx_assemble_c3 / fx_update_c3_linear / fx_element_stiffness_c3: what STF_C3 / UPDATE_C3 serve (361 has its own entries)
+static bool c3_linear_type(int32_t etype) { return etype != 361 && c3_nodes(etype) != 0; }
+#define FX_C3_UNSUPPORTED "element type not supported on the device (341, 342, 351, 352, 362; 361 through "
+
+// g_fx_error = "<who>: <formatted text>"; returns code
+static thread_local char g_fail_msg[240];
+static int fx_fail(const char *who, int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  const int n = snprintf(g_fail_msg, sizeof g_fail_msg, "%s: ", who);
+  vsnprintf(g_fail_msg + n, sizeof g_fail_msg - (size_t)n, fmt, ap);
+  va_end(ap);
+  g_fx_error = g_fail_msg;
+  return code;
+}
+// what the stiffness kernels report through their error word
+static int assembly_error(int32_t herr) {
+  if (herr == 1) { g_fx_error = "PIVOT ERROR in the incompatible-mode condensation (calInverse)"; return FX_ERROR_RUNTIME; }
+  if (herr == 2) { g_fx_error = "###ERROR### : cannot find connectivity (element not covered by the profile)"; return FX_ERROR_RUNTIME; }
+  return 0;
+}
+// hecmw_mat_clear (fstr_StiffMatrix.f90:40)
+static int mat_clear(fx_context *c) {
+  DevCSR &A = c->A;
+  HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));
+  HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
+  HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
+  return 0;
+}
+
+// the position map of k_scatter_map for the resident profile and the device connectivity d_conn of the elements of type etype
+// (FX_ASM_MAP=0: search every time); without first-write flags
+static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, int32_t etype) {
   static const bool off = getenv("FX_ASM_MAP") && atoi(getenv("FX_ASM_MAP")) == 0;
   if (off || ec.pos || ec.offsets.empty()) return 0;
+  const int nn = c3_nodes(etype);
   const int64_t nmap = (int64_t)nn * nn * n_elem;
   if (dev_alloc(&ec.pos, (size_t)nmap)) { (void)hipGetLastError(); ec.pos = nullptr; return 0; }  // no memory: keep searching
   const DevCSR &A = c->A;
-  hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_map), dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, c->stream, n_elem, d_conn,
-                     A.indexL, A.itemL, A.indexU, A.itemU, ec.pos);
-  HIP_TRY(hipGetLastError());
-  // first-write flags (FX_ASM_FIRST=0: off): which contribution to a block comes first in the order of the colour launches
-  static const bool no_first = getenv("FX_ASM_FIRST") && atoi(getenv("FX_ASM_FIRST")) == 0;
   ec.first_write = false;
-  if (!with_first || no_first || ec.dup_nodes) return 0;  // (the nonlinear kernels keep their own map, without flags: fx_nonlinear_host.h)
-  {
-    DevScratch tmp;
-    int32_t *ecol = nullptr, *minD = nullptr, *minL = nullptr, *minU = nullptr;
-    unsigned long long *cnt = nullptr;
-    if (tmp.alloc(&ecol, (size_t)n_elem) || tmp.alloc(&minD, (size_t)A.NP) || tmp.alloc(&minL, (size_t)std::max(A.NPL, 1)) ||
-        tmp.alloc(&minU, (size_t)std::max(A.NPU, 1)) || tmp.alloc(&cnt, 1)) {
-      (void)hipGetLastError();
-      return 0;  // no memory for the temporaries: the scatter stays read-modify-write everywhere
-    }
-    std::vector<int32_t> order((size_t)n_elem), color((size_t)n_elem, 0);
-    HIP_TRY(hipMemcpy(order.data(), ec.order, (size_t)n_elem * 4, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k + 1 < ec.offsets.size(); k++)
-      for (int32_t e = ec.offsets[k]; e < ec.offsets[k + 1]; e++) color[order[e]] = (int32_t)k;
-    HIP_TRY(hipMemcpyAsync(ecol, color.data(), (size_t)n_elem * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(minD, 0x7F, (size_t)A.NP * 4, c->stream));  // FXA_NO_COLOR = 0x7F7F7F7F: above every colour
-    HIP_TRY(hipMemsetAsync(minL, 0x7F, (size_t)std::max(A.NPL, 1) * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(minU, 0x7F, (size_t)std::max(A.NPU, 1) * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
-    const dim3 g((unsigned)((nmap + 255) / 256)), b(256);
-    hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_min), g, b, 0, c->stream, n_elem, d_conn, (const int32_t *)ec.pos,
-                       (const int32_t *)ecol, minD, minL, minU);
-    hipLaunchKernelGGL(FX_NN_DISPATCH(nn, k_scatter_first_flag), g, b, 0, c->stream, n_elem, d_conn, ec.pos, (const int32_t *)ecol,
-                       (const int32_t *)minD, (const int32_t *)minL, (const int32_t *)minU);
-    hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NP, (const int32_t *)minD, cnt);
-    if (A.NPL > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPL, (const int32_t *)minL, cnt);
-    if (A.NPU > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPU, (const int32_t *)minU, cnt);
-    unsigned long long uncovered = 1;
-    HIP_TRY(hipMemcpyAsync(&uncovered, cnt, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // also: `color` is a host temporary
-    HIP_TRY(hipGetLastError());
-    ec.first_write = (uncovered == 0);  // a block nobody writes would keep what it held: then the matrix is cleared as before (the flags are harmless)
-  }
+  with_solid_type(etype, [&](auto t) {
+    hipLaunchKernelGGL((k_scatter_map<C3El<decltype(t)::value>::NN>), dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, c->stream, n_elem, d_conn,
+                       A.indexL, A.itemL, A.indexU, A.itemU, ec.pos);
+  });
+  HIP_TRY(hipGetLastError());
   return 0;
+}
+
+// First-write flags (FX_ASM_FIRST=0: off) in the position maps of element groups that are launched one after another, each
+// colour by colour: which contribution to a block comes first in that order.  An element's colour is "colours of the groups
+// before its own + its colour" (k_elem_colors), k_scatter_first_min runs over every group's map into one set of per-block
+// minima, then k_scatter_first_flag over every group's map.  The flags are set only where every group is coloured, has its map
+// and no collapsed element; *covered: they are set and no block of the profile is left without a contribution, so the
+// matrix needs no clearing.
+struct FirstWriteGroup {
+  ElemColors *ec;
+  const int32_t *d_conn;
+};
+static int build_first_write(fx_context *c, const std::vector<FirstWriteGroup> &groups, bool *covered) {
+  static const bool no_first = getenv("FX_ASM_FIRST") && atoi(getenv("FX_ASM_FIRST")) == 0;
+  const DevCSR &A = c->A;
+  *covered = false;
+  if (groups.empty()) return 0;
+  std::vector<int32_t> offs;  // every group's colour offsets, back to back
+  for (const FirstWriteGroup &g : groups) {
+    g.ec->first_write = false;
+    if (!g.ec->pos || g.ec->offsets.empty() || g.ec->dup_nodes) return 0;
+    offs.insert(offs.end(), g.ec->offsets.begin(), g.ec->offsets.end());
+  }
+  if (no_first) return 0;
+  DevScratch tmp;
+  int32_t *d_offs = nullptr, *minD = nullptr, *minL = nullptr, *minU = nullptr;
+  unsigned long long *cnt = nullptr;
+  std::vector<int32_t *> ecol(groups.size(), nullptr);
+  bool mem = !(tmp.alloc(&d_offs, offs.size()) || tmp.alloc(&minD, (size_t)A.NP) || tmp.alloc(&minL, (size_t)std::max(A.NPL, 1)) ||
+               tmp.alloc(&minU, (size_t)std::max(A.NPU, 1)) || tmp.alloc(&cnt, 1));
+  for (size_t g = 0; g < groups.size() && mem; g++) mem = !tmp.alloc(&ecol[g], (size_t)groups[g].ec->n_elem);
+  if (!mem) { (void)hipGetLastError(); return 0; }  // no memory for the temporaries: read-modify-write everywhere, cleared matrix
+  HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(minD, 0x7F, (size_t)A.NP * 4, c->stream));  // FXA_NO_COLOR = 0x7F7F7F7F: above every colour
+  HIP_TRY(hipMemsetAsync(minL, 0x7F, (size_t)std::max(A.NPL, 1) * 4, c->stream));
+  HIP_TRY(hipMemsetAsync(minU, 0x7F, (size_t)std::max(A.NPU, 1) * 4, c->stream));
+  HIP_TRY(hipMemsetAsync(cnt, 0, 8, c->stream));
+  const dim3 b(256);
+  for (int pass = 0; pass < 2; pass++) {  // the minima over all groups, then the flags
+    const int32_t *go = d_offs;
+    int32_t base = 0;
+    for (size_t g = 0; g < groups.size(); g++) {
+      const ElemColors &ec = *groups[g].ec;
+      const int32_t ne = ec.n_elem, ncolor = (int32_t)ec.offsets.size() - 1;
+      const int nn = c3_nodes(ec.etype);
+      const dim3 gr((unsigned)(((int64_t)nn * nn * ne + 255) / 256));
+      with_solid_type(ec.etype, [&](auto t) {
+        constexpr int NN = C3El<decltype(t)::value>::NN;
+        if (pass == 0) {
+          hipLaunchKernelGGL(k_elem_colors, dim3((unsigned)((ne + 255) / 256)), b, 0, c->stream, ne, (const int32_t *)ec.order, go, ncolor,
+                             base, ecol[g]);
+          hipLaunchKernelGGL((k_scatter_first_min<NN>), gr, b, 0, c->stream, ne, groups[g].d_conn, (const int32_t *)ec.pos,
+                             (const int32_t *)ecol[g], minD, minL, minU);
+        } else {
+          hipLaunchKernelGGL((k_scatter_first_flag<NN>), gr, b, 0, c->stream, ne, groups[g].d_conn, ec.pos, (const int32_t *)ecol[g],
+                             (const int32_t *)minD, (const int32_t *)minL, (const int32_t *)minU);
+        }
+      });
+      base += ncolor;
+      go += ncolor + 1;
+    }
+  }
+  hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NP, (const int32_t *)minD, cnt);
+  if (A.NPL > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPL, (const int32_t *)minL, cnt);
+  if (A.NPU > 0) hipLaunchKernelGGL(k_count_uncovered, dim3(1024), b, 0, c->stream, (int64_t)A.NPU, (const int32_t *)minU, cnt);
+  unsigned long long uncovered = 1;
+  HIP_TRY(hipMemcpyAsync(&uncovered, cnt, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // also: `offs` is a host temporary
+  HIP_TRY(hipGetLastError());
+  *covered = (uncovered == 0);  // a block nobody writes would keep what it held: then the matrix is cleared as before (the flags are harmless)
+  for (const FirstWriteGroup &g : groups) g.ec->first_write = *covered;
+  return 0;
+}
+// the map of one colouring with its own first-write flags, made once (the single-type entry points, fx_nl_init_c3)
+static int ensure_scatter_map_flagged(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, int32_t etype) {
+  if (ec.pos) return 0;
+  if (ensure_scatter_map(c, ec, n_elem, d_conn, etype)) return FX_ERROR_RUNTIME;
+  bool covered;
+  return build_first_write(c, {{&ec, d_conn}}, &covered);
 }
 // Moves the elements that name a node twice out of the colour lists (order, off) into their own list (dups, dup_off), colour by
 // colour, each list keeping the colour order; an empty dup_off: there are none.  k_add_elem_blocks adds them after the colours.
@@ -292,67 +386,60 @@ static int ensure_elem_colors(fx_context *c, ElemColors &ec, int32_t n_elem, con
   return 0;
 }
 
-template <int EO>
-static void launch_assemble(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
-                            double D44, double *Kout, int32_t *err, const int32_t *elem_mat = nullptr,
-                            const double *mat_tab = nullptr, const ElemColors *ec = nullptr, double *dup_k = nullptr) {
+// launch(grid, e0, e1) for every non-empty range [off[k], off[k + 1]) of an element list -- one launch per colour -- with
+// epb elements per workgroup; one_range: a single launch over [off.front(), off.back()).
+template <class L>
+static void for_colour_ranges(const std::vector<int32_t> &off, bool one_range, int epb, L &&launch) {
+  for (size_t k = 0; k + 1 < off.size(); k++) {
+    const int32_t e0 = one_range ? off.front() : off[k], e1 = one_range ? off.back() : off[k + 1];
+    if (e1 > e0) launch(dim3((unsigned)((e1 - e0 + epb - 1) / epb)), e0, e1);
+    if (one_range) break;
+  }
+}
+// One linear stiffness kernel (k_assemble_c3d8, k_assemble_tet, k_assemble_c3: epb elements per workgroup of bs lanes) over a mesh:
+// colour by colour through the position map, or -- not coloured, or element matrices out (Kout) -- all elements in one launch.
+using AssembleKernel = void (*)(int32_t, const double *, const int32_t *, double, double, double, const int32_t *, const int32_t *,
+                                const int32_t *, const int32_t *, double *, double *, double *, double *, int32_t *, const int32_t *,
+                                const double *, const int32_t *, int32_t, const int32_t *);
+static void launch_coloured(fx_context *c, AssembleKernel kern, int epb, int bs, int32_t n_elem, const double *coord, const int32_t *conn,
+                            double D11, double D12, double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
+                            const ElemColors *ec) {
   const DevCSR &A = c->A;
-  if (ec && !ec->offsets.empty() && !Kout) {
-    for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
-      const int32_t e0 = ec->offsets[k], e1 = ec->offsets[k + 1];
-      if (e1 <= e0) continue;
-      hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3((e1 - e0 + FXA_EPB(EO) - 1) / FXA_EPB(EO)), dim3(FXA_BS(EO)), 0, c->stream, e1, coord,
-                         conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
-                         (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
-    }
-    if (!ec->dup_off.empty()) {  // collapsed elements: element matrices (dup_k, by position), then added colour by colour
-      const int32_t nd = ec->dup_off.back();
-      hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3((nd + FXA_EPB(EO) - 1) / FXA_EPB(EO)), dim3(FXA_BS(EO)), 0, c->stream, nd, coord,
-                         conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, dup_k, err, elem_mat, mat_tab,
-                         (const int32_t *)ec->dup, 0, (const int32_t *)nullptr);
-      for (size_t k = 0; k + 1 < ec->dup_off.size(); k++) {
-        const int32_t p0 = ec->dup_off[k], p1 = ec->dup_off[k + 1];
-        if (p1 > p0)
-          hipLaunchKernelGGL(k_add_elem_blocks, dim3((p1 - p0 + 63) / 64), dim3(64), 0, c->stream, p0, p1, (const int32_t *)ec->dup,
-                             (const double *)dup_k, conn, (const int32_t *)ec->pos, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL,
-                             A.AU, err);
-      }
-    }
+  const bool coloured = ec && !ec->offsets.empty() && !Kout;
+  const int32_t *list = coloured ? ec->order : nullptr, *pos = coloured ? ec->pos : nullptr;
+  for_colour_ranges(coloured ? ec->offsets : std::vector<int32_t>{0, n_elem}, false, epb, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL(kern, grid, dim3(bs), 0, c->stream, e1, coord, conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL,
+                       A.AU, Kout, err, elem_mat, mat_tab, list, e0, pos);
+  });
+}
+
+// TYPE=361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8, 341 / 342 through k_assemble_tet, 351 / 352 / 362 through
+// k_assemble_c3 (elemopt unused).  dup_k: room for the element matrices of the collapsed hexahedra of ec.
+static void launch_assemble(fx_context *c, int32_t etype, int elemopt, int32_t n_elem, const double *coord, const int32_t *conn, double D11,
+                            double D12, double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
+                            const ElemColors *ec, double *dup_k = nullptr) {
+  if (with_c3_type(etype, [&](auto t) {
+        using El = C3El<decltype(t)::value>;
+        AssembleKernel kern;
+        if constexpr (El::TET) kern = k_assemble_tet<decltype(t)::value>;
+        else kern = k_assemble_c3<decltype(t)::value>;
+        launch_coloured(c, kern, El::EPB, El::BS, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec);
+      }))
     return;
-  }
-  hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3((n_elem + FXA_EPB(EO) - 1) / FXA_EPB(EO)), dim3(FXA_BS(EO)), 0, c->stream, n_elem,
-                     coord, conn, D11, D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat,
-                     mat_tab, (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
+  const AssembleKernel kern = elemopt == 1 ? k_assemble_c3d8<1> : (elemopt == 2 ? k_assemble_c3d8<2> : k_assemble_c3d8<3>);
+  const int epb = elemopt == 1 ? FXA_EPB(1) : FXA_EPB(3), bs = elemopt == 1 ? FXA_BS(1) : FXA_BS(3);
+  launch_coloured(c, kern, epb, bs, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec);
+  if (Kout || !ec || ec->dup_off.empty()) return;
+  // collapsed elements: element matrices (dup_k, by position), then added colour by colour
+  const DevCSR &A = c->A;
+  const int32_t nd = ec->dup_off.back();
+  hipLaunchKernelGGL(kern, dim3((nd + epb - 1) / epb), dim3(bs), 0, c->stream, nd, coord, conn, D11, D12, D44, A.indexL, A.itemL, A.indexU,
+                     A.itemU, A.D, A.AL, A.AU, dup_k, err, elem_mat, mat_tab, (const int32_t *)ec->dup, 0, (const int32_t *)nullptr);
+  for_colour_ranges(ec->dup_off, false, 64, [&](dim3 grid, int32_t p0, int32_t p1) {
+    hipLaunchKernelGGL(k_add_elem_blocks, grid, dim3(64), 0, c->stream, p0, p1, (const int32_t *)ec->dup, (const double *)dup_k, conn,
+                       (const int32_t *)ec->pos, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, err);
+  });
 }
-
-// nodes per element of the types the linear device assembly knows; 0: none of them
-static int c3_nodes(int32_t etype) {
-  switch (etype) {
-    case 361: return 8;
-    case 341: return 4;
-    case 342: return 10;
-    case 351: return 6;
-    case 352: return 15;
-    case 362: return 20;
-    default: return 0;
-  }
-}
-// the types of fx_assemble_c3 / fx_update_c3_linear / fx_element_stiffness_c3: what STF_C3 / UPDATE_C3 serve (361 has its own entries)
-static bool c3_linear_type(int32_t etype) { return etype != 361 && c3_nodes(etype) != 0; }
-// quadrature points per element (NumOfQuadPoints, element.f90:415-447)
-static int c3_points(int32_t etype) {
-  switch (etype) {
-    case 361: return 8;
-    case 341: return 1;
-    case 342: return 4;
-    case 351: return 2;
-    case 352: return 9;
-    case 362: return 27;
-    default: return 0;
-  }
-}
-#define FX_C3_UNSUPPORTED "element type not supported on the device (341, 342, 351, 352, 362; 361 through "
-
 
 // A tetrahedron, wedge or 20-node hexahedron that names a node twice is degenerate (the reference stops in getJacobian or
 // assembles a singular element): refused, never assembled.
@@ -384,61 +471,6 @@ static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int
   return 0;
 }
 
-template <int ETYPE>
-static void launch_assemble_tet(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
-                                double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
-                                const ElemColors *ec) {
-  const DevCSR &A = c->A;
-  constexpr int EPB = FXT_EPB(ETYPE);
-  if (ec && !ec->offsets.empty() && !Kout) {
-    for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
-      const int32_t e0 = ec->offsets[k], e1 = ec->offsets[k + 1];
-      if (e1 > e0)
-        hipLaunchKernelGGL((k_assemble_tet<ETYPE>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, e1, coord, conn, D11,
-                           D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
-                           (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
-    }
-    return;
-  }
-  hipLaunchKernelGGL((k_assemble_tet<ETYPE>), dim3((n_elem + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, n_elem, coord, conn, D11, D12,
-                     D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
-                     (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
-}
-
-template <int ETYPE>
-static void launch_assemble_c3(fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11, double D12,
-                               double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
-                               const ElemColors *ec) {
-  const DevCSR &A = c->A;
-  constexpr int EPB = FXC_EPB(ETYPE);
-  if (ec && !ec->offsets.empty() && !Kout) {
-    for (size_t k = 0; k + 1 < ec->offsets.size(); k++) {
-      const int32_t e0 = ec->offsets[k], e1 = ec->offsets[k + 1];
-      if (e1 > e0)
-        hipLaunchKernelGGL((k_assemble_c3<ETYPE>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXC_BS), 0, c->stream, e1, coord, conn, D11,
-                           D12, D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
-                           (const int32_t *)ec->order, e0, (const int32_t *)ec->pos);
-    }
-    return;
-  }
-  hipLaunchKernelGGL((k_assemble_c3<ETYPE>), dim3((n_elem + EPB - 1) / EPB), dim3(FXC_BS), 0, c->stream, n_elem, coord, conn, D11, D12,
-                     D44, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, err, elem_mat, mat_tab,
-                     (const int32_t *)nullptr, 0, (const int32_t *)nullptr);
-}
-// 341 / 342 through k_assemble_tet, 351 / 352 / 362 through k_assemble_c3; false: not one of them
-static bool launch_assemble_c3_type(int32_t etype, fx_context *c, int32_t n_elem, const double *coord, const int32_t *conn, double D11,
-                                    double D12, double D44, double *Kout, int32_t *err, const int32_t *elem_mat, const double *mat_tab,
-                                    const ElemColors *ec) {
-  switch (etype) {
-    case 341: launch_assemble_tet<341>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
-    case 342: launch_assemble_tet<342>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
-    case 351: launch_assemble_c3<351>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
-    case 352: launch_assemble_c3<352>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
-    case 362: launch_assemble_c3<362>(c, n_elem, coord, conn, D11, D12, D44, Kout, err, elem_mat, mat_tab, ec); return true;
-    default: return false;
-  }
-}
-
 // `load` (or zero) becomes B, then hecmw_mat_ass_bc (hecmw_mat_ass.f90:292) for the listed dofs: once per assembly, after the last
 // element group.  The temporaries live in the caller's scratch until its synchronize.
 static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const double *load, int32_t n_bc, const int32_t *bc_node,
@@ -447,12 +479,6 @@ static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const do
   double *d_bcv = nullptr, *d_val = nullptr;
   int32_t *d_node = nullptr, *d_dof = nullptr;
   uint8_t *d_flag = nullptr;
-  static thread_local char msg[200];
-  auto fail = [&](const char *what, int code) {
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    g_fx_error = msg;
-    return code;
-  };
   if (load) HIP_TRY(hipMemcpyAsync(A.B, load, (size_t)3 * A.NP * 8, hipMemcpyHostToDevice, c->stream));
   else HIP_TRY(hipMemsetAsync(A.B, 0, (size_t)3 * A.NP * 8, c->stream));
   if (n_bc > 0) {
@@ -460,7 +486,7 @@ static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const do
         tmp.alloc(&d_dof, (size_t)n_bc) || tmp.alloc(&d_val, (size_t)n_bc))
       return FX_ERROR_RUNTIME;
     for (int32_t k = 0; k < n_bc; k++)
-      if (bc_node[k] < 1 || bc_node[k] > A.NP) return fail("BC node id out of range", FX_ERROR_RUNTIME);
+      if (bc_node[k] < 1 || bc_node[k] > A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "BC node id out of range");
     HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
     HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
     HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
@@ -477,7 +503,7 @@ static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const do
   return 0;
 }
 
-// etype 361 (elemopt 1 IC, 2 B-bar, 3 FI) through k_assemble_c3d8; the other types as launch_assemble_c3_type (elemopt unused)
+// one element type over the whole mesh (launch_assemble), cached colouring c->asm_colors
 static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int32_t n_mat, const double *Es,
                                 const double *nus, const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
                                 const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble,
@@ -485,18 +511,11 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   HIP_TRY(hipSetDevice(c->device));
   const int nn = c3_nodes(etype);
   const char *who = etype == 361 ? "fx_assemble_c3d8" : "fx_assemble_c3";
-  static thread_local char msg[200];
-  auto fail = [&](const char *what, int code) {
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    g_fx_error = msg;
-    return code;
-  };
-  if (!c->have_profile) return fail("upload the profile first (fx_upload FX_UP_PROFILE)", FX_ERROR_RUNTIME);
-  if (mesh->n_node != c->A.NP) return fail("mesh/profile size mismatch", FX_ERROR_RUNTIME);
-  if (etype == 361 && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
-  if (nn == 0) return fail(FX_C3_UNSUPPORTED "fx_assemble_c3d8)", FX_ERROR_UNSUPPORTED);
+  if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
+  if (mesh->n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
+  if (etype == 361 && (elemopt < 1 || elemopt > 3)) return fx_fail(who, FX_ERROR_UNSUPPORTED, "elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)");
+  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_assemble_c3d8)");
   if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;  // (361: its checks stay in the colouring)
-  DevCSR &A = c->A;
   DevScratch tmp;
   double *d_coord = nullptr;
   int32_t *d_conn = nullptr, *d_err = nullptr;
@@ -506,7 +525,7 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)nn * mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
   if (ensure_elem_colors(c, c->asm_colors, mesh->n_elem, mesh->conn, mesh->n_node, nn, etype) ||
-      ensure_scatter_map(c, c->asm_colors, mesh->n_elem, d_conn, true, nn))
+      ensure_scatter_map_flagged(c, c->asm_colors, mesh->n_elem, d_conn, etype))
     return FX_ERROR_RUNTIME;  // both cached per (profile, mesh, element type)
   double D11 = 0.0, D12 = 0.0, D44 = 0.0;
   int32_t *d_emat = nullptr;
@@ -529,16 +548,9 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   double *d_dupk = nullptr;  // element matrices of the collapsed elements
   if (!c->asm_colors.dup_off.empty() && tmp.alloc(&d_dupk, (size_t)576 * c->asm_colors.dup_off.back())) return FX_ERROR_RUNTIME;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  // hecmw_mat_clear (fstr_StiffMatrix.f90:40)
-  if (!(c->asm_colors.first_write && c->asm_colors.pos && !c->asm_colors.offsets.empty())) {  // first-write scatter: every block is stored before it is added to
-    HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
-  }
-  if (launch_assemble_c3_type(etype, c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors)) {
-  } else if (elemopt == 1) launch_assemble<1>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
-  else if (elemopt == 2) launch_assemble<2>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
-  else launch_assemble<3>(c, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
+  // first-write scatter: every block is stored before it is added to, no clearing
+  if (!(c->asm_colors.first_write && c->asm_colors.pos && !c->asm_colors.offsets.empty()) && mat_clear(c)) return FX_ERROR_RUNTIME;
+  launch_assemble(c, etype, elemopt, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
   HIP_TRY(hipGetLastError());
   if (int rc = load_and_bc(c, tmp, who, load, n_bc, bc_node, bc_dof, bc_val)) return rc;
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
@@ -548,8 +560,7 @@ static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double 
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_assemble) *ms_assemble = ms;
-  if (herr == 1) { g_fx_error = "PIVOT ERROR in the incompatible-mode condensation (calInverse)"; return FX_ERROR_RUNTIME; }
-  if (herr == 2) { g_fx_error = "###ERROR### : cannot find connectivity (element not covered by the profile)"; return FX_ERROR_RUNTIME; }
+  if (int rc = assembly_error(herr)) return rc;
   c->have_values = true;
   c->bell_valid = false;   // the preconditioner is refreshed by the flags / recycle policy of the next solve, not here
   return 0;
@@ -583,16 +594,8 @@ extern "C" int fx_element_stiffness_c3d8(fx_context *c, int elemopt, const doubl
   HIP_TRY(hipMemset(d_err, 0, 4));
   double D11, D12, D44;
   elastic_constants(E, nu, D11, D12, D44);
-  const int32_t *nul = nullptr;
-  double *nud = nullptr;
-#define ONE(EO)                                                                                                         \
-  hipLaunchKernelGGL((k_assemble_c3d8<EO>), dim3(1), dim3(FXA_BS(EO)), 0, c->stream, 1, d_coord, d_conn, D11, D12, D44, nul, \
-                     nul, nul, nul, nud, nud, nud, d_k, d_err, nul, (const double *)nullptr, nul, 0, nul)
-  if (elemopt == 1) ONE(1);
-  else if (elemopt == 2) ONE(2);
-  else if (elemopt == 3) ONE(3);
-  else { g_fx_error = "elemopt must be 1, 2 or 3"; return FX_ERROR_UNSUPPORTED; }
-#undef ONE
+  if (elemopt < 1 || elemopt > 3) { g_fx_error = "elemopt must be 1, 2 or 3"; return FX_ERROR_UNSUPPORTED; }
+  launch_assemble(c, 361, elemopt, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(stiff, d_k, 576 * 8, hipMemcpyDeviceToHost));
@@ -632,7 +635,7 @@ extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const doubl
   HIP_TRY(hipMemset(d_err, 0, 4));
   double D11, D12, D44;
   elastic_constants(E, nu, D11, D12, D44);
-  (void)launch_assemble_c3_type(etype, c, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
+  launch_assemble(c, etype, 0, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(stiff, d_k, (size_t)w * w * 8, hipMemcpyDeviceToHost));

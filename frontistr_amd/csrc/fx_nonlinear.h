@@ -42,19 +42,8 @@ __device__ __forceinline__ void hex8_gderiv(const double (&ec)[8][3], double xi,
       for (int a = 0; a < 8; a++) s += ec[a][i] * dN[a][j];
       J[i][j] = s;
     }
-  det = J[0][0] * J[1][1] * J[2][2] + J[1][0] * J[2][1] * J[0][2] + J[2][0] * J[0][1] * J[1][2] -
-        J[2][0] * J[1][1] * J[0][2] - J[1][0] * J[0][1] * J[2][2] - J[0][0] * J[2][1] * J[1][2];
-  const double dum = 1.0 / det;
   double inv[3][3];
-  inv[0][0] = dum * (J[1][1] * J[2][2] - J[2][1] * J[1][2]);
-  inv[0][1] = dum * (-J[0][1] * J[2][2] + J[2][1] * J[0][2]);
-  inv[0][2] = dum * (J[0][1] * J[1][2] - J[1][1] * J[0][2]);
-  inv[1][0] = dum * (-J[1][0] * J[2][2] + J[2][0] * J[1][2]);
-  inv[1][1] = dum * (J[0][0] * J[2][2] - J[2][0] * J[0][2]);
-  inv[1][2] = dum * (-J[0][0] * J[1][2] + J[1][0] * J[0][2]);
-  inv[2][0] = dum * (J[1][0] * J[2][1] - J[2][0] * J[1][1]);
-  inv[2][1] = dum * (-J[0][0] * J[2][1] + J[2][0] * J[0][1]);
-  inv[2][2] = dum * (J[0][0] * J[1][1] - J[1][0] * J[0][1]);
+  invert3(J, det, inv);
 #pragma unroll
   for (int a = 0; a < 8; a++)
 #pragma unroll
@@ -140,9 +129,8 @@ __device__ __forceinline__ constexpr int sym21(int i, int j) { return (i <= j) ?
 // minus GEOMAT_C3 for the updated-Lagrange flag.
 __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int flag, const double (&s)[6], int istat, double fstat1,
                                                 double (&Dm)[21]) {
-  const double D11 = m.E * (1.0 - m.nu) / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D12 = m.E * m.nu / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D44 = m.E / (1.0 + m.nu) * 0.5;
+  double D11, D12, D44;
+  elastic_constants(m.E, m.nu, D11, D12, D44);
 #pragma unroll
   for (int k = 0; k < 21; k++) Dm[k] = 0.0;
   Dm[sym21(0, 0)] = D11; Dm[sym21(1, 1)] = D11; Dm[sym21(2, 2)] = D11;
@@ -154,8 +142,8 @@ __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int f
     const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
     const double q = 2.0 * sqrt(J2), r3 = sqrt(3.0);
     const double a[6] = {r3 * (dv[0] / q), r3 * (dv[1] / q), r3 * (dv[2] / q), r3 * (2.0 * dv[3] / q), r3 * (2.0 * dv[4] / q), r3 * (2.0 * dv[5] / q)};
-    const double da[6] = {D11 * a[0] + D12 * a[1] + D12 * a[2], D12 * a[0] + D11 * a[1] + D12 * a[2], D12 * a[0] + D12 * a[1] + D11 * a[2],
-                          D44 * a[3], D44 * a[4], D44 * a[5]};
+    double da[6];
+    iso_stress(D11, D12, D44, a, da);
     double dum = 0.0;
 #pragma unroll
     for (int i = 0; i < 6; i++) dum += da[i] * a[i];
@@ -430,10 +418,10 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
       g[i][j] = s;
     }
   const double dvol = vol0 - (g[0][0] + g[1][1] + g[2][2]) / 3.0;
-  const double D11 = m.E * (1.0 - m.nu) / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D12 = m.E * m.nu / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D44 = m.E / (1.0 + m.nu) * 0.5;
-  double de[6] = {g[0][0] + dvol, g[1][1] + dvol, g[2][2] + dvol, g[0][1] + g[1][0], g[1][2] + g[2][1], g[2][0] + g[0][2]};
+  double D11, D12, D44, de[6];
+  elastic_constants(m.E, m.nu, D11, D12, D44);
+  small_strain(g, de);
+  de[0] += dvol; de[1] += dvol; de[2] += dvol;
   if (NLGEOM == 1) {  // Green-Lagrange strain :378-388
 #pragma unroll
     for (int c = 0; c < 3; c++) de[c] += 0.5 * (g[0][c] * g[0][c] + g[1][c] * g[1][c] + g[2][c] * g[2][c]);
@@ -441,8 +429,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
     de[4] += g[0][1] * g[0][2] + g[1][1] * g[1][2] + g[2][1] * g[2][2];
     de[5] += g[0][0] * g[0][2] + g[1][0] * g[1][2] + g[2][0] * g[2][2];
   }
-  const double ds[6] = {D11 * de[0] + D12 * de[1] + D12 * de[2], D12 * de[0] + D11 * de[1] + D12 * de[2],
-                        D12 * de[0] + D12 * de[1] + D11 * de[2], D44 * de[3], D44 * de[4], D44 * de[5]};
+  double ds[6];
+  iso_stress(D11, D12, D44, de, ds);
   const size_t gp = (size_t)8 * elem + LX;
   double sg[6], eg[6];
   if (NLGEOM == 2) {  // :407-432

@@ -132,7 +132,9 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
         for (size_t k = 1; k < n.grp_off[g].size(); k++)
           if (n.grp_off[g][k] > n.colors.offsets.back()) n.colors.offsets.push_back(n.grp_off[g][k]);
     }
-    if (ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn, etype != 361 && coloured, nn)) return FX_ERROR_RUNTIME;
+    if (etype != 361 && coloured ? ensure_scatter_map_flagged(c, n.colors, mesh->n_elem, n.conn, etype)
+                                 : ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn, etype))
+      return FX_ERROR_RUNTIME;
   }
   for (double *p : {n.stress, n.strain, n.stress_bak, n.strain_bak}) HIP_TRY(hipMemsetAsync(p, 0, 6 * npt * 8, c->stream));
   for (double *p : {n.plstrain, n.fstat}) HIP_TRY(hipMemsetAsync(p, 0, npt * 8, c->stream));
@@ -175,18 +177,14 @@ template <int ETYPE, int G>
 static void nl_launch_stiffness_tet_group(fx_context *c, double *Kout) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
-  const std::vector<int32_t> &off = n.grp_off[G];
-  constexpr int EPB = FXT_EPB(ETYPE);
-  const bool one_range = Kout || n.scatter_atomic;  // element matrices out, or atomics: the group's colours in one launch
-  for (size_t k = 0; k + 1 < off.size(); k++) {
-    const int32_t e0 = one_range ? off.front() : off[k], e1 = one_range ? off.back() : off[k + 1];
-    if (e1 > e0)
-      hipLaunchKernelGGL((k_nl_stiffness_tet<ETYPE, G>), dim3((e1 - e0 + EPB - 1) / EPB), dim3(FXT_BS), 0, c->stream, e1, n.coord, n.conn,
-                         n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL,
-                         A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos,
-                         n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat);
-    if (one_range) break;
-  }
+  using El = C3El<ETYPE>;
+  // element matrices out, or atomics: the group's colours in one launch
+  for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL((k_nl_stiffness_tet<ETYPE, G>), grid, dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat,
+                       n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
+                       (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0,
+                       (const NlMat *)n.mats, (const int32_t *)n.emat);
+  });
 }
 template <int ETYPE, int G>
 static void nl_launch_update_tet_group(fx_context *c, double *qf_out) {
@@ -195,39 +193,40 @@ static void nl_launch_update_tet_group(fx_context *c, double *qf_out) {
   if (off.empty() || off.back() <= off.front()) return;
   const int32_t e0 = off.front(), e1 = off.back();
   const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;  // as nl_launch_update_group
-  const int64_t lanes = (int64_t)(e1 - e0) * TetEl<ETYPE>::NQ;
-  hipLaunchKernelGGL((k_nl_update_tet<ETYPE, G>), dim3((unsigned)((lanes + FXU_TET_BS - 1) / FXU_TET_BS)), dim3(FXU_TET_BS), 0, c->stream,
-                     e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat,
+  using El = C3El<ETYPE>;
+  hipLaunchKernelGGL((k_nl_update_tet<ETYPE, G>), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1,
+                     n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat,
                      n.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
 }
-template <int ETYPE>
+// the three NLGEOM groups of a context of tetrahedra: tangent (update == false) or stress update
 static void nl_launch_tet(fx_context *c, double *Kout, double *qf_out, bool update) {
-  if (update) {
-    nl_launch_update_tet_group<ETYPE, 0>(c, qf_out);
-    nl_launch_update_tet_group<ETYPE, 1>(c, qf_out);
-    nl_launch_update_tet_group<ETYPE, 2>(c, qf_out);
-  } else {
-    nl_launch_stiffness_tet_group<ETYPE, 0>(c, Kout);
-    nl_launch_stiffness_tet_group<ETYPE, 1>(c, Kout);
-    nl_launch_stiffness_tet_group<ETYPE, 2>(c, Kout);
-  }
+  with_c3_type(c->nl.etype, [&](auto t) {
+    constexpr int ET = decltype(t)::value;
+    if constexpr (C3El<ET>::TET) {
+      if (update) {
+        nl_launch_update_tet_group<ET, 0>(c, qf_out);
+        nl_launch_update_tet_group<ET, 1>(c, qf_out);
+        nl_launch_update_tet_group<ET, 2>(c, qf_out);
+      } else {
+        nl_launch_stiffness_tet_group<ET, 0>(c, Kout);
+        nl_launch_stiffness_tet_group<ET, 1>(c, Kout);
+        nl_launch_stiffness_tet_group<ET, 2>(c, Kout);
+      }
+    }
+  });
 }
 
 template <int G>
 static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
-  const std::vector<int32_t> &off = n.grp_off[G];
-  const bool one_range = Kout || n.scatter_atomic;  // element matrices out, or atomics: the group's colours in one launch
-  for (size_t k = 0; k + 1 < off.size(); k++) {
-    const int32_t e0 = one_range ? off.front() : off[k], e1 = one_range ? off.back() : off[k + 1];
-    if (e1 > e0)
-      hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord,
-                         n.conn, n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU,
-                         A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos,
-                         n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat, 0);
-    if (one_range) break;
-  }
+  // element matrices out, or atomics: the group's colours in one launch
+  for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, FXN_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL((k_nl_stiffness<G>), grid, dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch,
+                       n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
+                       (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0,
+                       (const NlMat *)n.mats, (const int32_t *)n.emat, 0);
+  });
   // collapsed elements: their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter --
   // added colour by colour (k_add_elem_blocks)
   const std::vector<int32_t> &doff = n.dup_off[G];
@@ -245,8 +244,7 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
                          A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
 static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
-  if (c->nl.etype == 341) { nl_launch_tet<341>(c, Kout, nullptr, false); return 0; }
-  if (c->nl.etype == 342) { nl_launch_tet<342>(c, Kout, nullptr, false); return 0; }
+  if (c->nl.etype != 361) { nl_launch_tet(c, Kout, nullptr, false); return 0; }
   DevScratch tmp;
   double *dup_k = nullptr;
   if (!Kout && c->nl.n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * c->nl.n_dup)) return FX_ERROR_RUNTIME;
@@ -277,8 +275,7 @@ static void nl_launch_update_group(fx_context *c, double *qf_out) {
                        (const int32_t *)n.emat);
 }
 static void nl_launch_update(fx_context *c, double *qf_out) {
-  if (c->nl.etype == 341) { nl_launch_tet<341>(c, nullptr, qf_out, true); return; }
-  if (c->nl.etype == 342) { nl_launch_tet<342>(c, nullptr, qf_out, true); return; }
+  if (c->nl.etype != 361) { nl_launch_tet(c, nullptr, qf_out, true); return; }
   nl_launch_update_group<0>(c, qf_out);
   nl_launch_update_group<1>(c, qf_out);
   nl_launch_update_group<2>(c, qf_out);
@@ -296,11 +293,8 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
     if (bc_node[k] < 1 || bc_node[k] > A.NP) { g_fx_error = "fx_nl_stiffness: BC node id out of range"; return FX_ERROR_RUNTIME; }
   HIP_TRY(hipMemsetAsync(n.err, 0, 4, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  if (!(n.colors.first_write && n.colors.pos && !n.scatter_atomic)) {  // first-write scatter (tetrahedra): every block is stored before it is added to
-    HIP_TRY(hipMemsetAsync(A.D, 0, (size_t)9 * A.NP * 8, c->stream));  // hecmw_mat_clear
-    HIP_TRY(hipMemsetAsync(A.AL, 0, (size_t)9 * A.NPL * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(A.AU, 0, (size_t)9 * A.NPU * 8, c->stream));
-  }
+  // first-write scatter (tetrahedra): every block is stored before it is added to, no clearing
+  if (!(n.colors.first_write && n.colors.pos && !n.scatter_atomic) && mat_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(n.bc_flag, 0, (size_t)3 * A.NP, c->stream));
@@ -328,7 +322,7 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
   HIP_TRY(hipMemcpyAsync(&herr, n.err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (ms_assemble) HIP_TRY(hipEventElapsedTime(ms_assemble, c->ev0, c->ev1));
-  if (herr == 2) { g_fx_error = "###ERROR### : cannot find connectivity (element not covered by the profile)"; return FX_ERROR_RUNTIME; }
+  if (int rc = assembly_error(herr)) return rc;
   c->have_values = true;
   c->bell_valid = false;   // the preconditioner is refreshed by the flags / recycle policy of the next solve, not here
   return 0;

@@ -1,7 +1,7 @@
 // Nonlinear (total / updated Lagrange, Mises elastoplastic) path of the tetrahedra TYPE=341 and TYPE=342: STF_C3
 // (static_LIB_3d.f90:47-205) with `u` present and UPDATE_C3 (:516-837) without temperatures, as fstr_StiffMatrix.f90:134-144 and
-// fstr_Update.f90:182-189 call them inside fstr_Newton.  The element data (shape functions, quadrature, Jacobian) is that of
-// fx_assemble_tet.h, the material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening) that of fx_nonlinear.h.
+// fstr_Update.f90:182-189 call them inside fstr_Newton.  The element data (shape functions, quadrature) is that of
+// fx_c3_element.h, the Jacobian fx_assemble_tet.h's, the material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening) that of fx_nonlinear.h.
 //
 // k_nl_stiffness_tet keeps the lane mapping of k_assemble_tet: the element matrix is symmetric in all three branches (D is held
 // as 21 entries, the initial-stress term is symmetric), so one lane owns one upper block a <= b (10 lanes at 341, 55 at 342) and
@@ -26,7 +26,7 @@ __device__ __forceinline__ double fx_real_default(double x) { return (double)(fl
 template <int ETYPE>
 __device__ __forceinline__ void tet_node_gderiv(int n, double xi, double et, double ze, const double *inv, double *g) {
   double d[3];
-  tet_shape_deriv<ETYPE>(n, xi, et, ze, d);
+  c3_shape_deriv<ETYPE>(n, xi, et, ze, d);
 #pragma unroll
   for (int j = 0; j < 3; j++) g[j] = d[0] * inv[j] + d[1] * inv[3 + j] + d[2] * inv[6 + j];
 }
@@ -35,7 +35,7 @@ __device__ __forceinline__ void tet_node_gderiv(int n, double xi, double et, dou
 // colour, scattered with plain read-modify-writes (a block whose first-write flag is set in pos_map is stored, not added to).
 // Kout: element matrices out ((3 NN)^2 each, row-major, by element id), no scatter.
 template <int ETYPE, int NLGEOM>
-__global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, const double *__restrict__ coord,
+__global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_elem, const double *__restrict__ coord,
                                                             const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                             const double *__restrict__ dunode, NlMat m, int latch,
                                                             const double *__restrict__ stress, const double *__restrict__ fstat,
@@ -47,8 +47,8 @@ __global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, con
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
-  constexpr int NN = TetEl<ETYPE>::NN, NQ = TetEl<ETYPE>::NQ, EPB = FXT_EPB(ETYPE), LPE = FXT_LPE(ETYPE);
-  constexpr int NB = FXT_NB(ETYPE);
+  using El = C3El<ETYPE>;
+  constexpr int NN = El::NN, NQ = El::NQ, EPB = El::EPB, LPE = El::LPE, NB = El::NB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1, NS = NLGEOM != 0 ? 6 : 1;
   __shared__ double Jsh[EPB][NQ][10];     // per quadrature point: inverse Jacobian (row-major), weight * determinant
   __shared__ double Gsh[EPB][NQ][NN][3];  // global derivatives of every node at every point
@@ -56,9 +56,9 @@ __global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, con
   __shared__ double Ssh[EPB][NQ][NS];     // stress (initial-stress term)
   __shared__ double Fsh[EPB][NQ][NF];     // gdispderiv = u . gderiv (TOTALLAG)
   const int wave = threadIdx.x >> 6, wl = threadIdx.x & 63;
-  const int el = wave * TetEl<ETYPE>::EPW + wl / LPE, k = wl % LPE;
+  const int el = wave * El::EPW + wl / LPE, k = wl % LPE;
   const int32_t epos = e0 + blockIdx.x * EPB + el;
-  const bool active = wl < TetEl<ETYPE>::EPW * LPE && epos < n_elem;
+  const bool active = wl < El::EPW * LPE && epos < n_elem;
   const int32_t elem = !active ? 0 : (elem_list ? elem_list[epos] : epos);
   if (active && k < NQ) {
     if (mats) m = mats[emat[elem] - 1];
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, con
     }
     double det, inv[3][3], xi, et, ze, w;
     tet_jacobian<ETYPE>(ec, k, det, inv);
-    tet_gauss<ETYPE>(k, xi, et, ze, w);
+    c3_gauss<ETYPE>(k, xi, et, ze, w);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -114,41 +114,17 @@ __global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, con
   if (active && k < NQ * NN) {
     const int q = k / NN, n = k % NN;
     double xi, et, ze, w;
-    tet_gauss<ETYPE>(q, xi, et, ze, w);
+    c3_gauss<ETYPE>(q, xi, et, ze, w);
     tet_node_gderiv<ETYPE>(n, xi, et, ze, Jsh[el][q], Gsh[el][q][n]);
   }
   __syncthreads();
   if (!active || k >= NB) return;
   int a, b;
   upper_block<NN>(k, a, b);
-  const int32_t inod = conn[(size_t)NN * elem + a], jnod = conn[(size_t)NN * elem + b];
-  auto block_ptr = [&](int ra, int rb, int32_t rnod, int32_t cnod, bool &first) -> double * {  // hecmw_mat_add_node
-    const int32_t raw = pos_map ? pos_map[(size_t)(NN * NN) * elem + NN * ra + rb] : 0;
-    first = pos_map && raw >= 0 && (raw & FXA_FIRST_BIT);
-    if (rnod == cnod) return D + (size_t)9 * (rnod - 1);
-    if (cnod < rnod) {
-      const int32_t p = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemL, indexL[rnod - 1], indexL[rnod], cnod);
-      return p < 0 ? nullptr : AL + (size_t)9 * p;
-    }
-    const int32_t p = pos_map ? (raw < 0 ? raw : (raw & ~FXA_FIRST_BIT)) : item_search(itemU, indexU[rnod - 1], indexU[rnod], cnod);
-    return p < 0 ? nullptr : AU + (size_t)9 * p;
-  };
-  double *dst = nullptr, *dstT = nullptr;
-  double old[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oldT[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (!Kout) {  // destinations and old values first: the reads' latency runs under the arithmetic
-    bool first = false, firstT = false;
-    dst = block_ptr(a, b, inod, jnod, first);
-    if (a != b) dstT = block_ptr(b, a, jnod, inod, firstT);
-    if (!dst || (a != b && !dstT)) { if (err) atomicExch(err, 2); return; }
-    if (!atomic && !first) {
-#pragma unroll
-      for (int e = 0; e < 9; e++) old[e] = dst[e];
-    }
-    if (!atomic && a != b && !firstT) {
-#pragma unroll
-      for (int e = 0; e < 9; e++) oldT[e] = dstT[e];
-    }
-  }
+  BlockScatter<NN> sc;  // destinations and old values first: the reads' latency runs under the arithmetic
+  if (!sc.prepare({indexL, itemL, indexU, itemU, D, AL, AU, pos_map}, Kout != nullptr, conn + (size_t)NN * elem, elem, a, b, a != b,
+                  !atomic, err))
+    return;
   double K[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int q = 0; q < NQ; q++) {
@@ -190,46 +166,16 @@ __global__ __launch_bounds__(FXT_BS) void k_nl_stiffness_tet(int32_t n_elem, con
       K[0] += geo; K[4] += geo; K[8] += geo;
     }
   }
-  if (Kout) {
-    constexpr int W = 3 * NN;
-    const size_t ko = (size_t)elem * W * W;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        Kout[ko + (size_t)(3 * a + i) * W + 3 * b + j] = K[3 * i + j];
-        if (a != b) Kout[ko + (size_t)(3 * b + j) * W + 3 * a + i] = K[3 * i + j];
-      }
-    return;
-  }
-  if (!atomic) {
-#pragma unroll
-    for (int e = 0; e < 9; e++) dst[e] = old[e] + K[e];
-    if (a != b) {
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) dstT[3 * j + i] = oldT[3 * j + i] + K[3 * i + j];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 9; e++) unsafeAtomicAdd(dst + e, K[e]);
-    if (a != b) {
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) unsafeAtomicAdd(dstT + 3 * j + i, K[3 * i + j]);
-    }
-  }
+  sc.commit(K, Kout, (size_t)elem * (9 * NN * NN));
 }
 
 // Node coordinates of the configuration x + (u + alpha du) the derivatives are taken in, and the Jacobian of point g there.
 // alpha = 0.5: `(0.5 ddu + u) + ecoord` (:563), alpha = 1: `(ddu + u) + ecoord` (:564); UPDATELAG only, else the initial coordinates.
 template <int ETYPE, int NLGEOM>
-__device__ __forceinline__ void nl_tet_config_jacobian(const int32_t (&nod)[TetEl<ETYPE>::NN], const double *__restrict__ coord,
+__device__ __forceinline__ void nl_tet_config_jacobian(const int32_t (&nod)[C3El<ETYPE>::NN], const double *__restrict__ coord,
                                                        const double *__restrict__ unode, const double *__restrict__ dunode, double alpha,
                                                        int g, double &det, double (&inv)[3][3]) {
-  constexpr int NN = TetEl<ETYPE>::NN;
+  constexpr int NN = C3El<ETYPE>::NN;
   double ec[NN][3];
 #pragma unroll
   for (int j = 0; j < NN; j++)
@@ -245,7 +191,7 @@ __device__ __forceinline__ void nl_tet_config_jacobian(const int32_t (&nod)[TetE
 // UPDATE_C3 + scatter of the internal force.  Arguments as k_nl_update; state arrays [elem][NQ][.]; qf_out (tests): per-element
 // qf[3 NN] instead of the scatter.
 template <int ETYPE, int NLGEOM>
-__global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, const double *__restrict__ coord,
+__global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_elem, const double *__restrict__ coord,
                                                              const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                              const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
                                                              double *__restrict__ strain, const double *__restrict__ stress_bak,
@@ -254,8 +200,8 @@ __global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, co
                                                              double *__restrict__ qforce, double *__restrict__ qf_out,
                                                              const int32_t *__restrict__ elem_list, int32_t e0,
                                                              const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
-  constexpr int NN = TetEl<ETYPE>::NN, NQ = TetEl<ETYPE>::NQ;
-  const int64_t t = (int64_t)blockIdx.x * FXU_TET_BS + threadIdx.x;
+  constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
+  const int64_t t = (int64_t)blockIdx.x * C3El<ETYPE>::BS + threadIdx.x;
   const int g = (int)(t % NQ);
   int64_t epos = e0 + t / NQ;
   const bool active = epos < n_elem;
@@ -266,7 +212,7 @@ __global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, co
 #pragma unroll
   for (int j = 0; j < NN; j++) nod[j] = conn[(size_t)NN * elem + j];
   double det, inv[3][3], xi, et, ze, w;
-  tet_gauss<ETYPE>(g, xi, et, ze, w);
+  c3_gauss<ETYPE>(g, xi, et, ze, w);
   nl_tet_config_jacobian<ETYPE, NLGEOM>(nod, coord, unode, dunode, 0.5, g, det, inv);
   // gdispderiv = matmul(totaldisp, gderiv) (:646); totaldisp = u + ddu, or ddu for UPDATELAG (:561-566)
   double gu[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
@@ -282,7 +228,8 @@ __global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, co
       for (int j = 0; j < 3; j++) gu[i][j] += td * gd[j];
     }
   }
-  double de[6] = {gu[0][0], gu[1][1], gu[2][2], gu[0][1] + gu[1][0], gu[1][2] + gu[2][1], gu[2][0] + gu[0][2]};
+  double de[6];
+  small_strain(gu, de);
   if (NLGEOM == 1) {  // Green-Lagrange strain (:671-679)
 #pragma unroll
     for (int c = 0; c < 3; c++) de[c] += 0.5 * (gu[0][c] * gu[0][c] + gu[1][c] * gu[1][c] + gu[2][c] * gu[2][c]);
@@ -291,11 +238,9 @@ __global__ __launch_bounds__(FXU_TET_BS) void k_nl_update_tet(int32_t n_elem, co
     de[5] += gu[0][0] * gu[0][2] + gu[1][0] * gu[1][2] + gu[2][0] * gu[2][2];
   }
   // MatlMatrix with isEp: the elastic matrix (the call itself sets the latch for an elastoplastic material)
-  const double D11 = m.E * (1.0 - m.nu) / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D12 = m.E * m.nu / (1.0 - 2.0 * m.nu) / (1.0 + m.nu);
-  const double D44 = m.E / (1.0 + m.nu) * 0.5;
-  const double ds[6] = {D11 * de[0] + D12 * de[1] + D12 * de[2], D12 * de[0] + D11 * de[1] + D12 * de[2],
-                        D12 * de[0] + D12 * de[1] + D11 * de[2], D44 * de[3], D44 * de[4], D44 * de[5]};
+  double D11, D12, D44, ds[6];
+  elastic_constants(m.E, m.nu, D11, D12, D44);
+  iso_stress(D11, D12, D44, de, ds);
   const size_t gp = (size_t)NQ * elem + g;
   double sg[6], eg[6];
   if (NLGEOM == 2) {  // :702-732

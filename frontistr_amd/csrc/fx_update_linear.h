@@ -87,15 +87,10 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
   double eps[6];
   {
     const double dvol = (ELEMOPT == 2) ? vol0 - (gu[0][0] + gu[1][1] + gu[2][2]) / 3.0 : 0.0;
-    eps[0] = gu[0][0] + dvol; eps[1] = gu[1][1] + dvol; eps[2] = gu[2][2] + dvol;
-    eps[3] = gu[0][1] + gu[1][0]; eps[4] = gu[1][2] + gu[2][1]; eps[5] = gu[2][0] + gu[0][2];
+    small_strain(gu, eps);
+    eps[0] += dvol; eps[1] += dvol; eps[2] += dvol;
   }
-  auto stress_of = [&](const double *e, double *s) {
-    s[0] = D11 * e[0] + D12 * e[1] + D12 * e[2];
-    s[1] = D12 * e[0] + D11 * e[1] + D12 * e[2];
-    s[2] = D12 * e[0] + D12 * e[1] + D11 * e[2];
-    s[3] = D44 * e[3]; s[4] = D44 * e[4]; s[5] = D44 * e[5];
-  };
+  auto stress_of = [&](const double *e, double *s) { iso_stress(D11, D12, D44, e, s); };
   if (ELEMOPT == 1) {
     // incompatible modes: derivatives of mode m at this point (3dIC.f90:296-298), B of the three modes, alpha
 #pragma unroll
@@ -275,29 +270,21 @@ extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
 static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
                                  double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
                                  const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err) {
-  const int nq = c3_points(etype);
-  const dim3 grid((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), blk(FXU_BS);
-#define FXU_LAUNCH(EO)                                                                                                       \
-  hipLaunchKernelGGL((k_update_c3d8_linear<EO>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, \
-                     d_disp, d_strain, d_stress, d_q, d_err)
-  const dim3 tgrid((unsigned)(((int64_t)nq * ne + FXU_TET_BS - 1) / FXU_TET_BS)), tblk(FXU_TET_BS);
-  if (etype == 341)
-    hipLaunchKernelGGL((k_update_tet<341>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
-                       d_strain, d_stress, d_q);
-  else if (etype == 342)
-    hipLaunchKernelGGL((k_update_tet<342>), tgrid, tblk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
-                       d_strain, d_stress, d_q);
-#define FXU_C3_LAUNCH(ET)                                                                                                      \
-  hipLaunchKernelGGL((k_update_c3<ET>), dim3((unsigned)((ne + FXC_UEPB(ET) - 1) / FXC_UEPB(ET))), dim3(FXC_BS), 0, c->stream, ne, \
-                     d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q)
-  else if (etype == 351) FXU_C3_LAUNCH(351);
-  else if (etype == 352) FXU_C3_LAUNCH(352);
-  else if (etype == 362) FXU_C3_LAUNCH(362);
-#undef FXU_C3_LAUNCH
-  else if (elemopt == 1) FXU_LAUNCH(1);
-  else if (elemopt == 2) FXU_LAUNCH(2);
-  else FXU_LAUNCH(3);
-#undef FXU_LAUNCH
+  if (with_c3_type(etype, [&](auto t) {
+        constexpr int ET = decltype(t)::value;
+        using El = C3El<ET>;
+        const dim3 grid((unsigned)((ne + El::UEPB - 1) / El::UEPB)), blk(El::BS);
+        if constexpr (El::TET)
+          hipLaunchKernelGGL((k_update_tet<ET>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain,
+                             d_stress, d_q);
+        else
+          hipLaunchKernelGGL((k_update_c3<ET>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain,
+                             d_stress, d_q);
+      }))
+    return;
+  const auto kern = elemopt == 1 ? k_update_c3d8_linear<1> : (elemopt == 2 ? k_update_c3d8_linear<2> : k_update_c3d8_linear<3>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), dim3(FXU_BS), 0, c->stream, ne, d_coord, d_conn, D11, D12, D44,
+                     d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err);
 }
 
 // fstr_UpdateNewton of a linear static analysis (see the header of this file).  mesh: coordinates + connectivity (host); n_mat
@@ -313,22 +300,16 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   HIP_TRY(hipSetDevice(c->device));
   const bool hex = etype == 361;
   const char *who = hex ? "fx_update_c3d8_linear" : "fx_update_c3_linear";
-  static thread_local char msg[200];
-  auto fail = [&](const char *what, int code) {
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    g_fx_error = msg;
-    return code;
-  };
-  if (!mesh || !E || !nu || !disp || n_mat < 1) return fail("null argument", FX_ERROR_RUNTIME);
-  if (hex && (elemopt < 1 || elemopt > 3)) return fail("elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", FX_ERROR_UNSUPPORTED);
-  if (!hex && !c3_linear_type(etype)) return fail(FX_C3_UNSUPPORTED "fx_update_c3d8_linear)", FX_ERROR_UNSUPPORTED);
+  if (!mesh || !E || !nu || !disp || n_mat < 1) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  if (hex && (elemopt < 1 || elemopt > 3)) return fx_fail(who, FX_ERROR_UNSUPPORTED, "elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)");
+  if (!hex && !c3_linear_type(etype)) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_update_c3d8_linear)");
   const int32_t ne = mesh->n_elem, nn = mesh->n_node;
   const int enn = c3_nodes(etype), nq = c3_points(etype);
   const size_t per_elem = (size_t)6 * nq;  // doubles of strain (and of stress) per element
-  if (ne < 1 || nn < 1) return fail("empty mesh", FX_ERROR_RUNTIME);
+  if (ne < 1 || nn < 1) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
   if (hex) {
     for (int64_t k = 0; k < (int64_t)enn * ne; k++)
-      if (mesh->conn[k] < 1 || mesh->conn[k] > nn) return fail("node id out of range", FX_ERROR_RUNTIME);
+      if (mesh->conn[k] < 1 || mesh->conn[k] > nn) return fx_fail(who, FX_ERROR_RUNTIME, "node id out of range");
   } else if (refuse_degenerate_tets(who, mesh, enn)) {
     return FX_ERROR_RUNTIME;
   }
@@ -349,9 +330,9 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   std::vector<double> tab((size_t)3 * n_mat);
   for (int32_t k = 0; k < n_mat; k++) elastic_constants(E[k], nu[k], tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]);
   if (n_mat > 1 || elem_mat) {
-    if (!elem_mat) return fail("several materials need elem_mat", FX_ERROR_RUNTIME);
+    if (!elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "several materials need elem_mat");
     for (int32_t e = 0; e < ne; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) return fail("material id out of range", FX_ERROR_RUNTIME);
+      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) return fx_fail(who, FX_ERROR_RUNTIME, "material id out of range");
     if (tmp.alloc(&d_emat, (size_t)ne) || tmp.alloc(&d_mtab, tab.size())) return FX_ERROR_RUNTIME;
     HIP_TRY(hipMemcpyAsync(d_emat, elem_mat, (size_t)ne * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_mtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -363,7 +344,7 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   upd_stage_wait();
   if (g_upd_stage.make_err || g_upd_stage.cap < per_elem * ne) {
     g_upd_stage.make_err = 0;
-    if (upd_stage_make(c->device, per_elem * ne)) { (void)hipGetLastError(); return fail("cannot pin the host staging", FX_ERROR_RUNTIME); }
+    if (upd_stage_make(c->device, per_elem * ne)) { (void)hipGetLastError(); return fx_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
   }
   pt.lap("pinned staging");
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
