@@ -18,6 +18,7 @@
 #include "fx_kernels.h"
 #include "fx_nonlinear.h"
 #include "fx_nonlinear_tet.h"
+#include "fx_nonlinear_c3.h"
 
 namespace fxo {
 struct Graph {

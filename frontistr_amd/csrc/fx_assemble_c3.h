@@ -19,17 +19,23 @@
 // The three staging steps both kernels share, for the element whose LPE lanes call this together (k = lane of the element,
 // `active`: the element exists).  In: nothing staged.  Out: X = node coordinates, Jq[q] = inverse Jacobian (row-major) and
 // weight * determinant, G[q][n] = global derivatives (getGlobalDeriv, element.f90:693-744).  Every lane of the workgroup
-// must call it (it holds the barriers).
-template <int ETYPE, int LPE>
+// must call it (it holds the barriers).  DISP (the nonlinear kernels' updated Lagrange branch, fx_nonlinear_c3.h): the
+// configuration is X = (alpha dunode + unode) + coord instead of the initial coordinates.
+template <int ETYPE, int LPE, bool DISP = false>
 __device__ __forceinline__ void c3_stage(bool active, int k, int32_t elem, const double *__restrict__ coord,
                                          const int32_t *__restrict__ conn, double (*X)[3], double (*Jq)[10],
-                                         double (*G)[C3El<ETYPE>::NN][3]) {
+                                         double (*G)[C3El<ETYPE>::NN][3], const double *__restrict__ unode = nullptr,
+                                         const double *__restrict__ dunode = nullptr, double alpha = 0.0) {
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
   if (active) {
     for (int t = k; t < NN; t += LPE) {
       const int32_t nd = conn[(size_t)NN * elem + t];
 #pragma unroll
-      for (int d = 0; d < 3; d++) X[t][d] = coord[(size_t)3 * (nd - 1) + d];
+      for (int d = 0; d < 3; d++) {
+        const size_t o = (size_t)3 * (nd - 1) + d;
+        if (DISP) X[t][d] = (alpha * dunode[o] + unode[o]) + coord[o];
+        else X[t][d] = coord[o];
+      }
     }
     for (int t = k; t < NQ * NN; t += LPE) {  // natural derivatives of node n at point q
       const int q = t / NN, n = t % NN;

@@ -29,7 +29,7 @@ static int nl_check_material(const fx_material_view *mat) {
 }
 
 static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                          const int32_t *elem_mat, int32_t etype = 361) {
+                          const int32_t *elem_mat, int32_t etype, const char *who) {
   HIP_TRY(hipSetDevice(c->device));
   const int nn = c3_nodes(etype), nq = c3_points(etype);
   if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
@@ -43,7 +43,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   if (n_mat > 1)
     for (int32_t e = 0; e < mesh->n_elem; e++)
       if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
-  if (etype != 361 && refuse_degenerate_tets("fx_nl_init_c3", mesh, nn)) return FX_ERROR_RUNTIME;
+  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;
   nl_free(c);
   NlDev &n = c->nl;
   n.n_elem = mesh->n_elem;
@@ -125,8 +125,8 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     n.colors.etype = etype;
     n.colors.offsets = {0, mesh->n_elem};       // marks the lists as built (ensure_scatter_map)
     if (etype != 361 && coloured) {
-      // tetrahedra: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
-      // of all the launches are the `colours` the flags are made for (no tetrahedron is in colors.dup: they were refused above)
+      // STF_C3 types: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
+      // of all the launches are the `colours` the flags are made for (none of their elements is in colors.dup: they were refused above)
       n.colors.offsets.assign(1, 0);
       for (int g = 0; g < 3; g++)
         for (size_t k = 1; k < n.grp_off[g].size(); k++)
@@ -148,14 +148,14 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
 }
 
 extern "C" int fx_nl_init(fx_context *c, const fx_mesh_view *mesh, const fx_material_view *mat) {
-  return nl_init_common(c, mesh, 1, mat, nullptr);
+  return nl_init_common(c, mesh, 1, mat, nullptr, 361, "fx_nl_init");
 }
 
 // Several sections (hecMESH%section_ID -> fstrSOLID%materials, fstr_setup.f90:325-400): elem_mat[e] in 1..n_mat.  The materials may
 // carry different NLGEOM flags (an elastic TOTALLAG part next to an elastoplastic UPDATELAG part).
 extern "C" int fx_nl_init_sections(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
                                    const int32_t *elem_mat) {
-  return nl_init_common(c, mesh, n_mat, mats, elem_mat);
+  return nl_init_common(c, mesh, n_mat, mats, elem_mat, 361, "fx_nl_init_sections");
 }
 
 // The same context for a mesh of tetrahedra, etype 341 or 342 (STF_C3 / UPDATE_C3, fx_nonlinear_tet.h): n_mat materials,
@@ -166,52 +166,74 @@ extern "C" int fx_nl_init_c3(fx_context *c, const fx_mesh_view *mesh, int32_t et
     g_fx_error = "fx_nl_init_c3: the nonlinear loop covers TYPE=341 and 342 (361 through fx_nl_init / fx_nl_init_sections)";
     return FX_ERROR_UNSUPPORTED;
   }
-  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype);
+  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype, "fx_nl_init_c3");
+}
+
+// The same for any of the five types STF_C3 / UPDATE_C3 serve: 341, 342 (fx_nonlinear_tet.h), 351, 352, 362 (fx_nonlinear_c3.h).
+// fx_mesh_view carries no nodes-per-element, so the caller states it: nn_elem is the row length of mesh->conn, and a type whose
+// node count it is not is refused before anything reads the connectivity.
+extern "C" int fx_nl_init_type(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t nn_elem, int32_t n_mat,
+                               const fx_material_view *mats, const int32_t *elem_mat) {
+  if (!c3_linear_type(etype))
+    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED,
+                   "TYPE=%d: the STF_C3 nonlinear loop covers 341, 342, 351, 352 and 362 (361 through fx_nl_init / fx_nl_init_sections)", (int)etype);
+  if (nn_elem != c3_nodes(etype))
+    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED, "TYPE=%d has %d nodes per element, the connectivity has %d", (int)etype,
+                   c3_nodes(etype), (int)nn_elem);
+  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype, "fx_nl_init_type");
 }
 
 #define NL_READY(name)                                                                              \
   HIP_TRY(hipSetDevice(c->device));                                                                 \
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }
 
+// One NLGEOM group of a context of an STF_C3 type: k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362
+template <int ETYPE, int G, bool UPDATE>
+static constexpr auto nl_c3_kernel() {
+  if constexpr (UPDATE) {
+    if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
+    else return k_nl_update_c3<ETYPE, G>;
+  } else {
+    if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G>;
+    else return k_nl_stiffness_c3<ETYPE, G>;
+  }
+}
 template <int ETYPE, int G>
-static void nl_launch_stiffness_tet_group(fx_context *c, double *Kout) {
+static void nl_launch_stiffness_c3_group(fx_context *c, double *Kout) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
   using El = C3El<ETYPE>;
   // element matrices out, or atomics: the group's colours in one launch
   for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((k_nl_stiffness_tet<ETYPE, G>), grid, dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat,
-                       n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
-                       (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0,
-                       (const NlMat *)n.mats, (const int32_t *)n.emat);
+    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, false>()), grid, dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat,
+                       n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0,
+                       (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat);
   });
 }
 template <int ETYPE, int G>
-static void nl_launch_update_tet_group(fx_context *c, double *qf_out) {
+static void nl_launch_update_c3_group(fx_context *c, double *qf_out) {
   NlDev &n = c->nl;
   const std::vector<int32_t> &off = n.grp_off[G];
   if (off.empty() || off.back() <= off.front()) return;
   const int32_t e0 = off.front(), e1 = off.back();
   const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;  // as nl_launch_update_group
   using El = C3El<ETYPE>;
-  hipLaunchKernelGGL((k_nl_update_tet<ETYPE, G>), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1,
-                     n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat,
-                     n.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode,
+                     n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce, qf_out, list,
+                     e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
 }
-// the three NLGEOM groups of a context of tetrahedra: tangent (update == false) or stress update
-static void nl_launch_tet(fx_context *c, double *Kout, double *qf_out, bool update) {
+// the three NLGEOM groups of a context of an STF_C3 type: tangent (update == false) or stress update
+static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool update) {
   with_c3_type(c->nl.etype, [&](auto t) {
     constexpr int ET = decltype(t)::value;
-    if constexpr (C3El<ET>::TET) {
-      if (update) {
-        nl_launch_update_tet_group<ET, 0>(c, qf_out);
-        nl_launch_update_tet_group<ET, 1>(c, qf_out);
-        nl_launch_update_tet_group<ET, 2>(c, qf_out);
-      } else {
-        nl_launch_stiffness_tet_group<ET, 0>(c, Kout);
-        nl_launch_stiffness_tet_group<ET, 1>(c, Kout);
-        nl_launch_stiffness_tet_group<ET, 2>(c, Kout);
-      }
+    if (update) {
+      nl_launch_update_c3_group<ET, 0>(c, qf_out);
+      nl_launch_update_c3_group<ET, 1>(c, qf_out);
+      nl_launch_update_c3_group<ET, 2>(c, qf_out);
+    } else {
+      nl_launch_stiffness_c3_group<ET, 0>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 1>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 2>(c, Kout);
     }
   });
 }
@@ -244,7 +266,7 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
                          A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
 static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
-  if (c->nl.etype != 361) { nl_launch_tet(c, Kout, nullptr, false); return 0; }
+  if (c->nl.etype != 361) { nl_launch_c3(c, Kout, nullptr, false); return 0; }
   DevScratch tmp;
   double *dup_k = nullptr;
   if (!Kout && c->nl.n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * c->nl.n_dup)) return FX_ERROR_RUNTIME;
@@ -275,7 +297,7 @@ static void nl_launch_update_group(fx_context *c, double *qf_out) {
                        (const int32_t *)n.emat);
 }
 static void nl_launch_update(fx_context *c, double *qf_out) {
-  if (c->nl.etype != 361) { nl_launch_tet(c, nullptr, qf_out, true); return; }
+  if (c->nl.etype != 361) { nl_launch_c3(c, nullptr, qf_out, true); return; }
   nl_launch_update_group<0>(c, qf_out);
   nl_launch_update_group<1>(c, qf_out);
   nl_launch_update_group<2>(c, qf_out);
@@ -293,7 +315,7 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
     if (bc_node[k] < 1 || bc_node[k] > A.NP) { g_fx_error = "fx_nl_stiffness: BC node id out of range"; return FX_ERROR_RUNTIME; }
   HIP_TRY(hipMemsetAsync(n.err, 0, 4, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  // first-write scatter (tetrahedra): every block is stored before it is added to, no clearing
+  // first-write scatter (the STF_C3 types): every block is stored before it is added to, no clearing
   if (!(n.colors.first_write && n.colors.pos && !n.scatter_atomic) && mat_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());

@@ -13,7 +13,8 @@
     fstr_Newton          fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
 
-for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342 (fstr_solid(..., etype=341 | 342): STF_C3 / UPDATE_C3),
+for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
+(fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3),
 with one isotropic (Mises elastoplastic or elastic) material per section.  Everything is resident on the GPU; there is NO CPU
 fallback.
 """
@@ -64,12 +65,13 @@ class tMaterial:
 class fstr_solid:
     """The resident nonlinear state of one context (created by fx_nl_init)."""
 
-    NODES = {361: 8, 341: 4, 342: 10}     # nodes per element
-    POINTS = {361: 8, 341: 1, 342: 4}     # quadrature points per element (NumOfQuadPoints)
+    NODES = {361: 8, 341: 4, 342: 10, 351: 6, 352: 15, 362: 20}     # nodes per element
+    POINTS = {361: 8, 341: 1, 342: 4, 351: 2, 352: 9, 362: 27}      # quadrature points per element (NumOfQuadPoints)
 
     def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361):
         """material: one tMaterial, or a list of them with elem_mat (1-based material id per element = the section's
-        material, hecMESH%section_ID -> fstrSOLID%materials).  etype: 361 (B-bar), or 341 / 342 (fx_nl_init_c3)."""
+        material, hecMESH%section_ID -> fstrSOLID%materials).  etype: 361 (B-bar), 341 / 342 (fx_nl_init_c3), or 351 / 352 / 362
+        (fx_nl_init_type with the row length of hecMESH_conn)."""
         self.ctx = ctx
         self.etype = int(etype)
         self.nn, self.nq = self.NODES.get(self.etype, 0), self.POINTS.get(self.etype, 0)
@@ -85,7 +87,11 @@ class fstr_solid:
             self.elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
             if len(views) > 1 and (self.elem_mat is None or self.elem_mat.shape != (self.n_elem,)):
                 raise ValueError("elem_mat: one material id per element")
-            _chk(lib().fx_nl_init_c3(ctx.h, C.byref(mv), self.etype, len(views), arr, _ptr(self.elem_mat)))
+            if self.etype in (351, 352, 362):
+                nn_elem = self.conn.shape[1] if self.conn.ndim == 2 else 0
+                _chk(lib().fx_nl_init_type(ctx.h, C.byref(mv), self.etype, nn_elem, len(views), arr, _ptr(self.elem_mat)))
+            else:
+                _chk(lib().fx_nl_init_c3(ctx.h, C.byref(mv), self.etype, len(views), arr, _ptr(self.elem_mat)))
             return
         if isinstance(material, (list, tuple)):
             views = [m.view() for m in material]

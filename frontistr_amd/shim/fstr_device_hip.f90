@@ -8,12 +8,13 @@
 !>   fstr_UpdateNewton -> fx_nl_update_at (dunode up, QFORCE down)
 !>   fstr_UpdateState  -> fx_nl_commit + the quadrature-point history down (once per sub-step: results, restart)
 !> Taken only for what the device kernels cover -- static analysis with NLGEOM, every element TYPE=361 with the B-bar formulation,
-!> or (on one process) every element a tetrahedron TYPE=341 or every element TYPE=342, isotropic ELASTIC or Mises-elastoplastic
+!> or (on one process) every element of one type of STF_C3 (TYPE=341, 342, 351, 352 or 362), isotropic ELASTIC or Mises-elastoplastic
 !> materials with isotropic hardening, no temperature / contact / MPC / spring / local coordinate system; fixed or automatic
 !> increments (a cutback rolls the device's history back too, fsd_cutback); anything else runs the reference's own routines (kept,
 !> renamed, in the same binary).
 !> HECMW_GPU_ASSEMBLY=0 keeps the reference's element loops on the host for every deck; the tetrahedra are taken only with
-!> HECMW_GPU_NL_TET=1 (opt-in until their end-to-end time against the host loops is on record).
+!> HECMW_GPU_NL_TET=1, the five STF_C3 types with HECMW_GPU_NL_C3=1 (opt-in until their end-to-end time against the host loops
+!> is on record).
 module fstr_device_hip
   use iso_c_binding
   use hecmw
@@ -37,7 +38,7 @@ module fstr_device_hip
   logical, save :: lin_mixed = .false.             ! several element types: fx_assemble_groups / fx_update_groups_linear
   type(fx_elem_group), allocatable, save :: lin_groups(:)    ! hecMESH%elem_type_index / elem_type_item as the library takes them
   integer(c_int32_t), save :: n_elem = 0
-  integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or 341 / 342 (STF_C3 / UPDATE_C3, fx_nl_init_c3)
+  integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or a type of STF_C3 / UPDATE_C3 (fx_nl_init_type)
   integer, save :: nl_nq = 8                       ! its quadrature points per element
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
   real(c_double), allocatable, target, save :: b6(:,:,:), b1(:,:), b6b(:,:,:)
@@ -72,6 +73,7 @@ contains
     character(len=8) :: env
     character(len=3) :: tname
     integer :: elen, estat, i, icel, cid, nn
+    logical :: opted
     if (decided) then
       fsd_eligible = eligible
       return
@@ -88,11 +90,16 @@ contains
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return                       ! the solve must run on the device too: same predicate as hecmw_solve (method, preconditioner, no MPC / contact)
     if (hecMESH%n_elem_type /= 1) return
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
-    if (lin_etype /= 361 .and. lin_etype /= 341 .and. lin_etype /= 342) return   ! the nonlinear kernels: 361 B-bar and the tetrahedra
+    if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return             ! the nonlinear kernels: 361 B-bar and the types of STF_C3
     if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
-    if (lin_etype /= 361) then      ! tetrahedra opt in: no end-to-end timing against the host loops has been recorded yet (DESIGN.md section 4)
-      call get_environment_variable('HECMW_GPU_NL_TET', env, elen, estat)
-      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+    if (lin_etype /= 361) then      ! these opt in: no end-to-end timing against the host loops has been recorded yet (DESIGN.md section 4)
+      call get_environment_variable('HECMW_GPU_NL_C3', env, elen, estat)          ! the five types of STF_C3
+      opted = (estat == 0 .and. elen > 0 .and. env(1:1) == '1')
+      if (.not. opted .and. (lin_etype == 341 .or. lin_etype == 342)) then
+        call get_environment_variable('HECMW_GPU_NL_TET', env, elen, estat)       ! the tetrahedra alone
+        opted = (estat == 0 .and. elen > 0 .and. env(1:1) == '1')
+      endif
+      if (.not. opted) return
     endif
     nn = 8
     if (lin_etype /= 361) nn = c3_type_nodes(lin_etype)
@@ -401,8 +408,8 @@ contains
       ierr = fx_nl_init_sections(ctx, mesh, int(nmat, c_int32_t), mats, emat)
       if (ierr /= 0) call fsd_fail('fx_nl_init_sections')
     else
-      ierr = fx_nl_init_c3(ctx, mesh, nl_etype, int(nmat, c_int32_t), mats, emat)
-      if (ierr /= 0) call fsd_fail('fx_nl_init_c3')
+      ierr = fx_nl_init_type(ctx, mesh, nl_etype, int(c3_type_nodes(nl_etype), c_int32_t), int(nmat, c_int32_t), mats, emat)
+      if (ierr /= 0) call fsd_fail('fx_nl_init_type')
     endif
     deallocate(mats, emat)
     if (allocated(b6)) deallocate(b6, b6b, b1, bi)

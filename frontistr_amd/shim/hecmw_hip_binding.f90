@@ -21,7 +21,7 @@ module hecmw_hip_binding
   public :: fx_solve, fx_matvec, fx_last_error, fx_solve_attempts, fx_solve_attempt_history
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
   public :: fx_mesh_view, fx_material_view, fx_nl_state_view, fx_elem_group
-  public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
+  public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_init_type, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
             fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
             fx_assemble_c3, fx_update_c3_linear, fx_assemble_groups, fx_update_groups_linear, fx_update_groups_linear_prepare
   public :: fxb_values_owner, fxb_values_addr
@@ -213,6 +213,14 @@ module hecmw_hip_binding
       type(fx_material_view) :: mats(*)
       integer(c_int32_t) :: elem_mat(*)
     end function fx_nl_init_c3
+    integer(c_int) function fx_nl_init_type(ctx, mesh, etype, nn_elem, n_mat, mats, elem_mat) bind(C, name='fx_nl_init_type')
+      import :: c_int, c_ptr, c_int32_t, fx_mesh_view, fx_material_view
+      type(c_ptr), value :: ctx
+      type(fx_mesh_view) :: mesh
+      integer(c_int32_t), value :: etype, nn_elem, n_mat
+      type(fx_material_view) :: mats(*)
+      integer(c_int32_t) :: elem_mat(*)
+    end function fx_nl_init_type
     integer(c_int) function fx_nl_stiffness_at(ctx, unode, dunode, ms) bind(C, name='fx_nl_stiffness_at')
       import :: c_int, c_ptr, c_double, c_float
       type(c_ptr), value :: ctx

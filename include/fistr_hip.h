@@ -355,6 +355,13 @@ int fx_nl_init_sections(fx_context *ctx, const fx_mesh_view *mesh, int32_t n_mat
  * outputs (3 nn)^2 and 3 nn doubles per element. */
 int fx_nl_init_c3(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const fx_material_view *mats,
                   const int32_t *elem_mat);
+/* The same context for a mesh of any one of the five types STF_C3 / UPDATE_C3 serve: etype 341, 342, 351 (6 nodes, 2 quadrature
+ * points), 352 (15 nodes, 9 points) or 362 (20 nodes, 27 points).  fx_mesh_view carries no nodes-per-element, so the caller states
+ * the row length of mesh->conn in nn_elem: another etype, or an nn_elem that is not the type's node count, is refused with
+ * FX_ERROR_UNSUPPORTED before the connectivity is read; an element that names a node twice: FX_ERROR_RUNTIME.  Otherwise as
+ * fx_nl_init_c3 (which keeps its two types). */
+int fx_nl_init_type(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t nn_elem, int32_t n_mat,
+                    const fx_material_view *mats, const int32_t *elem_mat);
 /* fstr_Newton :63-68 + fstr_ass_load: dunode = 0, GL (3*NP, may be NULL), B = GL - QFORCE. */
 int fx_nl_begin_substep(fx_context *ctx, const double *GL);
 /* fstr_StiffMatrix (fstr_StiffMatrix.f90:18-212) + fstr_AddBC (fstr_AddBC.f90:17-190) with the

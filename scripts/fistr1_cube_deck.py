@@ -5,12 +5,12 @@ Lagrange (NLSTATIC default), SUBSTEPS sub-steps, CG + SSOR (or what --solver say
 hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to time fistr1_hip end to end: device assembly
 (default) against HECMW_GPU_ASSEMBLY=0 (scripts/r3/fistr1_big.sh).  usage: fistr1_cube_deck.py DIR N [SUBSTEPS] [METHOD] [PRECOND] [STRAIN]
 --etype 341|342 (with or without --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
-mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with --linear): the cube split into wedges
+mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with or without --linear): the cube split into wedges
 (WedgeMesh, 2 per hexahedron; 352 with mid-edge nodes) or as 20-node hexahedra (Hex20Mesh).  --two-sections (with --linear): the second half of the elements
 forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33).  --mixed 1|2 (with --linear): the cube as a mesh of
 three element types (frontistr_amd.mesh.MixedMesh: 361 + 351 + 341, or 362 + 352 + 342 with shared mid-edge nodes), one !ELEMENT
 card per type in mesh order; with --two-sections the second half of the elements in that order is EGRP=E2.
-NLSTATIC decks of tetrahedra (--etype 341|342 without --linear) take two more options:
+NLSTATIC decks of the STF_C3 types (--etype 341|342|351|352|362 without --linear) take two more options:
   --nl-material multilinear|bilinear|elastic_tl|elastic_ul   MAT1: Mises MULTILINEAR (default) or BILINEAR, both updated Lagrange;
                                                              ELASTIC total Lagrange; `!ELASTIC, CAUCHY`, updated Lagrange.
   --two-sections                                             the second half of the elements is MAT2, ELASTIC 70000 / 0.33, TOTAL
@@ -26,11 +26,11 @@ if linear:
 form361 = None                       # --form361 FI|BBAR|IC: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's (IC)
 if "--form361" in sys.argv:
     k = sys.argv.index("--form361"); form361 = sys.argv[k + 1]; del sys.argv[k:k + 2]
-etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra (351 / 352 / 362: linear decks only)
+etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra
 if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
-    if etype not in (341, 342, 351, 352, 362) or (not linear and etype not in (341, 342)):
-        sys.exit("--etype takes 341 or 342, or with --linear 351, 352 or 362")
+    if etype not in (341, 342, 351, 352, 362):
+        sys.exit("--etype takes 341, 342, 351, 352 or 362")
 mixed = 0                            # --mixed 1|2: hexahedra + wedges + tetrahedra of that order (linear decks only)
 if "--mixed" in sys.argv:
     k = sys.argv.index("--mixed"); mixed = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
@@ -39,8 +39,8 @@ if "--mixed" in sys.argv:
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear and etype not in (341, 342):
-        sys.exit("--two-sections needs --linear, or --etype 341|342")
+    if not linear and etype == 361:
+        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362")
 nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
 if "--nl-material" in sys.argv:
     k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
