@@ -18,6 +18,7 @@
 #pragma once
 #include "fx_internal.h"
 #include "fx_c3_element.h"
+#include "fx_thermal.h"
 
 #define FXA_BLOCK 256
 #define FXA_LPE(EO) 8                               // lanes per element: lane a owns the 3-row block of node a

@@ -138,12 +138,13 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_assemble_c3(int32_t n_elem,
 // then computes strain = B u (total displacement) and stress = D strain at its point, writes both out and leaves the stress
 // in LDS; lane t < 3 NN sums component t % 3 of node t / 3's internal force wg B_a^T stress over the points in the
 // reference's order and adds it to QFORCE with an fp64 atomic (elements share nodes).  strain / stress: [n_elem][NQ][6].
-template <int ETYPE>
+// TH: the thermal switch of k_update_c3d8_linear (1: stress = D (strain - EPSTH); 2: TLOAD_C3, qforce += sum_g wg B^T D EPSTH).
+template <int ETYPE, int TH = 0>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_update_c3(int32_t n_elem, const double *__restrict__ coord,
                                                      const int32_t *__restrict__ conn, double D11, double D12, double D44,
                                                      const int32_t *__restrict__ elem_mat, const double *__restrict__ mat_tab,
                                                      const double *__restrict__ disp, double *__restrict__ strain,
-                                                     double *__restrict__ stress, double *__restrict__ qforce) {
+                                                     double *__restrict__ stress, double *__restrict__ qforce, ThermalDev th) {
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ, LPE = C3El<ETYPE>::ULPE, EPB = C3El<ETYPE>::UEPB;
   __shared__ double Xsh[EPB][NN][3];
   __shared__ double Jsh[EPB][NQ][10];
@@ -161,22 +162,45 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_update_c3(int32_t n_elem, c
     }
     for (int g = k; g < NQ; g += LPE) {
       double gu[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};  // gdispderiv = matmul(totaldisp, gderiv)
+      double tc = 0.0, t0 = 0.0, xi, et, ze, w;                              // TH: TEMPC, TEMP0 at this point
+      if (TH) c3_gauss<ETYPE>(g, xi, et, ze, w);
 #pragma unroll 2
       for (int a = 0; a < NN; a++) {
         const int32_t nd = conn[(size_t)NN * elem + a];
+        if (TH != 2) {
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
-          const double u = disp[(size_t)3 * (nd - 1) + i];
+          for (int i = 0; i < 3; i++) {
+            const double u = disp[(size_t)3 * (nd - 1) + i];
 #pragma unroll
-          for (int j = 0; j < 3; j++) gu[i][j] += u * Gsh[el][g][a][j];
+            for (int j = 0; j < 3; j++) gu[i][j] += u * Gsh[el][g][a][j];
+          }
+        }
+        if (TH) {
+          const double h = c3_shape_func<ETYPE>(a, xi, et, ze);
+          tc += h * th.temp[nd - 1];
+          t0 += h * th.temp0[nd - 1];
         }
       }
       double eps[6], sg[6];
       small_strain(gu, eps);
-      iso_stress(D11, D12, D44, eps, sg);
-      double *se = strain + ((size_t)NQ * elem + g) * 6, *ss = stress + ((size_t)NQ * elem + g) * 6;
+      if (TH) {
+        const double e = thermal_eps(th.alpha[elem_mat ? elem_mat[elem] - 1 : 0], tc, t0, th.ref_temp);
+        double em[6] = {e, e, e, 0.0, 0.0, 0.0};
+        if (TH == 1) {
 #pragma unroll
-      for (int c = 0; c < 6; c++) { se[c] = eps[c]; ss[c] = sg[c]; Ssh[el][g][c] = sg[c]; }
+          for (int c = 0; c < 6; c++) em[c] = eps[c] - em[c];
+        }
+        iso_stress_fixed(D11, D12, D44, em, sg);
+      } else {
+        iso_stress_fixed(D11, D12, D44, eps, sg);
+      }
+      if (TH != 2) {
+        double *se = strain + ((size_t)NQ * elem + g) * 6, *ss = stress + ((size_t)NQ * elem + g) * 6;
+#pragma unroll
+        for (int c = 0; c < 6; c++) { se[c] = eps[c]; ss[c] = sg[c]; }
+      }
+#pragma unroll
+      for (int c = 0; c < 6; c++) Ssh[el][g][c] = sg[c];
     }
   }
   __syncthreads();

@@ -198,17 +198,18 @@ extern "C" int fx_update_groups_linear_prepare(fx_context *c, int32_t n_group, c
   return 0;
 }
 
-extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                                       int32_t n_mat, const double *E, const double *nu, const double *disp, const double **strain,
-                                       const double **stress, double *qforce, float *ms_kernel) {
-  const char *who = "fx_update_groups_linear";
-  if (!c || !disp) { g_fx_error = "fx_update_groups_linear: null argument"; return FX_ERROR_RUNTIME; }
+// fx_update_groups_linear (thermal == nullptr) and fx_update_groups_linear_thermal
+static int update_groups_linear_impl(const char *who, fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
+                                     const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu, const double *disp,
+                                     const double **strain, const double **stress, double *qforce, float *ms_kernel,
+                                     const fx_thermal_view *thermal) {
+  if (!c || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
   if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E, nu)) return rc;
   if (n_group == 1) {
     const fx_elem_group &G = groups[0];
     const fx_mesh_view mesh = {n_node, G.n_elem, coord, G.conn};
     return update_linear_common(c, &mesh, G.etype, n_mat, E, nu, G.elem_mat, G.etype == 361 ? G.elemopt : 3, disp,
-                                strain, stress, qforce, ms_kernel);
+                                strain, stress, qforce, ms_kernel, thermal);
   }
   HIP_TRY(hipSetDevice(c->device));
   const size_t total = groups_stage_doubles(n_group, groups);
@@ -225,6 +226,8 @@ extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const doub
   HIP_TRY(hipMemsetAsync(d_q, 0, (size_t)3 * n_node * 8, c->stream));
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
   if (int rc = upload_groups(c, tmp, n_group, groups, n_mat, E, nu, up)) return rc;
+  ThermalDev td;
+  if (thermal && upload_thermal(c, tmp, n_node, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
   upd_stage_wait();
   if (g_upd_stage.make_err || g_upd_stage.cap < total) {
     g_upd_stage.make_err = 0;
@@ -238,7 +241,7 @@ extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const doub
     if (stress) stress[g] = g_upd_stage.stress + at;
     if (G.n_elem < 1) continue;
     launch_update_linear(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, up.emat[g],
-                         up.emat[g] ? up.mtab : nullptr, d_disp, d_strain + at, d_stress + at, d_q, d_err);
+                         up.emat[g] ? up.mtab : nullptr, d_disp, d_strain + at, d_stress + at, d_q, d_err, thermal ? &td : nullptr);
     at += (size_t)6 * c3_points(G.etype) * G.n_elem;
   }
   HIP_TRY(hipGetLastError());
@@ -253,5 +256,67 @@ extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const doub
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_kernel) *ms_kernel = ms;
   if (herr) { g_fx_error = "PIVOT ERROR in the incompatible-mode block of an element (UpdateST_C3D8IC, calInverse)"; return FX_ERROR_RUNTIME; }
+  return 0;
+}
+
+extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                       int32_t n_mat, const double *E, const double *nu, const double *disp, const double **strain,
+                                       const double **stress, double *qforce, float *ms_kernel) {
+  return update_groups_linear_impl("fx_update_groups_linear", c, n_node, coord, n_group, groups, n_mat, E, nu, disp, strain, stress, qforce,
+                                   ms_kernel, nullptr);
+}
+
+// ---- thermal strain (fx_thermal.h) ------------------------------------------------------------------------------------------
+extern "C" int fx_update_groups_linear_thermal(fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
+                                               const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu,
+                                               const fx_thermal_view *thermal, const double *disp, const double **strain,
+                                               const double **stress, double *qforce, float *ms_kernel) {
+  const char *who = "fx_update_groups_linear_thermal";
+  if (!c) { g_fx_error = "fx_update_groups_linear_thermal: null argument"; return FX_ERROR_RUNTIME; }
+  if (int rc = thermal_view_ok(who, thermal)) return rc;
+  return update_groups_linear_impl(who, c, n_node, coord, n_group, groups, n_mat, E, nu, disp, strain, stress, qforce, ms_kernel, thermal);
+}
+
+// fstr_ass_load.f90:287-428 for the solid types: every element's TLOAD vector added to load_inout (3 * n_node, host).  The
+// kernels are the update kernels with TH = 2, one group after another on one stream; elements that share a node add with fp64
+// atomics, so the sum is reproducible to rounding, not bit for bit.
+extern "C" int fx_thermal_load_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                      int32_t n_mat, const double *E, const double *nu, const fx_thermal_view *thermal,
+                                      double *load_inout, float *ms_kernel) {
+  const char *who = "fx_thermal_load_groups";
+  if (!c || !load_inout) { g_fx_error = "fx_thermal_load_groups: null argument"; return FX_ERROR_RUNTIME; }
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E, nu)) return rc;
+  if (int rc = thermal_view_ok(who, thermal)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  DevScratch tmp;
+  GroupUploads up;
+  ThermalDev td;
+  double *d_coord = nullptr, *d_q = nullptr;
+  int32_t *d_err = nullptr;
+  if (tmp.alloc(&d_coord, (size_t)3 * n_node) || tmp.alloc(&d_q, (size_t)3 * n_node) || tmp.alloc(&d_err, 1)) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpyAsync(d_coord, coord, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_q, load_inout, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
+  if (int rc = upload_groups(c, tmp, n_group, groups, n_mat, E, nu, up)) return rc;
+  if (upload_thermal(c, tmp, n_node, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  for (int32_t g = 0; g < n_group; g++) {
+    const fx_elem_group &G = groups[g];
+    if (G.n_elem < 1) continue;
+    launch_update_linear_th<2>(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, up.emat[g],
+                               up.emat[g] ? up.mtab : nullptr, nullptr, nullptr, nullptr, d_q, d_err, td);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  int32_t herr = 0;
+  std::vector<double> out((size_t)3 * n_node);  // the caller's vector changes only when everything went well
+  HIP_TRY(hipMemcpyAsync(out.data(), d_q, (size_t)3 * n_node * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  if (ms_kernel) *ms_kernel = ms;
+  if (herr) { g_fx_error = "PIVOT ERROR in the incompatible-mode block of an element (TLOAD_C3D8IC, calInverse)"; return FX_ERROR_RUNTIME; }
+  memcpy(load_inout, out.data(), out.size() * 8);
   return 0;
 }

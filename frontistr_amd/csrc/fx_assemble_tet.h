@@ -111,12 +111,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_assemble_tet(int32_t n_elem
 // the global derivatives at its point, strain = B u (total displacement), stress = D strain, and its share wg B_a^T stress of
 // every node's internal force; the shares are summed over the element's lanes (xor shuffles) and lane g adds the nodes a with
 // a % NQ == g to QFORCE with fp64 atomics (elements share nodes).  strain / stress: [n_elem][NQ][6].
-template <int ETYPE>
+// TH: the thermal switch of k_update_c3d8_linear (1: stress = D (strain - EPSTH); 2: TLOAD_C3, qforce += sum_g wg B^T D EPSTH).
+template <int ETYPE, int TH = 0>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_update_tet(int32_t n_elem, const double *__restrict__ coord,
                                                           const int32_t *__restrict__ conn, double D11, double D12, double D44,
                                                           const int32_t *__restrict__ elem_mat, const double *__restrict__ mat_tab,
                                                           const double *__restrict__ disp, double *__restrict__ strain,
-                                                          double *__restrict__ stress, double *__restrict__ qforce) {
+                                                          double *__restrict__ stress, double *__restrict__ qforce,
+                                                          ThermalDev th) {
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
   const int64_t t = (int64_t)blockIdx.x * C3El<ETYPE>::BS + threadIdx.x;
   const int g = (int)(t % NQ);
@@ -147,15 +149,38 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_update_tet(int32_t n_elem, 
     for (int j = 0; j < 3; j++) gd[a][j] = d[0] * inv[0][j] + d[1] * inv[1][j] + d[2] * inv[2][j];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-      const double u = disp[(size_t)3 * (nod[a] - 1) + i];
+      const double u = TH == 2 ? 0.0 : disp[(size_t)3 * (nod[a] - 1) + i];
 #pragma unroll
       for (int j = 0; j < 3; j++) gu[i][j] += u * gd[a][j];
     }
   }
   double eps[6], sg[6];
   small_strain(gu, eps);
-  iso_stress(D11, D12, D44, eps, sg);
-  if (active) {
+  // the stored stress in the written-out form (fx_c3_element.h) where that is what the compiler had made of iso_stress (342); 341,
+  // where it had chosen another, keeps iso_stress and with it the bits it always gave
+  auto stress_of = [&](const double *e, double *s) {
+    if (ETYPE == 341) iso_stress(D11, D12, D44, e, s);
+    else iso_stress_fixed(D11, D12, D44, e, s);
+  };
+  if (TH) {
+    double tc = 0.0, t0 = 0.0;
+#pragma unroll
+    for (int a = 0; a < NN; a++) {
+      const double h = c3_shape_func<ETYPE>(a, xi, et, ze);
+      tc += h * th.temp[nod[a] - 1];
+      t0 += h * th.temp0[nod[a] - 1];
+    }
+    const double e = thermal_eps(th.alpha[elem_mat ? elem_mat[elem] - 1 : 0], tc, t0, th.ref_temp);
+    double em[6] = {e, e, e, 0.0, 0.0, 0.0};
+    if (TH == 1) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) em[k] = eps[k] - em[k];
+    }
+    stress_of(em, sg);
+  } else {
+    stress_of(eps, sg);
+  }
+  if (active && TH != 2) {
     double *se = strain + ((size_t)NQ * elem + g) * 6, *ss = stress + ((size_t)NQ * elem + g) * 6;
 #pragma unroll
     for (int k = 0; k < 6; k++) { se[k] = eps[k]; ss[k] = sg[k]; }

@@ -184,6 +184,16 @@ __device__ __forceinline__ void iso_stress(double D11, double D12, double D44, c
   s[2] = D12 * e[0] + D12 * e[1] + D11 * e[2];
   s[3] = D44 * e[3]; s[4] = D44 * e[4]; s[5] = D44 * e[5];
 }
+// The same with its fused multiply-adds written out instead of left to the compiler: the product of the yy strain is rounded, the
+// xx and zz products are fused onto it in that order.  Two instantiations of a kernel that both use this form give the same bits
+// for the same strain, which contraction left to the compiler does not promise (it chooses by the use counts of the products in
+// the surrounding code).  This is the form the compiler had chosen in the linear update kernels of every type but 341, whose machine code is unchanged by it.
+__device__ __forceinline__ void iso_stress_fixed(double D11, double D12, double D44, const double *e, double *s) {
+  s[0] = __builtin_fma(D12, e[2], __builtin_fma(D11, e[0], D12 * e[1]));
+  s[1] = __builtin_fma(D12, e[2], __builtin_fma(D12, e[0], D11 * e[1]));
+  s[2] = __builtin_fma(D11, e[2], __builtin_fma(D12, e[0], D12 * e[1]));
+  s[3] = D44 * e[3]; s[4] = D44 * e[4]; s[5] = D44 * e[5];
+}
 // calElasticMatrix, 3-D case (ElasticLinear.f90:43-55)
 __host__ __device__ __forceinline__ void elastic_constants(double E, double nu, double &D11, double &D12, double &D44) {
   D11 = E * (1.0 - nu) / (1.0 - 2.0 * nu) / (1.0 + nu);

@@ -24,13 +24,17 @@ __device__ __forceinline__ double sum8(double v) {  // over the 8 lanes of an el
   return v;
 }
 
-template <int ELEMOPT>
+// TH (fx_thermal.h): 0 no temperature (the kernel as it always was); 1 the routines' thermal branches -- stored strain = total
+// strain, stress = D (strain - EPSTH), and IC's qf less its TLOAD_C3D8IC vector (3dIC.f90:337-342); 2 the thermal load vector
+// alone (TLOAD_C3D8IC / TLOAD_C3D8Bbar / TLOAD_C3): no displacement read, nothing stored, qforce += sum_g wg B^T D EPSTH.
+template <int ELEMOPT, int TH = 0>
 __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, const double *__restrict__ coord,
                                                               const int32_t *__restrict__ conn, double D11, double D12, double D44,
                                                               const int32_t *__restrict__ elem_mat,
                                                               const double *__restrict__ mat_tab, const double *__restrict__ disp,
                                                               double *__restrict__ strain, double *__restrict__ stress,
-                                                              double *__restrict__ qforce, int32_t *__restrict__ err) {
+                                                              double *__restrict__ qforce, int32_t *__restrict__ err,
+                                                              ThermalDev th) {
   const int el = threadIdx.x >> 3, g = threadIdx.x & 7;
   const int64_t e_raw = (int64_t)blockIdx.x * FXU_EPB + el;
   const bool active = e_raw < n_elem;
@@ -40,6 +44,7 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
     const int32_t mid = elem_mat[elem] - 1;
     D11 = mat_tab[3 * mid]; D12 = mat_tab[3 * mid + 1]; D44 = mat_tab[3 * mid + 2];
   }
+  const double alp = TH ? th.alpha[elem_mat ? elem_mat[elem] - 1 : 0] : 0.0;
   int32_t nod[8];
   double ec[8][3], ue[8][3];
 #pragma unroll
@@ -48,10 +53,22 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
 #pragma unroll
     for (int d = 0; d < 3; d++) {
       ec[j][d] = coord[(size_t)3 * (nod[j] - 1) + d];
-      ue[j][d] = disp[(size_t)3 * (nod[j] - 1) + d];
+      ue[j][d] = TH == 2 ? 0.0 : disp[(size_t)3 * (nod[j] - 1) + d];
     }
   }
   const double xi = (g & 1) ? GP : -GP, et = (g & 2) ? GP : -GP, ze = (g & 4) ? GP : -GP;
+  double eth[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // EPSTH at this point; TLOAD_C3D8Bbar takes the centroid's temperatures (C3D8.f90:607-608, :688)
+  if (TH) {
+    const bool centre = TH == 2 && ELEMOPT == 2;
+    double tc = 0.0, t0 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const double h = centre ? 0.125 : hex8_shape_func(j, xi, et, ze);
+      tc += h * th.temp[nod[j] - 1];
+      t0 += h * th.temp0[nod[j] - 1];
+    }
+    eth[0] = eth[1] = eth[2] = thermal_eps(alp, tc, t0, th.ref_temp);
+  }
   double det, inv[3][3], gd[11][3];
   double c0[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // IC: det0 * inverse Jacobian at the centre (3dIC.f90:268-270)
   double bbar[8][3];                                     // B-bar: global derivatives at the centroid (C3D8.f90:271-272)
@@ -91,6 +108,7 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
     eps[0] += dvol; eps[1] += dvol; eps[2] += dvol;
   }
   auto stress_of = [&](const double *e, double *s) { iso_stress(D11, D12, D44, e, s); };
+  double ic[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // TH, IC: Ba Kaa^-1 fa, the strain of the condensed thermal mode load
   if (ELEMOPT == 1) {
     // incompatible modes: derivatives of mode m at this point (3dIC.f90:296-298), B of the three modes, alpha
 #pragma unroll
@@ -162,21 +180,26 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
       }
     }
     if (bad && active && g == 0 && err) atomicExch(err, 1);
+    auto kaa_solve = [&](double *v9) {  // v9 <- Kaa^-1 v9: L y = v9, then L^T x = y
+#pragma unroll
+      for (int q = 0; q < 9; q++) {
+        double v = v9[q];
+#pragma unroll
+        for (int j = 0; j < q; j++) v -= Kaa[q * (q + 1) / 2 + j] * v9[j];
+        v9[q] = v * Kaa[q * (q + 1) / 2 + q];
+      }
+#pragma unroll
+      for (int q = 8; q >= 0; q--) {
+        double v = v9[q];
+#pragma unroll
+        for (int j = q + 1; j < 9; j++) v -= Kaa[j * (j + 1) / 2 + q] * v9[j];
+        v9[q] = v * Kaa[q * (q + 1) / 2 + q];
+      }
+    };
     double al[9];
 #pragma unroll
-    for (int q = 0; q < 9; q++) {  // L y = -f
-      double v = -f[q];
-#pragma unroll
-      for (int j = 0; j < q; j++) v -= Kaa[q * (q + 1) / 2 + j] * al[j];
-      al[q] = v * Kaa[q * (q + 1) / 2 + q];
-    }
-#pragma unroll
-    for (int q = 8; q >= 0; q--) {  // L^T alpha = y
-      double v = al[q];
-#pragma unroll
-      for (int j = q + 1; j < 9; j++) v -= Kaa[j * (j + 1) / 2 + q] * al[j];
-      al[q] = v * Kaa[q * (q + 1) / 2 + q];
-    }
+    for (int q = 0; q < 9; q++) al[q] = -f[q];
+    kaa_solve(al);
     // strain += Ba alpha (3dIC.f90:433)
 #pragma unroll
     for (int m = 0; m < 3; m++) {
@@ -186,13 +209,53 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
       eps[4] += q[2] * a3[1] + q[1] * a3[2];
       eps[5] += q[2] * a3[0] + q[0] * a3[2];
     }
+    if (TH) {
+      // TLOAD_C3D8IC condensed: vect = fd - Kda Kaa^-1 fa with fa = sum_g wg Ba^T D EPSTH (3dIC.f90:611-623).  Kda y is
+      // sum_g wg B^T D (Ba y), so the vector is the internal force of the strain EPSTH - Ba y: eth becomes that strain.
+      double st[6], fa[9];
+      stress_of(eth, st);
+#pragma unroll
+      for (int m = 0; m < 3; m++) {
+        double o[3];
+        BaT(m, st, o);
+#pragma unroll
+        for (int d = 0; d < 3; d++) fa[3 * m + d] = sum8(o[d] * wg);
+      }
+      kaa_solve(fa);
+#pragma unroll
+      for (int m = 0; m < 3; m++) {
+        const double *q = gd[8 + m], *a3 = fa + 3 * m;
+        ic[0] += q[0] * a3[0]; ic[1] += q[1] * a3[1]; ic[2] += q[2] * a3[2];
+        ic[3] += q[1] * a3[0] + q[0] * a3[1];
+        ic[4] += q[2] * a3[1] + q[1] * a3[2];
+        ic[5] += q[2] * a3[0] + q[0] * a3[2];
+      }
+    }
   }
   double sg[6];
-  stress_of(eps, sg);
-  if (active) {
+  // the stored stress in the written-out form (iso_stress_fixed), so that a temperature that causes no thermal strain gives
+  // the bits of the kernel without one
+  auto stored_stress_of = [&](const double *e, double *s) {
+    iso_stress_fixed(D11, D12, D44, e, s);
+  };
+  if (TH) {  // stress = D (strain - EPSTH); the stored strain is the total one (dstrain + EPSTH, static_LIB_3d.f90:653-658)
+    double em[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) em[k] = TH == 2 ? eth[k] : eps[k] - eth[k];
+    stored_stress_of(em, sg);
+  } else {
+    stored_stress_of(eps, sg);
+  }
+  if (active && TH != 2) {
     double *se = strain + (size_t)48 * elem + 6 * g, *ss = stress + (size_t)48 * elem + 6 * g;
 #pragma unroll
     for (int k = 0; k < 6; k++) { se[k] = eps[k]; ss[k] = sg[k]; }
+  }
+  if (TH && ELEMOPT == 1) {  // the force comes from the stress of (strain - EPSTH + Ba y), the load vector from that of (EPSTH - Ba y)
+    double em[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) em[k] = TH == 2 ? eth[k] - ic[k] : eps[k] - eth[k] + ic[k];
+    stress_of(em, sg);
   }
   // internal force: qf_a = sum_g wg B_a^T sigma_g  (B-bar: with the dilatational correction of C3D8.f90:458-481)
   double mine[3] = {0.0, 0.0, 0.0};
@@ -267,24 +330,54 @@ extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
 }
 
 // One group's update kernel: 361 (elemopt 1..3) k_update_c3d8_linear, 341 / 342 k_update_tet, 351 / 352 / 362 k_update_c3.
-static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
-                                 double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
-                                 const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err) {
+// TH = 0: no temperature; 1: the thermal branch of the update; 2: the thermal load vector added to d_q (fx_thermal.h).
+template <int TH>
+static void launch_update_linear_th(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
+                                    double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
+                                    const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err,
+                                    const ThermalDev &th) {
   if (with_c3_type(etype, [&](auto t) {
         constexpr int ET = decltype(t)::value;
         using El = C3El<ET>;
         const dim3 grid((unsigned)((ne + El::UEPB - 1) / El::UEPB)), blk(El::BS);
         if constexpr (El::TET)
-          hipLaunchKernelGGL((k_update_tet<ET>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain,
-                             d_stress, d_q);
+          hipLaunchKernelGGL((k_update_tet<ET, TH>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                             d_strain, d_stress, d_q, th);
         else
-          hipLaunchKernelGGL((k_update_c3<ET>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain,
-                             d_stress, d_q);
+          hipLaunchKernelGGL((k_update_c3<ET, TH>), grid, blk, 0, c->stream, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp,
+                             d_strain, d_stress, d_q, th);
       }))
     return;
-  const auto kern = elemopt == 1 ? k_update_c3d8_linear<1> : (elemopt == 2 ? k_update_c3d8_linear<2> : k_update_c3d8_linear<3>);
+  const auto kern = elemopt == 1 ? k_update_c3d8_linear<1, TH> : (elemopt == 2 ? k_update_c3d8_linear<2, TH> : k_update_c3d8_linear<3, TH>);
   hipLaunchKernelGGL(kern, dim3((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), dim3(FXU_BS), 0, c->stream, ne, d_coord, d_conn, D11, D12, D44,
-                     d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err);
+                     d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err, th);
+}
+static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
+                                 double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
+                                 const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err,
+                                 const ThermalDev *th = nullptr) {
+  if (th)
+    launch_update_linear_th<1>(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err, *th);
+  else
+    launch_update_linear_th<0>(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err,
+                               ThermalDev{nullptr, nullptr, nullptr, 0.0});
+}
+
+// The caller's temperatures and expansion coefficients on the device.  `who` has checked the view (thermal_view_ok).
+static int upload_thermal(fx_context *c, DevScratch &tmp, int32_t n_node, int32_t n_mat, const fx_thermal_view *tv, ThermalDev &td) {
+  double *d_t = nullptr, *d_t0 = nullptr, *d_al = nullptr;
+  if (tmp.alloc(&d_t, (size_t)n_node) || tmp.alloc(&d_t0, (size_t)n_node) || tmp.alloc(&d_al, (size_t)n_mat)) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpyAsync(d_t, tv->temp, (size_t)n_node * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_t0, tv->temp0, (size_t)n_node * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_al, tv->alpha, (size_t)n_mat * 8, hipMemcpyHostToDevice, c->stream));
+  td = ThermalDev{d_t, d_t0, d_al, tv->ref_temp};
+  return 0;
+}
+static int thermal_view_ok(const char *who, const fx_thermal_view *tv) {
+  if (!tv) return fx_fail(who, FX_ERROR_RUNTIME, "thermal view missing");
+  if (!tv->temp || !tv->temp0) return fx_fail(who, FX_ERROR_RUNTIME, "temperature array missing");
+  if (!tv->alpha) return fx_fail(who, FX_ERROR_RUNTIME, "expansion coefficients missing");
+  return 0;
 }
 
 // fstr_UpdateNewton of a linear static analysis (see the header of this file).  mesh: coordinates + connectivity (host); n_mat
@@ -296,10 +389,10 @@ static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int3
 // Results: [n_elem][nq][6] in the pinned staging.
 static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                                 const double *nu, const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
-                                const double **stress, double *qforce, float *ms_kernel) {
+                                const double **stress, double *qforce, float *ms_kernel, const fx_thermal_view *thermal = nullptr) {
   HIP_TRY(hipSetDevice(c->device));
   const bool hex = etype == 361;
-  const char *who = hex ? "fx_update_c3d8_linear" : "fx_update_c3_linear";
+  const char *who = thermal ? "fx_update_groups_linear_thermal" : (hex ? "fx_update_c3d8_linear" : "fx_update_c3_linear");
   if (!mesh || !E || !nu || !disp || n_mat < 1) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
   if (hex && (elemopt < 1 || elemopt > 3)) return fx_fail(who, FX_ERROR_UNSUPPORTED, "elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)");
   if (!hex && !c3_linear_type(etype)) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_update_c3d8_linear)");
@@ -339,6 +432,8 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   } else {
     D11 = tab[0]; D12 = tab[1]; D44 = tab[2];
   }
+  ThermalDev td;
+  if (thermal && upload_thermal(c, tmp, nn, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
   if (pt.on) HIP_TRY(hipStreamSynchronize(c->stream));
   pt.lap("device buffers + uploads");
   upd_stage_wait();
@@ -348,7 +443,8 @@ static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t
   }
   pt.lap("pinned staging");
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  launch_update_linear(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err);
+  launch_update_linear(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err,
+                       thermal ? &td : nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;

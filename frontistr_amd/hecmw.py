@@ -71,6 +71,10 @@ class _ElemGroup(C.Structure):      # fx_elem_group
                 ("elem_mat", C.c_void_p)]
 
 
+class _ThermalView(C.Structure):    # fx_thermal_view
+    _fields_ = [("temp", C.c_void_p), ("temp0", C.c_void_p), ("ref_temp", C.c_double), ("alpha", C.c_void_p)]
+
+
 def lib():
     """Load libfistr_hip.so (built by `make -C frontistr_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -543,8 +547,43 @@ class SolverContext:
         del keep
         return ms.value
 
-    def update_groups_linear(self, coord, groups, E, nu, disp):
-        """fstr_UpdateNewton of a linear static analysis on the device for the same groups (fx_update_groups_linear).
+    @staticmethod
+    def _thermal_view(thermal):
+        """fx_thermal_view of ``thermal`` = (temp, temp0, ref_temp, alpha): node temperatures now and in the reference state
+        (n_node each), !REFTEMP, one expansion coefficient per material.  A None entry is passed on as NULL (refused)."""
+        temp, temp0, ref_temp, alpha = thermal
+        arr = [None if a is None else np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64) for a in (temp, temp0, alpha)]
+        return _ThermalView(_ptr(arr[0]), _ptr(arr[1]), float(ref_temp), _ptr(arr[2])), arr
+
+    def thermal_load_groups(self, coord, groups, E, nu, thermal, load=None):
+        """The thermal load vector of fstr_ass_load for the solid element groups (fx_thermal_load_groups), added to ``load``
+        (3 * n_node, zeros when None).  groups, E, nu as assemble_groups; thermal = (temp, temp0, ref_temp, alpha).  Returns
+        (the vector, kernel ms); ``load`` itself is not changed."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
+        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        tab, keep = self._group_table(groups)
+        tv, keep_t = self._thermal_view(thermal)
+        out = np.zeros(3 * coord.shape[0]) if load is None else np.array(load, dtype=np.float64).ravel()
+        ms = C.c_float(0)
+        _chk(lib().fx_thermal_load_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, int(Es.size), _ptr(Es), _ptr(nus),
+                                          C.byref(tv), _ptr(out), C.byref(ms)))
+        del keep, keep_t
+        return out, ms.value
+
+    def thermal_load(self, mesh, E, nu, thermal, elemopt=1, elem_mat=None, load=None):
+        """thermal_load_groups for one of mesh.py's meshes (a single-type mesh is one group; mesh.mesh_groups)."""
+        from .mesh import mesh_groups
+        return self.thermal_load_groups(mesh.coord, mesh_groups(mesh, elemopt, elem_mat), E, nu, thermal, load=load)
+
+    def update_linear(self, mesh, E, nu, disp, elemopt=1, elem_mat=None, thermal=None):
+        """update_groups_linear for one of mesh.py's meshes (a single-type mesh is one group; mesh.mesh_groups)."""
+        from .mesh import mesh_groups
+        return self.update_groups_linear(mesh.coord, mesh_groups(mesh, elemopt, elem_mat), E, nu, disp, thermal=thermal)
+
+    def update_groups_linear(self, coord, groups, E, nu, disp, thermal=None):
+        """fstr_UpdateNewton of a linear static analysis on the device for the same groups (fx_update_groups_linear; with
+        thermal = (temp, temp0, ref_temp, alpha) fx_update_groups_linear_thermal: stress = D (strain - thermal strain)).
         Returns ([strain per group (n_elem, nq, 6)], [stress per group], qforce (3 * n_node) summed over the groups, kernel ms)."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         disp = np.ascontiguousarray(disp, dtype=np.float64)
@@ -555,8 +594,14 @@ class SolverContext:
         ps, pt = (C.POINTER(C.c_double) * max(ng, 1))(), (C.POINTER(C.c_double) * max(ng, 1))()
         qf = np.zeros(3 * coord.shape[0])
         ms = C.c_float(0)
-        _chk(lib().fx_update_groups_linear(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es), _ptr(nus),
-                                           _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
+        if thermal is None:
+            _chk(lib().fx_update_groups_linear(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es), _ptr(nus),
+                                               _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
+        else:
+            tv, keep_t = self._thermal_view(thermal)
+            _chk(lib().fx_update_groups_linear_thermal(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es),
+                                                       _ptr(nus), C.byref(tv), _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
+            del keep_t
         strain, stress = [], []
         for g in range(ng):
             nq = 8 if tab[g].etype == 361 else _C3_POINTS[tab[g].etype]

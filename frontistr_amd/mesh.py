@@ -426,6 +426,16 @@ class MixedMesh(_CubeOfSolids):
         return self.groups_with()
 
 
+def mesh_groups(mesh, elemopt=1, elem_mat=None):
+    """[(etype, conn, elemopt, elem_mat)] of any mesh of this module, the ``groups`` argument of SolverContext.assemble_groups,
+    update_groups_linear and thermal_load_groups: MixedMesh / RenumberedGroups give their own, a single-type mesh gives one
+    group (CubeMesh, PieMesh: TYPE=361; the others their ``etype``).  elem_mat: 1-based material id per element, mesh order."""
+    if hasattr(mesh, "groups_with"):
+        return mesh.groups_with(elemopt, elem_mat)
+    em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+    return [(int(getattr(mesh, "etype", 361)), mesh.conn, elemopt, em)]
+
+
 class RenumberedGroups:
     """A mesh of element groups (MixedMesh) with its node ids permuted at random and the elements of every group shuffled
     within the group (np.random.default_rng(seed)); what RenumberedMesh is to the single-type builders."""

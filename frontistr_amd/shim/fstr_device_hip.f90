@@ -35,7 +35,10 @@ module fstr_device_hip
   integer(c_int32_t), save :: lin_etype = 361      ! 361, or a type of STF_C3: 341 / 342 / 351 / 352 / 362 (fx_assemble_c3 / fx_update_c3_linear)
   real(c_double), allocatable, target, save :: lin_E(:), lin_nu(:)
   integer(c_int32_t), allocatable, target, save :: lin_emat(:)
+  logical, save :: lin_thermal = .false.           ! !TEMPERATURE in a linear static deck (HECMW_GPU_THERMAL=1): fx_update_groups_linear_thermal
+  real(c_double), allocatable, target, save :: lin_alpha(:)      ! M_EXAPNSION per material
   logical, save :: lin_mixed = .false.             ! several element types: fx_assemble_groups / fx_update_groups_linear
+  ! (the stress update of a thermal deck goes through the groups too, lin_update_by_groups: a single type is one group there)
   type(fx_elem_group), allocatable, save :: lin_groups(:)    ! hecMESH%elem_type_index / elem_type_item as the library takes them
   integer(c_int32_t), save :: n_elem = 0
   integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or a type of STF_C3 / UPDATE_C3 (fx_nl_init_type)
@@ -157,6 +160,13 @@ contains
     endif
   end function lin_update_on_device
 
+  !> Does the stress update go through the groups entry points?  A mesh of several types, and any thermal deck: the thermal
+  !> update has no single-type entry point, so a single type is one group there.  (The assembly of a single-type thermal deck
+  !> stays with the single-type entry points: the stiffness knows no temperature.)
+  logical function lin_update_by_groups()
+    lin_update_by_groups = lin_mixed .or. lin_thermal
+  end function lin_update_by_groups
+
   !> Nodes per element of the types STF_C3 / UPDATE_C3 serve on the device beside 361; 0: not one of them.
   pure integer function c3_type_nodes(etype)
     integer(c_int32_t), intent(in) :: etype
@@ -201,6 +211,7 @@ contains
     integer(c_int32_t) :: et
     character(len=3) :: tname
     character(len=64) :: tnames
+    character(len=9) :: suffix
     logical :: has361
     if (lin_decided) then
       fsd_eligible_linear = lin_eligible
@@ -229,7 +240,14 @@ contains
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
     if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
     if (hecMESH%mpc%n_mpc > 0) return
-    if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return      ! thermal strains enter the element routine
+    lin_thermal = fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0
+    if (lin_thermal) then      ! thermal strains enter the element routines: fx_update_groups_linear_thermal has them, one constant
+      ! isotropic expansion coefficient per material.  No end-to-end timing against the host loops has been recorded yet, so
+      ! thermal decks opt in (DESIGN.md section 7); one rank only.
+      call get_environment_variable('HECMW_GPU_THERMAL', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+      if (hecMESH%PETOT > 1) return
+    endif
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
     if (associated(fstrSOLID%contacts)) then
       if (size(fstrSOLID%contacts) > 0) return
@@ -265,6 +283,10 @@ contains
       if (fstrSOLID%materials(i)%mtype /= ELASTIC) return
       if (fstrSOLID%materials(i)%nlgeom_flag /= INFINITE) return
       if (fetch_TableRow(MC_ISOELASTIC, fstrSOLID%materials(i)%dict) > 1) return     ! temperature-dependent constants
+      if (lin_thermal) then
+        if (fetch_TableRow(MC_THEMOEXP, fstrSOLID%materials(i)%dict) > 1) return     ! a table of expansion coefficients
+        if (fetch_TableRow(MC_ORTHOEXP, fstrSOLID%materials(i)%dict) > 0) return     ! orthotropic expansion
+      endif
     enddo
     lin_eligible = .true.
     fsd_eligible_linear = .true.
@@ -274,8 +296,10 @@ contains
       write(tname, '(i3)') hecMESH%elem_type_item(itype)
       tnames = trim(tnames)//'+'//tname
     enddo
+    suffix = ''
+    if (lin_thermal) suffix = ', thermal'
     if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly on the device (linear static, TYPE='//trim(tnames)//'); '// &
-      'HECMW_GPU_ASSEMBLY=0 keeps it on the host'
+      'HECMW_GPU_ASSEMBLY=0 keeps it on the host'//trim(suffix)
   end function fsd_eligible_linear
 
   subroutine fsd_init_linear(hecMESH, hecMAT, fstrSOLID)
@@ -302,10 +326,19 @@ contains
       lin_E(i) = fstrSOLID%materials(i)%variables(M_YOUNGS)
       lin_nu(i) = fstrSOLID%materials(i)%variables(M_POISSON)
     enddo
+    if (lin_thermal) then
+      if (allocated(lin_alpha)) deallocate(lin_alpha)
+      allocate(lin_alpha(nmat))
+      lin_alpha = 0.d0
+      do i = 1, nmat
+        if (fstrSOLID%materials(i)%mtype == -1) cycle
+        lin_alpha(i) = fstrSOLID%materials(i)%variables(M_EXAPNSION)
+      enddo
+    endif
     do icel = 1, hecMESH%n_elem
       lin_emat(icel) = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
     enddo
-    if (lin_mixed) then     ! elem_node_item holds the elements type by type: a group is a pointer into it (and into lin_emat)
+    if (lin_update_by_groups()) then     ! elem_node_item holds the elements type by type: a group is a pointer into it (and into lin_emat)
       if (allocated(lin_groups)) deallocate(lin_groups)
       allocate(lin_groups(hecMESH%n_elem_type))
       do itype = 1, hecMESH%n_elem_type
@@ -568,6 +601,27 @@ contains
     integer :: elen, estat, icel, g, nq, itype, first
     real(kind=kreal) :: t0
     type(c_ptr), allocatable :: gps(:), gpt(:)
+    type, bind(C) :: fx_thermal_view
+      type(c_ptr) :: temp, temp0
+      real(c_double) :: ref_temp
+      type(c_ptr) :: alpha
+    end type fx_thermal_view
+    interface
+      integer(c_int) function fx_update_groups_linear_thermal(ctx, n_node, coord, n_group, groups, n_mat, E, nu, thermal, disp, &
+          strain, stress, qforce, ms) bind(C, name='fx_update_groups_linear_thermal')
+        import :: c_int, c_int32_t, c_ptr, c_double, c_float, fx_elem_group, fx_thermal_view
+        type(c_ptr), value :: ctx
+        integer(c_int32_t), value :: n_node, n_group, n_mat
+        real(c_double), intent(in) :: coord(*), E(*), nu(*), disp(*)
+        type(fx_elem_group), intent(in) :: groups(*)
+        type(fx_thermal_view), intent(in) :: thermal
+        type(c_ptr), intent(out) :: strain(*), stress(*)
+        real(c_double), intent(inout) :: qforce(*)
+        real(c_float), intent(out) :: ms
+      end function fx_update_groups_linear_thermal
+    end interface
+    type(fx_thermal_view) :: tv
+    real(c_double), allocatable, target :: tt0(:)
     fsd_update_newton_linear = .false.
     if (.not. lin_update_on_device()) return
     allocate(tot(3*hecMESH%n_node))
@@ -576,12 +630,25 @@ contains
     mesh%coord = c_loc(hecMESH%node(1)); mesh%conn = c_loc(hecMESH%elem_node_item(1))
     t0 = hecmw_Wtime()
     nq = 8
-    if (lin_mixed) then              ! every group's results come back in its own (6, nq, n_elem) block of the staging
+    if (lin_update_by_groups()) then ! every group's results come back in its own (6, nq, n_elem) block of the staging
       allocate(gps(size(lin_groups)), gpt(size(lin_groups)))
-      ierr = fx_update_groups_linear(fxb_context(hecMESH), int(hecMESH%n_node, c_int32_t), hecMESH%node, &
-                                     int(size(lin_groups), c_int32_t), lin_groups, int(size(lin_E), c_int32_t), lin_E, lin_nu, &
-                                     tot, gps, gpt, fstrSOLID%QFORCE, ms)
-      if (ierr /= 0) call fsd_fail('fx_update_groups_linear')
+      if (lin_thermal) then          ! tt0 of fstr_Update.f90:92-102 for elastic materials: the initial condition, or 0
+        allocate(tt0(hecMESH%n_node))
+        tt0 = 0.d0
+        if (hecMESH%hecmw_flag_initcon == 1) tt0(:) = hecMESH%node_init_val_item(1:hecMESH%n_node)
+        tv%temp = c_loc(fstrSOLID%temperature(1)); tv%temp0 = c_loc(tt0(1))
+        tv%ref_temp = ref_temp; tv%alpha = c_loc(lin_alpha(1))
+        ierr = fx_update_groups_linear_thermal(fxb_context(hecMESH), int(hecMESH%n_node, c_int32_t), hecMESH%node, &
+                                               int(size(lin_groups), c_int32_t), lin_groups, int(size(lin_E), c_int32_t), lin_E, &
+                                               lin_nu, tv, tot, gps, gpt, fstrSOLID%QFORCE, ms)
+        if (ierr /= 0) call fsd_fail('fx_update_groups_linear_thermal')
+        deallocate(tt0)
+      else
+        ierr = fx_update_groups_linear(fxb_context(hecMESH), int(hecMESH%n_node, c_int32_t), hecMESH%node, &
+                                       int(size(lin_groups), c_int32_t), lin_groups, int(size(lin_E), c_int32_t), lin_E, lin_nu, &
+                                       tot, gps, gpt, fstrSOLID%QFORCE, ms)
+        if (ierr /= 0) call fsd_fail('fx_update_groups_linear')
+      endif
       deallocate(tot)
       call fsd_report('  of which the library call (uploads, kernel, strain / stress / QFORCE back)', hecmw_Wtime() - t0)
       call fsd_report('  of which the element kernel alone', real(ms, kreal) * 1.d-3)

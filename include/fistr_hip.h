@@ -319,6 +319,33 @@ int fx_update_groups_linear(fx_context *ctx, int32_t n_node, const double *coord
 /* As fx_update_c3d8_linear_prepare, for the staging that fx_update_groups_linear needs for these groups (conn is not read). */
 int fx_update_groups_linear_prepare(fx_context *ctx, int32_t n_group, const fx_elem_group *groups);
 
+/* ---- thermal strain in the linear static paths (!TEMPERATURE, !REFTEMP, !INITIAL CONDITION TYPE=TEMPERATURE) ----
+ * Every material carries ONE constant isotropic expansion coefficient (fstrSOLID%materials(m)%variables(M_EXAPNSION)); tables
+ * of E, nu or the coefficient over temperature, MC_ORTHOEXP and section orientation are not restated: keep such decks on the host.
+ * The stiffness matrix does not depend on the temperature then -- fstr_StiffMatrix.f90:72-73 passes it to the element routines
+ * for table lookups only -- so fx_assemble_groups serves thermal decks unchanged and there is no thermal variant of it. */
+typedef struct fx_thermal_view {
+  const double *temp;   /* n_node: fstrSOLID%temperature */
+  const double *temp0;  /* n_node: the reference state's, tt0 of fstr_Update.f90:92-102 (initial condition, or 0) */
+  double ref_temp;      /* !REFTEMP */
+  const double *alpha;  /* n_mat */
+} fx_thermal_view;
+/* The thermal load of fstr_ass_load.f90:287-428 for the solid types: TLOAD_C3D8IC / TLOAD_C3D8Bbar / TLOAD_C3 of every element,
+ * ADDED to load_inout (3*n_node, host), so it composes with the `load` of fx_assemble_groups.  Elements that share a node add
+ * with fp64 atomics (as QFORCE): equal to rounding from call to call, not bit for bit.  Errors as fx_assemble_groups, and a NULL
+ * temperature array or NULL alpha: FX_ERROR_RUNTIME; load_inout is untouched on any error.  Needs no profile. */
+int fx_thermal_load_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                           int32_t n_mat, const double *E, const double *nu, const fx_thermal_view *thermal,
+                           double *load_inout, float *ms_kernel);
+/* fx_update_groups_linear with the routines' thermal branches: stored strain = the total strain, stress = D (strain - EPSTH),
+ * qforce from that stress; the IC element also subtracts its TLOAD_C3D8IC vector (static_LIB_3dIC.f90:337-342).  Same pinned
+ * staging and results layout; one group runs the single-type kernels.  With temp == temp0 == ref_temp everywhere the strain and
+ * stress are those of fx_update_groups_linear. */
+int fx_update_groups_linear_thermal(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group,
+                                    const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu,
+                                    const fx_thermal_view *thermal, const double *disp, const double **strain,
+                                    const double **stress, double *qforce, float *ms_kernel);
+
 /* ---- nonlinear static loop: the steps of fstr_Newton either side of the solve -------------
  * (fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29-167).  One TYPE=361 group with the
  * B-bar formulation (the reference's default for NLSTATIC, fstr_setup.f90:366-368) and one

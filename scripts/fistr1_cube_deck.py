@@ -14,7 +14,10 @@ NLSTATIC decks of the STF_C3 types (--etype 341|342|351|352|362 without --linear
   --nl-material multilinear|bilinear|elastic_tl|elastic_ul   MAT1: Mises MULTILINEAR (default) or BILINEAR, both updated Lagrange;
                                                              ELASTIC total Lagrange; `!ELASTIC, CAUCHY`, updated Lagrange.
   --two-sections                                             the second half of the elements is MAT2, ELASTIC 70000 / 0.33, TOTAL
-                                                             Lagrange: next to an updated-Lagrange MAT1 the deck mixes the two flags."""
+                                                             Lagrange: next to an updated-Lagrange MAT1 the deck mixes the two flags.
+--thermal (with --linear): a thermal-stress deck.  `!REFTEMP 20`, `!INITIAL CONDITION, TYPE=TEMPERATURE` (ALL, 25) in the mesh file,
+`!TEMPERATURE` on the node groups FIX (35) and TOP (120) -- every other node keeps the initial condition's, so the temperature
+varies inside the elements -- and `!EXPANSION_COEFF` 1.2e-5 for MAT1, 2.3e-5 for MAT2."""
 import os
 import sys
 
@@ -41,6 +44,11 @@ if two:
     sys.argv.remove("--two-sections")
     if not linear and etype == 361:
         sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362")
+thermal = "--thermal" in sys.argv
+if thermal:
+    sys.argv.remove("--thermal")
+    if not linear:
+        sys.exit("--thermal needs --linear")
 nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
 if "--nl-material" in sys.argv:
     k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
@@ -95,6 +103,8 @@ with open(os.path.join(d, "cube.msh"), "w") as fh:
     fh.write("!MATERIAL,NAME=MAT1,ITEM=1\n!ITEM=1,SUBITEM=2\n 206900.0,0.29\n!SECTION,TYPE=SOLID,EGRP=E1,MATERIAL=MAT1\n")
     if two:
         fh.write("!MATERIAL,NAME=MAT2,ITEM=1\n!ITEM=1,SUBITEM=2\n 70000.0,0.33\n!SECTION,TYPE=SOLID,EGRP=E2,MATERIAL=MAT2\n")
+    if thermal:
+        fh.write("!INITIAL CONDITION, TYPE=TEMPERATURE\n ALL, 25.0\n")
     if etype == 361 and not mixed:
         fh.write("!NGROUP, NGRP=FIX, GENERATE\n 1,%d,1\n" % (m * m))
         fh.write("!NGROUP, NGRP=TOP, GENERATE\n %d,%d,1\n!END\n" % (m * m * n + 1, m * m * m))
@@ -109,19 +119,21 @@ if linear:
  3
 !SOLUTION, TYPE=STATIC
 !WRITE,RESULT,FREQUENCY=100000
-!BOUNDARY
+%s!BOUNDARY
  FIX, 1, 3, 0.0
 !CLOAD
  TOP, 1, 1.0
-!MATERIAL, NAME=MAT1
+%s!MATERIAL, NAME=MAT1
 !ELASTIC
  210000.0, 0.3
-%s%s!RESTART, FREQUENCY=100000
+%s%s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  10000, 1
  1.0e-8, 1.0, 0.0
 !END
-""" % ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" if two else "",
+""" % ("!REFTEMP\n 20.0\n" if thermal else "", "!TEMPERATURE\n FIX, 35.0\n TOP, 120.0\n" if thermal else "",
+       "!EXPANSION_COEFF\n 1.2e-5\n" if thermal else "",
+       ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" + ("!EXPANSION_COEFF\n 2.3e-5\n" if thermal else "")) if two else "",
        "!SECTION, SECNUM=1, FORM361=%s\n" % form361 if form361 else "", method, precond))
 # MAT1 of the NLSTATIC deck.  multilinear / bilinear: Mises, updated Lagrange (the default of !PLASTIC); elastic_tl: total Lagrange
 # (the default of !ELASTIC under NLSTATIC); elastic_ul: `!ELASTIC, CAUCHY`, updated Lagrange.  --two-sections: MAT2 is ELASTIC (total Lagrange).
