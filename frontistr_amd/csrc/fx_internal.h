@@ -1,6 +1,7 @@
 // Internal declarations of libfistr_hip (gfx950 only).  See include/fistr_hip.h for the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -167,12 +168,20 @@ struct HaloDev {
   int32_t n_export = 0, n_import = 0;
 };
 
-// Material of the nonlinear path as the kernels take it (one isotropic Mises material per context).
+// Material of one section as the nonlinear kernels take it: isotropic ELASTIC, Mises elastoplastic, or hyperelastic.  The layout is
+// part of every element kernel's argument list, so a hyperelastic material reuses the slot of the hardening law for its kind
+// (a hyperelastic material has no hardening law): read it through nl_hyper_kind().
 struct NlMat {
-  double E, nu, pl[3];
-  int32_t plastic, harden, nlgeom, ntab;
+  double E, nu, pl[3];      // pl: M_PLCONST1..3 (hardening constants, or C10 / C01 / D1, or mu / lambda_m / D)
+  int32_t plastic;          // 1: Mises elastoplastic (state history, the latch); 0: ELASTIC and hyperelastic
+  int32_t harden;           // Mises: hardening law 0..3; group 3: the kind, FX_MAT_MOONEY or FX_MAT_ARRUDA
+  int32_t group;            // compile-time group of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic (total Lagrange)
+  int32_t ntab;
   const double *tab;  // device, ntab rows (yield stress, plastic strain)
 };
+static_assert(sizeof(NlMat) == 64 && offsetof(NlMat, plastic) == 40 && offsetof(NlMat, harden) == 44 && offsetof(NlMat, group) == 48 &&
+                  offsetof(NlMat, tab) == 56,
+              "NlMat is an argument of every element kernel: its layout stays what it was before the hyperelastic kinds");
 
 // fstr_solid members of the nonlinear static loop (m_fstr.f90:560-700) for one TYPE=361 B-bar group, resident.
 // Elements grouped by colour (fxo::color_elements): the atomic-free scatter of the stiffness kernels.
@@ -203,8 +212,8 @@ struct NlDev {
   int32_t etype = 361;                // element type of the context: 361 (B-bar, fx_nl_init) or 341 / 342 (fx_nl_init_c3)
   int nn = 8, nq = 8;                 // its nodes and quadrature points per element
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
-  std::vector<int32_t> grp_off[3];    // per NLGEOM flag (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG): positions of its colours in order (+ end)
-  std::vector<int32_t> dup_off[3];    // per NLGEOM flag: its collapsed elements' colours in colors.dup (+ end); empty = none
+  std::vector<int32_t> grp_off[4];    // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic): positions of its colours in order (+ end)
+  std::vector<int32_t> dup_off[4];    // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
   bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements): one range per group, fp64 atomics
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material

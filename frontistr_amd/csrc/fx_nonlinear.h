@@ -8,6 +8,8 @@
 //                    + BackwardEuler Elastoplastic.f90:351-558 (Mises, isotropic hardening)
 //   k_nl_residual    fstr_Update_NDForce fstr_Residual.f90:23-71
 //   fx_nl_commit     fstr_UpdateState fstr_Update.f90:296-345
+// Hyperelastic materials (MatlMatrix :81-86 from the stored strain, StressUpdate :126-129): group 3 of the two element kernels,
+// point functions in fx_hyperelastic.h.
 //
 // Work decomposition: 8 lanes per element (8 elements per wave64).  A lane first acts as quadrature
 // point LX = lane: Jacobian, global derivatives, material matrix, stress update and return mapping of
@@ -23,6 +25,7 @@
 // from then on the tangent uses the elastic matrix, exactly as the reference does.
 #pragma once
 #include "fx_assemble.h"
+#include "fx_hyperelastic.h"
 
 #define FXN_BLOCK 256
 #define FXN_EPB (FXN_BLOCK / 8)
@@ -183,7 +186,12 @@ __device__ __forceinline__ void nl_node_B(const double *g, const double *h, cons
 
 __device__ __forceinline__ double bcast8(double v, int src) { return __shfl(v, src, 8); }
 
-template <int NLGEOM>
+// Compile-time group G of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG -- the NLGEOM flag of an ELASTIC / Mises material --
+// and 3: total-Lagrange kinematics with the hyperelastic point functions of fx_hyperelastic.h (the material kind, Mooney-Rivlin family
+// or Arruda-Boyce, is a run-time branch on the element's NlMat).  `strain` (the points' stored strain) is read by group 3 only.
+__device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : G; }
+
+template <int G>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, const double *__restrict__ coord,
                                                             const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                             const double *__restrict__ dunode, NlMat m, int latch,
@@ -196,7 +204,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                            int kout_pos) {
+                                                            int kout_pos, const double *__restrict__ strain) {
+  constexpr int NLGEOM = nl_group_flag(G);
   // positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one colour (no shared node),
   // scattered without atomics, see k_assemble_c3d8.  mats / emat: several sections, element e uses mats[emat[e] - 1].
   // Kout: element matrices out instead of the scatter, by element id (kout_pos == 0) or by position in elem_list.
@@ -208,6 +217,16 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
   if (mats) m = mats[emat[elem] - 1];
   int32_t nod[8];
   double gd[8][3], bbar[8][3], Dm[21], S[6], F[9], wg;
+  // group 3: the 21 tangent entries of every point and the element's centroid derivatives wait in LDS (42 + 6 KB a workgroup), not
+  // in registers, for the node-row loop -- the TOTALLAG instantiation, whose registers it shares otherwise, spills; with one wave per
+  // SIMD either way the LDS costs no occupancy
+  double *Dsh = nullptr, *Bsh = nullptr;
+  if constexpr (G == 3) {
+    __shared__ double dsh[FXN_EPB][8][21];
+    __shared__ double bsh[FXN_EPB][24];
+    Dsh = &dsh[threadIdx.x >> 3][0][0];
+    Bsh = &bsh[threadIdx.x >> 3][0];
+  }
   {
     double ec[8][3], ut[8][3];
 #pragma unroll
@@ -223,13 +242,27 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
     }
     double det;
     hex8_gderiv(ec, 0.0, 0.0, 0.0, det, bbar);  // dilatation at the centroid (:72-73)
+    if (G == 3) {  // the same 24 numbers in the element's eight lanes: lane b keeps node b's
+#pragma unroll
+      for (int b = 0; b < 8; b++)
+        if (b == lane8) { Bsh[3 * b] = bbar[b][0]; Bsh[3 * b + 1] = bbar[b][1]; Bsh[3 * b + 2] = bbar[b][2]; }
+    }
     const double GP = 0.577350269189626;
     const double xi = (lane8 & 1) ? GP : -GP, et = (lane8 & 2) ? GP : -GP, ze = (lane8 & 4) ? GP : -GP;
     hex8_gderiv(ec, xi, et, ze, det, gd);
     wg = det;
 #pragma unroll
     for (int i = 0; i < 6; i++) S[i] = stress[((size_t)8 * elem + lane8) * 6 + i];
-    nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm);
+    if (G == 3) {  // MatlMatrix of a hyperelastic point: from the stored strain (calMatMatrix.f90:81-86)
+      double E[6];
+#pragma unroll
+      for (int i = 0; i < 6; i++) E[i] = strain[((size_t)8 * elem + lane8) * 6 + i];
+      hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
+#pragma unroll
+      for (int k = 0; k < 21; k++) Dsh[21 * lane8 + k] = Dm[k];
+    } else {
+      nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm);
+    }
 #pragma unroll
     for (int k = 0; k < 9; k++) F[k] = 0.0;
     if (NLGEOM == 1) {  // gdispderiv = u . gderiv (:131)
@@ -244,6 +277,10 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
         }
     }
   }
+  // the LDS values only pass between the eight lanes of one element, which share a wave; the barrier is what makes the writes
+  // visible to the reads in the language's terms (no wave-level fence is relied on), and it is safe: every lane reaches it, the idle
+  // ones shadow the last element.  One barrier per workgroup against eight passes over 24 x 24 blocks: not measurable.
+  if (G == 3) __syncthreads();
   // ---- lanes become node rows
   const int a = lane8;
   double K[8][9];
@@ -258,7 +295,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 #pragma unroll
       for (int d = 0; d < 3; d++) g[b][d] = bcast8(gd[b][d], LX);
 #pragma unroll
-    for (int k = 0; k < 21; k++) Dl[k] = bcast8(Dm[k], LX);
+    for (int k = 0; k < 21; k++) Dl[k] = G == 3 ? Dsh[21 * LX + k] : bcast8(Dm[k], LX);
     if (NLGEOM != 0) {
 #pragma unroll
       for (int k = 0; k < 6; k++) Sl[k] = bcast8(S[k], LX);
@@ -276,7 +313,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
     for (int b = 0; b < 8; b++)
       if (b == a) {
 #pragma unroll
-        for (int d = 0; d < 3; d++) { ga[d] = g[b][d]; ha[d] = (bbar[b][d] - g[b][d]) / 3.0; }
+        for (int d = 0; d < 3; d++) { ga[d] = g[b][d]; ha[d] = ((G == 3 ? Bsh[3 * b + d] : bbar[b][d]) - g[b][d]) / 3.0; }
       }
     double Ba[6][3];
     nl_node_B<NLGEOM>(ga, ha, Fl, Ba);
@@ -288,7 +325,9 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
     }
 #pragma unroll
     for (int b = 0; b < 8; b++) {
-      double hb[3] = {(bbar[b][0] - g[b][0]) / 3.0, (bbar[b][1] - g[b][1]) / 3.0, (bbar[b][2] - g[b][2]) / 3.0};
+      double hb[3];
+#pragma unroll
+      for (int d = 0; d < 3; d++) hb[d] = ((G == 3 ? Bsh[3 * b + d] : bbar[b][d]) - g[b][d]) / 3.0;
       double Bb[6][3], DB[6][3];
       nl_node_B<NLGEOM>(g[b], hb, Fl, Bb);
 #pragma unroll
@@ -353,7 +392,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 }
 
 // Update_C3D8Bbar + scatter of the internal force.  qf_out (tests): per-element qf[24] instead of the scatter.
-template <int NLGEOM>
+template <int G>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const double *__restrict__ coord,
                                                          const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                          const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
@@ -363,7 +402,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
                                                          double *__restrict__ qforce, double *__restrict__ qf_out,
                                                          const int32_t *__restrict__ elem_list, int32_t e0,
                                                          const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
-  // positions [e0, n_elem) of elem_list: the elements of this NLGEOM group; mats / emat: several sections
+  // positions [e0, n_elem) of elem_list: the elements of this group; mats / emat: several sections
+  constexpr int NLGEOM = nl_group_flag(G);
   const int LX = threadIdx.x & 7;
   int32_t epos = e0 + blockIdx.x * FXN_EPB + (threadIdx.x >> 3);
   const bool active = epos < n_elem;
@@ -418,8 +458,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
       g[i][j] = s;
     }
   const double dvol = vol0 - (g[0][0] + g[1][1] + g[2][2]) / 3.0;
-  double D11, D12, D44, de[6];
-  elastic_constants(m.E, m.nu, D11, D12, D44);
+  double de[6];
   small_strain(g, de);
   de[0] += dvol; de[1] += dvol; de[2] += dvol;
   if (NLGEOM == 1) {  // Green-Lagrange strain :378-388
@@ -430,7 +469,13 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
     de[5] += g[0][0] * g[0][2] + g[1][0] * g[1][2] + g[2][0] * g[2][2];
   }
   double ds[6];
-  iso_stress(D11, D12, D44, de, ds);
+  if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:387-390)
+    hyper_stress(nl_hyper_kind(m), m.pl, de, ds);
+  } else {
+    double D11, D12, D44;
+    elastic_constants(m.E, m.nu, D11, D12, D44);
+    iso_stress(D11, D12, D44, de, ds);
+  }
   const size_t gp = (size_t)8 * elem + LX;
   double sg[6], eg[6];
   if (NLGEOM == 2) {  // :407-432
@@ -463,7 +508,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
 #pragma unroll
     for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
   }
-  if (m.plastic) {
+  if (G != 3 && m.plastic) {
     int32_t ist = istat[gp];
     double fs = fstat[gp];
     nl_backward_euler(m, sg, plstrain[gp], ist, fs);

@@ -29,7 +29,7 @@
 #include "fx_nonlinear_tet.h"
 
 // Arguments as k_nl_stiffness_tet.
-template <int ETYPE, int NLGEOM>
+template <int ETYPE, int G>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_elem, const double *__restrict__ coord,
                                                            const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                            const double *__restrict__ dunode, NlMat m, int latch,
@@ -41,8 +41,10 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
                                                            double *__restrict__ Kout, int32_t *__restrict__ err,
                                                            const int32_t *__restrict__ elem_list, int32_t e0,
                                                            const int32_t *__restrict__ pos_map, int atomic,
-                                                           const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                           const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                           const double *__restrict__ strain) {
   using El = C3El<ETYPE>;
+  constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = El::NN, NQ = El::NQ, EPB = El::EPB, LPE = El::LPE, NB = El::NB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1, NS = NLGEOM != 0 ? 6 : 1;
   __shared__ double Xsh[EPB][NN][3];
@@ -74,7 +76,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
       double S[6], Dm[21];
 #pragma unroll
       for (int i = 0; i < 6; i++) S[i] = stress[gp * 6 + i];
-      nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+      if (G == 3) {  // MatlMatrix of a hyperelastic point: from the stored strain (calMatMatrix.f90:81-86)
+        double E[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) E[i] = strain[gp * 6 + i];
+        hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
+      } else {
+        nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+      }
 #pragma unroll
       for (int i = 0; i < 21; i++) Dsh[el][q][i] = Dm[i];
       if (NLGEOM != 0) {
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
 }
 
 // UPDATE_C3 + scatter of the internal force.  Arguments as k_nl_update_tet; state arrays [elem][NQ][.].
-template <int ETYPE, int NLGEOM>
+template <int ETYPE, int G>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem, const double *__restrict__ coord,
                                                         const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                         const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
@@ -163,6 +172,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
                                                         double *__restrict__ qforce, double *__restrict__ qf_out,
                                                         const int32_t *__restrict__ elem_list, int32_t e0,
                                                         const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+  constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ, LPE = C3El<ETYPE>::ULPE, EPB = C3El<ETYPE>::UEPB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1;
   __shared__ double Xsh[EPB][NN][3];
@@ -203,9 +213,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
         de[5] += gu[0][0] * gu[0][2] + gu[1][0] * gu[1][2] + gu[2][0] * gu[2][2];
       }
       // MatlMatrix with isEp: the elastic matrix (the call itself sets the latch for an elastoplastic material)
-      double D11, D12, D44, ds[6];
-      elastic_constants(m.E, m.nu, D11, D12, D44);
-      iso_stress(D11, D12, D44, de, ds);
+      double ds[6];
+      if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:681-684)
+        hyper_stress(nl_hyper_kind(m), m.pl, de, ds);
+      } else {
+        double D11, D12, D44;
+        elastic_constants(m.E, m.nu, D11, D12, D44);
+        iso_stress(D11, D12, D44, de, ds);
+      }
       const size_t gp = (size_t)NQ * elem + g;
       double sg[6], eg[6];
       if (NLGEOM == 2) {  // :702-732; the stress increment is rounded as `real()` rounds it (:718)
@@ -235,7 +250,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
 #pragma unroll
         for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
       }
-      if (m.plastic) {
+      if (G != 3 && m.plastic) {
         int32_t ist = istat[gp];
         double fs = fstat[gp];
         nl_backward_euler(m, sg, plstrain[gp], ist, fs);

@@ -20,6 +20,19 @@ static void nl_free(fx_context *c) {
 // fstr_solid / tGaussStatus set-up for one TYPE=361 B-bar group with one material (fstr_setup.f90:325-400,
 // fstr_init_gauss mechgauss.f90:37-71): zero state, zero displacement.
 static int nl_check_material(const fx_material_view *mat) {
+  if (mat->plastic == FX_MAT_MOONEY || mat->plastic == FX_MAT_ARRUDA) {  // E, nu, harden, tab are not read
+    if (mat->nlgeom != 1)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+                     "a hyperelastic material needs nlgeom = 1 (TOTALLAG): under UPDATELAG (CAUCHY) the reference multiplies the "
+                     "hyperelastic tangent with the strain increment, a different algorithm that is not on the device");
+    if (mat->plconst[2] == 0.0)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "hyperelastic material with plconst[2] = 0: cannot deal with incompressible material");
+    if (mat->plastic == FX_MAT_ARRUDA && mat->plconst[1] == 0.0)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Arruda-Boyce material with plconst[1] = 0 (locking stretch lambda_m)");
+    return 0;
+  }
+  if (mat->plastic < 0 || mat->plastic > FX_MAT_ARRUDA)
+    return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce", (int)mat->plastic);
   if (mat->harden < 0 || mat->harden > 3 || mat->nlgeom < 0 || mat->nlgeom > 2) {
     g_fx_error = "fx_nl_init: only Mises yield with BILINEAR/MULTILINEAR/SWIFT/RAMBERG-OSGOOD hardening is on the hot path";
     return FX_ERROR_UNSUPPORTED;
@@ -37,6 +50,16 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   if (n_mat < 1 || !mats || (n_mat > 1 && !elem_mat)) { g_fx_error = "fx_nl_init: materials missing"; return FX_ERROR_RUNTIME; }
   for (int32_t k = 0; k < n_mat; k++)
     if (int e = nl_check_material(&mats[k])) return e;
+  {
+    // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
+    // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
+    bool mises = false, hyper = false;
+    for (int32_t k = 0; k < n_mat; k++) { mises |= mats[k].plastic == 1; hyper |= mats[k].plastic >= FX_MAT_MOONEY; }
+    if (mises && hyper)
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                     "a Mises and a hyperelastic material in one context: after the first plastic update the reference takes the elastic "
+                     "matrix of every material, which a hyperelastic one does not define");
+  }
   if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
   for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
     if (mesh->conn[k] < 1 || mesh->conn[k] > mesh->n_node) { g_fx_error = "fx_nl_init: node id out of range"; return FX_ERROR_RUNTIME; }
@@ -69,7 +92,8 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     NlMat &m = n.h_mats[k];
     m.E = mv.E; m.nu = mv.nu;
     for (int i = 0; i < 3; i++) m.pl[i] = mv.plconst[i];
-    m.plastic = mv.plastic ? 1 : 0; m.harden = mv.harden; m.nlgeom = mv.nlgeom; m.ntab = mv.ntab;
+    m.plastic = mv.plastic == 1 ? 1 : 0; m.harden = mv.harden; m.group = mv.nlgeom; m.ntab = mv.ntab;
+    if (mv.plastic >= FX_MAT_MOONEY) { m.harden = mv.plastic; m.group = 3; m.ntab = 0; }  // group 3: no history, no latch
     m.tab = tab;
   }
   n.mat = n.h_mats[0];
@@ -79,7 +103,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     HIP_TRY(hipMemcpyAsync(n.mats, n.h_mats.data(), (size_t)n_mat * sizeof(NlMat), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(n.emat, elem_mat, (size_t)mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
   }
-  // element lists: grouped by the NLGEOM flag of the element's material (one kernel instantiation per flag), inside a group
+  // element lists: grouped by the NLGEOM flag of the element's material, hyperelastic ones apart (one kernel instantiation per group), inside a group
   // colour by colour (fx_order.cpp: color_elements) for the atomic-free scatter
   {
     static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
@@ -94,7 +118,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
     std::vector<int32_t> grouped, dups;
     grouped.reserve((size_t)mesh->n_elem);
-    for (int g = 0; g < 3; g++) {
+    for (int g = 0; g < 4; g++) {
       n.grp_off[g].clear();
       n.dup_off[g].clear();
       std::vector<int32_t> doff(1, (int32_t)dups.size());
@@ -103,8 +127,8 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
         const size_t before = grouped.size();
         for (int32_t q = off[k]; q < off[k + 1]; q++) {
           const int32_t e = order[q];
-          const int flag = n.h_mats[n_mat > 1 ? elem_mat[e] - 1 : 0].nlgeom;
-          if (flag == g) (coloured && names_a_node_twice(mesh->conn + (size_t)nn * e, nn) ? dups : grouped).push_back(e);
+          const int group = n.h_mats[n_mat > 1 ? elem_mat[e] - 1 : 0].group;
+          if (group == g) (coloured && names_a_node_twice(mesh->conn + (size_t)nn * e, nn) ? dups : grouped).push_back(e);
         }
         doff.push_back((int32_t)dups.size());
         if (grouped.size() > before || any) {
@@ -128,7 +152,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
       // STF_C3 types: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
       // of all the launches are the `colours` the flags are made for (none of their elements is in colors.dup: they were refused above)
       n.colors.offsets.assign(1, 0);
-      for (int g = 0; g < 3; g++)
+      for (int g = 0; g < 4; g++)
         for (size_t k = 1; k < n.grp_off[g].size(); k++)
           if (n.grp_off[g][k] > n.colors.offsets.back()) n.colors.offsets.push_back(n.grp_off[g][k]);
     }
@@ -207,7 +231,8 @@ static void nl_launch_stiffness_c3_group(fx_context *c, double *Kout) {
   for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
     hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, false>()), grid, dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat,
                        n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0,
-                       (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+                       (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat,
+                       (const double *)n.strain);
   });
 }
 template <int ETYPE, int G>
@@ -222,7 +247,7 @@ static void nl_launch_update_c3_group(fx_context *c, double *qf_out) {
                      n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce, qf_out, list,
                      e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
 }
-// the three NLGEOM groups of a context of an STF_C3 type: tangent (update == false) or stress update
+// the four groups of a context of an STF_C3 type: tangent (update == false) or stress update
 static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool update) {
   with_c3_type(c->nl.etype, [&](auto t) {
     constexpr int ET = decltype(t)::value;
@@ -230,10 +255,12 @@ static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool updat
       nl_launch_update_c3_group<ET, 0>(c, qf_out);
       nl_launch_update_c3_group<ET, 1>(c, qf_out);
       nl_launch_update_c3_group<ET, 2>(c, qf_out);
+      nl_launch_update_c3_group<ET, 3>(c, qf_out);
     } else {
       nl_launch_stiffness_c3_group<ET, 0>(c, Kout);
       nl_launch_stiffness_c3_group<ET, 1>(c, Kout);
       nl_launch_stiffness_c3_group<ET, 2>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 3>(c, Kout);
     }
   });
 }
@@ -247,7 +274,7 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
     hipLaunchKernelGGL((k_nl_stiffness<G>), grid, dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch,
                        n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
                        (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0,
-                       (const NlMat *)n.mats, (const int32_t *)n.emat, 0);
+                       (const NlMat *)n.mats, (const int32_t *)n.emat, 0, (const double *)n.strain);
   });
   // collapsed elements: their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter --
   // added colour by colour (k_add_elem_blocks)
@@ -257,7 +284,7 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
   hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((d1 - d0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, d1, n.coord, n.conn,
                      n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
                      Kout ? Kout : dup_k, n.err, (const int32_t *)n.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
-                     (const int32_t *)n.emat, Kout ? 0 : 1);
+                     (const int32_t *)n.emat, Kout ? 0 : 1, (const double *)n.strain);
   if (Kout) return;
   for (size_t k = 0; k + 1 < doff.size(); k++)
     if (doff[k + 1] > doff[k])
@@ -265,7 +292,7 @@ static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k
                          (const int32_t *)n.colors.dup, (const double *)dup_k, (const int32_t *)n.conn, (const int32_t *)n.colors.pos,
                          A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
-static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per NLGEOM flag present
+static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per group present
   if (c->nl.etype != 361) { nl_launch_c3(c, Kout, nullptr, false); return 0; }
   DevScratch tmp;
   double *dup_k = nullptr;
@@ -273,6 +300,7 @@ static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel ins
   nl_launch_stiffness_group<0>(c, Kout, dup_k);
   nl_launch_stiffness_group<1>(c, Kout, dup_k);
   nl_launch_stiffness_group<2>(c, Kout, dup_k);
+  nl_launch_stiffness_group<3>(c, Kout, dup_k);
   if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
   return 0;
 }
@@ -301,6 +329,7 @@ static void nl_launch_update(fx_context *c, double *qf_out) {
   nl_launch_update_group<0>(c, qf_out);
   nl_launch_update_group<1>(c, qf_out);
   nl_launch_update_group<2>(c, qf_out);
+  nl_launch_update_group<3>(c, qf_out);
 }
 
 // fstr_StiffMatrix + fstr_AddBC (fstr_StiffMatrix.f90:18-212, fstr_AddBC.f90:17-190): tangent of the current

@@ -33,8 +33,8 @@ __device__ __forceinline__ void tet_node_gderiv(int n, double xi, double et, dou
 
 // Arguments as k_nl_stiffness.  Positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one
 // colour, scattered with plain read-modify-writes (a block whose first-write flag is set in pos_map is stored, not added to).
-// Kout: element matrices out ((3 NN)^2 each, row-major, by element id), no scatter.
-template <int ETYPE, int NLGEOM>
+// Kout: element matrices out ((3 NN)^2 each, row-major, by element id), no scatter.  G: the group (nl_group_flag); strain: group 3.
+template <int ETYPE, int G>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_elem, const double *__restrict__ coord,
                                                             const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                             const double *__restrict__ dunode, NlMat m, int latch,
@@ -46,8 +46,10 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
                                                             double *__restrict__ Kout, int32_t *__restrict__ err,
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
-                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                            const double *__restrict__ strain) {
   using El = C3El<ETYPE>;
+  constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = El::NN, NQ = El::NQ, EPB = El::EPB, LPE = El::LPE, NB = El::NB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1, NS = NLGEOM != 0 ? 6 : 1;
   __shared__ double Jsh[EPB][NQ][10];     // per quadrature point: inverse Jacobian (row-major), weight * determinant
@@ -88,7 +90,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
     double S[6], Dm[21];
 #pragma unroll
     for (int i = 0; i < 6; i++) S[i] = stress[gp * 6 + i];
-    nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+    if (G == 3) {  // MatlMatrix of a hyperelastic point: from the stored strain (calMatMatrix.f90:81-86)
+      double E[6];
+#pragma unroll
+      for (int i = 0; i < 6; i++) E[i] = strain[gp * 6 + i];
+      hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
+    } else {
+      nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+    }
 #pragma unroll
     for (int i = 0; i < 21; i++) Dsh[el][k][i] = Dm[i];
     if (NLGEOM != 0) {
@@ -190,7 +199,7 @@ __device__ __forceinline__ void nl_tet_config_jacobian(const int32_t (&nod)[C3El
 
 // UPDATE_C3 + scatter of the internal force.  Arguments as k_nl_update; state arrays [elem][NQ][.]; qf_out (tests): per-element
 // qf[3 NN] instead of the scatter.
-template <int ETYPE, int NLGEOM>
+template <int ETYPE, int G>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_elem, const double *__restrict__ coord,
                                                              const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                              const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
@@ -200,6 +209,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
                                                              double *__restrict__ qforce, double *__restrict__ qf_out,
                                                              const int32_t *__restrict__ elem_list, int32_t e0,
                                                              const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+  constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
   const int64_t t = (int64_t)blockIdx.x * C3El<ETYPE>::BS + threadIdx.x;
   const int g = (int)(t % NQ);
@@ -238,9 +248,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
     de[5] += gu[0][0] * gu[0][2] + gu[1][0] * gu[1][2] + gu[2][0] * gu[2][2];
   }
   // MatlMatrix with isEp: the elastic matrix (the call itself sets the latch for an elastoplastic material)
-  double D11, D12, D44, ds[6];
-  elastic_constants(m.E, m.nu, D11, D12, D44);
-  iso_stress(D11, D12, D44, de, ds);
+  double ds[6];
+  if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:681-684)
+    hyper_stress(nl_hyper_kind(m), m.pl, de, ds);
+  } else {
+    double D11, D12, D44;
+    elastic_constants(m.E, m.nu, D11, D12, D44);
+    iso_stress(D11, D12, D44, de, ds);
+  }
   const size_t gp = (size_t)NQ * elem + g;
   double sg[6], eg[6];
   if (NLGEOM == 2) {  // :702-732
@@ -270,7 +285,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
 #pragma unroll
     for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
   }
-  if (m.plastic) {
+  if (G != 3 && m.plastic) {
     int32_t ist = active ? istat[gp] : 0;      // idle lanes read no state another workgroup may be writing
     double fs = active ? fstat[gp] : 0.0;
     nl_backward_euler(m, sg, active ? plstrain[gp] : 0.0, ist, fs);

@@ -15,7 +15,8 @@
 
 for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
 (fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3),
-with one isotropic (Mises elastoplastic or elastic) material per section.  Everything is resident on the GPU; there is NO CPU
+with one isotropic (Mises elastoplastic, elastic or hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce) material per
+section.  Everything is resident on the GPU; there is NO CPU
 fallback.
 """
 import ctypes as C
@@ -27,6 +28,7 @@ from .hecmw import _chk, _ptr, lib
 
 INFINITE, TOTALLAG, UPDATELAG = 0, 1, 2
 BILINEAR, MULTILINEAR, SWIFT, RAMBERG_OSGOOD = 0, 1, 2, 3
+ELASTIC, MISES, MOONEYRIVLIN, ARRUDABOYCE = 0, 1, 2, 3      # fx_material_view::plastic, the material kind (NEOHOOKE is MOONEYRIVLIN with C01 = 0)
 
 
 class _MaterialView(C.Structure):
@@ -42,21 +44,46 @@ class _StateView(C.Structure):
 class tMaterial:
     """!ELASTIC E, nu; optional !PLASTIC, YIELD=MISES, HARDEN=<harden> with `plconst` (BILINEAR: yield0, H;
     SWIFT / RAMBERG-OSGOOD: the three constants) or `table` rows (yield stress, plastic strain) for MULTILINEAR.
-    nlgeom_flag defaults to UPDATELAG as !PLASTIC does (KIRCHHOFF -> TOTALLAG, INFINITE -> INFINITE)."""
+    nlgeom_flag defaults to UPDATELAG as !PLASTIC does (KIRCHHOFF -> TOTALLAG, INFINITE -> INFINITE).
+    Hyperelastic materials come from the named constructors neohooke / mooney_rivlin / arruda_boyce; they default to TOTALLAG, the
+    only flag the device loop serves for them."""
 
     def __init__(self, E, nu, plastic=False, harden=BILINEAR, plconst=(0.0, 0.0, 0.0), table=None, nlgeom_flag=UPDATELAG):
         self.E, self.nu, self.plastic, self.harden = float(E), float(nu), bool(plastic), int(harden)
         self.plconst = tuple(float(v) for v in plconst)
         self.table = np.zeros((0, 2)) if table is None else np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 2)
         self.nlgeom_flag = int(nlgeom_flag)
+        self.kind = MISES if self.plastic else ELASTIC
         if self.plastic and self.harden == MULTILINEAR:
             if self.table.shape[0] < 1 or self.table[0, 1] != 0.0:
                 raise ValueError("Multilinear hardening: First plastic strain must be zero")   # fstr_ctrl_material.f90:416
             if (self.table[:, 1] < 0).any():
                 raise ValueError("Multilinear hardening: Error in plastic strain definition")
 
+    @classmethod
+    def _hyperelastic(cls, kind, plconst, nlgeom_flag):
+        m = cls(0.0, 0.0, plconst=plconst, nlgeom_flag=nlgeom_flag)
+        m.kind = kind
+        return m
+
+    @classmethod
+    def neohooke(cls, C10, D1, nlgeom_flag=TOTALLAG):
+        """!HYPERELASTIC, TYPE=NEOHOOKE: C10, D1 (fstr_ctrl_material.f90:166-255: Mooney-Rivlin with C01 = 0)."""
+        return cls._hyperelastic(MOONEYRIVLIN, (C10, 0.0, D1), nlgeom_flag)
+
+    @classmethod
+    def mooney_rivlin(cls, C10, C01, D1, nlgeom_flag=TOTALLAG):
+        """!HYPERELASTIC, TYPE=MOONEY-RIVLIN: C10, C01, D1."""
+        return cls._hyperelastic(MOONEYRIVLIN, (C10, C01, D1), nlgeom_flag)
+
+    @classmethod
+    def arruda_boyce(cls, mu, lam, D, nlgeom_flag=TOTALLAG):
+        """!HYPERELASTIC, TYPE=ARRUDA-BOYCE: mu, lambda_m, D."""
+        return cls._hyperelastic(ARRUDABOYCE, (mu, lam, D), nlgeom_flag)
+
     def view(self):
-        v = _MaterialView(self.E, self.nu, int(self.plastic), self.harden, self.nlgeom_flag, self.table.shape[0],
+        kind = self.kind if self.kind >= MOONEYRIVLIN else int(self.plastic)
+        v = _MaterialView(self.E, self.nu, kind, self.harden, self.nlgeom_flag, self.table.shape[0],
                           (C.c_double * 3)(*self.plconst), _ptr(self.table) if self.table.size else None)
         v._keep = self.table
         return v

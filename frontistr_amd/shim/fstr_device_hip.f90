@@ -75,7 +75,7 @@ contains
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
     character(len=3) :: tname
-    integer :: elen, estat, i, icel, cid, nn
+    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises
     logical :: opted
     if (decided) then
       fsd_eligible = eligible
@@ -125,9 +125,20 @@ contains
       cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
       if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
     enddo
+    n_hyper = 0
+    n_mises = 0
     do i = 1, size(fstrSOLID%materials)
       if (.not. material_covered(fstrSOLID%materials(i))) return
+      if (is_hyperelastic(fstrSOLID%materials(i)%mtype)) n_hyper = n_hyper + 1
+      if (fstrSOLID%materials(i)%mtype /= -1 .and. isElastoplastic(fstrSOLID%materials(i)%mtype)) n_mises = n_mises + 1
     enddo
+    if (n_hyper > 0) then
+      ! !HYPERELASTIC decks opt in (no end-to-end time against the host loops is on record); beside a plastic material they keep the
+      ! host loops: after the first plastic update MatlMatrix's saved flag sends every material to calElasticMatrix (DESIGN.md section 8)
+      if (n_mises > 0) return
+      call get_environment_variable('HECMW_GPU_NL_HYPER', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+    endif
     eligible = .true.
     fsd_eligible = .true.
     nl_etype = lin_etype
@@ -137,10 +148,12 @@ contains
       write(tname, '(i3)') nl_etype
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//tname//'); '// &
         'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+      if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
       return
     endif
     if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
       'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+    if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
   end function fsd_eligible
 
   !> Where fstr_UpdateNewton of an eligible linear static deck runs.  HECMW_GPU_UPDATE=0: the host, =1: the device.  Unset: the
@@ -372,8 +385,20 @@ contains
       if (isKinematicHarden(m%mtype)) return
       if (getHardenType(m%mtype) < 0 .or. getHardenType(m%mtype) > 3) return
       material_covered = .true.
+    else if (is_hyperelastic(m%mtype)) then
+      ! total Lagrange only (`CAUCHY` -> UPDATELAG is another algorithm in the reference).  A card with a DEPENDENCIES table never gets
+      ! here: fstr_ctrl_get_HYPERELASTIC reads data only when DEPENDENCIES is 0 and returns -1 otherwise, so set-up stops on such a deck.
+      if (m%nlgeom_flag /= TOTALLAG) return
+      if (m%variables(M_PLCONST3) == 0.d0) return
+      if (m%mtype == ARRUDABOYCE .and. m%variables(M_PLCONST2) == 0.d0) return
+      material_covered = .true.
     endif
   end function material_covered
+
+  logical function is_hyperelastic(mtype)
+    integer, intent(in) :: mtype
+    is_hyperelastic = (mtype == NEOHOOKE .or. mtype == MOONEYRIVLIN .or. mtype == ARRUDABOYCE)
+  end function is_hyperelastic
 
   !> First use: profile, mesh, materials and the current quadrature-point history go to the device.
   subroutine fsd_init(hecMESH, hecMAT, fstrSOLID)
@@ -418,6 +443,13 @@ contains
       mats(i)%E = fstrSOLID%materials(i)%variables(M_YOUNGS)
       mats(i)%nu = fstrSOLID%materials(i)%variables(M_POISSON)
       mats(i)%nlgeom = fstrSOLID%materials(i)%nlgeom_flag
+      if (is_hyperelastic(fstrSOLID%materials(i)%mtype)) then      ! the material kind: 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce
+        mats(i)%plastic = 2
+        if (fstrSOLID%materials(i)%mtype == ARRUDABOYCE) mats(i)%plastic = 3
+        mats(i)%plconst(1) = fstrSOLID%materials(i)%variables(M_PLCONST1)
+        mats(i)%plconst(2) = fstrSOLID%materials(i)%variables(M_PLCONST2)
+        mats(i)%plconst(3) = fstrSOLID%materials(i)%variables(M_PLCONST3)
+      endif
       if (isElastoplastic(fstrSOLID%materials(i)%mtype)) then
         mats(i)%plastic = 1
         mats(i)%harden = getHardenType(fstrSOLID%materials(i)%mtype)

@@ -351,10 +351,19 @@ int fx_update_groups_linear_thermal(fx_context *ctx, int32_t n_node, const doubl
  * B-bar formulation (the reference's default for NLSTATIC, fstr_setup.f90:366-368) and one
  * isotropic material: ELASTIC or Mises elastoplastic (!PLASTIC, YIELD=MISES) with BILINEAR /
  * MULTILINEAR / SWIFT / RAMBERG-OSGOOD isotropic hardening, INFINITE / TOTALLAG (KIRCHHOFF) /
- * UPDATELAG kinematics.  Everything stays resident: gauss-point history, unode/dunode, QFORCE. */
+ * UPDATELAG kinematics.  Everything stays resident: gauss-point history, unode/dunode, QFORCE.
+ *
+ * Hyperelastic materials (!HYPERELASTIC, fstr_ctrl_material.f90:166-255; Hyperelastic.f90): `plastic` is the material kind, 2 for
+ * NEOHOOKE / MOONEYRIVLIN with plconst = C10, C01, D1 (Neo-Hooke: C01 = 0) and 3 for ARRUDABOYCE with plconst = mu, lambda_m, D.
+ * E, nu, harden and tab are not read for them.  They need nlgeom = 1 (TOTALLAG, the card's default): the tangent comes from the
+ * point's stored Green-Lagrange strain, the 2nd Piola-Kirchhoff stress from the total strain; no history, no latch.  Every
+ * fx_nl_init* refuses with FX_ERROR_UNSUPPORTED: kind 2 / 3 with another nlgeom (CAUCHY -> UPDATELAG is a different algorithm in the
+ * reference), plconst[2] == 0 ("cannot deal with incompressible"), Arruda-Boyce with plconst[1] == 0, and a Mises and a hyperelastic
+ * material in one context.  A hyperelastic section beside ELASTIC sections of any NLGEOM flag is served.  A kind outside 0..3 is
+ * refused too (before the kinds 2 and 3 existed, every non-zero value was read as Mises). */
 typedef struct fx_material_view { /* tMaterial after fstr_ctrl_get_ELASTICITY/_PLASTICITY (fstr_ctrl_material.f90:60-106, :341-480) */
   double E, nu;         /* M_YOUNGS, M_POISSON */
-  int32_t plastic;      /* 0: mtype ELASTIC; 1: elastoplastic, Mises */
+  int32_t plastic;      /* material kind.  0: mtype ELASTIC; 1: elastoplastic, Mises; 2: Neo-Hooke / Mooney-Rivlin; 3: Arruda-Boyce */
   int32_t harden;       /* fifth digit of mtype: 0 BILINEAR 1 MULTILINEAR 2 SWIFT 3 RAMBERG-OSGOOD */
   int32_t nlgeom;       /* nlgeom_flag: 0 INFINITE 1 TOTALLAG 2 UPDATELAG */
   int32_t ntab;         /* MULTILINEAR: rows of the MC_YIELD table */

@@ -15,6 +15,12 @@ NLSTATIC decks of the STF_C3 types (--etype 341|342|351|352|362 without --linear
                                                              ELASTIC total Lagrange; `!ELASTIC, CAUCHY`, updated Lagrange.
   --two-sections                                             the second half of the elements is MAT2, ELASTIC 70000 / 0.33, TOTAL
                                                              Lagrange: next to an updated-Lagrange MAT1 the deck mixes the two flags.
+  --nl-material neohooke|mooney|arruda                       MAT1: `!HYPERELASTIC` NEOHOOKE (0.1486, 0.0789), MOONEY-RIVLIN (0.1486, 0.4849,
+                                                             0.0789) or ARRUDA-BOYCE (0.71, 1.7029, 0.1408), the constants of the reference's
+                                                             tutorials; total Lagrange.  Also for the plain TYPE=361 cube, also with
+                                                             --two-sections: MAT2 is then ELASTIC 2.5 / 0.3, a material as soft as MAT1.
+                                                             The fourth positional argument after DIR N, STRAIN, is the stretch to ask for
+                                                             (rubber takes 0.1 where the steel decks take 0.005).
 --thermal (with --linear): a thermal-stress deck.  `!REFTEMP 20`, `!INITIAL CONDITION, TYPE=TEMPERATURE` (ALL, 25) in the mesh file,
 `!TEMPERATURE` on the node groups FIX (35) and TOP (120) -- every other node keeps the initial condition's, so the temperature
 varies inside the elements -- and `!EXPANSION_COEFF` 1.2e-5 for MAT1, 2.3e-5 for MAT2."""
@@ -39,21 +45,22 @@ if "--mixed" in sys.argv:
     k = sys.argv.index("--mixed"); mixed = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
     if mixed not in (1, 2) or not linear or etype != 361:
         sys.exit("--mixed takes 1 or 2, with --linear and without --etype")
+nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
+if "--nl-material" in sys.argv:
+    k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
+    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul", "neohooke", "mooney", "arruda"):
+        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl, elastic_ul, neohooke, mooney or arruda, without --linear")
+hyper = nlmat in ("neohooke", "mooney", "arruda")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear and etype == 361:
-        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362")
+    if not linear and etype == 361 and not hyper:
+        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or a hyperelastic --nl-material")
 thermal = "--thermal" in sys.argv
 if thermal:
     sys.argv.remove("--thermal")
     if not linear:
         sys.exit("--thermal needs --linear")
-nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
-if "--nl-material" in sys.argv:
-    k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
-    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul"):
-        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl or elastic_ul, without --linear")
 d, n = sys.argv[1], int(sys.argv[2])
 nsub = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 method = sys.argv[4] if len(sys.argv) > 4 else "CG"
@@ -152,6 +159,9 @@ NL_MATERIALS = {
     "bilinear": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MISES, HARDEN=BILINEAR\n 450.0, 2000.0\n",
     "elastic_tl": "!ELASTIC\n 206900.0, 0.29\n",
     "elastic_ul": "!ELASTIC, CAUCHY\n 206900.0, 0.29\n",
+    "neohooke": "!HYPERELASTIC, TYPE=NEOHOOKE\n 0.1486, 0.0789\n",
+    "mooney": "!HYPERELASTIC, TYPE=MOONEY-RIVLIN\n 0.1486, 0.4849, 0.0789\n",
+    "arruda": "!HYPERELASTIC, TYPE=ARRUDA-BOYCE\n 0.71, 1.7029, 0.1408\n",
 }
 with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
     if not linear:
@@ -172,7 +182,7 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
  1.0e-8, 1.0, 0.0
 !END
 """ % (strain * n, 0.2 * strain * n, nsub, NL_MATERIALS[nlmat],
-       "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" if two else "", method, precond))
+       ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 2.5, 0.3\n" if hyper else "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n") if two else "", method, precond))
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
