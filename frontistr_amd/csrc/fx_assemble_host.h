@@ -208,6 +208,10 @@ static int fx_fail(const char *who, int code, const char *fmt, ...) {
 static int assembly_error(int32_t herr) {
   if (herr == 1) { g_fx_error = "PIVOT ERROR in the incompatible-mode condensation (calInverse)"; return FX_ERROR_RUNTIME; }
   if (herr == 2) { g_fx_error = "###ERROR### : cannot find connectivity (element not covered by the profile)"; return FX_ERROR_RUNTIME; }
+  // the `stop` statements of the Mohr-Coulomb / Drucker-Prager material point (FX_YERR_*, fx_yield.h)
+  if (herr == 3) { g_fx_error = "Math Error in Mohr-Coulomb calculation (|sin 3 theta| > 1, Elastoplastic.f90:85, :338, :474)"; return FX_ERROR_RUNTIME; }
+  if (herr == 4) { g_fx_error = "Math error in return mapping (Elastoplastic.f90:496, :541)"; return FX_ERROR_RUNTIME; }
+  if (herr == 5) { g_fx_error = "Jacobi iteration unable to converge (eigen3, utilities.f90:200)"; return FX_ERROR_RUNTIME; }
   return 0;
 }
 // hecmw_mat_clear (fstr_StiffMatrix.f90:40)

@@ -168,20 +168,23 @@ struct HaloDev {
   int32_t n_export = 0, n_import = 0;
 };
 
-// Material of one section as the nonlinear kernels take it: isotropic ELASTIC, Mises elastoplastic, or hyperelastic.  The layout is
-// part of every element kernel's argument list, so a hyperelastic material reuses the slot of the hardening law for its kind
-// (a hyperelastic material has no hardening law): read it through nl_hyper_kind().
+// Material of one section as the nonlinear kernels take it: isotropic ELASTIC, elastoplastic (Mises, Mohr-Coulomb, Drucker-Prager), or
+// hyperelastic.  The layout is part of every element kernel's argument list, so a hyperelastic material reuses the slot of the
+// hardening law for its kind (a hyperelastic material has no hardening law): read it through nl_hyper_kind().
 struct NlMat {
-  double E, nu, pl[3];      // pl: M_PLCONST1..3 (hardening constants, or C10 / C01 / D1, or mu / lambda_m / D)
-  int32_t plastic;          // 1: Mises elastoplastic (state history, the latch); 0: ELASTIC and hyperelastic
-  int32_t harden;           // Mises: hardening law 0..3; group 3: the kind, FX_MAT_MOONEY or FX_MAT_ARRUDA
-  int32_t group;            // compile-time group of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic (total Lagrange)
+  double E, nu, pl[3];      // pl: M_PLCONST1..3 (hardening constants; c / H / phi or eta; C10 / C01 / D1; mu / lambda_m / D)
+  int32_t plastic;          // non-zero: elastoplastic (state history, the latch) -- 1 Mises, FX_MAT_MOHR, FX_MAT_DRUCKER; 0: ELASTIC and hyperelastic
+  int32_t harden;           // Mises: hardening law 0..3 (0 for the other two yield functions); group 3: the kind, FX_MAT_MOONEY or FX_MAT_ARRUDA
+  int32_t group;            // compile-time group of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic (total Lagrange),
+                            // 4..6: the three flags again for Mohr-Coulomb / Drucker-Prager (nl_group_flag, nl_group_yield)
   int32_t ntab;
   const double *tab;  // device, ntab rows (yield stress, plastic strain)
+  double pl4;         // M_PLCONST4: xi of Drucker-Prager
 };
-static_assert(sizeof(NlMat) == 64 && offsetof(NlMat, plastic) == 40 && offsetof(NlMat, harden) == 44 && offsetof(NlMat, group) == 48 &&
-                  offsetof(NlMat, tab) == 56,
-              "NlMat is an argument of every element kernel: its layout stays what it was before the hyperelastic kinds");
+static_assert(sizeof(NlMat) == 72 && offsetof(NlMat, plastic) == 40 && offsetof(NlMat, harden) == 44 && offsetof(NlMat, group) == 48 &&
+                  offsetof(NlMat, tab) == 56 && offsetof(NlMat, pl4) == 64,
+              "NlMat is an argument of every element kernel: every member keeps the offset it had before the hyperelastic kinds; the "
+              "struct grew from 64 to 72 bytes by M_PLCONST4 at its end, which only Drucker-Prager reads");
 
 // fstr_solid members of the nonlinear static loop (m_fstr.f90:560-700) for one TYPE=361 B-bar group, resident.
 // Elements grouped by colour (fxo::color_elements): the atomic-free scatter of the stiffness kernels.
@@ -212,9 +215,10 @@ struct NlDev {
   int32_t etype = 361;                // element type of the context: 361 (B-bar, fx_nl_init) or 341 / 342 (fx_nl_init_c3)
   int nn = 8, nq = 8;                 // its nodes and quadrature points per element
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
-  std::vector<int32_t> grp_off[4];    // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic): positions of its colours in order (+ end)
-  std::vector<int32_t> dup_off[4];    // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
+  std::vector<int32_t> grp_off[7];    // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager): positions of its colours in order (+ end)
+  std::vector<int32_t> dup_off[7];    // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
   bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements): one range per group, fp64 atomics
+  bool has_yield = false;             // a Mohr-Coulomb or Drucker-Prager section: the stress update reports through the error word too
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material
   int32_t *emat = nullptr;            // device, 1-based material id per element; null with one material

@@ -5,7 +5,8 @@
 //                    (+ GEOMAT_C3 static_LIB_3d.f90:15-37, MatlMatrix calMatMatrix.f90:28-113,
 //                    calElastoPlasticMatrix Elastoplastic.f90:16-117) + hecmw_mat_ass_elem scatter
 //   k_nl_update      fstr_UpdateNewton fstr_Update.f90:25-293 -> Update_C3D8Bbar static_LIB_C3D8.f90:203-547
-//                    + BackwardEuler Elastoplastic.f90:351-558 (Mises, isotropic hardening)
+//                    + BackwardEuler Elastoplastic.f90:351-558 (Mises, isotropic hardening; Mohr-Coulomb and Drucker-Prager:
+//                    fx_yield.h, groups 4..6 of the two element kernels)
 //   k_nl_residual    fstr_Update_NDForce fstr_Residual.f90:23-71
 //   fx_nl_commit     fstr_UpdateState fstr_Update.f90:296-345
 // Hyperelastic materials (MatlMatrix :81-86 from the stored strain, StressUpdate :126-129): group 3 of the two element kernels,
@@ -26,6 +27,7 @@
 #pragma once
 #include "fx_assemble.h"
 #include "fx_hyperelastic.h"
+#include "fx_yield.h"
 
 #define FXN_BLOCK 256
 #define FXN_EPB (FXN_BLOCK / 8)
@@ -99,39 +101,47 @@ __device__ __forceinline__ double nl_harden_coeff(const NlMat &m, double p) {
   return -1.0;
 }
 
-// BackwardEuler, Mises branch (Elastoplastic.f90:351-459, :557)
-__device__ __forceinline__ void nl_backward_euler(const NlMat &m, double (&s)[6], double plstrain, int32_t &istat, double &fstat1) {
-  const double tol = 1.0e-3;
-  const double J1 = (s[0] + s[1] + s[2]) / 3.0;
-  double dv[6] = {s[0] - J1, s[1] - J1, s[2] - J1, s[3], s[4], s[5]};
-  const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
-  const double yd = sqrt(3.0 * J2);
-  double f = yd - nl_curr_yield(m, plstrain);
-  if (fabs(f) < tol) { istat = 1; return; }
-  if (f < 0.0) { istat = 0; return; }
-  istat = 1;
-  const double G = m.E / (2.0 * (1.0 + m.nu));
-  double dlambda = 0.0;
-  for (int i = 0; i < 5; i++) {
-    const double H = nl_harden_coeff(m, plstrain + dlambda);
-    dlambda = dlambda + f / (3.0 * G + H);
-    if (dlambda < 0.0) { dlambda = 0.0; istat = 0; break; }
-    f = yd - 3.0 * G * dlambda - nl_curr_yield(m, plstrain + dlambda);
-    if (fabs(f) < tol * tol) break;
+// BackwardEuler, Mises branch (Elastoplastic.f90:351-459, :557); Y != 0: the Mohr-Coulomb / Drucker-Prager branches of fx_yield.h, whose
+// `stop` statements report through err
+template <int Y = 0>
+__device__ __forceinline__ void nl_backward_euler(const NlMat &m, double (&s)[6], double plstrain, int32_t &istat, double &fstat1,
+                                                  int32_t *err = nullptr) {
+  if constexpr (Y != 0) {
+    yield_backward_euler(m.plastic, m.E, m.nu, m.pl[0], m.pl[1], m.pl[2], m.pl4, s, plstrain, istat, fstat1, err);
+  } else {
+    const double tol = 1.0e-3;
+    const double J1 = (s[0] + s[1] + s[2]) / 3.0;
+    double dv[6] = {s[0] - J1, s[1] - J1, s[2] - J1, s[3], s[4], s[5]};
+    const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
+    const double yd = sqrt(3.0 * J2);
+    double f = yd - nl_curr_yield(m, plstrain);
+    if (fabs(f) < tol) { istat = 1; return; }
+    if (f < 0.0) { istat = 0; return; }
+    istat = 1;
+    const double G = m.E / (2.0 * (1.0 + m.nu));
+    double dlambda = 0.0;
+    for (int i = 0; i < 5; i++) {
+      const double H = nl_harden_coeff(m, plstrain + dlambda);
+      dlambda = dlambda + f / (3.0 * G + H);
+      if (dlambda < 0.0) { dlambda = 0.0; istat = 0; break; }
+      f = yd - 3.0 * G * dlambda - nl_curr_yield(m, plstrain + dlambda);
+      if (fabs(f) < tol * tol) break;
+    }
+    const double fac = 1.0 - 3.0 * dlambda * G / yd;
+    s[0] = fac * dv[0] + J1; s[1] = fac * dv[1] + J1; s[2] = fac * dv[2] + J1;
+    s[3] = fac * dv[3]; s[4] = fac * dv[4]; s[5] = fac * dv[5];
+    fstat1 = plstrain + dlambda;
   }
-  const double fac = 1.0 - 3.0 * dlambda * G / yd;
-  s[0] = fac * dv[0] + J1; s[1] = fac * dv[1] + J1; s[2] = fac * dv[2] + J1;
-  s[3] = fac * dv[3]; s[4] = fac * dv[4]; s[5] = fac * dv[5];
-  fstat1 = plstrain + dlambda;
 }
 
 // symmetric 6x6 in 21 entries, row-major upper triangle: index of (i,j), i<=j
 __device__ __forceinline__ constexpr int sym21(int i, int j) { return (i <= j) ? (i * (13 - i)) / 2 + (j - i) : (j * (13 - j)) / 2 + (i - j); }
 
 // material matrix of one quadrature point, as STF_C3D8Bbar uses it (:90-101): MatlMatrix with the latch,
-// minus GEOMAT_C3 for the updated-Lagrange flag.
+// minus GEOMAT_C3 for the updated-Lagrange flag.  Y != 0: the flow vector of Mohr-Coulomb / Drucker-Prager (fx_yield.h).
+template <int Y = 0>
 __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int flag, const double (&s)[6], int istat, double fstat1,
-                                                double (&Dm)[21]) {
+                                                double (&Dm)[21], int32_t *err = nullptr) {
   double D11, D12, D44;
   elastic_constants(m.E, m.nu, D11, D12, D44);
 #pragma unroll
@@ -143,18 +153,27 @@ __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int f
     const double J1 = s[0] + s[1] + s[2];
     const double dv[6] = {s[0] - J1 / 3.0, s[1] - J1 / 3.0, s[2] - J1 / 3.0, s[3], s[4], s[5]};
     const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
-    const double q = 2.0 * sqrt(J2), r3 = sqrt(3.0);
-    const double a[6] = {r3 * (dv[0] / q), r3 * (dv[1] / q), r3 * (dv[2] / q), r3 * (2.0 * dv[3] / q), r3 * (2.0 * dv[4] / q), r3 * (2.0 * dv[5] / q)};
-    double da[6];
-    iso_stress(D11, D12, D44, a, da);
-    double dum = 0.0;
+    double a[6];
+    bool flow = true;
+    if constexpr (Y != 0) {
+      flow = yield_flow_vector(m.plastic, m.pl[2], dv, J2, a, err);
+    } else {
+      const double q = 2.0 * sqrt(J2), r3 = sqrt(3.0);
+      a[0] = r3 * (dv[0] / q); a[1] = r3 * (dv[1] / q); a[2] = r3 * (dv[2] / q);
+      a[3] = r3 * (2.0 * dv[3] / q); a[4] = r3 * (2.0 * dv[4] / q); a[5] = r3 * (2.0 * dv[5] / q);
+    }
+    if (flow) {
+      double da[6];
+      iso_stress(D11, D12, D44, a, da);
+      double dum = 0.0;
 #pragma unroll
-    for (int i = 0; i < 6; i++) dum += da[i] * a[i];
-    dum = nl_harden_coeff(m, fstat1) + dum;
+      for (int i = 0; i < 6; i++) dum += da[i] * a[i];
+      dum = nl_harden_coeff(m, fstat1) + dum;
 #pragma unroll
-    for (int i = 0; i < 6; i++)
+      for (int i = 0; i < 6; i++)
 #pragma unroll
-      for (int j = i; j < 6; j++) Dm[sym21(i, j)] -= da[i] * da[j] / dum;
+        for (int j = i; j < 6; j++) Dm[sym21(i, j)] -= da[i] * da[j] / dum;
+    }
   }
   if (flag == 2) {  // GEOMAT_C3
     Dm[sym21(0, 0)] -= 2.0 * s[0]; Dm[sym21(0, 3)] -= s[3]; Dm[sym21(0, 5)] -= s[5];
@@ -189,7 +208,11 @@ __device__ __forceinline__ double bcast8(double v, int src) { return __shfl(v, s
 // Compile-time group G of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG -- the NLGEOM flag of an ELASTIC / Mises material --
 // and 3: total-Lagrange kinematics with the hyperelastic point functions of fx_hyperelastic.h (the material kind, Mooney-Rivlin family
 // or Arruda-Boyce, is a run-time branch on the element's NlMat).  `strain` (the points' stored strain) is read by group 3 only.
-__device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : G; }
+// Groups 4, 5, 6: the three flags again for a Mohr-Coulomb or Drucker-Prager material (fx_yield.h; which of the two is a run-time
+// branch on NlMat::plastic).  The yield family is a compile-time parameter so that the instantiations 0..3 stay what they were:
+// k_nl_stiffness<1> sits at 512 VGPRs with scratch and has no register to give to another branch.
+__device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : (G >= 4 ? G - 4 : G); }
+__device__ __forceinline__ constexpr int nl_group_yield(int G) { return G >= 4 ? 1 : 0; }
 
 template <int G>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, const double *__restrict__ coord,
@@ -261,7 +284,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 #pragma unroll
       for (int k = 0; k < 21; k++) Dsh[21 * lane8 + k] = Dm[k];
     } else {
-      nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm);
+      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr);
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) F[k] = 0.0;
@@ -401,7 +424,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
                                                          double *__restrict__ fstat, int32_t *__restrict__ istat,
                                                          double *__restrict__ qforce, double *__restrict__ qf_out,
                                                          const int32_t *__restrict__ elem_list, int32_t e0,
-                                                         const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                         const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                         int32_t *__restrict__ err) {
   // positions [e0, n_elem) of elem_list: the elements of this group; mats / emat: several sections
   constexpr int NLGEOM = nl_group_flag(G);
   const int LX = threadIdx.x & 7;
@@ -511,7 +535,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
   if (G != 3 && m.plastic) {
     int32_t ist = istat[gp];
     double fs = fstat[gp];
-    nl_backward_euler(m, sg, plstrain[gp], ist, fs);
+    nl_backward_euler<nl_group_yield(G)>(m, sg, plstrain[gp], ist, fs, active ? err : nullptr);  // idle lanes recompute the last element: they report nothing
     if (active) { istat[gp] = ist; fstat[gp] = fs; }
   }
   if (active) {

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
         for (int i = 0; i < 6; i++) E[i] = strain[gp * 6 + i];
         hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
       } else {
-        nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+        // (inside `if (active)`: only lanes that own a real point get here, so err needs no `active ?` guard as in k_nl_stiffness)
+        nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm, err);
       }
 #pragma unroll
       for (int i = 0; i < 21; i++) Dsh[el][q][i] = Dm[i];
@@ -171,7 +172,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
                                                         double *__restrict__ fstat, int32_t *__restrict__ istat,
                                                         double *__restrict__ qforce, double *__restrict__ qf_out,
                                                         const int32_t *__restrict__ elem_list, int32_t e0,
-                                                        const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                        const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                        int32_t *__restrict__ err) {
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ, LPE = C3El<ETYPE>::ULPE, EPB = C3El<ETYPE>::UEPB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1;
@@ -253,7 +255,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
       if (G != 3 && m.plastic) {
         int32_t ist = istat[gp];
         double fs = fstat[gp];
-        nl_backward_euler(m, sg, plstrain[gp], ist, fs);
+        nl_backward_euler<nl_group_yield(G)>(m, sg, plstrain[gp], ist, fs, err);  // inside `if (active)`: real points only, err unguarded
         istat[gp] = ist;
         fstat[gp] = fs;
       }

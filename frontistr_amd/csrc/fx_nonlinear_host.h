@@ -31,8 +31,20 @@ static int nl_check_material(const fx_material_view *mat) {
       return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Arruda-Boyce material with plconst[1] = 0 (locking stretch lambda_m)");
     return 0;
   }
-  if (mat->plastic < 0 || mat->plastic > FX_MAT_ARRUDA)
-    return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce", (int)mat->plastic);
+  if (mat->plastic < 0 || mat->plastic > FX_MAT_DRUCKER)
+    return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+                   "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce, 4 Mohr-Coulomb, 5 Drucker-Prager", (int)mat->plastic);
+  if (mat->plastic == FX_MAT_MOHR || mat->plastic == FX_MAT_DRUCKER) {  // fstr_ctrl_material.f90:451-469: linear hardening, no table
+    if (mat->harden != 0 || mat->nlgeom < 0 || mat->nlgeom > 2)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+                     "a Mohr-Coulomb / Drucker-Prager material has harden = 0 (the card forces linear hardening) and nlgeom 0, 1 or 2");
+    // the constants at which BackwardEuler would stop with `Math error in return mapping` (Elastoplastic.f90:496, :541)
+    if (mat->plastic == FX_MAT_MOHR && cos(mat->plconst[2]) == 0.0)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Mohr-Coulomb material with cos(phi) = 0 (plconst[2] is the friction angle in radians)");
+    if (mat->plastic == FX_MAT_DRUCKER && mat->plconst4 == 0.0)
+      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Drucker-Prager material with xi = 0 (plconst4)");
+    return 0;
+  }
   if (mat->harden < 0 || mat->harden > 3 || mat->nlgeom < 0 || mat->nlgeom > 2) {
     g_fx_error = "fx_nl_init: only Mises yield with BILINEAR/MULTILINEAR/SWIFT/RAMBERG-OSGOOD hardening is on the hot path";
     return FX_ERROR_UNSUPPORTED;
@@ -53,12 +65,20 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   {
     // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
     // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
-    bool mises = false, hyper = false;
-    for (int32_t k = 0; k < n_mat; k++) { mises |= mats[k].plastic == 1; hyper |= mats[k].plastic >= FX_MAT_MOONEY; }
+    bool mises = false, hyper = false, yield = false;
+    for (int32_t k = 0; k < n_mat; k++) {
+      mises |= mats[k].plastic == 1;
+      hyper |= mats[k].plastic == FX_MAT_MOONEY || mats[k].plastic == FX_MAT_ARRUDA;
+      yield |= mats[k].plastic == FX_MAT_MOHR || mats[k].plastic == FX_MAT_DRUCKER;
+    }
     if (mises && hyper)
       return fx_fail(who, FX_ERROR_UNSUPPORTED,
                      "a Mises and a hyperelastic material in one context: after the first plastic update the reference takes the elastic "
                      "matrix of every material, which a hyperelastic one does not define");
+    if (yield && hyper)
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                     "a Mohr-Coulomb / Drucker-Prager and a hyperelastic material in one context: after the first plastic update the "
+                     "reference takes the elastic matrix of every material, which a hyperelastic one does not define");
   }
   if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
   for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
@@ -93,7 +113,12 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     m.E = mv.E; m.nu = mv.nu;
     for (int i = 0; i < 3; i++) m.pl[i] = mv.plconst[i];
     m.plastic = mv.plastic == 1 ? 1 : 0; m.harden = mv.harden; m.group = mv.nlgeom; m.ntab = mv.ntab;
-    if (mv.plastic >= FX_MAT_MOONEY) { m.harden = mv.plastic; m.group = 3; m.ntab = 0; }  // group 3: no history, no latch
+    m.pl4 = 0.0;
+    if (mv.plastic == FX_MAT_MOONEY || mv.plastic == FX_MAT_ARRUDA) { m.harden = mv.plastic; m.group = 3; m.ntab = 0; }  // group 3: no history, no latch
+    if (mv.plastic == FX_MAT_MOHR || mv.plastic == FX_MAT_DRUCKER) {  // groups 4..6: plastic in every piece of history, its own point functions
+      m.plastic = mv.plastic; m.harden = 0; m.group = 4 + mv.nlgeom; m.ntab = 0; m.pl4 = mv.plconst4;
+      n.has_yield = true;
+    }
     m.tab = tab;
   }
   n.mat = n.h_mats[0];
@@ -118,7 +143,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
     std::vector<int32_t> grouped, dups;
     grouped.reserve((size_t)mesh->n_elem);
-    for (int g = 0; g < 4; g++) {
+    for (int g = 0; g < 7; g++) {
       n.grp_off[g].clear();
       n.dup_off[g].clear();
       std::vector<int32_t> doff(1, (int32_t)dups.size());
@@ -152,7 +177,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
       // STF_C3 types: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
       // of all the launches are the `colours` the flags are made for (none of their elements is in colors.dup: they were refused above)
       n.colors.offsets.assign(1, 0);
-      for (int g = 0; g < 4; g++)
+      for (int g = 0; g < 7; g++)
         for (size_t k = 1; k < n.grp_off[g].size(); k++)
           if (n.grp_off[g][k] > n.colors.offsets.back()) n.colors.offsets.push_back(n.grp_off[g][k]);
     }
@@ -245,9 +270,9 @@ static void nl_launch_update_c3_group(fx_context *c, double *qf_out) {
   using El = C3El<ETYPE>;
   hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode,
                      n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce, qf_out, list,
-                     e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+                     e0, (const NlMat *)n.mats, (const int32_t *)n.emat, n.err);
 }
-// the four groups of a context of an STF_C3 type: tangent (update == false) or stress update
+// the seven groups of a context of an STF_C3 type: tangent (update == false) or stress update
 static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool update) {
   with_c3_type(c->nl.etype, [&](auto t) {
     constexpr int ET = decltype(t)::value;
@@ -256,11 +281,17 @@ static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool updat
       nl_launch_update_c3_group<ET, 1>(c, qf_out);
       nl_launch_update_c3_group<ET, 2>(c, qf_out);
       nl_launch_update_c3_group<ET, 3>(c, qf_out);
+      nl_launch_update_c3_group<ET, 4>(c, qf_out);
+      nl_launch_update_c3_group<ET, 5>(c, qf_out);
+      nl_launch_update_c3_group<ET, 6>(c, qf_out);
     } else {
       nl_launch_stiffness_c3_group<ET, 0>(c, Kout);
       nl_launch_stiffness_c3_group<ET, 1>(c, Kout);
       nl_launch_stiffness_c3_group<ET, 2>(c, Kout);
       nl_launch_stiffness_c3_group<ET, 3>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 4>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 5>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 6>(c, Kout);
     }
   });
 }
@@ -301,6 +332,9 @@ static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel ins
   nl_launch_stiffness_group<1>(c, Kout, dup_k);
   nl_launch_stiffness_group<2>(c, Kout, dup_k);
   nl_launch_stiffness_group<3>(c, Kout, dup_k);
+  nl_launch_stiffness_group<4>(c, Kout, dup_k);
+  nl_launch_stiffness_group<5>(c, Kout, dup_k);
+  nl_launch_stiffness_group<6>(c, Kout, dup_k);
   if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
   return 0;
 }
@@ -315,14 +349,14 @@ static void nl_launch_update_group(fx_context *c, double *qf_out) {
     const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;
     hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn,
                        n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce,
-                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat);
+                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat, n.err);
   }
   const std::vector<int32_t> &doff = n.dup_off[G];  // the collapsed elements of the group
   if (!doff.empty())
     hipLaunchKernelGGL((k_nl_update<G>), dim3((doff.back() - doff.front() + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream,
                        doff.back(), n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain,
                        n.fstat, n.istat, n.qforce, qf_out, (const int32_t *)n.colors.dup, doff.front(), (const NlMat *)n.mats,
-                       (const int32_t *)n.emat);
+                       (const int32_t *)n.emat, n.err);
 }
 static void nl_launch_update(fx_context *c, double *qf_out) {
   if (c->nl.etype != 361) { nl_launch_c3(c, nullptr, qf_out, true); return; }
@@ -330,6 +364,22 @@ static void nl_launch_update(fx_context *c, double *qf_out) {
   nl_launch_update_group<1>(c, qf_out);
   nl_launch_update_group<2>(c, qf_out);
   nl_launch_update_group<3>(c, qf_out);
+  nl_launch_update_group<4>(c, qf_out);
+  nl_launch_update_group<5>(c, qf_out);
+  nl_launch_update_group<6>(c, qf_out);
+}
+// The stress update of a context with a Mohr-Coulomb / Drucker-Prager section reports the reference's `stop` statements through the
+// error word: cleared before the launches, read after them (one 4-byte copy; contexts without such a section skip both).
+static int nl_update_err_clear(fx_context *c) {
+  if (c->nl.has_yield) HIP_TRY(hipMemsetAsync(c->nl.err, 0, 4, c->stream));
+  return 0;
+}
+static int nl_update_err_check(fx_context *c) {
+  if (!c->nl.has_yield) return 0;
+  int32_t herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, c->nl.err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return assembly_error(herr);
 }
 
 // fstr_StiffMatrix + fstr_AddBC (fstr_StiffMatrix.f90:18-212, fstr_AddBC.f90:17-190): tangent of the current
@@ -425,9 +475,11 @@ extern "C" int fx_nl_update(fx_context *c, double out[4], float *ms_update) {
   hipLaunchKernelGGL(k_axpy_plain, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, 1.0, c->A.X, n.dunode);
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   HIP_TRY(hipMemsetAsync(n.qforce, 0, (size_t)np3 * 8, c->stream));
+  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   nl_launch_update(c, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  if (int rc = nl_update_err_check(c)) return rc;
   for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45); the flag is the process's, whichever section set it
   if (nl_halo_natural(c, n.qforce)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, n.GL, n.qforce, n.bc_flag, c->A.B);
@@ -466,9 +518,11 @@ extern "C" int fx_nl_update_at(fx_context *c, const double *dunode, double *qfor
   if (dunode) HIP_TRY(hipMemcpyAsync(n.dunode, dunode, np3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   HIP_TRY(hipMemsetAsync(n.qforce, 0, np3, c->stream));
+  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   nl_launch_update(c, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  if (int rc = nl_update_err_check(c)) return rc;
   if (n.mat.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45)
   for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;
   if (qforce) HIP_TRY(hipMemcpyAsync(qforce, n.qforce, np3, hipMemcpyDeviceToHost, c->stream));
@@ -588,11 +642,12 @@ extern "C" int fx_nl_element_tangents(fx_context *c, double *ke) {
   double *d = nullptr;
   const size_t nk = (size_t)(3 * n.nn) * (3 * n.nn) * n.n_elem;
   if (tmp.alloc(&d, nk)) return FX_ERROR_RUNTIME;
+  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, d)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ke, d, nk * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return nl_update_err_check(c);
 }
 extern "C" int fx_nl_element_update(fx_context *c, double *qf) {
   NL_READY("fx_nl_element_update");
@@ -601,8 +656,10 @@ extern "C" int fx_nl_element_update(fx_context *c, double *qf) {
   double *d = nullptr;
   const size_t nqf = (size_t)3 * n.nn * n.n_elem;
   if (tmp.alloc(&d, nqf)) return FX_ERROR_RUNTIME;
+  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   nl_launch_update(c, d);
   HIP_TRY(hipGetLastError());
+  if (int rc = nl_update_err_check(c)) return rc;  // as fx_nl_update: an update that stopped sets no latch
   for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;
   HIP_TRY(hipMemcpyAsync(qf, d, nqf * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -96,7 +96,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
       for (int i = 0; i < 6; i++) E[i] = strain[gp * 6 + i];
       hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
     } else {
-      nl_point_matrix(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm);
+      // (inside `if (active && k < NQ)`: only lanes that own a real point get here, so err needs no `active ?` guard)
+      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm, err);
     }
 #pragma unroll
     for (int i = 0; i < 21; i++) Dsh[el][k][i] = Dm[i];
@@ -208,7 +209,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
                                                              double *__restrict__ fstat, int32_t *__restrict__ istat,
                                                              double *__restrict__ qforce, double *__restrict__ qf_out,
                                                              const int32_t *__restrict__ elem_list, int32_t e0,
-                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
+                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
+                                                             int32_t *__restrict__ err) {
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
   const int64_t t = (int64_t)blockIdx.x * C3El<ETYPE>::BS + threadIdx.x;
@@ -288,7 +290,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
   if (G != 3 && m.plastic) {
     int32_t ist = active ? istat[gp] : 0;      // idle lanes read no state another workgroup may be writing
     double fs = active ? fstat[gp] : 0.0;
-    nl_backward_euler(m, sg, active ? plstrain[gp] : 0.0, ist, fs);
+    nl_backward_euler<nl_group_yield(G)>(m, sg, active ? plstrain[gp] : 0.0, ist, fs, active ? err : nullptr);  // an idle lane's stress is no point's: it reports nothing
     if (active) { istat[gp] = ist; fstat[gp] = fs; }
   }
   if (active) {

@@ -15,8 +15,8 @@
 
 for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
 (fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3),
-with one isotropic (Mises elastoplastic, elastic or hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce) material per
-section.  Everything is resident on the GPU; there is NO CPU
+with one isotropic (elastic; Mises, Mohr-Coulomb or Drucker-Prager elastoplastic: tMaterial.mohr_coulomb / .drucker_prager; or
+hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce) material per section.  Everything is resident on the GPU; there is NO CPU
 fallback.
 """
 import ctypes as C
@@ -29,11 +29,14 @@ from .hecmw import _chk, _ptr, lib
 INFINITE, TOTALLAG, UPDATELAG = 0, 1, 2
 BILINEAR, MULTILINEAR, SWIFT, RAMBERG_OSGOOD = 0, 1, 2, 3
 ELASTIC, MISES, MOONEYRIVLIN, ARRUDABOYCE = 0, 1, 2, 3      # fx_material_view::plastic, the material kind (NEOHOOKE is MOONEYRIVLIN with C01 = 0)
+MOHRCOULOMB, DRUCKERPRAGER = 4, 5                           # !PLASTIC, YIELD=MOHR-COULOMB | DRUCKER-PRAGER
+_PLASTICITY_PI = 3.14159265358979                           # fstr_ctrl_get_PLASTICITY's own PI (fstr_ctrl_material.f90:355)
 
 
 class _MaterialView(C.Structure):
     _fields_ = [("E", C.c_double), ("nu", C.c_double), ("plastic", C.c_int32), ("harden", C.c_int32),
-                ("nlgeom", C.c_int32), ("ntab", C.c_int32), ("plconst", C.c_double * 3), ("tab", C.c_void_p)]
+                ("nlgeom", C.c_int32), ("ntab", C.c_int32), ("plconst", C.c_double * 3), ("tab", C.c_void_p),
+                ("plconst4", C.c_double)]
 
 
 class _StateView(C.Structure):
@@ -46,7 +49,7 @@ class tMaterial:
     SWIFT / RAMBERG-OSGOOD: the three constants) or `table` rows (yield stress, plastic strain) for MULTILINEAR.
     nlgeom_flag defaults to UPDATELAG as !PLASTIC does (KIRCHHOFF -> TOTALLAG, INFINITE -> INFINITE).
     Hyperelastic materials come from the named constructors neohooke / mooney_rivlin / arruda_boyce; they default to TOTALLAG, the
-    only flag the device loop serves for them."""
+    only flag the device loop serves for them.  Mohr-Coulomb and Drucker-Prager materials come from mohr_coulomb / drucker_prager."""
 
     def __init__(self, E, nu, plastic=False, harden=BILINEAR, plconst=(0.0, 0.0, 0.0), table=None, nlgeom_flag=UPDATELAG):
         self.E, self.nu, self.plastic, self.harden = float(E), float(nu), bool(plastic), int(harden)
@@ -54,6 +57,7 @@ class tMaterial:
         self.table = np.zeros((0, 2)) if table is None else np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 2)
         self.nlgeom_flag = int(nlgeom_flag)
         self.kind = MISES if self.plastic else ELASTIC
+        self.plconst4 = 0.0
         if self.plastic and self.harden == MULTILINEAR:
             if self.table.shape[0] < 1 or self.table[0, 1] != 0.0:
                 raise ValueError("Multilinear hardening: First plastic strain must be zero")   # fstr_ctrl_material.f90:416
@@ -81,10 +85,31 @@ class tMaterial:
         """!HYPERELASTIC, TYPE=ARRUDA-BOYCE: mu, lambda_m, D."""
         return cls._hyperelastic(ARRUDABOYCE, (mu, lam, D), nlgeom_flag)
 
+    @classmethod
+    def mohr_coulomb(cls, E, nu, c, phi_deg, H=0.0, nlgeom_flag=UPDATELAG):
+        """!PLASTIC, YIELD=MOHR-COULOMB with the data line c, phi [degrees], H: M_PLCONST1..3 = c, H, phi in radians, computed as
+        fstr_ctrl_get_PLASTICITY does (fstr_ctrl_material.f90:451-469, with its own 15-digit PI), so the material equals the parsed
+        one bit for bit."""
+        m = cls(E, nu, plastic=True, harden=BILINEAR, plconst=(c, H, float(phi_deg) * _PLASTICITY_PI / 180.0), nlgeom_flag=nlgeom_flag)
+        m.kind = MOHRCOULOMB
+        return m
+
+    @classmethod
+    def drucker_prager(cls, E, nu, c, phi_deg, H=0.0, nlgeom_flag=UPDATELAG):
+        """!PLASTIC, YIELD=DRUCKER-PRAGER with the data line c, phi [degrees], H: M_PLCONST1..4 = c, H, eta, xi with
+        eta = 2 sin(phi) / (sqrt(3) (3 + sin(phi))), xi = 6 cos(phi) / (sqrt(3) (3 + sin(phi))) (fstr_ctrl_material.f90:460-465)."""
+        dum = float(phi_deg) * _PLASTICITY_PI / 180.0
+        eta = 2.0 * np.sin(dum) / (np.sqrt(3.0) * (3.0 + np.sin(dum)))
+        xi = 6.0 * np.cos(dum) / (np.sqrt(3.0) * (3.0 + np.sin(dum)))
+        m = cls(E, nu, plastic=True, harden=BILINEAR, plconst=(c, H, float(eta)), nlgeom_flag=nlgeom_flag)
+        m.kind = DRUCKERPRAGER
+        m.plconst4 = float(xi)
+        return m
+
     def view(self):
         kind = self.kind if self.kind >= MOONEYRIVLIN else int(self.plastic)
         v = _MaterialView(self.E, self.nu, kind, self.harden, self.nlgeom_flag, self.table.shape[0],
-                          (C.c_double * 3)(*self.plconst), _ptr(self.table) if self.table.size else None)
+                          (C.c_double * 3)(*self.plconst), _ptr(self.table) if self.table.size else None, self.plconst4)
         v._keep = self.table
         return v
 

@@ -75,7 +75,7 @@ contains
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
     character(len=3) :: tname
-    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises
+    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield
     logical :: opted
     if (decided) then
       fsd_eligible = eligible
@@ -127,11 +127,20 @@ contains
     enddo
     n_hyper = 0
     n_mises = 0
+    n_yield = 0
     do i = 1, size(fstrSOLID%materials)
       if (.not. material_covered(fstrSOLID%materials(i))) return
       if (is_hyperelastic(fstrSOLID%materials(i)%mtype)) n_hyper = n_hyper + 1
-      if (fstrSOLID%materials(i)%mtype /= -1 .and. isElastoplastic(fstrSOLID%materials(i)%mtype)) n_mises = n_mises + 1
+      if (fstrSOLID%materials(i)%mtype /= -1 .and. isElastoplastic(fstrSOLID%materials(i)%mtype)) then
+        n_mises = n_mises + 1      ! every elastoplastic material, whatever its yield function: what sets MatlMatrix's saved flag
+        if (getYieldFunction(fstrSOLID%materials(i)%mtype) /= 0) n_yield = n_yield + 1
+      endif
     enddo
+    if (n_yield > 0) then
+      ! YIELD=MOHR-COULOMB / DRUCKER-PRAGER decks opt in: no end-to-end time against the host loops is on record (DESIGN.md section 7)
+      call get_environment_variable('HECMW_GPU_NL_YIELD', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+    endif
     if (n_hyper > 0) then
       ! !HYPERELASTIC decks opt in (no end-to-end time against the host loops is on record); beside a plastic material they keep the
       ! host loops: after the first plastic update MatlMatrix's saved flag sends every material to calElasticMatrix (DESIGN.md section 8)
@@ -149,11 +158,13 @@ contains
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//tname//'); '// &
         'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
       if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
+      if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
       return
     endif
     if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
       'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
     if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
+    if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
   end function fsd_eligible
 
   !> Where fstr_UpdateNewton of an eligible linear static deck runs.  HECMW_GPU_UPDATE=0: the host, =1: the device.  Unset: the
@@ -381,8 +392,17 @@ contains
     if (m%mtype == ELASTIC) then
       material_covered = .true.
     else if (isElastoplastic(m%mtype)) then
-      if (getYieldFunction(m%mtype) /= 0) return         ! Mises
       if (isKinematicHarden(m%mtype)) return
+      if (getYieldFunction(m%mtype) == 1 .or. getYieldFunction(m%mtype) == 2) then
+        ! Mohr-Coulomb, Drucker-Prager: the card forces linear hardening (fstr_ctrl_material.f90:452); the constants at which the
+        ! return would stop are left to the host loops
+        if (getHardenType(m%mtype) /= 0) return
+        if (getYieldFunction(m%mtype) == 1 .and. cos(m%variables(M_PLCONST3)) == 0.d0) return
+        if (getYieldFunction(m%mtype) == 2 .and. m%variables(M_PLCONST4) == 0.d0) return
+        material_covered = .true.
+        return
+      endif
+      if (getYieldFunction(m%mtype) /= 0) return         ! Mises
       if (getHardenType(m%mtype) < 0 .or. getHardenType(m%mtype) > 3) return
       material_covered = .true.
     else if (is_hyperelastic(m%mtype)) then
@@ -438,7 +458,7 @@ contains
     tabs = 0.d0
     do i = 1, nmat
       mats(i)%E = 1.d0; mats(i)%nu = 0.d0; mats(i)%plastic = 0; mats(i)%harden = 0; mats(i)%nlgeom = 0; mats(i)%ntab = 0
-      mats(i)%plconst = 0.d0; mats(i)%tab = c_null_ptr
+      mats(i)%plconst = 0.d0; mats(i)%tab = c_null_ptr; mats(i)%plconst4 = 0.d0
       if (fstrSOLID%materials(i)%mtype == -1) cycle
       mats(i)%E = fstrSOLID%materials(i)%variables(M_YOUNGS)
       mats(i)%nu = fstrSOLID%materials(i)%variables(M_POISSON)
@@ -452,6 +472,9 @@ contains
       endif
       if (isElastoplastic(fstrSOLID%materials(i)%mtype)) then
         mats(i)%plastic = 1
+        if (getYieldFunction(fstrSOLID%materials(i)%mtype) == 1) mats(i)%plastic = 4      ! Mohr-Coulomb: c, H, phi
+        if (getYieldFunction(fstrSOLID%materials(i)%mtype) == 2) mats(i)%plastic = 5      ! Drucker-Prager: c, H, eta, xi
+        mats(i)%plconst4 = fstrSOLID%materials(i)%variables(M_PLCONST4)
         mats(i)%harden = getHardenType(fstrSOLID%materials(i)%mtype)
         mats(i)%plconst(1) = fstrSOLID%materials(i)%variables(M_PLCONST1)
         mats(i)%plconst(2) = fstrSOLID%materials(i)%variables(M_PLCONST2)

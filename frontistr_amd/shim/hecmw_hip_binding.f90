@@ -54,6 +54,7 @@ module hecmw_hip_binding
     integer(c_int32_t) :: plastic, harden, nlgeom, ntab
     real(c_double) :: plconst(3)
     type(c_ptr) :: tab
+    real(c_double) :: plconst4                   ! M_PLCONST4 (xi of Drucker-Prager), appended: the older members keep their offsets
   end type fx_material_view
 
   type, bind(C) :: fx_nl_state_view

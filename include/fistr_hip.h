@@ -360,15 +360,29 @@ int fx_update_groups_linear_thermal(fx_context *ctx, int32_t n_node, const doubl
  * fx_nl_init* refuses with FX_ERROR_UNSUPPORTED: kind 2 / 3 with another nlgeom (CAUCHY -> UPDATELAG is a different algorithm in the
  * reference), plconst[2] == 0 ("cannot deal with incompressible"), Arruda-Boyce with plconst[1] == 0, and a Mises and a hyperelastic
  * material in one context.  A hyperelastic section beside ELASTIC sections of any NLGEOM flag is served.  A kind outside 0..3 is
- * refused too (before the kinds 2 and 3 existed, every non-zero value was read as Mises). */
+ * refused too (before the kinds 2 and 3 existed, every non-zero value was read as Mises).
+ *
+ * Mohr-Coulomb and Drucker-Prager (!PLASTIC, YIELD=MOHR-COULOMB | DRUCKER-PRAGER; Elastoplastic.f90 yield types 1 and 2, restated as
+ * written in csrc/fx_yield.h): kind 4 with plconst = c, H, phi in radians, and kind 5 with plconst = c, H, eta and plconst4 = xi --
+ * M_PLCONST1..4 as fstr_ctrl_get_PLASTICITY leaves them (fstr_ctrl_material.f90:451-469).  Hardening is the linear law c + H p; harden
+ * must be 0 (the card forces the digit), any of the three nlgeom flags is served.  Both are "plastic" for every piece of history
+ * (plstrain, fstat, istat, commit, snapshot) and for the latch: after the first stress update every tangent is the elastic one.
+ * Refused with FX_ERROR_UNSUPPORTED: cos(phi) == 0, xi == 0, harden != 0, a kind above 5, and kind 4 / 5 beside a hyperelastic
+ * material (as Mises is); beside Mises or ELASTIC sections they are served.  The reference's `stop` statements of these branches --
+ * `Math Error in Mohr-Coulomb calculation`, `Math error in return mapping`, `Jacobi iteration unable to converge` -- set the
+ * context's device error word: fx_nl_stiffness, fx_nl_update, their _at forms and the element-level entry points then return
+ * FX_ERROR_RUNTIME with that text.
+ * plconst4 was appended at the end of the struct: every older member keeps its offset, the struct grew from 56 to 64 bytes. */
 typedef struct fx_material_view { /* tMaterial after fstr_ctrl_get_ELASTICITY/_PLASTICITY (fstr_ctrl_material.f90:60-106, :341-480) */
   double E, nu;         /* M_YOUNGS, M_POISSON */
-  int32_t plastic;      /* material kind.  0: mtype ELASTIC; 1: elastoplastic, Mises; 2: Neo-Hooke / Mooney-Rivlin; 3: Arruda-Boyce */
+  int32_t plastic;      /* material kind.  0: mtype ELASTIC; 1: elastoplastic, Mises; 2: Neo-Hooke / Mooney-Rivlin; 3: Arruda-Boyce;
+                         * 4: elastoplastic, Mohr-Coulomb; 5: elastoplastic, Drucker-Prager */
   int32_t harden;       /* fifth digit of mtype: 0 BILINEAR 1 MULTILINEAR 2 SWIFT 3 RAMBERG-OSGOOD */
   int32_t nlgeom;       /* nlgeom_flag: 0 INFINITE 1 TOTALLAG 2 UPDATELAG */
   int32_t ntab;         /* MULTILINEAR: rows of the MC_YIELD table */
   double plconst[3];    /* M_PLCONST1..3 */
   const double *tab;    /* ntab rows (yield stress, plastic strain) */
+  double plconst4;      /* M_PLCONST4: xi of Drucker-Prager; not read for another kind */
 } fx_material_view;
 typedef struct fx_nl_state_view { /* host arrays, any may be NULL (skipped).  tGaussStatus members (mechgauss.f90:13-22) */
   double *stress, *strain, *stress_bak, *strain_bak; /* n_elem*nq*6 (nq = 8 at 361) */

@@ -21,6 +21,16 @@ NLSTATIC decks of the STF_C3 types (--etype 341|342|351|352|362 without --linear
                                                              --two-sections: MAT2 is then ELASTIC 2.5 / 0.3, a material as soft as MAT1.
                                                              The fourth positional argument after DIR N, STRAIN, is the stretch to ask for
                                                              (rubber takes 0.1 where the steel decks take 0.005).
+  --nl-material drucker|mohr                                 MAT1: `!PLASTIC, YIELD=DRUCKER-PRAGER` or `YIELD=MOHR-COULOMB` on ELASTIC 206900 / 0.29
+                                                             with the data line c, phi, H = 300, 20 degrees, 2000 (Drucker-Prager) or
+                                                             300, 5 degrees, 20000 (Mohr-Coulomb: at 20 degrees and H = 2000 the reference
+                                                             program itself stops converging in the second sub-step); updated Lagrange.  Also for
+                                                             the plain TYPE=361 cube, also with --two-sections: MAT2 is then Mises BILINEAR
+                                                             (206900 / 0.29, 450, 2000), so that two yield functions share the mesh.
+                                                             These decks ask the linear solver for 1e-12 where the others ask for 1e-8: after
+                                                             the first plastic update every tangent is the elastic one, the sub-steps take 10
+                                                             to 40 Newton iterations to CONVERG = 1e-3, and what the linear solves leave
+                                                             unconverged stays in the printed stresses (2e-4 of 1.5 at 1e-8).
 --thermal (with --linear): a thermal-stress deck.  `!REFTEMP 20`, `!INITIAL CONDITION, TYPE=TEMPERATURE` (ALL, 25) in the mesh file,
 `!TEMPERATURE` on the node groups FIX (35) and TOP (120) -- every other node keeps the initial condition's, so the temperature
 varies inside the elements -- and `!EXPANSION_COEFF` 1.2e-5 for MAT1, 2.3e-5 for MAT2."""
@@ -48,14 +58,15 @@ if "--mixed" in sys.argv:
 nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
 if "--nl-material" in sys.argv:
     k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
-    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul", "neohooke", "mooney", "arruda"):
-        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl, elastic_ul, neohooke, mooney or arruda, without --linear")
+    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul", "neohooke", "mooney", "arruda", "drucker", "mohr"):
+        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl, elastic_ul, neohooke, mooney, arruda, drucker or mohr, without --linear")
 hyper = nlmat in ("neohooke", "mooney", "arruda")
+yieldf = nlmat in ("drucker", "mohr")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear and etype == 361 and not hyper:
-        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or a hyperelastic --nl-material")
+    if not linear and etype == 361 and not hyper and not yieldf:
+        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or a hyperelastic or drucker / mohr --nl-material")
 thermal = "--thermal" in sys.argv
 if thermal:
     sys.argv.remove("--thermal")
@@ -162,7 +173,14 @@ NL_MATERIALS = {
     "neohooke": "!HYPERELASTIC, TYPE=NEOHOOKE\n 0.1486, 0.0789\n",
     "mooney": "!HYPERELASTIC, TYPE=MOONEY-RIVLIN\n 0.1486, 0.4849, 0.0789\n",
     "arruda": "!HYPERELASTIC, TYPE=ARRUDA-BOYCE\n 0.71, 1.7029, 0.1408\n",
+    "drucker": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=DRUCKER-PRAGER\n 300.0, 20.0, 2000.0\n",
+    "mohr": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MOHR-COULOMB\n 300.0, 5.0, 20000.0\n",
 }
+MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n"
+if hyper:
+    MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 2.5, 0.3\n"
+if yieldf:
+    MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MISES, HARDEN=BILINEAR\n 450.0, 2000.0\n"
 with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
     if not linear:
       fh.write("""!VERSION
@@ -179,10 +197,10 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
 %s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  5000, 1
- 1.0e-8, 1.0, 0.0
+ %s, 1.0, 0.0
 !END
 """ % (strain * n, 0.2 * strain * n, nsub, NL_MATERIALS[nlmat],
-       ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 2.5, 0.3\n" if hyper else "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n") if two else "", method, precond))
+       MAT2 if two else "", method, precond, "1.0e-12" if yieldf else "1.0e-8"))
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
