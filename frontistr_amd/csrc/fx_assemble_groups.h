@@ -41,10 +41,10 @@ static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group
   return 0;
 }
 
-// What both entry points refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
+// What the entry points that take groups (these, and fx_nl_init_groups) refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
 // material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
 static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                        int32_t n_mat, const double *E, const double *nu) {
+                        int32_t n_mat, bool have_mats) {
   if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
   for (int32_t g = 0; g < n_group; g++) {
     if (c3_nodes(groups[g].etype) == 0)
@@ -54,7 +54,7 @@ static int check_groups(const char *who, int32_t n_node, const double *coord, in
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
   }
   if (n_node < 1 || !coord) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
-  if (n_mat < 1 || !E || !nu) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
+  if (n_mat < 1 || !have_mats) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
     if (G.n_elem < 0 || (G.n_elem > 0 && !G.conn)) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: connectivity missing", (int)g + 1);
@@ -123,7 +123,7 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
                                   const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
   const char *who = "fx_assemble_groups";
   if (!c) { g_fx_error = "fx_assemble_groups: null argument"; return FX_ERROR_RUNTIME; }
-  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E, nu)) return rc;
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
   if (n_group == 1) {  // the single-type entry points, and their cache (c->asm_colors)
     const fx_elem_group &G = groups[0];
     const fx_mesh_view mesh = {n_node, G.n_elem, coord, G.conn};
@@ -204,7 +204,7 @@ static int update_groups_linear_impl(const char *who, fx_context *c, int32_t n_n
                                      const double **strain, const double **stress, double *qforce, float *ms_kernel,
                                      const fx_thermal_view *thermal) {
   if (!c || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E, nu)) return rc;
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
   if (n_group == 1) {
     const fx_elem_group &G = groups[0];
     const fx_mesh_view mesh = {n_node, G.n_elem, coord, G.conn};
@@ -285,7 +285,7 @@ extern "C" int fx_thermal_load_groups(fx_context *c, int32_t n_node, const doubl
                                       double *load_inout, float *ms_kernel) {
   const char *who = "fx_thermal_load_groups";
   if (!c || !load_inout) { g_fx_error = "fx_thermal_load_groups: null argument"; return FX_ERROR_RUNTIME; }
-  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E, nu)) return rc;
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
   if (int rc = thermal_view_ok(who, thermal)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   DevScratch tmp;

@@ -186,7 +186,7 @@ static_assert(sizeof(NlMat) == 72 && offsetof(NlMat, plastic) == 40 && offsetof(
               "NlMat is an argument of every element kernel: every member keeps the offset it had before the hyperelastic kinds; the "
               "struct grew from 64 to 72 bytes by M_PLCONST4 at its end, which only Drucker-Prager reads");
 
-// fstr_solid members of the nonlinear static loop (m_fstr.f90:560-700) for one TYPE=361 B-bar group, resident.
+// fstr_solid members of the nonlinear static loop (m_fstr.f90:560-700), resident.
 // Elements grouped by colour (fxo::color_elements): the atomic-free scatter of the stiffness kernels.
 struct ElemColors {
   int32_t n_elem = 0;
@@ -210,26 +210,40 @@ struct AsmGroups {
   bool first_write = false;  // the maps carry those flags and every block of the profile is covered: no clearing
 };
 
-struct NlDev {
-  bool ready = false;
-  int32_t etype = 361;                // element type of the context: 361 (B-bar, fx_nl_init) or 341 / 342 (fx_nl_init_c3)
+// One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
+// conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
+struct NlPart {
+  int32_t etype = 361;                // 361 (B-bar), 341, 342, 351, 352 or 362
   int nn = 8, nq = 8;                 // its nodes and quadrature points per element
+  int32_t n_elem = 0;
+  int64_t elem_off = 0, pt_off = 0;   // elements / quadrature points of the parts before this one
+  size_t k_off = 0, qf_off = 0;       // doubles of the parts before this one in the element outputs ((3 nn)^2 and 3 nn per element)
+  int32_t *conn = nullptr;            // device, nn * n_elem
+  int32_t *emat = nullptr;            // device, 1-based material id per element; null with one material
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
   std::vector<int32_t> grp_off[7];    // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager): positions of its colours in order (+ end)
   std::vector<int32_t> dup_off[7];    // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
-  bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements): one range per group, fp64 atomics
+  bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements) or FX_ASM_ATOMIC=1: one range per group, fp64 atomics
+  int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
+};
+
+// The context of the nonlinear static loop: element groups (parts) of the six solid types over one set of nodes, materials and
+// per-point arrays.  fx_nl_init / _sections / _c3 / _type make the one-part case, fx_nl_init_groups any number of parts.
+struct NlDev {
+  bool ready = false;
+  std::vector<NlPart> parts;          // in the order given; the per-point arrays and the element outputs hold them one after the other
+  bool first_write = false;           // every part's map carries first-write flags in the launch order of ALL parts and every block is covered: no clearing
   bool has_yield = false;             // a Mohr-Coulomb or Drucker-Prager section: the stress update reports through the error word too
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material
-  int32_t *emat = nullptr;            // device, 1-based material id per element; null with one material
   std::vector<NlMat> h_mats;
   std::vector<double *> tabs;         // device tables of the materials
-  int32_t n_elem = 0, n_bc = 0;
-  int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
+  int32_t n_elem = 0, n_bc = 0;       // n_elem: all parts'
+  int64_t n_pt = 0;                   // quadrature points of all parts
+  size_t n_k = 0, n_qf = 0;           // doubles of the element outputs of all parts
   NlMat mat = {};
   double *tab = nullptr;
   double *coord = nullptr;
-  int32_t *conn = nullptr;
   // tGaussStatus (mechgauss.f90:13-22), flat over (element, quadrature point)
   double *stress = nullptr, *strain = nullptr, *stress_bak = nullptr, *strain_bak = nullptr;  // 6 per point
   double *plstrain = nullptr, *fstat = nullptr;                                               // 1 per point

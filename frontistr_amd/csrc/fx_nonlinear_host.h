@@ -4,21 +4,23 @@
 
 static void nl_free(fx_context *c) {
   NlDev &n = c->nl;
-  dev_free(n.tab); dev_free(n.coord); dev_free(n.conn);
+  dev_free(n.tab); dev_free(n.coord);
+  for (NlPart &p : n.parts) {
+    dev_free(p.conn); dev_free(p.emat);
+    elem_colors_free(p.colors);
+  }
   dev_free(n.stress); dev_free(n.strain); dev_free(n.stress_bak); dev_free(n.strain_bak);
   dev_free(n.plstrain); dev_free(n.fstat); dev_free(n.istat);
   dev_free(n.unode); dev_free(n.dunode); dev_free(n.qforce); dev_free(n.GL);
   dev_free(n.bc_flag); dev_free(n.bc_val); dev_free(n.bc_node); dev_free(n.bc_dof); dev_free(n.bc_v); dev_free(n.err);
-  dev_free(n.colors.order); dev_free(n.colors.pos); dev_free(n.colors.dup);
-  dev_free(n.mats); dev_free(n.emat);
+  dev_free(n.mats);
   dev_free(n.bk_stress); dev_free(n.bk_strain); dev_free(n.bk_stress_bak); dev_free(n.bk_strain_bak);
   dev_free(n.bk_plstrain); dev_free(n.bk_fstat); dev_free(n.bk_istat);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
   n = NlDev();
 }
 
-// fstr_solid / tGaussStatus set-up for one TYPE=361 B-bar group with one material (fstr_setup.f90:325-400,
-// fstr_init_gauss mechgauss.f90:37-71): zero state, zero displacement.
+// What the device loop serves of one material; everything else is refused by name
 static int nl_check_material(const fx_material_view *mat) {
   if (mat->plastic == FX_MAT_MOONEY || mat->plastic == FX_MAT_ARRUDA) {  // E, nu, harden, tab are not read
     if (mat->nlgeom != 1)
@@ -53,54 +55,117 @@ static int nl_check_material(const fx_material_view *mat) {
   return 0;
 }
 
-static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                          const int32_t *elem_mat, int32_t etype, const char *who) {
-  HIP_TRY(hipSetDevice(c->device));
-  const int nn = c3_nodes(etype), nq = c3_points(etype);
-  if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
-  if (mesh->n_node != c->A.NP) { g_fx_error = "fx_nl_init: mesh/profile size mismatch"; return FX_ERROR_RUNTIME; }
-  if (n_mat < 1 || !mats || (n_mat > 1 && !elem_mat)) { g_fx_error = "fx_nl_init: materials missing"; return FX_ERROR_RUNTIME; }
+// nl_check_material for every material, and the refusal of an elastoplastic beside a hyperelastic one, over the whole context
+static int nl_check_materials(const char *who, int32_t n_mat, const fx_material_view *mats) {
   for (int32_t k = 0; k < n_mat; k++)
     if (int e = nl_check_material(&mats[k])) return e;
-  {
-    // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
-    // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
-    bool mises = false, hyper = false, yield = false;
-    for (int32_t k = 0; k < n_mat; k++) {
-      mises |= mats[k].plastic == 1;
-      hyper |= mats[k].plastic == FX_MAT_MOONEY || mats[k].plastic == FX_MAT_ARRUDA;
-      yield |= mats[k].plastic == FX_MAT_MOHR || mats[k].plastic == FX_MAT_DRUCKER;
-    }
-    if (mises && hyper)
-      return fx_fail(who, FX_ERROR_UNSUPPORTED,
-                     "a Mises and a hyperelastic material in one context: after the first plastic update the reference takes the elastic "
-                     "matrix of every material, which a hyperelastic one does not define");
-    if (yield && hyper)
-      return fx_fail(who, FX_ERROR_UNSUPPORTED,
-                     "a Mohr-Coulomb / Drucker-Prager and a hyperelastic material in one context: after the first plastic update the "
-                     "reference takes the elastic matrix of every material, which a hyperelastic one does not define");
+  // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
+  // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
+  bool mises = false, hyper = false, yield = false;
+  for (int32_t k = 0; k < n_mat; k++) {
+    mises |= mats[k].plastic == 1;
+    hyper |= mats[k].plastic == FX_MAT_MOONEY || mats[k].plastic == FX_MAT_ARRUDA;
+    yield |= mats[k].plastic == FX_MAT_MOHR || mats[k].plastic == FX_MAT_DRUCKER;
   }
-  if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
-  for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
-    if (mesh->conn[k] < 1 || mesh->conn[k] > mesh->n_node) { g_fx_error = "fx_nl_init: node id out of range"; return FX_ERROR_RUNTIME; }
-  if (n_mat > 1)
-    for (int32_t e = 0; e < mesh->n_elem; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
-  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;
+  if (mises && hyper)
+    return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                   "a Mises and a hyperelastic material in one context: after the first plastic update the reference takes the elastic "
+                   "matrix of every material, which a hyperelastic one does not define");
+  if (yield && hyper)
+    return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                   "a Mohr-Coulomb / Drucker-Prager and a hyperelastic material in one context: after the first plastic update the "
+                   "reference takes the elastic matrix of every material, which a hyperelastic one does not define");
+  return 0;
+}
+
+// One element group as the caller holds it (checked): what a part is made from
+struct NlPartIn {
+  int32_t etype, n_elem;
+  const int32_t *conn, *elem_mat;  // elem_mat: null with one material
+};
+
+// Element lists of one part: grouped by the NLGEOM flag of the element's material, hyperelastic ones apart (one kernel instantiation
+// per group), inside a group colour by colour (fx_order.cpp: color_elements) for the atomic-free scatter
+static int nl_part_lists(fx_context *c, NlPart &p, const NlPartIn &in, int32_t n_node) {
+  const NlDev &n = c->nl;
+  const int nn = p.nn;
+  static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
+  std::vector<int32_t> order, off;
+  const bool coloured = !force_atomic && fxo::color_elements(in.n_elem, nn, in.conn, n_node, order, off);
+  if (!coloured) {
+    order.resize((size_t)in.n_elem);
+    for (int32_t e = 0; e < in.n_elem; e++) order[e] = e;
+    off = {0, in.n_elem};
+  }
+  p.scatter_atomic = !coloured;
+  // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
+  std::vector<int32_t> grouped, dups;
+  grouped.reserve((size_t)in.n_elem);
+  for (int g = 0; g < 7; g++) {
+    p.grp_off[g].clear();
+    p.dup_off[g].clear();
+    std::vector<int32_t> doff(1, (int32_t)dups.size());
+    bool any = false;
+    for (size_t k = 0; k + 1 < off.size(); k++) {
+      const size_t before = grouped.size();
+      for (int32_t q = off[k]; q < off[k + 1]; q++) {
+        const int32_t e = order[q];
+        const int group = n.h_mats[in.elem_mat ? in.elem_mat[e] - 1 : 0].group;
+        if (group == g) (coloured && names_a_node_twice(in.conn + (size_t)nn * e, nn) ? dups : grouped).push_back(e);
+      }
+      doff.push_back((int32_t)dups.size());
+      if (grouped.size() > before || any) {
+        if (!any) p.grp_off[g].push_back((int32_t)before);
+        any = true;
+        p.grp_off[g].push_back((int32_t)grouped.size());
+      }
+    }
+    if (doff.back() > doff.front()) p.dup_off[g] = doff;
+  }
+  p.n_dup = (int32_t)dups.size();
+  if (dev_alloc(&p.colors.order, std::max<size_t>(grouped.size(), 1)) || (p.n_dup > 0 && dev_alloc(&p.colors.dup, dups.size())))
+    return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpyAsync(p.colors.order, grouped.data(), grouped.size() * 4, hipMemcpyHostToDevice, c->stream));
+  if (p.n_dup > 0) HIP_TRY(hipMemcpyAsync(p.colors.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // grouped and dups are host temporaries
+  p.colors.n_elem = in.n_elem;
+  p.colors.etype = p.etype;
+  p.colors.offsets = {0, in.n_elem};       // marks the lists as built (ensure_scatter_map)
+  return 0;
+}
+
+// The context for checked parts (none empty) and checked materials: the single-type entry points pass one part
+static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, const std::vector<NlPartIn> &in, int32_t n_mat,
+                         const fx_material_view *mats) {
   nl_free(c);
   NlDev &n = c->nl;
-  n.n_elem = mesh->n_elem;
   n.n_mat = n_mat;
-  n.etype = etype; n.nn = nn; n.nq = nq;
-  const size_t np3 = (size_t)3 * c->A.NP, npt = (size_t)nq * mesh->n_elem, ncn = (size_t)nn * mesh->n_elem;
-  if (dev_alloc(&n.coord, np3) || dev_alloc(&n.conn, ncn) || dev_alloc(&n.stress, 6 * npt) || dev_alloc(&n.strain, 6 * npt) ||
+  n.parts.resize(in.size());
+  for (size_t i = 0; i < in.size(); i++) {
+    NlPart &p = n.parts[i];
+    p.etype = in[i].etype; p.nn = c3_nodes(p.etype); p.nq = c3_points(p.etype);
+    p.n_elem = in[i].n_elem;
+    p.elem_off = n.n_elem; p.pt_off = n.n_pt; p.k_off = n.n_k; p.qf_off = n.n_qf;
+    if ((int64_t)n.n_elem + p.n_elem > INT32_MAX) { g_fx_error = "fx_nl_init: more than 2^31 - 1 elements"; return FX_ERROR_RUNTIME; }
+    n.n_elem += p.n_elem;
+    n.n_pt += (int64_t)p.nq * p.n_elem;
+    n.n_k += (size_t)(3 * p.nn) * (3 * p.nn) * p.n_elem;
+    n.n_qf += (size_t)3 * p.nn * p.n_elem;
+  }
+  const size_t np3 = (size_t)3 * c->A.NP, npt = (size_t)n.n_pt;
+  if (dev_alloc(&n.coord, np3) || dev_alloc(&n.stress, 6 * npt) || dev_alloc(&n.strain, 6 * npt) ||
       dev_alloc(&n.stress_bak, 6 * npt) || dev_alloc(&n.strain_bak, 6 * npt) || dev_alloc(&n.plstrain, npt) ||
       dev_alloc(&n.fstat, npt) || dev_alloc(&n.istat, npt) || dev_alloc(&n.unode, np3) || dev_alloc(&n.dunode, np3) ||
       dev_alloc(&n.qforce, np3) || dev_alloc(&n.GL, np3) || dev_alloc(&n.bc_flag, np3) || dev_alloc(&n.bc_val, np3) ||
       dev_alloc(&n.err, 1))
     return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(n.coord, mesh->coord, np3 * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(n.conn, mesh->conn, ncn * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(n.coord, coord, np3 * 8, hipMemcpyHostToDevice, c->stream));
+  for (size_t i = 0; i < in.size(); i++) {
+    NlPart &p = n.parts[i];
+    const size_t ncn = (size_t)p.nn * p.n_elem;
+    if (dev_alloc(&p.conn, ncn)) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(p.conn, in[i].conn, ncn * 4, hipMemcpyHostToDevice, c->stream));
+  }
   // materials: one NlMat per section, hardening tables on the device
   n.h_mats.resize((size_t)n_mat);
   for (int32_t k = 0; k < n_mat; k++) {
@@ -124,67 +189,34 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   n.mat = n.h_mats[0];
   n.tab = nullptr;
   if (n_mat > 1) {
-    if (dev_alloc(&n.mats, (size_t)n_mat) || dev_alloc(&n.emat, (size_t)mesh->n_elem)) return FX_ERROR_RUNTIME;
+    if (dev_alloc(&n.mats, (size_t)n_mat)) return FX_ERROR_RUNTIME;
     HIP_TRY(hipMemcpyAsync(n.mats, n.h_mats.data(), (size_t)n_mat * sizeof(NlMat), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(n.emat, elem_mat, (size_t)mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
+    for (size_t i = 0; i < in.size(); i++) {
+      NlPart &p = n.parts[i];
+      if (dev_alloc(&p.emat, (size_t)p.n_elem)) return FX_ERROR_RUNTIME;
+      HIP_TRY(hipMemcpyAsync(p.emat, in[i].elem_mat, (size_t)p.n_elem * 4, hipMemcpyHostToDevice, c->stream));
+    }
   }
-  // element lists: grouped by the NLGEOM flag of the element's material, hyperelastic ones apart (one kernel instantiation per group), inside a group
-  // colour by colour (fx_order.cpp: color_elements) for the atomic-free scatter
-  {
-    static const bool force_atomic = getenv("FX_ASM_ATOMIC") && atoi(getenv("FX_ASM_ATOMIC")) != 0;
-    std::vector<int32_t> order, off;
-    const bool coloured = !force_atomic && fxo::color_elements(mesh->n_elem, nn, mesh->conn, mesh->n_node, order, off);
-    if (!coloured) {
-      order.resize((size_t)mesh->n_elem);
-      for (int32_t e = 0; e < mesh->n_elem; e++) order[e] = e;
-      off = {0, mesh->n_elem};
-    }
-    n.scatter_atomic = !coloured;
-    // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
-    std::vector<int32_t> grouped, dups;
-    grouped.reserve((size_t)mesh->n_elem);
-    for (int g = 0; g < 7; g++) {
-      n.grp_off[g].clear();
-      n.dup_off[g].clear();
-      std::vector<int32_t> doff(1, (int32_t)dups.size());
-      bool any = false;
-      for (size_t k = 0; k + 1 < off.size(); k++) {
-        const size_t before = grouped.size();
-        for (int32_t q = off[k]; q < off[k + 1]; q++) {
-          const int32_t e = order[q];
-          const int group = n.h_mats[n_mat > 1 ? elem_mat[e] - 1 : 0].group;
-          if (group == g) (coloured && names_a_node_twice(mesh->conn + (size_t)nn * e, nn) ? dups : grouped).push_back(e);
-        }
-        doff.push_back((int32_t)dups.size());
-        if (grouped.size() > before || any) {
-          if (!any) n.grp_off[g].push_back((int32_t)before);
-          any = true;
-          n.grp_off[g].push_back((int32_t)grouped.size());
-        }
-      }
-      if (doff.back() > doff.front()) n.dup_off[g] = doff;
-    }
-    n.n_dup = (int32_t)dups.size();
-    if (dev_alloc(&n.colors.order, std::max<size_t>(grouped.size(), 1)) || (n.n_dup > 0 && dev_alloc(&n.colors.dup, dups.size())))
-      return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(n.colors.order, grouped.data(), grouped.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (n.n_dup > 0) HIP_TRY(hipMemcpyAsync(n.colors.dup, dups.data(), dups.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // grouped and dups are host temporaries
-    n.colors.n_elem = mesh->n_elem;
-    n.colors.etype = etype;
-    n.colors.offsets = {0, mesh->n_elem};       // marks the lists as built (ensure_scatter_map)
-    if (etype != 361 && coloured) {
-      // STF_C3 types: first-write flags in the order of the launches (group after group, colour after colour): the boundaries
-      // of all the launches are the `colours` the flags are made for (none of their elements is in colors.dup: they were refused above)
-      n.colors.offsets.assign(1, 0);
+  bool flags = true;  // STF_C3 parts only, all coloured: k_nl_stiffness<G> (361) does not read first-write flags
+  for (size_t i = 0; i < in.size(); i++) {
+    if (int rc = nl_part_lists(c, n.parts[i], in[i], n_node)) return rc;
+    flags &= n.parts[i].etype != 361 && !n.parts[i].scatter_atomic;
+  }
+  std::vector<FirstWriteGroup> fw;
+  for (NlPart &p : n.parts) {
+    if (flags) {
+      // first-write flags in the order of the launches (part after part, group after group, colour after colour): the boundaries
+      // of all the launches are the `colours` the flags are made for (none of the elements is in colors.dup: they were refused)
+      p.colors.offsets.assign(1, 0);
       for (int g = 0; g < 7; g++)
-        for (size_t k = 1; k < n.grp_off[g].size(); k++)
-          if (n.grp_off[g][k] > n.colors.offsets.back()) n.colors.offsets.push_back(n.grp_off[g][k]);
+        for (size_t k = 1; k < p.grp_off[g].size(); k++)
+          if (p.grp_off[g][k] > p.colors.offsets.back()) p.colors.offsets.push_back(p.grp_off[g][k]);
     }
-    if (etype != 361 && coloured ? ensure_scatter_map_flagged(c, n.colors, mesh->n_elem, n.conn, etype)
-                                 : ensure_scatter_map(c, n.colors, mesh->n_elem, n.conn, etype))
-      return FX_ERROR_RUNTIME;
+    if (ensure_scatter_map(c, p.colors, p.n_elem, p.conn, p.etype)) return FX_ERROR_RUNTIME;
+    fw.push_back({&p.colors, p.conn});
   }
+  // otherwise unflagged maps in every part and the matrix is cleared once: never both uncleared and unflagged
+  if (flags && build_first_write(c, fw, &n.first_write)) return FX_ERROR_RUNTIME;
   for (double *p : {n.stress, n.strain, n.stress_bak, n.strain_bak}) HIP_TRY(hipMemsetAsync(p, 0, 6 * npt * 8, c->stream));
   for (double *p : {n.plstrain, n.fstat}) HIP_TRY(hipMemsetAsync(p, 0, npt * 8, c->stream));
   HIP_TRY(hipMemsetAsync(n.istat, 0, npt * 4, c->stream));
@@ -194,6 +226,26 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
   n.latch = 0;
   n.ready = true;
   return 0;
+}
+
+// fstr_solid / tGaussStatus set-up for one group of one type (fstr_setup.f90:325-400, fstr_init_gauss mechgauss.f90:37-71): zero
+// state, zero displacement.
+static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
+                          const int32_t *elem_mat, int32_t etype, const char *who) {
+  HIP_TRY(hipSetDevice(c->device));
+  const int nn = c3_nodes(etype);
+  if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
+  if (mesh->n_node != c->A.NP) { g_fx_error = "fx_nl_init: mesh/profile size mismatch"; return FX_ERROR_RUNTIME; }
+  if (n_mat < 1 || !mats || (n_mat > 1 && !elem_mat)) { g_fx_error = "fx_nl_init: materials missing"; return FX_ERROR_RUNTIME; }
+  if (int e = nl_check_materials(who, n_mat, mats)) return e;
+  if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
+  for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
+    if (mesh->conn[k] < 1 || mesh->conn[k] > mesh->n_node) { g_fx_error = "fx_nl_init: node id out of range"; return FX_ERROR_RUNTIME; }
+  if (n_mat > 1)
+    for (int32_t e = 0; e < mesh->n_elem; e++)
+      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
+  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;
+  return nl_init_parts(c, mesh->n_node, mesh->coord, {{etype, mesh->n_elem, mesh->conn, n_mat > 1 ? elem_mat : nullptr}}, n_mat, mats);
 }
 
 extern "C" int fx_nl_init(fx_context *c, const fx_mesh_view *mesh, const fx_material_view *mat) {
@@ -232,6 +284,33 @@ extern "C" int fx_nl_init_type(fx_context *c, const fx_mesh_view *mesh, int32_t 
   return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype, "fx_nl_init_type");
 }
 
+// The same context for a mesh of several solid element types (fstr_StiffMatrix.f90:43-212 and fstr_Update.f90:73-264 loop over
+// hecMESH%elem_type_item; a group is one entry of that loop).  One material table serves all groups.
+extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                 int32_t n_mat, const fx_material_view *mats) {
+  const char *who = "fx_nl_init_groups";
+  if (!c) { g_fx_error = "fx_nl_init_groups: null argument"; return FX_ERROR_RUNTIME; }
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, mats != nullptr)) return rc;
+  for (int32_t g = 0; g < n_group; g++)
+    if (groups[g].etype == 361 && groups[g].elemopt != 2)
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                     "group %d: elemopt %d of TYPE=361; the nonlinear loop serves 361 with elemopt 2 (B-bar) only", (int)g + 1,
+                     (int)groups[g].elemopt);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
+  if (n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
+  if (int e = nl_check_materials(who, n_mat, mats)) return e;
+  std::vector<NlPartIn> in;
+  for (int32_t g = 0; g < n_group; g++)
+    if (groups[g].n_elem > 0) in.push_back({groups[g].etype, groups[g].n_elem, groups[g].conn, n_mat > 1 ? groups[g].elem_mat : nullptr});
+  if (in.empty()) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  if (in.size() == 1) {  // the single-type context
+    const fx_mesh_view mesh = {n_node, in[0].n_elem, coord, in[0].conn};
+    return nl_init_common(c, &mesh, n_mat, mats, in[0].elem_mat, in[0].etype, who);
+  }
+  return nl_init_parts(c, n_node, coord, in, n_mat, mats);
+}
+
 #define NL_READY(name)                                                                              \
   HIP_TRY(hipSetDevice(c->device));                                                                 \
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }
@@ -247,126 +326,152 @@ static constexpr auto nl_c3_kernel() {
     else return k_nl_stiffness_c3<ETYPE, G>;
   }
 }
+// A part's block of the per-point arrays
+struct NlPartState {
+  double *stress, *strain, *stress_bak, *strain_bak, *plstrain, *fstat;
+  int32_t *istat;
+};
+static NlPartState nl_part_state(const NlDev &n, const NlPart &p) {
+  const int64_t o = p.pt_off;
+  return {n.stress + 6 * o, n.strain + 6 * o, n.stress_bak + 6 * o, n.strain_bak + 6 * o, n.plstrain + o, n.fstat + o, n.istat + o};
+}
+// Kout / qf_out: the part's block of the element outputs, or null
 template <int ETYPE, int G>
-static void nl_launch_stiffness_c3_group(fx_context *c, double *Kout) {
+static void nl_launch_stiffness_c3_group(fx_context *c, const NlPart &p, double *Kout) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
+  const NlPartState s = nl_part_state(n, p);
   using El = C3El<ETYPE>;
   // element matrices out, or atomics: the group's colours in one launch
-  for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, false>()), grid, dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat,
-                       n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)n.colors.order, e0,
-                       (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)n.emat,
-                       (const double *)n.strain);
+  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, false>()), grid, dim3(El::BS), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch, s.stress, s.fstat,
+                       s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)p.colors.order, e0,
+                       (const int32_t *)p.colors.pos, p.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)p.emat,
+                       (const double *)s.strain);
   });
 }
 template <int ETYPE, int G>
-static void nl_launch_update_c3_group(fx_context *c, double *qf_out) {
+static void nl_launch_update_c3_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
-  const std::vector<int32_t> &off = n.grp_off[G];
+  const std::vector<int32_t> &off = p.grp_off[G];
   if (off.empty() || off.back() <= off.front()) return;
+  const NlPartState s = nl_part_state(n, p);
   const int32_t e0 = off.front(), e1 = off.back();
-  const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;  // as nl_launch_update_group
+  const int32_t *list = (e0 == 0 && e1 == p.n_elem) ? nullptr : p.colors.order;  // as nl_launch_update_group
   using El = C3El<ETYPE>;
-  hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1, n.coord, n.conn, n.unode,
-                     n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce, qf_out, list,
-                     e0, (const NlMat *)n.mats, (const int32_t *)n.emat, n.err);
+  hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1, n.coord, p.conn, n.unode,
+                     n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out, list,
+                     e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
 }
-// the seven groups of a context of an STF_C3 type: tangent (update == false) or stress update
-static void nl_launch_c3(fx_context *c, double *Kout, double *qf_out, bool update) {
-  with_c3_type(c->nl.etype, [&](auto t) {
+// the seven groups of a part of an STF_C3 type: tangent (update == false) or stress update
+static void nl_launch_c3(fx_context *c, const NlPart &p, double *Kout, double *qf_out, bool update) {
+  with_c3_type(p.etype, [&](auto t) {
     constexpr int ET = decltype(t)::value;
     if (update) {
-      nl_launch_update_c3_group<ET, 0>(c, qf_out);
-      nl_launch_update_c3_group<ET, 1>(c, qf_out);
-      nl_launch_update_c3_group<ET, 2>(c, qf_out);
-      nl_launch_update_c3_group<ET, 3>(c, qf_out);
-      nl_launch_update_c3_group<ET, 4>(c, qf_out);
-      nl_launch_update_c3_group<ET, 5>(c, qf_out);
-      nl_launch_update_c3_group<ET, 6>(c, qf_out);
+      nl_launch_update_c3_group<ET, 0>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 1>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 2>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 3>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 4>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 5>(c, p, qf_out);
+      nl_launch_update_c3_group<ET, 6>(c, p, qf_out);
     } else {
-      nl_launch_stiffness_c3_group<ET, 0>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 1>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 2>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 3>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 4>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 5>(c, Kout);
-      nl_launch_stiffness_c3_group<ET, 6>(c, Kout);
+      nl_launch_stiffness_c3_group<ET, 0>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 1>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 2>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 3>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 4>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 5>(c, p, Kout);
+      nl_launch_stiffness_c3_group<ET, 6>(c, p, Kout);
     }
   });
 }
 
 template <int G>
-static void nl_launch_stiffness_group(fx_context *c, double *Kout, double *dup_k) {
+static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Kout, double *dup_k) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
+  const NlPartState s = nl_part_state(n, p);
   // element matrices out, or atomics: the group's colours in one launch
-  for_colour_ranges(n.grp_off[G], Kout || n.scatter_atomic, FXN_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((k_nl_stiffness<G>), grid, dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn, n.unode, n.dunode, n.mat, n.latch,
-                       n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
-                       (const int32_t *)n.colors.order, e0, (const int32_t *)n.colors.pos, n.scatter_atomic ? 1 : 0,
-                       (const NlMat *)n.mats, (const int32_t *)n.emat, 0, (const double *)n.strain);
+  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, FXN_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL((k_nl_stiffness<G>), grid, dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch,
+                       s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
+                       (const int32_t *)p.colors.order, e0, (const int32_t *)p.colors.pos, p.scatter_atomic ? 1 : 0,
+                       (const NlMat *)n.mats, (const int32_t *)p.emat, 0, (const double *)s.strain);
   });
   // collapsed elements: their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter --
   // added colour by colour (k_add_elem_blocks)
-  const std::vector<int32_t> &doff = n.dup_off[G];
+  const std::vector<int32_t> &doff = p.dup_off[G];
   if (doff.empty()) return;
   const int32_t d0 = doff.front(), d1 = doff.back();
-  hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((d1 - d0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, d1, n.coord, n.conn,
-                     n.unode, n.dunode, n.mat, n.latch, n.stress, n.fstat, n.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                     Kout ? Kout : dup_k, n.err, (const int32_t *)n.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
-                     (const int32_t *)n.emat, Kout ? 0 : 1, (const double *)n.strain);
+  hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((d1 - d0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, d1, n.coord, p.conn,
+                     n.unode, n.dunode, n.mat, n.latch, s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
+                     Kout ? Kout : dup_k, n.err, (const int32_t *)p.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
+                     (const int32_t *)p.emat, Kout ? 0 : 1, (const double *)s.strain);
   if (Kout) return;
   for (size_t k = 0; k + 1 < doff.size(); k++)
     if (doff[k + 1] > doff[k])
       hipLaunchKernelGGL(k_add_elem_blocks, dim3((doff[k + 1] - doff[k] + 63) / 64), dim3(64), 0, c->stream, doff[k], doff[k + 1],
-                         (const int32_t *)n.colors.dup, (const double *)dup_k, (const int32_t *)n.conn, (const int32_t *)n.colors.pos,
+                         (const int32_t *)p.colors.dup, (const double *)dup_k, (const int32_t *)p.conn, (const int32_t *)p.colors.pos,
                          A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
 }
-static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per group present
-  if (c->nl.etype != 361) { nl_launch_c3(c, Kout, nullptr, false); return 0; }
+// Part after part, NLGEOM group after group, colour after colour on one stream; Kout: the element matrices of all parts one after the other
+static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per type and group present
   DevScratch tmp;
   double *dup_k = nullptr;
-  if (!Kout && c->nl.n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * c->nl.n_dup)) return FX_ERROR_RUNTIME;
-  nl_launch_stiffness_group<0>(c, Kout, dup_k);
-  nl_launch_stiffness_group<1>(c, Kout, dup_k);
-  nl_launch_stiffness_group<2>(c, Kout, dup_k);
-  nl_launch_stiffness_group<3>(c, Kout, dup_k);
-  nl_launch_stiffness_group<4>(c, Kout, dup_k);
-  nl_launch_stiffness_group<5>(c, Kout, dup_k);
-  nl_launch_stiffness_group<6>(c, Kout, dup_k);
+  size_t n_dup = 0;
+  for (const NlPart &p : c->nl.parts) n_dup += (size_t)p.n_dup;
+  if (!Kout && n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * n_dup)) return FX_ERROR_RUNTIME;
+  size_t dup_at = 0;
+  for (const NlPart &p : c->nl.parts) {
+    double *K = Kout ? Kout + p.k_off : nullptr;
+    if (p.etype != 361) { nl_launch_c3(c, p, K, nullptr, false); continue; }
+    double *dk = dup_k ? dup_k + (size_t)576 * dup_at : nullptr;
+    dup_at += (size_t)p.n_dup;
+    nl_launch_stiffness_group<0>(c, p, K, dk);
+    nl_launch_stiffness_group<1>(c, p, K, dk);
+    nl_launch_stiffness_group<2>(c, p, K, dk);
+    nl_launch_stiffness_group<3>(c, p, K, dk);
+    nl_launch_stiffness_group<4>(c, p, K, dk);
+    nl_launch_stiffness_group<5>(c, p, K, dk);
+    nl_launch_stiffness_group<6>(c, p, K, dk);
+  }
   if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
   return 0;
 }
 template <int G>
-static void nl_launch_update_group(fx_context *c, double *qf_out) {
+static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
-  const std::vector<int32_t> &off = n.grp_off[G];
+  const NlPartState s = nl_part_state(n, p);
+  const std::vector<int32_t> &off = p.grp_off[G];
   if (!off.empty() && off.back() > off.front()) {
     const int32_t e0 = off.front(), e1 = off.back();
-    // a group that holds every element is walked in the elements' own order (contiguous history arrays); the internal force is
-    // scattered with atomics either way
-    const int32_t *list = (e0 == 0 && e1 == n.n_elem) ? nullptr : n.colors.order;
-    hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, n.conn,
-                       n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain, n.fstat, n.istat, n.qforce,
-                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)n.emat, n.err);
+    // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
+    // force is scattered with atomics either way
+    const int32_t *list = (e0 == 0 && e1 == p.n_elem) ? nullptr : p.colors.order;
+    hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, p.conn,
+                       n.unode, n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce,
+                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
   }
-  const std::vector<int32_t> &doff = n.dup_off[G];  // the collapsed elements of the group
+  const std::vector<int32_t> &doff = p.dup_off[G];  // the collapsed elements of the group
   if (!doff.empty())
     hipLaunchKernelGGL((k_nl_update<G>), dim3((doff.back() - doff.front() + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream,
-                       doff.back(), n.coord, n.conn, n.unode, n.dunode, n.mat, n.stress, n.strain, n.stress_bak, n.strain_bak, n.plstrain,
-                       n.fstat, n.istat, n.qforce, qf_out, (const int32_t *)n.colors.dup, doff.front(), (const NlMat *)n.mats,
-                       (const int32_t *)n.emat, n.err);
+                       doff.back(), n.coord, p.conn, n.unode, n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain,
+                       s.fstat, s.istat, n.qforce, qf_out, (const int32_t *)p.colors.dup, doff.front(), (const NlMat *)n.mats,
+                       (const int32_t *)p.emat, n.err);
 }
-static void nl_launch_update(fx_context *c, double *qf_out) {
-  if (c->nl.etype != 361) { nl_launch_c3(c, nullptr, qf_out, true); return; }
-  nl_launch_update_group<0>(c, qf_out);
-  nl_launch_update_group<1>(c, qf_out);
-  nl_launch_update_group<2>(c, qf_out);
-  nl_launch_update_group<3>(c, qf_out);
-  nl_launch_update_group<4>(c, qf_out);
-  nl_launch_update_group<5>(c, qf_out);
-  nl_launch_update_group<6>(c, qf_out);
+static void nl_launch_update(fx_context *c, double *qf_out) {  // qf_out: the element forces of all parts one after the other, or null
+  for (const NlPart &p : c->nl.parts) {
+    double *qf = qf_out ? qf_out + p.qf_off : nullptr;
+    if (p.etype != 361) { nl_launch_c3(c, p, nullptr, qf, true); continue; }
+    nl_launch_update_group<0>(c, p, qf);
+    nl_launch_update_group<1>(c, p, qf);
+    nl_launch_update_group<2>(c, p, qf);
+    nl_launch_update_group<3>(c, p, qf);
+    nl_launch_update_group<4>(c, p, qf);
+    nl_launch_update_group<5>(c, p, qf);
+    nl_launch_update_group<6>(c, p, qf);
+  }
 }
 // The stress update of a context with a Mohr-Coulomb / Drucker-Prager section reports the reference's `stop` statements through the
 // error word: cleared before the launches, read after them (one 4-byte copy; contexts without such a section skip both).
@@ -394,8 +499,8 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
     if (bc_node[k] < 1 || bc_node[k] > A.NP) { g_fx_error = "fx_nl_stiffness: BC node id out of range"; return FX_ERROR_RUNTIME; }
   HIP_TRY(hipMemsetAsync(n.err, 0, 4, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  // first-write scatter (the STF_C3 types): every block is stored before it is added to, no clearing
-  if (!(n.colors.first_write && n.colors.pos && !n.scatter_atomic) && mat_clear(c)) return FX_ERROR_RUNTIME;
+  // first-write scatter (parts of the STF_C3 types only): every block is stored before it is added to, no clearing
+  if (!n.first_write && mat_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(n.bc_flag, 0, (size_t)3 * A.NP, c->stream));
@@ -566,14 +671,18 @@ extern "C" int fx_mat_ass_bc(fx_context *c, int32_t n_bc, const int32_t *bc_node
 extern "C" int fx_nl_commit(fx_context *c) {
   NL_READY("fx_nl_commit");
   NlDev &n = c->nl;
-  const int64_t np3 = (int64_t)3 * c->A.NP, npt = (int64_t)n.nq * n.n_elem;
+  const int64_t np3 = (int64_t)3 * c->A.NP;
   hipLaunchKernelGGL(k_axpy_plain, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, 1.0, n.dunode, n.unode);
-  if (n.etype == 361)
-    hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.mat.plastic, n.fstat, n.plstrain, n.stress,
-                       n.strain, n.stress_bak, n.strain_bak, (const NlMat *)n.mats, (const int32_t *)n.emat);
-  else
-    hipLaunchKernelGGL(k_nl_commit_c3, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.nq, n.mat.plastic, n.fstat, n.plstrain,
-                       n.stress, n.strain, n.stress_bak, n.strain_bak, (const NlMat *)n.mats, (const int32_t *)n.emat);
+  for (const NlPart &p : n.parts) {  // the kernels find a point's material through its element: part by part
+    const NlPartState s = nl_part_state(n, p);
+    const int64_t npt = (int64_t)p.nq * p.n_elem;
+    if (p.etype == 361)
+      hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.mat.plastic, s.fstat, s.plstrain, s.stress,
+                         s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
+    else
+      hipLaunchKernelGGL(k_nl_commit_c3, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat.plastic, s.fstat, s.plstrain,
+                         s.stress, s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -586,7 +695,7 @@ extern "C" int fx_nl_commit(fx_context *c) {
 extern "C" int fx_nl_snapshot(fx_context *c, int load) {
   NL_READY("fx_nl_snapshot");
   NlDev &n = c->nl;
-  const size_t npt = (size_t)n.nq * n.n_elem;
+  const size_t npt = (size_t)n.n_pt;
   if (!n.bk_stress) {
     if (load) { g_fx_error = "fx_nl_snapshot: nothing was saved"; return FX_ERROR_RUNTIME; }
     if (dev_alloc(&n.bk_stress, 6 * npt) || dev_alloc(&n.bk_strain, 6 * npt) || dev_alloc(&n.bk_stress_bak, 6 * npt) ||
@@ -609,7 +718,7 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
 
 static int nl_copy_state(fx_context *c, const fx_nl_state_view *s, bool to_device) {
   NlDev &n = c->nl;
-  const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)n.nq * n.n_elem;
+  const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)n.n_pt;
   struct { void *h; void *d; size_t bytes; } f[] = {
       {s->stress, n.stress, 6 * npt * 8}, {s->strain, n.strain, 6 * npt * 8}, {s->stress_bak, n.stress_bak, 6 * npt * 8},
       {s->strain_bak, n.strain_bak, 6 * npt * 8}, {s->plstrain, n.plstrain, npt * 8}, {s->fstat, n.fstat, npt * 8},
@@ -633,14 +742,15 @@ extern "C" int fx_nl_set_state(fx_context *c, const fx_nl_state_view *s) {
   return nl_copy_state(c, s, true);
 }
 
-// Element-level outputs of the two kernels (tests): tangents ke (n_elem x 24 x 24 row-major) of the current state
-// with u = unode + dunode, or the stress update with per-element internal forces qf (n_elem x 24), no scatter.
+// Element-level outputs of the two kernels (tests): tangents ke (per element 3 nn x 3 nn row-major) of the current state
+// with u = unode + dunode, or the stress update with per-element internal forces qf (3 nn per element), no scatter; the parts
+// one after the other.
 extern "C" int fx_nl_element_tangents(fx_context *c, double *ke) {
   NL_READY("fx_nl_element_tangents");
   NlDev &n = c->nl;
   DevScratch tmp;
   double *d = nullptr;
-  const size_t nk = (size_t)(3 * n.nn) * (3 * n.nn) * n.n_elem;
+  const size_t nk = n.n_k;
   if (tmp.alloc(&d, nk)) return FX_ERROR_RUNTIME;
   if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, d)) return FX_ERROR_RUNTIME;
@@ -654,7 +764,7 @@ extern "C" int fx_nl_element_update(fx_context *c, double *qf) {
   NlDev &n = c->nl;
   DevScratch tmp;
   double *d = nullptr;
-  const size_t nqf = (size_t)3 * n.nn * n.n_elem;
+  const size_t nqf = n.n_qf;
   if (tmp.alloc(&d, nqf)) return FX_ERROR_RUNTIME;
   if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
   nl_launch_update(c, d);

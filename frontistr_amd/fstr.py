@@ -14,7 +14,8 @@
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
 
 for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
-(fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3),
+(fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3), or a mesh of several groups of these types
+(fstr_solid(ctx, coord, None, materials, groups=[...]): fx_nl_init_groups),
 with one isotropic (elastic; Mises, Mohr-Coulomb or Drucker-Prager elastoplastic: tMaterial.mohr_coulomb / .drucker_prager; or
 hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce) material per section.  Everything is resident on the GPU; there is NO CPU
 fallback.
@@ -120,17 +121,30 @@ class fstr_solid:
     NODES = {361: 8, 341: 4, 342: 10, 351: 6, 352: 15, 362: 20}     # nodes per element
     POINTS = {361: 8, 341: 1, 342: 4, 351: 2, 352: 9, 362: 27}      # quadrature points per element (NumOfQuadPoints)
 
-    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361):
+    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361, groups=None):
         """material: one tMaterial, or a list of them with elem_mat (1-based material id per element = the section's
         material, hecMESH%section_ID -> fstrSOLID%materials).  etype: 361 (B-bar), 341 / 342 (fx_nl_init_c3), or 351 / 352 / 362
-        (fx_nl_init_type with the row length of hecMESH_conn)."""
+        (fx_nl_init_type with the row length of hecMESH_conn).
+
+        A mesh of several solid element types (fx_nl_init_groups): hecMESH_conn = None and groups = [(etype, conn, elemopt,
+        elem_mat), ...], the tuples of SolverContext.assemble_groups / mesh.mesh_groups; a 361 group is B-bar (elemopt 2, also
+        taken when left out or None), elem_mat of every group is 1-based into the one list ``material``.  The state arrays and
+        the element outputs are then flat, the groups one after the other (point_offsets, elem_offsets; group_slices cuts them
+        into per-group views)."""
         self.ctx = ctx
+        self.coord = np.ascontiguousarray(hecMESH_coord, dtype=np.float64)
+        self.material = material
+        self.n_node = self.coord.shape[0]
+        if groups is not None:
+            if hecMESH_conn is not None:
+                raise ValueError("fstr_solid: give hecMESH_conn or groups, not both")
+            self._init_groups(groups, material)
+            return
         self.etype = int(etype)
         self.nn, self.nq = self.NODES.get(self.etype, 0), self.POINTS.get(self.etype, 0)
-        self.coord = np.ascontiguousarray(hecMESH_coord, dtype=np.float64)
         self.conn = np.ascontiguousarray(hecMESH_conn, dtype=np.int32)
-        self.material = material
-        self.n_node, self.n_elem = self.coord.shape[0], self.conn.shape[0]
+        self.n_elem = self.conn.shape[0]
+        self._set_parts([(self.etype, self.n_elem)])
         mv = hecmw._MeshView(self.n_node, self.n_elem, _ptr(self.coord), _ptr(self.conn))
         if self.etype != 361:
             mats = list(material) if isinstance(material, (list, tuple)) else [material]
@@ -156,12 +170,57 @@ class fstr_solid:
         m = material.view()
         _chk(lib().fx_nl_init(ctx.h, C.byref(mv), C.byref(m)))
 
+    def _set_parts(self, parts):
+        """parts: [(etype, n_elem)] in the context's order -> the offsets of the flat layouts (fx_nl_init_groups)."""
+        self.parts = [(int(et), int(ne), self.NODES.get(int(et), 0), self.POINTS.get(int(et), 0)) for et, ne in parts]
+        cum = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+        self.elem_offsets = cum([ne for _, ne, _, _ in self.parts])
+        self.point_offsets = cum([ne * q for _, ne, _, q in self.parts])            # P_g of the per-point arrays
+        self.tangent_offsets = cum([ne * 9 * nn * nn for _, ne, nn, _ in self.parts])  # doubles, element tangents
+        self.force_offsets = cum([ne * 3 * nn for _, ne, nn, _ in self.parts])         # doubles, element internal forces
+        self.n_point = int(self.point_offsets[-1])
+
+    def _init_groups(self, groups, material):
+        mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        groups = [(g[0], g[1], 2 if len(g) < 3 or g[2] is None else g[2], g[3] if len(g) > 3 else None) for g in groups]
+        tab, keep = hecmw.SolverContext._group_table(groups)
+        self.groups = groups
+        self.etype = self.nn = self.nq = self.conn = None       # no single type: see parts
+        self._set_parts([(tab[g].etype, tab[g].n_elem) for g in range(len(groups))])
+        self.n_elem = int(self.elem_offsets[-1])
+        views = [m.view() for m in mats]
+        arr = (_MaterialView * len(views))(*views)
+        _chk(lib().fx_nl_init_groups(self.ctx.h, self.n_node, _ptr(self.coord), len(groups), tab, len(views), arr))
+        del keep
+
+    def group_slices(self, name, array):
+        """Per-group views of a flat array of a context of several groups: ``name`` a state array ("stress", ..., "istat":
+        views (n_elem_g, nq_g[, 6])), "tangents" ((n_elem_g, 3 nn_g, 3 nn_g)) or "forces" ((n_elem_g, 3 nn_g))."""
+        a = np.asarray(array).ravel()
+        out = []
+        for g, (et, ne, nn, q) in enumerate(self.parts):
+            if name == "tangents":
+                out.append(a[self.tangent_offsets[g]:self.tangent_offsets[g + 1]].reshape(ne, 3 * nn, 3 * nn))
+            elif name == "forces":
+                out.append(a[self.force_offsets[g]:self.force_offsets[g + 1]].reshape(ne, 3 * nn))
+            elif name in ("plstrain", "fstat", "istat"):
+                out.append(a[self.point_offsets[g]:self.point_offsets[g + 1]].reshape(ne, q))
+            elif name in ("stress", "strain", "stress_bak", "strain_bak"):
+                out.append(a[6 * self.point_offsets[g]:6 * self.point_offsets[g + 1]].reshape(ne, q, 6))
+            else:
+                raise ValueError("group_slices: %r is no per-point or per-element array" % (name,))
+        return out
+
     # ---- state transfer (tests, restart, output)
     def get_state(self, names=("stress", "strain", "stress_bak", "strain_bak", "plstrain", "fstat", "istat",
                                "unode", "dunode", "qforce")):
         ne, nn, q = self.n_elem, self.n_node, self.nq
-        shapes = {"stress": (ne, q, 6), "strain": (ne, q, 6), "stress_bak": (ne, q, 6), "strain_bak": (ne, q, 6),
-                  "plstrain": (ne, q), "fstat": (ne, q), "istat": (ne, q), "unode": (3 * nn,), "dunode": (3 * nn,),
+        if self.etype is None:      # several groups: flat, the groups one after the other
+            p6, p1 = (self.n_point, 6), (self.n_point,)
+        else:
+            p6, p1 = (ne, q, 6), (ne, q)
+        shapes = {"stress": p6, "strain": p6, "stress_bak": p6, "strain_bak": p6,
+                  "plstrain": p1, "fstat": p1, "istat": p1, "unode": (3 * nn,), "dunode": (3 * nn,),
                   "qforce": (3 * nn,)}
         out = {k: np.zeros(shapes[k], dtype=np.int32 if k == "istat" else np.float64) for k in names}
         v = _StateView(*[_ptr(out.get(k)) for k in shapes], 0)
@@ -179,12 +238,12 @@ class fstr_solid:
         _chk(lib().fx_nl_set_state(self.ctx.h, C.byref(v)))
 
     def element_tangents(self):
-        ke = np.zeros((self.n_elem, 3 * self.nn, 3 * self.nn))
+        ke = np.zeros(int(self.tangent_offsets[-1])) if self.etype is None else np.zeros((self.n_elem, 3 * self.nn, 3 * self.nn))
         _chk(lib().fx_nl_element_tangents(self.ctx.h, _ptr(ke)))
         return ke
 
     def element_update(self):
-        qf = np.zeros((self.n_elem, 3 * self.nn))
+        qf = np.zeros(int(self.force_offsets[-1])) if self.etype is None else np.zeros((self.n_elem, 3 * self.nn))
         _chk(lib().fx_nl_element_update(self.ctx.h, _ptr(qf)))
         return qf
 

@@ -8,7 +8,8 @@
 !>   fstr_UpdateNewton -> fx_nl_update_at (dunode up, QFORCE down)
 !>   fstr_UpdateState  -> fx_nl_commit + the quadrature-point history down (once per sub-step: results, restart)
 !> Taken only for what the device kernels cover -- static analysis with NLGEOM, every element TYPE=361 with the B-bar formulation,
-!> or (on one process) every element of one type of STF_C3 (TYPE=341, 342, 351, 352 or 362), isotropic ELASTIC or Mises-elastoplastic
+!> or (on one process) every element of one type of STF_C3 (TYPE=341, 342, 351, 352 or 362), or (on one process, with
+!> HECMW_GPU_NL_MIXED=1) a mesh of several of these six types (fx_nl_init_groups, one group per elem_type_item entry), isotropic ELASTIC or Mises-elastoplastic
 !> materials with isotropic hardening, no temperature / contact / MPC / spring / local coordinate system; fixed or automatic
 !> increments (a cutback rolls the device's history back too, fsd_cutback); anything else runs the reference's own routines (kept,
 !> renamed, in the same binary).
@@ -43,9 +44,12 @@ module fstr_device_hip
   integer(c_int32_t), save :: n_elem = 0
   integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or a type of STF_C3 / UPDATE_C3 (fx_nl_init_type)
   integer, save :: nl_nq = 8                       ! its quadrature points per element
+  logical, save :: nl_mixed = .false.              ! several of the six solid types (HECMW_GPU_NL_MIXED=1): fx_nl_init_groups
+  integer, allocatable, save :: el_nq(:), el_p0(:) ! per element: its type's quadrature points, and the points of the elements before it
+  integer, save :: n_pt = 0                        ! quadrature points of the mesh: the per-point arrays are flat over them, in hecMESH's element order
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
-  real(c_double), allocatable, target, save :: b6(:,:,:), b1(:,:), b6b(:,:,:)
-  integer(c_int32_t), allocatable, target, save :: bi(:,:)
+  real(c_double), allocatable, target, save :: b6(:,:)
+  integer(c_int32_t), allocatable, target, save :: bi(:)
 
 contains
 
@@ -75,7 +79,9 @@ contains
     type(fstr_solid), intent(in) :: fstrSOLID
     character(len=8) :: env
     character(len=3) :: tname
-    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield
+    character(len=64) :: tnames
+    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype
+    integer(c_int32_t) :: et
     logical :: opted
     if (decided) then
       fsd_eligible = eligible
@@ -91,11 +97,23 @@ contains
     if (hecMAT%NDOF /= 3 .or. hecMESH%n_dof /= 3) return
     if (fstrPR%solution_type /= kstSTATIC .or. .not. fstrPR%nlgeom) return
     if (.not. fxb_on_gpu_path(hecMESH, hecMAT)) return                       ! the solve must run on the device too: same predicate as hecmw_solve (method, preconditioner, no MPC / contact)
-    if (hecMESH%n_elem_type /= 1) return
+    if (hecMESH%n_elem_type < 1) return
+    nl_mixed = hecMESH%n_elem_type > 1
+    if (nl_mixed) then      ! a mesh of several of the six solid types (fx_nl_init_groups): opt-in like the other nonlinear types, one process
+      call get_environment_variable('HECMW_GPU_NL_MIXED', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+      if (hecMESH%PETOT > 1) return
+      if (hecMESH%n_elem_type > 16) return        ! (the report line names every type)
+      do itype = 1, hecMESH%n_elem_type           ! any other type (371, beams, shells, 301) keeps the host loops
+        et = int(hecMESH%elem_type_item(itype), c_int32_t)
+        if (et /= 361 .and. c3_type_nodes(et) == 0) return
+      enddo
+      if (hecMESH%elem_type_index(hecMESH%n_elem_type) /= hecMESH%n_elem) return
+    endif
     lin_etype = int(hecMESH%elem_type_item(1), c_int32_t)
     if (lin_etype /= 361 .and. c3_type_nodes(lin_etype) == 0) return             ! the nonlinear kernels: 361 B-bar and the types of STF_C3
     if (lin_etype /= 361 .and. hecMESH%PETOT > 1) return      ! decomposed meshes of these types: not yet on the device
-    if (lin_etype /= 361) then      ! these opt in: no end-to-end timing against the host loops has been recorded yet (DESIGN.md section 4)
+    if (lin_etype /= 361 .and. .not. nl_mixed) then      ! these opt in: no end-to-end timing against the host loops has been recorded yet (DESIGN.md section 4)
       call get_environment_variable('HECMW_GPU_NL_C3', env, elen, estat)          ! the five types of STF_C3
       opted = (estat == 0 .and. elen > 0 .and. env(1:1) == '1')
       if (.not. opted .and. (lin_etype == 341 .or. lin_etype == 342)) then
@@ -117,14 +135,30 @@ contains
     !  host's, shim/fstr_Cutback_hip.f90 -> fsd_cutback.  A run continued from a restart file: the history read from the file is what
     !  fsd_init pushes to the device at the first fstr_StiffMatrix, after fstr_read_restart, fstr_solve_NLGEOM.f90:70-76.)
     do i = 1, hecMESH%section%n_sect
-      if (lin_etype == 361 .and. fstrSOLID%sections(i)%elemopt361 /= kel361BBAR) return
+      if (lin_etype == 361 .and. .not. nl_mixed .and. fstrSOLID%sections(i)%elemopt361 /= kel361BBAR) return
       if (hecMESH%section%sect_orien_ID(i) > 0) return
     enddo
-    do icel = 1, hecMESH%n_elem
-      if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
-      cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
-      if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
-    enddo
+    if (nl_mixed) then      ! the node count per element, checked per type range; B-bar for the sections of the 361 elements
+      do itype = 1, hecMESH%n_elem_type
+        et = int(hecMESH%elem_type_item(itype), c_int32_t)
+        nn = 8
+        if (et /= 361) nn = c3_type_nodes(et)
+        do icel = hecMESH%elem_type_index(itype-1) + 1, hecMESH%elem_type_index(itype)
+          if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
+          if (et == 361) then
+            if (fstrSOLID%sections(hecMESH%section_ID(icel))%elemopt361 /= kel361BBAR) return
+          endif
+          cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
+          if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
+        enddo
+      enddo
+    else
+      do icel = 1, hecMESH%n_elem
+        if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
+        cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
+        if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
+      enddo
+    endif
     n_hyper = 0
     n_mises = 0
     n_yield = 0
@@ -153,6 +187,19 @@ contains
     nl_etype = lin_etype
     nl_nq = 8
     if (nl_etype /= 361) nl_nq = c3_type_points(nl_etype)
+    if (nl_mixed) then      ! the types in hecMESH's order: TYPE=341+351+361
+      write(tname, '(i3)') nl_etype
+      tnames = tname
+      do itype = 2, hecMESH%n_elem_type
+        write(tname, '(i3)') hecMESH%elem_type_item(itype)
+        tnames = trim(tnames)//'+'//tname
+      enddo
+      if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//trim(tnames)//'); '// &
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+      if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
+      if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
+      return
+    endif
     if (nl_etype /= 361) then
       write(tname, '(i3)') nl_etype
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//tname//'); '// &
@@ -431,10 +478,11 @@ contains
     type(fx_mesh_view) :: mesh
     type(fx_material_view), allocatable :: mats(:)
     integer(c_int32_t), allocatable, target :: emat(:)
+    type(fx_elem_group), allocatable :: groups(:)
     type(DICT_DATA), pointer :: tbl
     logical :: ierr_l
     integer(c_int) :: ierr
-    integer :: i, nmat, ntmax, nt, icel
+    integer :: i, nmat, ntmax, nt, icel, itype, first, nq
     ctx = fxb_context(hecMESH)
     call fxb_ensure_transport(hecMESH, 3)
     call fxb_views(hecMESH, hecMAT, mv, cv)
@@ -492,7 +540,38 @@ contains
     do icel = 1, n_elem
       emat(icel) = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
     enddo
-    if (nl_etype == 361) then
+    if (allocated(el_nq)) deallocate(el_nq, el_p0)
+    allocate(el_nq(n_elem), el_p0(n_elem))
+    el_nq = nl_nq
+    if (nl_mixed) then      ! elem_node_item holds the elements type by type: a group is a pointer into it (and into emat), B-bar for 361
+      allocate(groups(hecMESH%n_elem_type))
+      do itype = 1, hecMESH%n_elem_type
+        first = hecMESH%elem_type_index(itype-1) + 1
+        groups(itype)%etype = int(hecMESH%elem_type_item(itype), c_int32_t)
+        groups(itype)%elemopt = 2
+        groups(itype)%n_elem = int(hecMESH%elem_type_index(itype) - hecMESH%elem_type_index(itype-1), c_int32_t)
+        groups(itype)%conn = c_null_ptr
+        groups(itype)%elem_mat = c_null_ptr
+        if (groups(itype)%n_elem > 0) then
+          groups(itype)%conn = c_loc(hecMESH%elem_node_item(hecMESH%elem_node_index(first-1) + 1))
+          groups(itype)%elem_mat = c_loc(emat(first))
+        endif
+        nq = 8
+        if (groups(itype)%etype /= 361) nq = c3_type_points(groups(itype)%etype)
+        el_nq(first:hecMESH%elem_type_index(itype)) = nq
+      enddo
+    endif
+    n_pt = 0      ! the per-point arrays: the elements in hecMESH's order, each with its own type's points
+    do icel = 1, n_elem
+      el_p0(icel) = n_pt
+      n_pt = n_pt + el_nq(icel)
+    enddo
+    if (nl_mixed) then
+      ierr = fx_nl_init_groups(ctx, int(hecMESH%n_node, c_int32_t), hecMESH%node, int(size(groups), c_int32_t), groups, &
+                               int(nmat, c_int32_t), mats)
+      if (ierr /= 0) call fsd_fail('fx_nl_init_groups')
+      deallocate(groups)
+    else if (nl_etype == 361) then
       ierr = fx_nl_init_sections(ctx, mesh, int(nmat, c_int32_t), mats, emat)
       if (ierr /= 0) call fsd_fail('fx_nl_init_sections')
     else
@@ -500,8 +579,8 @@ contains
       if (ierr /= 0) call fsd_fail('fx_nl_init_type')
     endif
     deallocate(mats, emat)
-    if (allocated(b6)) deallocate(b6, b6b, b1, bi)
-    allocate(b6(6, nl_nq, n_elem), b6b(6, nl_nq, n_elem), b1(nl_nq, n_elem), bi(nl_nq, n_elem))
+    if (allocated(b6)) deallocate(b6, bi)
+    allocate(b6(6, n_pt), bi(n_pt))
     call fsd_push_state(ctx, fstrSOLID)
     ready = .true.
     the_ctx_saved = ctx
@@ -536,23 +615,24 @@ contains
     type(fstr_solid), intent(inout), target :: fstrSOLID
     type(fx_nl_state_view) :: sv
     integer(c_int) :: ierr
-    integer :: icel, g
-    real(c_double), allocatable, target :: s6(:,:,:), sb6(:,:,:), e6b(:,:,:), pl(:,:), fs(:,:)
-    allocate(s6(6, nl_nq, n_elem), sb6(6, nl_nq, n_elem), e6b(6, nl_nq, n_elem), pl(nl_nq, n_elem), fs(nl_nq, n_elem))
+    integer :: icel, g, p
+    real(c_double), allocatable, target :: s6(:,:), sb6(:,:), e6b(:,:), pl(:), fs(:)
+    allocate(s6(6, n_pt), sb6(6, n_pt), e6b(6, n_pt), pl(n_pt), fs(n_pt))
     bi = 0; fs = 0.d0
-    do icel = 1, n_elem
-      do g = 1, nl_nq
-        b6(:, g, icel)  = fstrSOLID%elements(icel)%gausses(g)%strain
-        s6(:, g, icel)  = fstrSOLID%elements(icel)%gausses(g)%stress
-        e6b(:, g, icel) = fstrSOLID%elements(icel)%gausses(g)%strain_bak
-        sb6(:, g, icel) = fstrSOLID%elements(icel)%gausses(g)%stress_bak
-        pl(g, icel)     = fstrSOLID%elements(icel)%gausses(g)%plstrain
-        if (associated(fstrSOLID%elements(icel)%gausses(g)%istatus)) bi(g, icel) = fstrSOLID%elements(icel)%gausses(g)%istatus(1)
-        if (associated(fstrSOLID%elements(icel)%gausses(g)%fstatus)) fs(g, icel) = fstrSOLID%elements(icel)%gausses(g)%fstatus(1)
+    do icel = 1, n_elem      ! every element with its own type's points, at the cumulative point offset
+      do g = 1, el_nq(icel)
+        p = el_p0(icel) + g
+        b6(:, p)  = fstrSOLID%elements(icel)%gausses(g)%strain
+        s6(:, p)  = fstrSOLID%elements(icel)%gausses(g)%stress
+        e6b(:, p) = fstrSOLID%elements(icel)%gausses(g)%strain_bak
+        sb6(:, p) = fstrSOLID%elements(icel)%gausses(g)%stress_bak
+        pl(p)     = fstrSOLID%elements(icel)%gausses(g)%plstrain
+        if (associated(fstrSOLID%elements(icel)%gausses(g)%istatus)) bi(p) = fstrSOLID%elements(icel)%gausses(g)%istatus(1)
+        if (associated(fstrSOLID%elements(icel)%gausses(g)%fstatus)) fs(p) = fstrSOLID%elements(icel)%gausses(g)%fstatus(1)
       enddo
     enddo
-    sv%stress = c_loc(s6(1,1,1)); sv%strain = c_loc(b6(1,1,1)); sv%stress_bak = c_loc(sb6(1,1,1)); sv%strain_bak = c_loc(e6b(1,1,1))
-    sv%plstrain = c_loc(pl(1,1)); sv%fstat = c_loc(fs(1,1)); sv%istat = c_loc(bi(1,1))
+    sv%stress = c_loc(s6(1,1)); sv%strain = c_loc(b6(1,1)); sv%stress_bak = c_loc(sb6(1,1)); sv%strain_bak = c_loc(e6b(1,1))
+    sv%plstrain = c_loc(pl(1)); sv%fstat = c_loc(fs(1)); sv%istat = c_loc(bi(1))
     sv%unode = c_loc(fstrSOLID%unode(1)); sv%dunode = c_loc(fstrSOLID%dunode(1)); sv%qforce = c_loc(fstrSOLID%QFORCE(1))
     sv%latch = -1
     ierr = fx_nl_set_state(ctx, sv)
@@ -763,29 +843,30 @@ contains
     type(fx_nl_state_view) :: sv
     type(c_ptr) :: ctx
     integer(c_int) :: ierr
-    integer :: icel, g
-    real(c_double), allocatable, target :: s6(:,:,:), pl(:,:), fs(:,:)
+    integer :: icel, g, p
+    real(c_double), allocatable, target :: s6(:,:), pl(:), fs(:)
     fsd_update_state = .false.
     if (.not. ready) return
     ctx = fxb_context(hecMESH)
     ierr = fx_nl_commit(ctx)      ! unode += dunode is the host's (fstr_Newton :156-158); the device does the same on its copy
     if (ierr /= 0) call fsd_fail('fx_nl_commit')
-    allocate(s6(6, nl_nq, n_elem), pl(nl_nq, n_elem), fs(nl_nq, n_elem))
-    sv%stress = c_loc(s6(1,1,1)); sv%strain = c_loc(b6(1,1,1)); sv%stress_bak = c_null_ptr; sv%strain_bak = c_null_ptr
-    sv%plstrain = c_loc(pl(1,1)); sv%fstat = c_loc(fs(1,1)); sv%istat = c_loc(bi(1,1))
+    allocate(s6(6, n_pt), pl(n_pt), fs(n_pt))
+    sv%stress = c_loc(s6(1,1)); sv%strain = c_loc(b6(1,1)); sv%stress_bak = c_null_ptr; sv%strain_bak = c_null_ptr
+    sv%plstrain = c_loc(pl(1)); sv%fstat = c_loc(fs(1)); sv%istat = c_loc(bi(1))
     sv%unode = c_null_ptr; sv%dunode = c_null_ptr; sv%qforce = c_null_ptr
     sv%latch = -1
     ierr = fx_nl_get_state(ctx, sv)
     if (ierr /= 0) call fsd_fail('fx_nl_get_state')
     do icel = 1, n_elem
-      do g = 1, nl_nq
-        fstrSOLID%elements(icel)%gausses(g)%strain = b6(:, g, icel)
-        fstrSOLID%elements(icel)%gausses(g)%stress = s6(:, g, icel)
-        fstrSOLID%elements(icel)%gausses(g)%strain_bak = b6(:, g, icel)     ! fstr_UpdateState :338-339
-        fstrSOLID%elements(icel)%gausses(g)%stress_bak = s6(:, g, icel)
-        fstrSOLID%elements(icel)%gausses(g)%plstrain = pl(g, icel)
-        if (associated(fstrSOLID%elements(icel)%gausses(g)%istatus)) fstrSOLID%elements(icel)%gausses(g)%istatus(1) = bi(g, icel)
-        if (associated(fstrSOLID%elements(icel)%gausses(g)%fstatus)) fstrSOLID%elements(icel)%gausses(g)%fstatus(1) = fs(g, icel)
+      do g = 1, el_nq(icel)
+        p = el_p0(icel) + g
+        fstrSOLID%elements(icel)%gausses(g)%strain = b6(:, p)
+        fstrSOLID%elements(icel)%gausses(g)%stress = s6(:, p)
+        fstrSOLID%elements(icel)%gausses(g)%strain_bak = b6(:, p)     ! fstr_UpdateState :338-339
+        fstrSOLID%elements(icel)%gausses(g)%stress_bak = s6(:, p)
+        fstrSOLID%elements(icel)%gausses(g)%plstrain = pl(p)
+        if (associated(fstrSOLID%elements(icel)%gausses(g)%istatus)) fstrSOLID%elements(icel)%gausses(g)%istatus(1) = bi(p)
+        if (associated(fstrSOLID%elements(icel)%gausses(g)%fstatus)) fstrSOLID%elements(icel)%gausses(g)%fstatus(1) = fs(p)
       enddo
     enddo
     deallocate(s6, pl, fs)

@@ -21,7 +21,7 @@ module hecmw_hip_binding
   public :: fx_solve, fx_matvec, fx_last_error, fx_solve_attempts, fx_solve_attempt_history
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
   public :: fx_mesh_view, fx_material_view, fx_nl_state_view, fx_elem_group
-  public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_init_type, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
+  public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_init_type, fx_nl_init_groups, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
             fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
             fx_assemble_c3, fx_update_c3_linear, fx_assemble_groups, fx_update_groups_linear, fx_update_groups_linear_prepare
   public :: fxb_values_owner, fxb_values_addr
@@ -222,6 +222,14 @@ module hecmw_hip_binding
       type(fx_material_view) :: mats(*)
       integer(c_int32_t) :: elem_mat(*)
     end function fx_nl_init_type
+    integer(c_int) function fx_nl_init_groups(ctx, n_node, coord, n_group, groups, n_mat, mats) bind(C, name='fx_nl_init_groups')
+      import :: c_int, c_ptr, c_int32_t, c_double, fx_elem_group, fx_material_view
+      type(c_ptr), value :: ctx
+      integer(c_int32_t), value :: n_node, n_group, n_mat
+      real(c_double), intent(in) :: coord(*)
+      type(fx_elem_group), intent(in) :: groups(*)
+      type(fx_material_view) :: mats(*)
+    end function fx_nl_init_groups
     integer(c_int) function fx_nl_stiffness_at(ctx, unode, dunode, ms) bind(C, name='fx_nl_stiffness_at')
       import :: c_int, c_ptr, c_double, c_float
       type(c_ptr), value :: ctx

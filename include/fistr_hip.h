@@ -385,7 +385,7 @@ typedef struct fx_material_view { /* tMaterial after fstr_ctrl_get_ELASTICITY/_P
   double plconst4;      /* M_PLCONST4: xi of Drucker-Prager; not read for another kind */
 } fx_material_view;
 typedef struct fx_nl_state_view { /* host arrays, any may be NULL (skipped).  tGaussStatus members (mechgauss.f90:13-22) */
-  double *stress, *strain, *stress_bak, *strain_bak; /* n_elem*nq*6 (nq = 8 at 361) */
+  double *stress, *strain, *stress_bak, *strain_bak; /* n_elem*nq*6 (nq = 8 at 361); several groups: see fx_nl_init_groups */
   double *plstrain, *fstat;                           /* n_elem*nq: plstrain, fstatus(1) */
   int32_t *istat;                                     /* n_elem*nq: istatus(1) */
   double *unode, *dunode, *qforce;                    /* 3*NP: fstrSOLID%unode, %dunode, %QFORCE */
@@ -412,6 +412,27 @@ int fx_nl_init_c3(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int3
  * fx_nl_init_c3 (which keeps its two types). */
 int fx_nl_init_type(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t nn_elem, int32_t n_mat,
                     const fx_material_view *mats, const int32_t *elem_mat);
+/* The same context for a mesh of SEVERAL solid element types (hex-dominant meshes with wedge or tetrahedron transitions): the
+ * groups of fx_assemble_groups, one material table for all of them, elem_mat of every group 1-based into it (may be NULL with
+ * n_mat == 1).  etype of a group: 361 with elemopt 2 (B-bar, what the 361 nonlinear kernels are), 341, 342, 351, 352 or 362; a
+ * type may appear in several groups; a group with n_elem == 0 is skipped.  Needs a profile.
+ *   Layout of the per-point arrays (fx_nl_state_view, snapshot, commit): flat, the groups one after the other in the order given;
+ *     group g starts at point P_g = sum over h < g of n_elem_h * nq(etype_h) and is [elem][point][.] inside.  With one group per
+ *     hecMESH%elem_type_item entry that is hecMESH's element order.
+ *   Layout of the element outputs (fx_nl_element_tangents, fx_nl_element_update): the groups one after the other in the same
+ *     order, (3 nn_g)^2 doubles (row-major) and 3 nn_g doubles per element of group g.
+ * Every other fx_nl_* entry point, fx_mat_ass_bc, fx_newton_substep and fx_solve_device_matrix work on such a context unchanged.
+ * The latch (MatlMatrix's saved flag is the process's), the Mohr-Coulomb / Drucker-Prager error word and the refusal of an
+ * elastoplastic beside a hyperelastic material are the context's: the first elastoplastic stress update in ANY group latches the
+ * tangents of EVERY group.  The scatter runs group after group, NLGEOM flag after flag, colour after colour on one stream, each
+ * group with its own colouring: no atomics, two fx_nl_stiffness calls on the same state give bitwise equal D / AL / AU.  Collapsed
+ * hexahedra of a 361 group are served as in fx_nl_init.  With ONE non-empty group the context and all it computes are bit for
+ * bit those of fx_nl_init_sections / fx_nl_init_type.
+ * Refused, the previous context untouched: an unknown etype, or elemopt 1 / 3 on a 361 group (named): FX_ERROR_UNSUPPORTED, as
+ * are the materials fx_nl_init* refuse; n_group < 1, no element at all, missing materials, a material or node id out of range, a
+ * degenerate element of a type other than 361 (named with group and element): FX_ERROR_RUNTIME. */
+int fx_nl_init_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                      int32_t n_mat, const fx_material_view *mats);
 /* fstr_Newton :63-68 + fstr_ass_load: dunode = 0, GL (3*NP, may be NULL), B = GL - QFORCE. */
 int fx_nl_begin_substep(fx_context *ctx, const double *GL);
 /* fstr_StiffMatrix (fstr_StiffMatrix.f90:18-212) + fstr_AddBC (fstr_AddBC.f90:17-190) with the
@@ -443,7 +464,8 @@ int fx_nl_commit(fx_context *ctx);
 int fx_nl_snapshot(fx_context *ctx, int load);
 int fx_nl_get_state(fx_context *ctx, fx_nl_state_view *s);
 int fx_nl_set_state(fx_context *ctx, const fx_nl_state_view *s);
-/* element-level outputs of the two kernels, no scatter (tests): ke n_elem*(3 nn)^2, qf n_elem*3 nn (nn = 8 at 361) */
+/* element-level outputs of the two kernels, no scatter (tests): ke n_elem*(3 nn)^2, qf n_elem*3 nn (nn = 8 at 361); a context of
+ * several groups: group after group, see fx_nl_init_groups */
 int fx_nl_element_tangents(fx_context *ctx, double *ke);
 int fx_nl_element_update(fx_context *ctx, double *qf);
 /* One substep of fstr_Newton around fx_solve_resident.  log: 7 doubles per Newton iteration

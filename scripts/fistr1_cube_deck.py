@@ -7,10 +7,11 @@ hecmw_ctrl.dat (with the restart work-around of oracle/fistr1_run.py).  Used to 
 --etype 341|342 (with or without --linear): the same cube split into tetrahedra (frontistr_amd.mesh.TetMesh, 6 per hexahedron; 342 with
 mid-edge nodes), the node groups FIX / TOP listed by coordinate.  --etype 351|352|362 (with or without --linear): the cube split into wedges
 (WedgeMesh, 2 per hexahedron; 352 with mid-edge nodes) or as 20-node hexahedra (Hex20Mesh).  --two-sections (with --linear): the second half of the elements
-forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33).  --mixed 1|2 (with --linear): the cube as a mesh of
+forms EGRP=E2 with its own section and material MAT2 (ELASTIC 70000, 0.33).  --mixed 1|2 (with or without --linear; without it an
+NLSTATIC deck with the materials, steps and --two-sections variant of the other nonlinear cube decks): the cube as a mesh of
 three element types (frontistr_amd.mesh.MixedMesh: 361 + 351 + 341, or 362 + 352 + 342 with shared mid-edge nodes), one !ELEMENT
 card per type in mesh order; with --two-sections the second half of the elements in that order is EGRP=E2.
-NLSTATIC decks of the STF_C3 types (--etype 341|342|351|352|362 without --linear) take two more options:
+NLSTATIC decks of the STF_C3 types and of the mixed cube (--etype 341|342|351|352|362 or --mixed 1|2, without --linear) take two more options:
   --nl-material multilinear|bilinear|elastic_tl|elastic_ul   MAT1: Mises MULTILINEAR (default) or BILINEAR, both updated Lagrange;
                                                              ELASTIC total Lagrange; `!ELASTIC, CAUCHY`, updated Lagrange.
   --two-sections                                             the second half of the elements is MAT2, ELASTIC 70000 / 0.33, TOTAL
@@ -50,11 +51,11 @@ if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
     if etype not in (341, 342, 351, 352, 362):
         sys.exit("--etype takes 341, 342, 351, 352 or 362")
-mixed = 0                            # --mixed 1|2: hexahedra + wedges + tetrahedra of that order (linear decks only)
+mixed = 0                            # --mixed 1|2: hexahedra + wedges + tetrahedra of that order (linear or NLSTATIC decks)
 if "--mixed" in sys.argv:
     k = sys.argv.index("--mixed"); mixed = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
-    if mixed not in (1, 2) or not linear or etype != 361:
-        sys.exit("--mixed takes 1 or 2, with --linear and without --etype")
+    if mixed not in (1, 2) or etype != 361:
+        sys.exit("--mixed takes 1 or 2, without --etype")
 nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
 if "--nl-material" in sys.argv:
     k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
@@ -65,8 +66,8 @@ yieldf = nlmat in ("drucker", "mohr")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear and etype == 361 and not hyper and not yieldf:
-        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or a hyperelastic or drucker / mohr --nl-material")
+    if not linear and etype == 361 and not mixed and not hyper and not yieldf:
+        sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or --mixed, or a hyperelastic or drucker / mohr --nl-material")
 thermal = "--thermal" in sys.argv
 if thermal:
     sys.argv.remove("--thermal")

@@ -1,0 +1,307 @@
+"""The nonlinear static loop on a mesh of several solid element types: a `Model` over element groups that composes the
+restatements already pinned to the reference, type by type --
+
+    341, 342         tet_nl_ref   (STF_C3 / UPDATE_C3 on tet_ref's elements)
+    351, 352, 362    c3_nl_ref    (the same routines on c3_ref's elements)
+    361 (B-bar)      oracle.pyoracle: orc_stf_c3d8bbar_nl, orc_update_c3d8bbar, the element's section material passed per call
+    hyperelastic / Mohr-Coulomb / Drucker-Prager materials, any type: hyper_ref / yield_ref
+
+-- as fstr_StiffMatrix.f90:43-212 and fstr_Update.f90:73-264 loop over hecMESH%elem_type_item.  A group is (etype, conn, elemopt,
+elem_mat), the tuple of mesh.mesh_groups; elem_mat is 1-based into ONE material list.
+
+There is ONE latch.  MatlMatrix's saved flag (calMatMatrix.f90:39) is the process's: the first elastoplastic stress update in any
+group latches the tangents of every group.  `Model.latch` is that flag; the C oracle keeps its own static copy, which
+`_set_c_latch` makes equal to the model's before every 361 call (reset, then -- when the model's is set -- one throw-away plastic
+update of one element).
+
+State: `Model.parts[g]["st"]` holds group g's arrays [elem][point][.]; `flat(name)` is the layout of fx_nl_init_groups: the
+groups one after the other in the order given.
+"""
+import ctypes as C
+
+import numpy as np
+
+import c3_nl_ref as CN
+import c3_ref as R
+import hyper_ref as H
+import tet_nl_ref as T
+import yield_ref as Y
+from tet_nl_ref import INFINITE, TOTALLAG, UPDATELAG  # noqa: F401
+
+NODES, POINTS = H.NODES, H.POINTS
+STATE6 = ("stress", "strain", "stress_bak", "strain_bak")
+STATE1 = ("plstrain", "fstat", "istat")
+
+
+def _set_c_latch(latch):
+    """The C oracle's static latch := latch."""
+    from oracle import pyoracle as po
+    from oracle.refrun import Material
+    po.nl_reset_latch()
+    if not latch:
+        return
+    mat = Material(1000.0, 0.3, plastic=True, harden=0, plconst=(1.0e9, 0.0, 0.0), nlgeom=INFINITE)
+    cm = po.cmaterial(mat)
+    z = lambda *s: np.zeros(s)
+    ec = np.ascontiguousarray(Y.ONE_ELEM_COORD)
+    ist = np.zeros(8, dtype=np.int32)
+    po.lib().orc_update_c3d8bbar(C.byref(cm), po._dp(ec), po._dp(z(8, 3)), po._dp(z(8, 3)), po._dp(z(8, 6)), po._dp(z(8, 6)),
+                                 po._dp(z(8, 6)), po._dp(z(8, 6)), po._dp(z(8)), po._ip(ist), po._dp(z(8)), po._dp(z(24)))
+
+
+def _stf(etype, ec, u, mat, latch, st, e):
+    """One element's tangent by the restatement of its type and material."""
+    s = st
+    if H.kind_of(mat) >= H.MOONEY and not Y.is_yield(mat):
+        return H.stf_c3d8bbar(ec, u, mat, s["strain"][e], s["stress"][e]) if etype == 361 else H.stf_c3(etype, ec, u, mat, s["strain"][e], s["stress"][e])
+    a = (ec, u, mat, latch, s["stress"][e], s["istat"][e], s["fstat"][e])
+    if Y.is_yield(mat):
+        return Y.stf_c3d8bbar(*a) if etype == 361 else Y.stf_c3(etype, *a)
+    if etype == 361:
+        from oracle import pyoracle as po
+        _set_c_latch(latch)
+        cm = po.cmaterial(mat)
+        out = np.zeros((24, 24))
+        ecc, ut = np.ascontiguousarray(ec), np.ascontiguousarray(u)
+        stress, istat, fstat = (np.ascontiguousarray(s[k][e]) for k in ("stress", "istat", "fstat"))
+        po.lib().orc_stf_c3d8bbar_nl(C.byref(cm), po._dp(ecc), po._dp(ut), po._dp(stress), po._ip(istat), po._dp(fstat), po._dp(out))
+        return out
+    return (T if etype in (341, 342) else CN).stf_c3(etype, *a)
+
+
+def _update(etype, ec, u, du, mat, st, e, order):
+    """One element's stress update -> (qf, stress, strain, istat, fstat, dstress)"""
+    s = st
+    nq = POINTS[etype]
+    zero = np.zeros((nq, 6))
+    if H.kind_of(mat) >= H.MOONEY and not Y.is_yield(mat):
+        qf, stress, strain = H.update_c3d8bbar(ec, u + du, mat) if etype == 361 else H.update_c3(etype, ec, u + du, mat)
+        return qf, stress, strain, s["istat"][e].copy(), s["fstat"][e].copy(), zero
+    a = (ec, u, du, mat, s["stress_bak"][e], s["strain_bak"][e], s["plstrain"][e], s["istat"][e], s["fstat"][e])
+    if Y.is_yield(mat):
+        return (Y.update_c3d8bbar(*a) if etype == 361 else Y.update_c3(etype, *a)) + (zero,)
+    if etype == 361:
+        from oracle import pyoracle as po
+        cm = po.cmaterial(mat)
+        c = lambda k, dt=np.float64: np.ascontiguousarray(s[k][e], dtype=dt).copy()
+        stress, strain, sb, eb, pl, fs = c("stress"), c("strain"), c("stress_bak"), c("strain_bak"), c("plstrain"), c("fstat")
+        ist = c("istat", np.int32)
+        qf = np.zeros(24)
+        po.lib().orc_update_c3d8bbar(C.byref(cm), po._dp(np.ascontiguousarray(ec)), po._dp(np.ascontiguousarray(u)),
+                                     po._dp(np.ascontiguousarray(du)), po._dp(stress), po._dp(strain), po._dp(sb), po._dp(eb), po._dp(pl),
+                                     po._ip(ist), po._dp(fs), po._dp(qf))
+        return qf, stress, strain, ist, fs, zero
+    od = None if order is None else order(NODES[etype])
+    return (T if etype in (341, 342) else CN).update_c3(etype, *a, od)
+
+
+def reverse(nn):
+    """An `order` of element_update: the element's nodes summed last to first."""
+    return list(range(nn))[::-1]
+
+
+class Model(T.Model):
+    """fstr_solid of a mesh of element groups; tet_nl_ref.Model's steps of fstr_Newton (dense solve) over all groups."""
+
+    def __init__(self, coord, groups, mats):
+        self.coord = np.asarray(coord, dtype=np.float64)
+        self.mats = list(mats) if isinstance(mats, (list, tuple)) else [mats]
+        self.parts = []
+        for g in groups:
+            etype, conn = int(g[0]), np.asarray(g[1]).reshape(-1, NODES[int(g[0])])
+            em = g[3] if len(g) > 3 and g[3] is not None else np.ones(conn.shape[0], dtype=np.int32)
+            ne, q = conn.shape[0], POINTS[etype]
+            st = {k: np.zeros((ne, q, 6)) for k in STATE6}
+            st.update(plstrain=np.zeros((ne, q)), fstat=np.zeros((ne, q)), istat=np.zeros((ne, q), dtype=np.int32))
+            self.parts.append(dict(etype=etype, conn=conn, elem_mat=np.asarray(em), st=st))
+        n = self.coord.shape[0]
+        self.unode, self.dunode, self.qforce = np.zeros(3 * n), np.zeros(3 * n), np.zeros(3 * n)
+        self.latch = 0
+
+    # ---- the flat layout of the device context
+    def flat(self, name):
+        return np.concatenate([p["st"][name].ravel() for p in self.parts])
+
+    def set_flat(self, state):
+        """state: {name: flat array}, cut into the groups (copies)"""
+        for name, a in state.items():
+            at, a = 0, np.asarray(a).ravel()
+            for p in self.parts:
+                cur = p["st"][name]
+                p["st"][name] = a[at:at + cur.size].reshape(cur.shape).astype(cur.dtype).copy()
+                at += cur.size
+            assert at == a.size, name
+
+    def mat_of(self, p, e):
+        return self.mats[p["elem_mat"][e] - 1]
+
+    # ---- the steps
+    def element_tangents(self):
+        """-> per group (n_elem_g, 3 nn_g, 3 nn_g)"""
+        u = (self.unode + self.dunode).reshape(-1, 3)
+        out = []
+        for p in self.parts:
+            nn = NODES[p["etype"]]
+            ke = np.zeros((p["conn"].shape[0], 3 * nn, 3 * nn))
+            for e, nd in enumerate(p["conn"] - 1):
+                ke[e] = _stf(p["etype"], self.coord[nd], u[nd], self.mat_of(p, e), self.latch, p["st"], e)
+            out.append(ke)
+        return out
+
+    def stiffness(self):
+        """fstr_StiffMatrix: dense global tangent; hecmw_mat_ass_elem adds every block (collapsed hexahedra: np.add.at)"""
+        n = self.coord.shape[0]
+        K = np.zeros((3 * n, 3 * n))
+        for p, kes in zip(self.parts, self.element_tangents()):
+            for e, ke in enumerate(kes):
+                dofs = (3 * (p["conn"][e][:, None] - 1) + np.arange(3)).ravel()
+                np.add.at(K, (dofs[:, None], dofs[None, :]), ke)
+        return K
+
+    def element_update(self, order=None):
+        """fstr_UpdateNewton's element loop over all groups -> per group qf (n_elem_g, 3 nn_g); self.dstress per group.
+        order: function nn -> node order of the sums (STF_C3 types, the summation-order check)."""
+        u, du = self.unode.reshape(-1, 3), self.dunode.reshape(-1, 3)
+        out, self.dstress = [], []
+        for p in self.parts:
+            s = p["st"]
+            qf = np.zeros((p["conn"].shape[0], 3 * NODES[p["etype"]]))
+            ds = np.zeros_like(s["stress"])
+            for e, nd in enumerate(p["conn"] - 1):
+                qf[e], s["stress"][e], s["strain"][e], s["istat"][e], s["fstat"][e], ds[e] = _update(
+                    p["etype"], self.coord[nd], u[nd], du[nd], self.mat_of(p, e), s, e, order)
+            out.append(qf)
+            self.dstress.append(ds)
+        if any(m.plastic for m in self.mats):       # whichever group held it
+            self.latch = 1
+        return out
+
+    def update(self):
+        qfs = self.element_update()
+        self.qforce[:] = 0.0
+        for p, qf in zip(self.parts, qfs):
+            for e, nd in enumerate(p["conn"] - 1):
+                np.add.at(self.qforce, (3 * nd[:, None] + np.arange(3)).ravel(), qf[e])
+        return self.qforce
+
+    def newton_substep(self, f0, f1, bc, cload, max_iter, converg, maxres=1.0e10):
+        """tet_nl_ref.Model.newton_substep, keeping the norms of every iteration in self.newton_log: rows (iteration, |B|, |X|,
+        |QFORCE|, |dunode|) as fx_newton_substep logs them."""
+        n3 = self.unode.size
+        node, dof, val = bc
+        idx = 3 * (np.asarray(node) - 1) + np.asarray(dof) - 1
+        fixed = np.zeros(n3, dtype=bool)
+        fixed[idx] = True
+        GL = np.zeros(n3) if cload is None else np.asarray(cload) * f1
+        self.dunode[:] = 0.0
+        rhs = GL - self.qforce
+        self.newton_log = []
+        for it in range(1, max_iter + 1):
+            inc = np.asarray(val, dtype=np.float64) * (f1 - f0) if it == 1 else np.zeros(len(idx))
+            K, b = R.apply_bc(self.stiffness(), rhs, (node, dof, inc))
+            x = np.linalg.solve(K, b)
+            self.dunode += x
+            self.update()
+            rhs = GL - self.qforce
+            rhs[fixed] = 0.0
+            res, xn = np.sqrt(rhs @ rhs), np.sqrt(x @ x)
+            qn = np.sqrt(self.qforce @ self.qforce)
+            if qn < 1.0e-8:
+                qn = 1.0
+            dun = xn if it == 1 else np.sqrt(self.dunode @ self.dunode)
+            self.newton_log.append((it, res, xn, qn, dun))
+            if res / qn < converg or xn / dun < converg:
+                self.commit()
+                return True, it
+            if res / qn > maxres:
+                return False, it
+        return False, max_iter
+
+    def commit(self):
+        """fstr_UpdateState"""
+        self.unode += self.dunode
+        self.dunode[:] = 0.0
+        for p in self.parts:
+            s = p["st"]
+            s["stress_bak"][:] = s["stress"]
+            s["strain_bak"][:] = s["strain"]
+            for e in range(p["conn"].shape[0]):
+                if self.mat_of(p, e).plastic:
+                    s["plstrain"][e] = s["fstat"][e]
+
+
+def random_case(mesh, groups, mats, seed, amp=2.0e-3, history=True):
+    """Inputs of an element-level comparison (tet_nl_ref.random_case over groups): smooth unode / dunode of relative size amp and,
+    with `history`, a committed state per group -> (unode, dunode, flat state dict)."""
+    rng = np.random.default_rng(seed)
+    x = mesh.coord
+    L = max(np.ptp(x, axis=0).max(), 1.0)
+    G1, G2 = rng.uniform(-1, 1, (3, 3)) * amp, rng.uniform(-1, 1, (3, 3)) * amp
+    unode = (x @ G1.T + 0.3 * amp * np.sin(2.0 * x / L) * L).ravel()
+    dunode = (x @ G2.T + 0.3 * amp * np.cos(1.5 * x[:, ::-1] / L) * L).ravel()
+    mats = list(mats) if isinstance(mats, (list, tuple)) else [mats]
+    flat = {k: [] for k in STATE6 + STATE1}
+    for g in groups:
+        etype = int(g[0])
+        ne, q = np.asarray(g[1]).size // NODES[etype], POINTS[etype]
+        em = g[3] if len(g) > 3 and g[3] is not None else np.ones(ne, dtype=np.int32)
+        st = {k: np.zeros((ne, q, 6)) for k in STATE6}
+        st.update(plstrain=np.zeros((ne, q)), fstat=np.zeros((ne, q)), istat=np.zeros((ne, q), dtype=np.int32))
+        if history and ne:
+            hyper = np.array([H.kind_of(mats[i - 1]) in (H.MOONEY, H.ARRUDA) for i in em])
+            E = np.array([mats[i - 1].E if mats[i - 1].E > 0 else 1.0 for i in em])
+            nu = np.array([mats[i - 1].nu for i in em])
+            st["strain_bak"] = rng.uniform(-1, 1, (ne, q, 6)) * amp
+            for e in range(ne):
+                st["stress_bak"][e] = st["strain_bak"][e] @ R.elastic_matrix(E[e], nu[e]).T
+            st["stress"] = st["stress_bak"] * (1.0 + 0.05 * rng.uniform(-1, 1, (ne, q, 1)))
+            st["strain"] = st["strain_bak"].copy()
+            pl = np.array([bool(mats[i - 1].plastic) for i in em])[:, None]
+            st["plstrain"] = rng.uniform(0.0, 2.0e-3, (ne, q)) * pl
+            st["fstat"] = st["plstrain"].copy()
+            st["istat"] = ((rng.uniform(size=(ne, q)) < 0.5) & pl).astype(np.int32)
+            del hyper
+        for k in flat:
+            flat[k].append(st[k].ravel())
+    return unode, dunode, {k: np.concatenate(v) for k, v in flat.items()}
+
+
+# ---- the inputs of the GPU comparisons (tests/test_gpu_mixed_nonlinear.py; the CPU test runs the restatement alone on them) ------------
+def _mesh(name, order):
+    from frontistr_amd.mesh import MixedMesh, renumber_groups
+    if name == "n2":
+        return MixedMesh(2, order)
+    if name == "n3":        # 3 hexahedra, 24 wedges, 72 tetrahedra: nq = 8 / 2 / 1 and 27 / 9 / 4 exercise the point offsets
+        return MixedMesh(3, order, skew=0.1, curve=0.03 if order == 2 else 0.0)
+    return renumber_groups(MixedMesh(2, order), 5)      # "n2r"
+
+
+MESHES = ("n2", "n3", "n2r")
+VARIANTS = ("mesh_order", "split_wedges", "empty_middle")
+
+
+def group_list(mesh, variant, elem_mat=None):
+    """The group list of `mesh` (B-bar for 361): the three groups in mesh order; the wedge group cut in two (MixedMesh: its two
+    quadrants), so that one type appears twice; or an empty group in the middle.  elem_mat: 1-based ids in mesh order."""
+    groups = mesh.groups_with(2, elem_mat)
+    if variant == "split_wedges":
+        et, conn, opt, em = groups[1]
+        h = conn.shape[0] // 2
+        groups[1:2] = [(et, np.ascontiguousarray(conn[:h]), opt, None if em is None else np.ascontiguousarray(em[:h])),
+                       (et, np.ascontiguousarray(conn[h:]), opt, None if em is None else np.ascontiguousarray(em[h:]))]
+    elif variant == "empty_middle":
+        et = groups[2][0]
+        groups.insert(1, (et, np.zeros((0, NODES[et]), dtype=np.int32), 2, None if elem_mat is None else np.zeros(0, dtype=np.int32)))
+    elif variant != "mesh_order":
+        raise ValueError(variant)
+    return groups
+
+
+def gpu_case(mesh_name, order, variant, mats, two, seed=17, history=True):
+    """-> (mesh, groups, unode, dunode, flat state).  two: the (arange * 7 // 3) % 2 material pattern of test_gpu_c3_nonlinear.py
+    over the mesh's elements, cut into the groups: odd element counts per NLGEOM group in every part."""
+    mesh = _mesh(mesh_name, order)
+    em = (1 + (np.arange(mesh.n_elem) * 7 // 3) % 2).astype(np.int32) if two else None
+    groups = group_list(mesh, variant, em)
+    unode, dunode, st = random_case(mesh, groups, mats, seed, history=history)
+    return mesh, groups, unode, dunode, st
