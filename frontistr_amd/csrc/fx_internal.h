@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/fistr_hip.h"
@@ -212,6 +213,7 @@ struct AsmGroups {
 
 // One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
 // conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
+constexpr int NL_GROUPS = 7;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
 struct NlPart {
   int32_t etype = 361;                // 361 (B-bar), 341, 342, 351, 352 or 362
   int nn = 8, nq = 8;                 // its nodes and quadrature points per element
@@ -221,8 +223,8 @@ struct NlPart {
   int32_t *conn = nullptr;            // device, nn * n_elem
   int32_t *emat = nullptr;            // device, 1-based material id per element; null with one material
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
-  std::vector<int32_t> grp_off[7];    // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager): positions of its colours in order (+ end)
-  std::vector<int32_t> dup_off[7];    // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
+  std::vector<int32_t> grp_off[NL_GROUPS];  // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager): positions of its colours in order (+ end)
+  std::vector<int32_t> dup_off[NL_GROUPS];  // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
   bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements) or FX_ASM_ATOMIC=1: one range per group, fp64 atomics
   int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
 };

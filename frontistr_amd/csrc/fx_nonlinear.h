@@ -8,9 +8,10 @@
 //                    + BackwardEuler Elastoplastic.f90:351-558 (Mises, isotropic hardening; Mohr-Coulomb and Drucker-Prager:
 //                    fx_yield.h, groups 4..6 of the two element kernels)
 //   k_nl_residual    fstr_Update_NDForce fstr_Residual.f90:23-71
-//   fx_nl_commit     fstr_UpdateState fstr_Update.f90:296-345
-// Hyperelastic materials (MatlMatrix :81-86 from the stored strain, StressUpdate :126-129): group 3 of the two element kernels,
-// point functions in fx_hyperelastic.h.
+//   fx_nl_commit     fstr_UpdateState fstr_Update.f90:296-345 (k_nl_commit, fx_nl_point.h)
+// The tangent of one quadrature point, its return mapping and hardening laws and the groups G are fx_nl_point.h's, shared
+// with the STF_C3 families (fx_nonlinear_tet.h, fx_nonlinear_c3.h); this file holds what is 361's own: hex8_gderiv, the lane
+// mapping of the two kernels, the B-bar terms, k_nl_residual.
 //
 // Work decomposition: 8 lanes per element (8 elements per wave64).  A lane first acts as quadrature
 // point LX = lane: Jacobian, global derivatives, material matrix, stress update and return mapping of
@@ -25,9 +26,7 @@
 // is state of the context: NlDev::latch is set by the first stress update of an elastoplastic material and
 // from then on the tangent uses the elastic matrix, exactly as the reference does.
 #pragma once
-#include "fx_assemble.h"
-#include "fx_hyperelastic.h"
-#include "fx_yield.h"
+#include "fx_nl_point.h"
 
 #define FXN_BLOCK 256
 #define FXN_EPB (FXN_BLOCK / 8)
@@ -55,164 +54,7 @@ __device__ __forceinline__ void hex8_gderiv(const double (&ec)[8][3], double xi,
     for (int j = 0; j < 3; j++) gd[a][j] = dN[a][0] * inv[0][j] + dN[a][1] * inv[1][j] + dN[a][2] * inv[2][j];
 }
 
-// 1-D table lookups (GetTableData / GetTableGrad, ttable.f90:320-335, :221-235)
-__device__ __forceinline__ double nl_table_value(const NlMat &m, double a) {
-  const int n = m.ntab;
-  const double *t = m.tab;
-  if (a < t[1]) return t[0];
-  if (a >= t[2 * (n - 1) + 1]) return t[2 * (n - 1)];
-  for (int i = 0; i < n - 1; i++)
-    if (a >= t[2 * i + 1] && a < t[2 * i + 3]) {
-      const double lambda = (a - t[2 * i + 1]) / (t[2 * i + 3] - t[2 * i + 1]);
-      return (1.0 - lambda) * t[2 * i] + lambda * t[2 * i + 2];
-    }
-  return t[2 * (n - 1)];
-}
-__device__ __forceinline__ double nl_table_grad(const NlMat &m, double a) {
-  const int n = m.ntab;
-  const double *t = m.tab;
-  if (a < t[1]) return 0.0;
-  if (a >= t[2 * (n - 1) + 1]) return 0.0;
-  for (int i = 0; i < n - 1; i++)
-    if (a >= t[2 * i + 1] && a < t[2 * i + 3]) return (t[2 * i + 2] - t[2 * i]) / (t[2 * i + 3] - t[2 * i + 1]);
-  return 0.0;
-}
-// calCurrYield, Elastoplastic.f90:254-292
-__device__ __forceinline__ double nl_curr_yield(const NlMat &m, double p) {
-  switch (m.harden) {
-    case 0: return m.pl[0] + m.pl[1] * p;
-    case 1: return nl_table_value(m, p);
-    case 2: return m.pl[1] * pow(m.pl[0] + p, m.pl[2]);
-    case 3: return (p <= m.pl[0]) ? m.pl[1] : m.pl[1] * pow(p / m.pl[0], 1.0 / m.pl[2]);
-  }
-  return -1.0;
-}
-// calHardenCoeff, Elastoplastic.f90:175-220
-__device__ __forceinline__ double nl_harden_coeff(const NlMat &m, double p) {
-  switch (m.harden) {
-    case 0: return m.pl[1];
-    case 1: return nl_table_grad(m, p);
-    case 2: return m.pl[1] * m.pl[2] * pow(m.pl[0] + p, m.pl[2] - 1.0);
-    case 3: {
-      const double ef = nl_curr_yield(m, p);
-      return m.pl[1] * pow(ef / m.pl[1], 1.0 - m.pl[2]) / (m.pl[0] * m.pl[2]);
-    }
-  }
-  return -1.0;
-}
-
-// BackwardEuler, Mises branch (Elastoplastic.f90:351-459, :557); Y != 0: the Mohr-Coulomb / Drucker-Prager branches of fx_yield.h, whose
-// `stop` statements report through err
-template <int Y = 0>
-__device__ __forceinline__ void nl_backward_euler(const NlMat &m, double (&s)[6], double plstrain, int32_t &istat, double &fstat1,
-                                                  int32_t *err = nullptr) {
-  if constexpr (Y != 0) {
-    yield_backward_euler(m.plastic, m.E, m.nu, m.pl[0], m.pl[1], m.pl[2], m.pl4, s, plstrain, istat, fstat1, err);
-  } else {
-    const double tol = 1.0e-3;
-    const double J1 = (s[0] + s[1] + s[2]) / 3.0;
-    double dv[6] = {s[0] - J1, s[1] - J1, s[2] - J1, s[3], s[4], s[5]};
-    const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
-    const double yd = sqrt(3.0 * J2);
-    double f = yd - nl_curr_yield(m, plstrain);
-    if (fabs(f) < tol) { istat = 1; return; }
-    if (f < 0.0) { istat = 0; return; }
-    istat = 1;
-    const double G = m.E / (2.0 * (1.0 + m.nu));
-    double dlambda = 0.0;
-    for (int i = 0; i < 5; i++) {
-      const double H = nl_harden_coeff(m, plstrain + dlambda);
-      dlambda = dlambda + f / (3.0 * G + H);
-      if (dlambda < 0.0) { dlambda = 0.0; istat = 0; break; }
-      f = yd - 3.0 * G * dlambda - nl_curr_yield(m, plstrain + dlambda);
-      if (fabs(f) < tol * tol) break;
-    }
-    const double fac = 1.0 - 3.0 * dlambda * G / yd;
-    s[0] = fac * dv[0] + J1; s[1] = fac * dv[1] + J1; s[2] = fac * dv[2] + J1;
-    s[3] = fac * dv[3]; s[4] = fac * dv[4]; s[5] = fac * dv[5];
-    fstat1 = plstrain + dlambda;
-  }
-}
-
-// symmetric 6x6 in 21 entries, row-major upper triangle: index of (i,j), i<=j
-__device__ __forceinline__ constexpr int sym21(int i, int j) { return (i <= j) ? (i * (13 - i)) / 2 + (j - i) : (j * (13 - j)) / 2 + (i - j); }
-
-// material matrix of one quadrature point, as STF_C3D8Bbar uses it (:90-101): MatlMatrix with the latch,
-// minus GEOMAT_C3 for the updated-Lagrange flag.  Y != 0: the flow vector of Mohr-Coulomb / Drucker-Prager (fx_yield.h).
-template <int Y = 0>
-__device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int flag, const double (&s)[6], int istat, double fstat1,
-                                                double (&Dm)[21], int32_t *err = nullptr) {
-  double D11, D12, D44;
-  elastic_constants(m.E, m.nu, D11, D12, D44);
-#pragma unroll
-  for (int k = 0; k < 21; k++) Dm[k] = 0.0;
-  Dm[sym21(0, 0)] = D11; Dm[sym21(1, 1)] = D11; Dm[sym21(2, 2)] = D11;
-  Dm[sym21(0, 1)] = D12; Dm[sym21(0, 2)] = D12; Dm[sym21(1, 2)] = D12;
-  Dm[sym21(3, 3)] = D44; Dm[sym21(4, 4)] = D44; Dm[sym21(5, 5)] = D44;
-  if (m.plastic && !latch && istat != 0) {  // calElastoPlasticMatrix, Mises (:49-115)
-    const double J1 = s[0] + s[1] + s[2];
-    const double dv[6] = {s[0] - J1 / 3.0, s[1] - J1 / 3.0, s[2] - J1 / 3.0, s[3], s[4], s[5]};
-    const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
-    double a[6];
-    bool flow = true;
-    if constexpr (Y != 0) {
-      flow = yield_flow_vector(m.plastic, m.pl[2], dv, J2, a, err);
-    } else {
-      const double q = 2.0 * sqrt(J2), r3 = sqrt(3.0);
-      a[0] = r3 * (dv[0] / q); a[1] = r3 * (dv[1] / q); a[2] = r3 * (dv[2] / q);
-      a[3] = r3 * (2.0 * dv[3] / q); a[4] = r3 * (2.0 * dv[4] / q); a[5] = r3 * (2.0 * dv[5] / q);
-    }
-    if (flow) {
-      double da[6];
-      iso_stress(D11, D12, D44, a, da);
-      double dum = 0.0;
-#pragma unroll
-      for (int i = 0; i < 6; i++) dum += da[i] * a[i];
-      dum = nl_harden_coeff(m, fstat1) + dum;
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++) Dm[sym21(i, j)] -= da[i] * da[j] / dum;
-    }
-  }
-  if (flag == 2) {  // GEOMAT_C3
-    Dm[sym21(0, 0)] -= 2.0 * s[0]; Dm[sym21(0, 3)] -= s[3]; Dm[sym21(0, 5)] -= s[5];
-    Dm[sym21(1, 1)] -= 2.0 * s[1]; Dm[sym21(1, 3)] -= s[3]; Dm[sym21(1, 4)] -= s[4];
-    Dm[sym21(2, 2)] -= 2.0 * s[2]; Dm[sym21(2, 4)] -= s[4]; Dm[sym21(2, 5)] -= s[5];
-    Dm[sym21(3, 3)] -= 0.5 * (s[0] + s[1]); Dm[sym21(3, 4)] -= 0.5 * s[5]; Dm[sym21(3, 5)] -= 0.5 * s[4];
-    Dm[sym21(4, 4)] -= 0.5 * (s[2] + s[1]); Dm[sym21(4, 5)] -= 0.5 * s[3];
-    Dm[sym21(5, 5)] -= 0.5 * (s[0] + s[2]);
-  }
-}
-
-// strain-displacement block of one node incl. the B-bar correction and, for the total-Lagrange flag, BL1
-// (static_LIB_C3D8.f90:103-158): g = global derivatives of the node, h = (Bbar - g)/3, F = gdispderiv.
-template <int NLGEOM>
-__device__ __forceinline__ void nl_node_B(const double *g, const double *h, const double (&F)[9], double (&B)[6][3]) {
-  node_B(g, h, B);
-  if (NLGEOM == 1) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) {  // F[3*c+d] = gdispderiv(c+1, d+1)
-      B[0][c] += F[3 * c + 0] * g[0];
-      B[1][c] += F[3 * c + 1] * g[1];
-      B[2][c] += F[3 * c + 2] * g[2];
-      B[3][c] += F[3 * c + 1] * g[0] + F[3 * c + 0] * g[1];
-      B[4][c] += F[3 * c + 1] * g[2] + F[3 * c + 2] * g[1];
-      B[5][c] += F[3 * c + 2] * g[0] + F[3 * c + 0] * g[2];
-    }
-  }
-}
-
 __device__ __forceinline__ double bcast8(double v, int src) { return __shfl(v, src, 8); }
-
-// Compile-time group G of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG -- the NLGEOM flag of an ELASTIC / Mises material --
-// and 3: total-Lagrange kinematics with the hyperelastic point functions of fx_hyperelastic.h (the material kind, Mooney-Rivlin family
-// or Arruda-Boyce, is a run-time branch on the element's NlMat).  `strain` (the points' stored strain) is read by group 3 only.
-// Groups 4, 5, 6: the three flags again for a Mohr-Coulomb or Drucker-Prager material (fx_yield.h; which of the two is a run-time
-// branch on NlMat::plastic).  The yield family is a compile-time parameter so that the instantiations 0..3 stay what they were:
-// k_nl_stiffness<1> sits at 512 VGPRs with scratch and has no register to give to another branch.
-__device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : (G >= 4 ? G - 4 : G); }
-__device__ __forceinline__ constexpr int nl_group_yield(int G) { return G >= 4 ? 1 : 0; }
 
 template <int G>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, const double *__restrict__ coord,
@@ -595,18 +437,4 @@ __global__ void k_nl_residual(int64_t n3, const double *__restrict__ GL, const d
                               const uint8_t *__restrict__ flag, double *__restrict__ B) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
     B[i] = (flag && flag[i]) ? 0.0 : GL[i] - Q[i];
-}
-
-// fstr_UpdateState: plstrain = fstatus(1) (updateEPState), strain_bak/stress_bak = strain/stress
-__global__ void k_nl_commit(int64_t npt, int plastic, const double *__restrict__ fstat, double *__restrict__ plstrain,
-                            const double *__restrict__ stress, const double *__restrict__ strain, double *__restrict__ stress_bak,
-                            double *__restrict__ strain_bak, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 6 * npt; i += (int64_t)gridDim.x * blockDim.x) {
-    stress_bak[i] = stress[i];
-    strain_bak[i] = strain[i];
-    if (i < npt) {  // isElastoplastic(pMaterial%mtype) of the point's element (fstr_Update.f90:323-326)
-      const int pl = mats ? mats[emat[i >> 3] - 1].plastic : plastic;
-      if (pl) plstrain[i] = fstat[i];
-    }
-  }
 }

@@ -2,7 +2,7 @@
 // TYPE=362: STF_C3 (static_LIB_3d.f90:47-205) with `u` present and UPDATE_C3 (:516-837) without temperatures -- with the
 // tetrahedra of fx_nonlinear_tet.h the five types fstr_StiffMatrix.f90:134-144 and fstr_Update.f90:182-189 send through these
 // two routines inside fstr_Newton.  Element data: fx_c3_element.h; staging (c3_stage) and lane mappings: fx_assemble_c3.h; the
-// material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening): fx_nonlinear.h.
+// material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening): fx_nl_point.h.
 //
 // k_nl_stiffness_c3 keeps k_assemble_c3's lane mapping (one lane per upper block a <= b: 21 / 120 / 210 lanes, 12 / 2 / 1
 // elements per workgroup) and its staging, in the configuration STF_C3 takes the derivatives in: ecoord + u for UPDATELAG (:91),
@@ -26,7 +26,7 @@
 // 27 / 43 / 38 KB per workgroup.
 #pragma once
 #include "fx_assemble_c3.h"
-#include "fx_nonlinear_tet.h"
+#include "fx_nl_point.h"
 
 // Arguments as k_nl_stiffness_tet.
 template <int ETYPE, int G>
@@ -119,6 +119,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
                   !atomic, err))
     return;
   double K[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  // The body is nl_block_point's (fx_nl_point.h), written out: called from this rolled loop, in any of five shapes tried, the
+  // function costs k_nl_stiffness_c3<352, 0> and <351, 4> a wave per SIMD ("What the nonlinear element kernels share")
 #pragma unroll 1
   for (int q = 0; q < NQ; q++) {
     const double h0[3] = {0.0, 0.0, 0.0};

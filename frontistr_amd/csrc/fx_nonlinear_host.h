@@ -101,7 +101,7 @@ static int nl_part_lists(fx_context *c, NlPart &p, const NlPartIn &in, int32_t n
   // coloured: the elements that name a node twice go to their own list (colors.dup, dup_off), as in the linear assembly
   std::vector<int32_t> grouped, dups;
   grouped.reserve((size_t)in.n_elem);
-  for (int g = 0; g < 7; g++) {
+  for (int g = 0; g < NL_GROUPS; g++) {
     p.grp_off[g].clear();
     p.dup_off[g].clear();
     std::vector<int32_t> doff(1, (int32_t)dups.size());
@@ -208,7 +208,7 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
       // first-write flags in the order of the launches (part after part, group after group, colour after colour): the boundaries
       // of all the launches are the `colours` the flags are made for (none of the elements is in colors.dup: they were refused)
       p.colors.offsets.assign(1, 0);
-      for (int g = 0; g < 7; g++)
+      for (int g = 0; g < NL_GROUPS; g++)
         for (size_t k = 1; k < p.grp_off[g].size(); k++)
           if (p.grp_off[g][k] > p.colors.offsets.back()) p.colors.offsets.push_back(p.grp_off[g][k]);
     }
@@ -315,17 +315,33 @@ extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *co
   HIP_TRY(hipSetDevice(c->device));                                                                 \
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }
 
-// One NLGEOM group of a context of an STF_C3 type: k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362
+// f(std::integral_constant<int, G>()) for every group G of the element kernels, in order
+template <class F, int... G>
+static void for_each_nl_group(F &&f, std::integer_sequence<int, G...>) {
+  (f(std::integral_constant<int, G>()), ...);
+}
+template <class F>
+static void for_each_nl_group(F &&f) {
+  for_each_nl_group(f, std::make_integer_sequence<int, NL_GROUPS>());
+}
+// The element kernel of one type and group: k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362, and for the stress
+// update, whose three kernels take the same arguments, k_nl_update of 361 (its tangent has a launcher of its own)
 template <int ETYPE, int G, bool UPDATE>
 static constexpr auto nl_c3_kernel() {
   if constexpr (UPDATE) {
-    if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
+    if constexpr (ETYPE == 361) return k_nl_update<G>;
+    else if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
     else return k_nl_update_c3<ETYPE, G>;
   } else {
+    static_assert(ETYPE != 361, "k_nl_stiffness<G>: nl_launch_stiffness_group");
     if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G>;
     else return k_nl_stiffness_c3<ETYPE, G>;
   }
 }
+template <int ETYPE>
+static constexpr int NL_UPDATE_EPB = ETYPE == 361 ? FXN_EPB : C3El<ETYPE>::UEPB;  // elements per workgroup of the update kernel
+template <int ETYPE>
+static constexpr int NL_UPDATE_BLOCK = ETYPE == 361 ? FXN_BLOCK : C3El<ETYPE>::BS;
 // A part's block of the per-point arrays
 struct NlPartState {
   double *stress, *strain, *stress_bak, *strain_bak, *plstrain, *fstat;
@@ -350,41 +366,26 @@ static void nl_launch_stiffness_c3_group(fx_context *c, const NlPart &p, double 
                        (const double *)s.strain);
   });
 }
+// The stress update of one group of a part of any of the six types
 template <int ETYPE, int G>
-static void nl_launch_update_c3_group(fx_context *c, const NlPart &p, double *qf_out) {
+static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
-  const std::vector<int32_t> &off = p.grp_off[G];
-  if (off.empty() || off.back() <= off.front()) return;
   const NlPartState s = nl_part_state(n, p);
-  const int32_t e0 = off.front(), e1 = off.back();
-  const int32_t *list = (e0 == 0 && e1 == p.n_elem) ? nullptr : p.colors.order;  // as nl_launch_update_group
-  using El = C3El<ETYPE>;
-  hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + El::UEPB - 1) / El::UEPB)), dim3(El::BS), 0, c->stream, e1, n.coord, p.conn, n.unode,
-                     n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out, list,
-                     e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
-}
-// the seven groups of a part of an STF_C3 type: tangent (update == false) or stress update
-static void nl_launch_c3(fx_context *c, const NlPart &p, double *Kout, double *qf_out, bool update) {
-  with_c3_type(p.etype, [&](auto t) {
-    constexpr int ET = decltype(t)::value;
-    if (update) {
-      nl_launch_update_c3_group<ET, 0>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 1>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 2>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 3>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 4>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 5>(c, p, qf_out);
-      nl_launch_update_c3_group<ET, 6>(c, p, qf_out);
-    } else {
-      nl_launch_stiffness_c3_group<ET, 0>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 1>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 2>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 3>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 4>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 5>(c, p, Kout);
-      nl_launch_stiffness_c3_group<ET, 6>(c, p, Kout);
-    }
-  });
+  auto launch = [&](const int32_t *list, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + NL_UPDATE_EPB<ETYPE> - 1) / NL_UPDATE_EPB<ETYPE>)),
+                       dim3(NL_UPDATE_BLOCK<ETYPE>), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, s.stress, s.strain,
+                       s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats,
+                       (const int32_t *)p.emat, n.err);
+  };
+  const std::vector<int32_t> &off = p.grp_off[G];
+  // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
+  // force is scattered with atomics either way
+  if (!off.empty() && off.back() > off.front())
+    launch((off.front() == 0 && off.back() == p.n_elem) ? nullptr : p.colors.order, off.front(), off.back());
+  if constexpr (ETYPE == 361) {  // the collapsed elements of the group: only 361 has them, the other types refuse them at init
+    const std::vector<int32_t> &doff = p.dup_off[G];
+    if (!doff.empty()) launch(p.colors.dup, doff.front(), doff.back());
+  }
 }
 
 template <int G>
@@ -425,53 +426,26 @@ static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel ins
   size_t dup_at = 0;
   for (const NlPart &p : c->nl.parts) {
     double *K = Kout ? Kout + p.k_off : nullptr;
-    if (p.etype != 361) { nl_launch_c3(c, p, K, nullptr, false); continue; }
+    if (p.etype != 361) {
+      with_c3_type(p.etype, [&](auto t) {
+        for_each_nl_group([&](auto g) { nl_launch_stiffness_c3_group<decltype(t)::value, decltype(g)::value>(c, p, K); });
+      });
+      continue;
+    }
     double *dk = dup_k ? dup_k + (size_t)576 * dup_at : nullptr;
     dup_at += (size_t)p.n_dup;
-    nl_launch_stiffness_group<0>(c, p, K, dk);
-    nl_launch_stiffness_group<1>(c, p, K, dk);
-    nl_launch_stiffness_group<2>(c, p, K, dk);
-    nl_launch_stiffness_group<3>(c, p, K, dk);
-    nl_launch_stiffness_group<4>(c, p, K, dk);
-    nl_launch_stiffness_group<5>(c, p, K, dk);
-    nl_launch_stiffness_group<6>(c, p, K, dk);
+    for_each_nl_group([&](auto g) { nl_launch_stiffness_group<decltype(g)::value>(c, p, K, dk); });
   }
   if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
   return 0;
 }
-template <int G>
-static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
-  NlDev &n = c->nl;
-  const NlPartState s = nl_part_state(n, p);
-  const std::vector<int32_t> &off = p.grp_off[G];
-  if (!off.empty() && off.back() > off.front()) {
-    const int32_t e0 = off.front(), e1 = off.back();
-    // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
-    // force is scattered with atomics either way
-    const int32_t *list = (e0 == 0 && e1 == p.n_elem) ? nullptr : p.colors.order;
-    hipLaunchKernelGGL((k_nl_update<G>), dim3((e1 - e0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, p.conn,
-                       n.unode, n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce,
-                       qf_out, list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
-  }
-  const std::vector<int32_t> &doff = p.dup_off[G];  // the collapsed elements of the group
-  if (!doff.empty())
-    hipLaunchKernelGGL((k_nl_update<G>), dim3((doff.back() - doff.front() + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream,
-                       doff.back(), n.coord, p.conn, n.unode, n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain,
-                       s.fstat, s.istat, n.qforce, qf_out, (const int32_t *)p.colors.dup, doff.front(), (const NlMat *)n.mats,
-                       (const int32_t *)p.emat, n.err);
-}
 static void nl_launch_update(fx_context *c, double *qf_out) {  // qf_out: the element forces of all parts one after the other, or null
-  for (const NlPart &p : c->nl.parts) {
-    double *qf = qf_out ? qf_out + p.qf_off : nullptr;
-    if (p.etype != 361) { nl_launch_c3(c, p, nullptr, qf, true); continue; }
-    nl_launch_update_group<0>(c, p, qf);
-    nl_launch_update_group<1>(c, p, qf);
-    nl_launch_update_group<2>(c, p, qf);
-    nl_launch_update_group<3>(c, p, qf);
-    nl_launch_update_group<4>(c, p, qf);
-    nl_launch_update_group<5>(c, p, qf);
-    nl_launch_update_group<6>(c, p, qf);
-  }
+  for (const NlPart &p : c->nl.parts)
+    with_solid_type(p.etype, [&](auto t) {
+      for_each_nl_group([&](auto g) {
+        nl_launch_update_group<decltype(t)::value, decltype(g)::value>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
+      });
+    });
 }
 // The stress update of a context with a Mohr-Coulomb / Drucker-Prager section reports the reference's `stop` statements through the
 // error word: cleared before the launches, read after them (one 4-byte copy; contexts without such a section skip both).
@@ -676,12 +650,8 @@ extern "C" int fx_nl_commit(fx_context *c) {
   for (const NlPart &p : n.parts) {  // the kernels find a point's material through its element: part by part
     const NlPartState s = nl_part_state(n, p);
     const int64_t npt = (int64_t)p.nq * p.n_elem;
-    if (p.etype == 361)
-      hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, n.mat.plastic, s.fstat, s.plstrain, s.stress,
-                         s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
-    else
-      hipLaunchKernelGGL(k_nl_commit_c3, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat.plastic, s.fstat, s.plstrain,
-                         s.stress, s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
+    hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat.plastic, s.fstat, s.plstrain,
+                       s.stress, s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -1,7 +1,7 @@
 // Nonlinear (total / updated Lagrange, Mises elastoplastic) path of the tetrahedra TYPE=341 and TYPE=342: STF_C3
 // (static_LIB_3d.f90:47-205) with `u` present and UPDATE_C3 (:516-837) without temperatures, as fstr_StiffMatrix.f90:134-144 and
 // fstr_Update.f90:182-189 call them inside fstr_Newton.  The element data (shape functions, quadrature) is that of
-// fx_c3_element.h, the Jacobian fx_assemble_tet.h's, the material point (MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening) that of fx_nonlinear.h.
+// fx_c3_element.h, the Jacobian fx_assemble_tet.h's, the material point (nl_block_point; MatlMatrix with its latch, GEOMAT_C3, BackwardEuler, hardening) that of fx_nl_point.h.
 //
 // k_nl_stiffness_tet keeps the lane mapping of k_assemble_tet: the element matrix is symmetric in all three branches (D is held
 // as 21 entries, the initial-stress term is symmetric), so one lane owns one upper block a <= b (10 lanes at 341, 55 at 342) and
@@ -15,12 +15,10 @@
 //
 // UPDATE_C3's UPDATELAG branch computes `dstress = real( matmul(D, dstrain) )` (:718): REAL() of a double-precision argument
 // without KIND is default real, so the reference rounds the stress increment to single precision before it adds it to the
-// stress of the last converged sub-step (Update_C3D8Bbar has no real() there).  fx_real_default() restates that.
+// stress of the last converged sub-step (Update_C3D8Bbar has no real() there).  fx_real_default() (fx_nl_point.h) restates that.
 #pragma once
 #include "fx_assemble_tet.h"
-#include "fx_nonlinear.h"
-
-__device__ __forceinline__ double fx_real_default(double x) { return (double)(float)x; }
+#include "fx_nl_point.h"
 
 // global derivatives of node n at a point whose inverse Jacobian is inv (row-major 3x3): getGlobalDeriv, element.f90:693-744
 template <int ETYPE>
@@ -137,45 +135,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
     return;
   double K[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int q = 0; q < NQ; q++) {
-    const double h0[3] = {0.0, 0.0, 0.0};
-    const double *ga = Gsh[el][q][a], *gb = Gsh[el][q][b], *Dl = Dsh[el][q];
-    const double w = Jsh[el][q][9];
-    double F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (NLGEOM == 1) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) F[i] = Fsh[el][q][i % NF];
-    }
-    double Ba[6][3], Bb[6][3], DB[6][3];
-    nl_node_B<NLGEOM>(ga, h0, F, Ba);  // BL0 (+ BL1 for TOTALLAG, :120-162)
-    nl_node_B<NLGEOM>(gb, h0, F, Bb);
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double s = 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; p++) s += Dl[sym21(r, p)] * Bb[p][j];
-        DB[r][j] = s;
-      }
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double s = 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; p++) s += Ba[p][i] * DB[p][j];
-        K[3 * i + j] += s * w;
-      }
-    if (NLGEOM != 0) {  // initial-stress matrix BN^T S BN (:170-199): (grad N_a . S grad N_b) on the diagonal of the block
-      const double *Sl = Ssh[el][q];
-      const double sb0 = Sl[0 % NS] * gb[0] + Sl[3 % NS] * gb[1] + Sl[5 % NS] * gb[2];
-      const double sb1 = Sl[3 % NS] * gb[0] + Sl[1 % NS] * gb[1] + Sl[4 % NS] * gb[2];
-      const double sb2 = Sl[5 % NS] * gb[0] + Sl[4 % NS] * gb[1] + Sl[2 % NS] * gb[2];
-      const double geo = (ga[0] * sb0 + ga[1] * sb1 + ga[2] * sb2) * w;
-      K[0] += geo; K[4] += geo; K[8] += geo;
-    }
-  }
+  for (int q = 0; q < NQ; q++)
+    nl_block_point<NLGEOM>(Gsh[el][q][a], Gsh[el][q][b], Dsh[el][q], Ssh[el][q], Fsh[el][q], Jsh[el][q][9], K);
   sc.commit(K, Kout, (size_t)elem * (9 * NN * NN));
 }
 
@@ -326,20 +287,6 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
         if (qf_out) qf_out[(size_t)elem * (3 * NN) + 3 * a + d] = o[d];
         else unsafeAtomicAdd(qforce + (size_t)3 * (nod[a] - 1) + d, o[d]);
       }
-    }
-  }
-}
-
-// fstr_UpdateState for nq points per element: as k_nl_commit, the element of point i is i / nq
-__global__ void k_nl_commit_c3(int64_t npt, int nq, int plastic, const double *__restrict__ fstat, double *__restrict__ plstrain,
-                               const double *__restrict__ stress, const double *__restrict__ strain, double *__restrict__ stress_bak,
-                               double *__restrict__ strain_bak, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 6 * npt; i += (int64_t)gridDim.x * blockDim.x) {
-    stress_bak[i] = stress[i];
-    strain_bak[i] = strain[i];
-    if (i < npt) {
-      const int pl = mats ? mats[emat[i / nq] - 1].plastic : plastic;
-      if (pl) plstrain[i] = fstat[i];
     }
   }
 }

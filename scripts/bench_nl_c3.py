@@ -5,7 +5,7 @@ case per kinematics: elastic INFINITE, elastic TOTALLAG and Mises multilinear UP
 block written once) + 8 (6 + 1 + 0.5) nq per element of state read (stress, fstatus, istatus) + two displacement vectors; update =
 the state read and written once (8 (6 + 6 + 6 + 6 + 1 + 1 + 1 + 0.5 + 0.5) nq: stress / strain out, stress_bak / strain_bak / plstrain
 in, fstatus and istatus both ways) + connectivity, coordinates, two displacement vectors and QFORCE.
-usage: bench_nl_c3.py [--etype 351|352|362] N"""
+usage: bench_nl_c3.py [--etype 351|352|362] [--lib PATH] N"""
 import ctypes as C
 import json
 import os
@@ -16,6 +16,9 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from frontistr_amd import fstr, hecmw as hip          # noqa: E402
 from frontistr_amd.mesh import solid_mesh             # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 etype = 362
 if "--etype" in sys.argv:

@@ -4,7 +4,7 @@ of the same mesh (fx_nl_stiffness_at / fx_nl_update_at, three warm calls each, i
 TYPE=361 (CubeMesh) and as TYPE=342 (TetMesh), materials elastic TOTALLAG, Mooney-Rivlin and Arruda-Boyce.  G = 3 does strictly more
 arithmetic than G = 1 on the same scatter and reads 48 bytes more per quadrature point (the stored strain), so there is no target
 ratio; the G = 1 figures are there to be compared with the same script on the parent commit.
-usage: bench_nl_hyper.py [--etype 361|342] [N]        (both types when --etype is not given; N = 40 as bench_nl_c3.py)"""
+usage: bench_nl_hyper.py [--etype 361|342] [--lib PATH] [N]        (both types when --etype is not given; N = 40 as bench_nl_c3.py)"""
 import ctypes as C
 import json
 import os
@@ -15,6 +15,9 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from frontistr_amd import fstr, hecmw as hip          # noqa: E402
 from frontistr_amd.mesh import CubeMesh, solid_mesh   # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 etypes = [361, 342]
 if "--etype" in sys.argv:

@@ -5,7 +5,7 @@ MixedMesh(n, order) beside the three single-type contexts that hold the same ele
 kernels are the same; what the figures show is launch and clearing overhead (a group context with a 361 part clears the matrix
 once and takes no first-write flags; a single-type STF_C3 context stores its first contributions instead).  No pass / fail bound.
 Materials: Mises BILINEAR UPDATELAG, or with --two-sections that beside ELASTIC TOTALLAG in the (arange * 7 // 3) % 2 pattern.
-usage: bench_nl_mixed.py [--order 1|2] [--two-sections] [N]        (both orders when --order is not given; N = 24)"""
+usage: bench_nl_mixed.py [--order 1|2] [--two-sections] [--lib PATH] [N]        (both orders when --order is not given; N = 24)"""
 import ctypes as C
 import json
 import os
@@ -16,6 +16,9 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from frontistr_amd import fstr, hecmw as hip          # noqa: E402
 from frontistr_amd.mesh import MixedMesh              # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 orders = [1, 2]
 if "--order" in sys.argv:

@@ -5,7 +5,7 @@ multilinear UPDATELAG.  Algorithmic bytes: stiffness = the linear count (connect
 block written once) + 8 (6 + 1 + 0.5) nq per element of state read (stress, fstatus, istatus) + two displacement vectors; update =
 the state read and written once (8 (6 + 6 + 6 + 6 + 1 + 1 + 1 + 0.5 + 0.5) nq: stress / strain out, stress_bak / strain_bak / plstrain
 in, fstatus and istatus both ways) + connectivity, coordinates, two displacement vectors and QFORCE.
-usage: bench_nl_tet.py [--etype 341|342] N"""
+usage: bench_nl_tet.py [--etype 341|342] [--lib PATH] N      (--lib: another build of libfistr_hip.so, e.g. the parent commit's)"""
 import ctypes as C
 import json
 import os
@@ -16,6 +16,9 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from frontistr_amd import fstr, hecmw as hip          # noqa: E402
 from frontistr_amd.mesh import TetMesh                # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 etype = 342
 if "--etype" in sys.argv:

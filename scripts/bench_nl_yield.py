@@ -23,12 +23,13 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from frontistr_amd import fstr, hecmw as hip          # noqa: E402
 from frontistr_amd.mesh import CubeMesh, solid_mesh   # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 etypes = [361, 342]
 if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etypes = [int(sys.argv[k + 1])]; del sys.argv[k:k + 2]
-if "--lib" in sys.argv:
-    k = sys.argv.index("--lib"); hip.LIBPATH = os.path.abspath(sys.argv[k + 1]); del sys.argv[k:k + 2]
 only_mises = "--only-mises" in sys.argv
 if only_mises:
     sys.argv.remove("--only-mises")

@@ -1,6 +1,6 @@
 """Timing of one Newton iteration of the nonlinear static loop (configs[4] shape: elastoplastic,
 updated Lagrange, B-bar) on the synthetic cube: tangent assembly, linear solve, stress update.
-usage: python scripts/bench_nonlinear.py [n_elem_per_edge] [method] [precond] [newton_iters]"""
+usage: python scripts/bench_nonlinear.py [--lib PATH] [n_elem_per_edge] [method] [precond] [newton_iters]"""
 import json
 import os
 import sys
@@ -11,6 +11,9 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from frontistr_amd import fstr, hecmw as hip              # noqa: E402
 from frontistr_amd.mesh import CubeMesh                   # noqa: E402
+from _libarg import take_lib                          # noqa: E402
+
+take_lib()
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 149
 method = int(sys.argv[2]) if len(sys.argv) > 2 else 1
