@@ -116,7 +116,7 @@ PhaseTimer::PhaseTimer(const char *w) : t0(now_s()), on(getenv("FX_TIMING") && a
 void PhaseTimer::lap(const char *phase) {
   if (!on) return;
   const double t = now_s();
-  fprintf(stderr, "[fx timing] %s / %s: %.3f s\n", what, phase, t - t0);
+  fprintf(stderr, "[fx timing] %s / %s: %.6f s\n", what, phase, t - t0);
   t0 = t;
 }
 
@@ -445,7 +445,8 @@ static void bell_free(Bell &b) {
 static void nl_free(fx_context *c);  // fx_nonlinear_host.h
 static void nn_free(fx_context *c);  // fx_nn_host.h
 static void graphs_destroy(fx_context *c);
-static void asm_groups_free(fx_context *c) {  // the groups' maps belong to the profile too
+static void upd_stage_free(fx_context *c);  // fx_assemble_groups.h
+static void asm_groups_free(fx_context *c) {  // the cache of the linear assembly: colourings and maps of the last call's groups
   for (ElemColors &ec : c->asm_groups.ec) { dev_free(ec.order); dev_free(ec.pos); dev_free(ec.dup); }
   c->asm_groups = AsmGroups();
 }
@@ -464,9 +465,7 @@ static void free_matrix(fx_context *c) {
   c->wlen = 0;
   c->max_partials = 0;
   c->have_profile = c->have_values = c->bell_valid = false;
-  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos); dev_free(c->asm_colors.dup);  // the scatter map belongs to the profile
-  c->asm_colors = ElemColors();
-  asm_groups_free(c);
+  asm_groups_free(c);  // the colourings' scatter maps belong to the profile
 }
 
 static void free_precond(fx_context *c) {
@@ -488,8 +487,7 @@ extern "C" void fx_destroy(fx_context *c) {
   graphs_destroy(c);
   nl_free(c);
   nn_free(c);
-  dev_free(c->asm_colors.order); dev_free(c->asm_colors.pos); dev_free(c->asm_colors.dup);
-  c->asm_colors = ElemColors();
+  upd_stage_free(c);
   free_precond(c);
   free_matrix(c);
   arena_destroy(c);

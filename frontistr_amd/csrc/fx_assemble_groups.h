@@ -41,7 +41,7 @@ static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group
   return 0;
 }
 
-// What the entry points that take groups (these, and fx_nl_init_groups) refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
+// What the linear entry points and fx_nl_init_groups refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
 // material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
 static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                         int32_t n_mat, bool have_mats) {
@@ -86,7 +86,7 @@ static int check_groups(const char *who, int32_t n_node, const double *coord, in
 // The (D11, D12, D44) table of the materials on the device, every group's connectivity and material ids.
 struct GroupUploads {
   std::vector<const int32_t *> conn, emat;
-  const double *mtab = nullptr;
+  const double *mtab = nullptr;            // null when no group has elem_mat
   double D11 = 0.0, D12 = 0.0, D44 = 0.0;  // material 1: what a group without elem_mat takes
   std::vector<double> tab;                 // host copy of mtab: lives until the caller's synchronize
 };
@@ -97,10 +97,14 @@ static int upload_groups(fx_context *c, DevScratch &tmp, int32_t n_group, const 
   up.tab.resize((size_t)3 * n_mat);
   for (int32_t k = 0; k < n_mat; k++) elastic_constants(E[k], nu[k], up.tab[3 * k], up.tab[3 * k + 1], up.tab[3 * k + 2]);
   up.D11 = up.tab[0]; up.D12 = up.tab[1]; up.D44 = up.tab[2];
-  double *d_mtab = nullptr;
-  if (tmp.alloc(&d_mtab, up.tab.size())) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(d_mtab, up.tab.data(), up.tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-  up.mtab = d_mtab;
+  bool by_element = false;  // some group selects its materials per element: the table goes to the device
+  for (int32_t g = 0; g < n_group; g++) by_element |= groups[g].n_elem > 0 && groups[g].elem_mat;
+  if (by_element) {
+    double *d_mtab = nullptr;
+    if (tmp.alloc(&d_mtab, up.tab.size())) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(d_mtab, up.tab.data(), up.tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    up.mtab = d_mtab;
+  }
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
     if (G.n_elem < 1) continue;
@@ -118,21 +122,15 @@ static int upload_groups(fx_context *c, DevScratch &tmp, int32_t n_group, const 
   return 0;
 }
 
-extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                                  int32_t n_mat, const double *E, const double *nu, const double *load, int32_t n_bc,
-                                  const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
-  const char *who = "fx_assemble_groups";
-  if (!c) { g_fx_error = "fx_assemble_groups: null argument"; return FX_ERROR_RUNTIME; }
+// The assembly of every linear entry point; `who` is the entry point called.  All groups into the resident matrix, group after
+// group, colour after colour; first-write (no clearing) where every group is coloured, mapped, free of collapsed elements and
+// the groups cover the profile, otherwise the matrix is cleared once.
+static int assemble_groups_driver(const char *who, fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
+                                  const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu, const double *load,
+                                  int32_t n_bc, const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
+  PhaseTimer pt("assemble");
   if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
-  if (n_group == 1) {  // the single-type entry points, and their cache (c->asm_colors)
-    const fx_elem_group &G = groups[0];
-    const fx_mesh_view mesh = {n_node, G.n_elem, coord, G.conn};
-    if (!G.elem_mat)
-      return assemble_c3d8_common(c, &mesh, E[0], nu[0], 0, nullptr, nullptr, nullptr, G.elemopt, load, n_bc, bc_node, bc_dof, bc_val,
-                                  ms_assemble, G.etype);
-    return assemble_c3d8_common(c, &mesh, 0.0, 0.0, n_mat, E, nu, G.elem_mat, G.elemopt, load, n_bc, bc_node, bc_dof, bc_val,
-                                ms_assemble, G.etype);
-  }
+  pt.lap("check_groups");
   HIP_TRY(hipSetDevice(c->device));
   if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
   if (n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
@@ -157,6 +155,7 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
   std::vector<double *> d_dupk((size_t)n_group, nullptr);  // element matrices of the collapsed hexahedra
   for (int32_t g = 0; g < n_group; g++)
     if (!ag.ec[g].dup_off.empty() && tmp.alloc(&d_dupk[g], (size_t)576 * ag.ec[g].dup_off.back())) return FX_ERROR_RUNTIME;
+  pt.lap("uploads, colours, maps");
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   if (!ag.first_write && mat_clear(c)) return FX_ERROR_RUNTIME;  // once
   for (int32_t g = 0; g < n_group; g++) {
@@ -168,155 +167,240 @@ extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *c
   HIP_TRY(hipGetLastError());
   if (int rc = load_and_bc(c, tmp, who, load, n_bc, bc_node, bc_dof, bc_val)) return rc;
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  int32_t herr = 0;
+  int32_t herr = 0;  // the streaming (BELL) layouts re-gather these values on next use (ensure_solver)
   HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  pt.lap("kernels");
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_assemble) *ms_assemble = ms;
   if (int rc = assembly_error(herr)) return rc;
   c->have_values = true;
-  c->bell_valid = false;
+  c->bell_valid = false;  // the preconditioner is refreshed by the flags / recycle policy of the next solve, not here
   return 0;
 }
 
+extern "C" int fx_assemble_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                  int32_t n_mat, const double *E, const double *nu, const double *load, int32_t n_bc,
+                                  const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
+  if (!c) return fx_fail("fx_assemble_groups", FX_ERROR_RUNTIME, "null argument");
+  return assemble_groups_driver("fx_assemble_groups", c, n_node, coord, n_group, groups, n_mat, E, nu, load, n_bc, bc_node, bc_dof,
+                                bc_val, ms_assemble);
+}
+
+// The single-type entry points: one group.
+extern "C" int fx_assemble_c3d8(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int elemopt, const double *load,
+                                int32_t n_bc, const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val,
+                                float *ms_assemble) {
+  if (!c || !mesh) return fx_fail("fx_assemble_c3d8", FX_ERROR_RUNTIME, "null argument");
+  const fx_elem_group G = {361, elemopt, mesh->n_elem, mesh->conn, nullptr};
+  return assemble_groups_driver("fx_assemble_c3d8", c, mesh->n_node, mesh->coord, 1, &G, 1, &E, &nu, load, n_bc, bc_node, bc_dof, bc_val,
+                                ms_assemble);
+}
+
+extern "C" int fx_assemble_c3d8_sections(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
+                                         const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
+                                         const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val,
+                                         float *ms_assemble) {
+  const char *who = "fx_assemble_c3d8_sections";
+  if (!c || !mesh) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  if (!elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
+  const fx_elem_group G = {361, elemopt, mesh->n_elem, mesh->conn, elem_mat};
+  return assemble_groups_driver(who, c, mesh->n_node, mesh->coord, 1, &G, n_mat, E, nu, load, n_bc, bc_node, bc_dof, bc_val, ms_assemble);
+}
+
+// tetrahedra, wedges, 20-node hexahedra (TYPE=341, 342, 351, 352, 362)
+extern "C" int fx_assemble_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
+                              const double *nu, const int32_t *elem_mat, const double *load, int32_t n_bc, const int32_t *bc_node,
+                              const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
+  const char *who = "fx_assemble_c3";
+  if (!c || !mesh) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  if (!c3_linear_type(etype)) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_assemble_c3d8)");
+  const fx_elem_group G = {etype, 0, mesh->n_elem, mesh->conn, elem_mat};
+  return assemble_groups_driver(who, c, mesh->n_node, mesh->coord, 1, &G, n_mat, E, nu, load, n_bc, bc_node, bc_dof, bc_val, ms_assemble);
+}
+
+// ---- stress update and thermal load -----------------------------------------------------------------------------------------
+static void upd_stage_wait(UpdStage &st) {
+  if (st.maker.joinable()) st.maker.join();
+}
+static int upd_stage_make(UpdStage *st, int device, size_t doubles) {  // (re)allocates both arrays; on the calling thread
+  if (hipSetDevice(device) != hipSuccess) return 1;
+  if (st->strain) (void)hipHostFree(st->strain);
+  if (st->stress) (void)hipHostFree(st->stress);
+  st->strain = st->stress = nullptr;
+  st->cap = 0;
+  if (hipHostMalloc((void **)&st->strain, doubles * 8, hipHostMallocDefault) != hipSuccess) return 1;
+  if (hipHostMalloc((void **)&st->stress, doubles * 8, hipHostMallocDefault) != hipSuccess) return 1;
+  st->cap = doubles;
+  return 0;
+}
+// fx_destroy: joins the helper thread, frees the pinned arrays
+static void upd_stage_free(fx_context *c) {
+  UpdStage &st = c->upd_stage;
+  upd_stage_wait(st);
+  if (st.strain) (void)hipHostFree(st.strain);
+  if (st.stress) (void)hipHostFree(st.stress);
+  st.strain = st.stress = nullptr;
+  st.cap = 0;
+}
+// Optional: start pinning the staging of an update with `doubles` of strain (and of stress) on a helper thread and return at
+// once (a caller that knows a stress update will follow the solve -- the fistr1 binding after fstr_StiffMatrix -- hides the 0.3 s).
+static int upd_stage_prepare(fx_context *c, size_t doubles) {
+  UpdStage *st = &c->upd_stage;
+  upd_stage_wait(*st);
+  if (doubles == 0 || st->cap >= doubles) return 0;
+  const int device = c->device;
+  st->make_err = 0;
+  st->maker = std::thread([st, device, doubles] { st->make_err = upd_stage_make(st, device, doubles); });
+  return 0;
+}
 static size_t groups_stage_doubles(int32_t n_group, const fx_elem_group *groups) {
   size_t tot = 0;
   for (int32_t g = 0; g < n_group; g++) tot += (size_t)6 * c3_points(groups[g].etype) * (size_t)std::max(groups[g].n_elem, 0);
   return tot;
 }
 
+extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
+  if (!c || n_elem < 1) return fx_fail("fx_update_c3d8_linear_prepare", FX_ERROR_RUNTIME, "bad argument");
+  return upd_stage_prepare(c, (size_t)48 * n_elem);
+}
 extern "C" int fx_update_groups_linear_prepare(fx_context *c, int32_t n_group, const fx_elem_group *groups) {
-  if (!c || n_group < 1 || !groups) { g_fx_error = "fx_update_groups_linear_prepare: bad argument"; return FX_ERROR_RUNTIME; }
-  const size_t doubles = groups_stage_doubles(n_group, groups);
-  upd_stage_wait();
-  if (doubles == 0 || g_upd_stage.cap >= doubles) return 0;
-  const int device = c->device;
-  g_upd_stage.making = true;
-  g_upd_stage.make_err = 0;
-  g_upd_stage.maker = std::thread([device, doubles] { g_upd_stage.make_err = upd_stage_make(device, doubles); });
-  return 0;
+  if (!c || n_group < 1 || !groups) return fx_fail("fx_update_groups_linear_prepare", FX_ERROR_RUNTIME, "bad argument");
+  return upd_stage_prepare(c, groups_stage_doubles(n_group, groups));
 }
 
-// fx_update_groups_linear (thermal == nullptr) and fx_update_groups_linear_thermal
-static int update_groups_linear_impl(const char *who, fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
-                                     const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu, const double *disp,
-                                     const double **strain, const double **stress, double *qforce, float *ms_kernel,
-                                     const fx_thermal_view *thermal) {
-  if (!c || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+// fstr_UpdateNewton of a linear static analysis over element groups (see the header of fx_update_linear.h), and the thermal load
+// of fstr_ass_load.f90:287-428, which is the update kernels with TH = 2.  coord, disp, E, nu: host.
+//   TH = 0 / 1 (without / with `thermal`): strain[g], stress[g] = group g's [n_elem][nq][6] in the context's pinned staging
+//     (valid until the next update or prepare on this context, or fx_destroy); q = qforce (3 * n_node, caller's, may be NULL).
+//   TH = 2: q = the caller's load vector, to which every element's TLOAD vector is added -- only when everything succeeded; no
+//     displacement, no staging.  Elements that share a node add with fp64 atomics: reproducible to rounding, not bit for bit.
+// 361 (elemopt 1..3, 8 points) runs k_update_c3d8_linear, 341 / 342 (1 / 4 points) k_update_tet, 351 / 352 / 362 (2 / 9 / 27
+// points) k_update_c3, group after group on one stream.
+template <int TH>
+static int update_groups_driver(const char *who, fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
+                                const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu,
+                                const fx_thermal_view *thermal, const double *disp, const double **strain, const double **stress,
+                                double *q, float *ms_kernel) {
   if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
-  if (n_group == 1) {
-    const fx_elem_group &G = groups[0];
-    const fx_mesh_view mesh = {n_node, G.n_elem, coord, G.conn};
-    return update_linear_common(c, &mesh, G.etype, n_mat, E, nu, G.elem_mat, G.etype == 361 ? G.elemopt : 3, disp,
-                                strain, stress, qforce, ms_kernel, thermal);
-  }
+  if (TH)
+    if (int rc = thermal_view_ok(who, thermal)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t total = groups_stage_doubles(n_group, groups);
-  if (total == 0) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  const size_t total = groups_stage_doubles(n_group, groups), nq3 = (size_t)3 * n_node;
+  if (total == 0 && TH < 2) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  PhaseTimer pt("update linear");
+  UpdStage &st = c->upd_stage;
   DevScratch tmp;
   GroupUploads up;
+  ThermalDev td{nullptr, nullptr, nullptr, 0.0};
   double *d_coord = nullptr, *d_disp = nullptr, *d_q = nullptr, *d_strain = nullptr, *d_stress = nullptr;
   int32_t *d_err = nullptr;
-  if (tmp.alloc(&d_coord, (size_t)3 * n_node) || tmp.alloc(&d_disp, (size_t)3 * n_node) || tmp.alloc(&d_q, (size_t)3 * n_node) ||
-      tmp.alloc(&d_strain, total) || tmp.alloc(&d_stress, total) || tmp.alloc(&d_err, 1))
-    return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(d_coord, coord, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_disp, disp, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(d_q, 0, (size_t)3 * n_node * 8, c->stream));
+  if (tmp.alloc(&d_coord, nq3) || tmp.alloc(&d_q, nq3) || tmp.alloc(&d_err, 1)) return FX_ERROR_RUNTIME;
+  if (TH < 2 && (tmp.alloc(&d_disp, nq3) || tmp.alloc(&d_strain, total) || tmp.alloc(&d_stress, total))) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpyAsync(d_coord, coord, nq3 * 8, hipMemcpyHostToDevice, c->stream));
+  if (TH < 2) {
+    HIP_TRY(hipMemcpyAsync(d_disp, disp, nq3 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_q, 0, nq3 * 8, c->stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(d_q, q, nq3 * 8, hipMemcpyHostToDevice, c->stream));
+  }
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
   if (int rc = upload_groups(c, tmp, n_group, groups, n_mat, E, nu, up)) return rc;
-  ThermalDev td;
-  if (thermal && upload_thermal(c, tmp, n_node, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
-  upd_stage_wait();
-  if (g_upd_stage.make_err || g_upd_stage.cap < total) {
-    g_upd_stage.make_err = 0;
-    if (upd_stage_make(c->device, total)) { (void)hipGetLastError(); return fx_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
+  if (TH && upload_thermal(c, tmp, n_node, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
+  if (pt.on) HIP_TRY(hipStreamSynchronize(c->stream));
+  pt.lap("device buffers + uploads");
+  if (TH < 2) {
+    upd_stage_wait(st);
+    if (st.make_err || st.cap < total) {
+      st.make_err = 0;
+      if (upd_stage_make(&st, c->device, total)) { (void)hipGetLastError(); return fx_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
+    }
+    pt.lap("pinned staging");
   }
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   size_t at = 0;  // group g's results start at `at` doubles, in the device arrays and in the staging
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
-    if (strain) strain[g] = g_upd_stage.strain + at;
-    if (stress) stress[g] = g_upd_stage.stress + at;
     if (G.n_elem < 1) continue;
-    launch_update_linear(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, up.emat[g],
-                         up.emat[g] ? up.mtab : nullptr, d_disp, d_strain + at, d_stress + at, d_q, d_err, thermal ? &td : nullptr);
+    launch_update_linear_th<TH>(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, up.emat[g],
+                                up.emat[g] ? up.mtab : nullptr, d_disp, TH < 2 ? d_strain + at : nullptr,
+                                TH < 2 ? d_stress + at : nullptr, d_q, d_err, td);
     at += (size_t)6 * c3_points(G.etype) * G.n_elem;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.strain, d_strain, total * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.stress, d_stress, total * 8, hipMemcpyDeviceToHost, c->stream));
-  if (qforce) HIP_TRY(hipMemcpyAsync(qforce, d_q, (size_t)3 * n_node * 8, hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> out(TH == 2 ? nq3 : 0);  // the caller's load vector changes only when everything went well
+  if (TH < 2) {
+    HIP_TRY(hipMemcpyAsync(st.strain, d_strain, total * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(st.stress, d_stress, total * 8, hipMemcpyDeviceToHost, c->stream));
+    if (q) HIP_TRY(hipMemcpyAsync(q, d_q, nq3 * 8, hipMemcpyDeviceToHost, c->stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(out.data(), d_q, nq3 * 8, hipMemcpyDeviceToHost, c->stream));
+  }
   HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  pt.lap("kernel + downloads");
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_kernel) *ms_kernel = ms;
-  if (herr) { g_fx_error = "PIVOT ERROR in the incompatible-mode block of an element (UpdateST_C3D8IC, calInverse)"; return FX_ERROR_RUNTIME; }
+  if (herr)
+    return fx_fail(who, FX_ERROR_RUNTIME, "PIVOT ERROR in the incompatible-mode block of an element (%s, calInverse)",
+                   TH == 2 ? "TLOAD_C3D8IC" : "UpdateST_C3D8IC");
+  if (TH == 2) memcpy(q, out.data(), nq3 * 8);
+  at = 0;
+  for (int32_t g = 0; g < n_group && TH < 2; g++) {
+    if (strain) strain[g] = st.strain + at;
+    if (stress) stress[g] = st.stress + at;
+    at += (size_t)6 * c3_points(groups[g].etype) * (size_t)groups[g].n_elem;
+  }
   return 0;
 }
 
 extern "C" int fx_update_groups_linear(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                                        int32_t n_mat, const double *E, const double *nu, const double *disp, const double **strain,
                                        const double **stress, double *qforce, float *ms_kernel) {
-  return update_groups_linear_impl("fx_update_groups_linear", c, n_node, coord, n_group, groups, n_mat, E, nu, disp, strain, stress, qforce,
-                                   ms_kernel, nullptr);
+  const char *who = "fx_update_groups_linear";
+  if (!c || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  return update_groups_driver<0>(who, c, n_node, coord, n_group, groups, n_mat, E, nu, nullptr, disp, strain, stress, qforce, ms_kernel);
 }
 
-// ---- thermal strain (fx_thermal.h) ------------------------------------------------------------------------------------------
+// the same with the routines' thermal branches (fx_thermal.h)
 extern "C" int fx_update_groups_linear_thermal(fx_context *c, int32_t n_node, const double *coord, int32_t n_group,
                                                const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu,
                                                const fx_thermal_view *thermal, const double *disp, const double **strain,
                                                const double **stress, double *qforce, float *ms_kernel) {
   const char *who = "fx_update_groups_linear_thermal";
-  if (!c) { g_fx_error = "fx_update_groups_linear_thermal: null argument"; return FX_ERROR_RUNTIME; }
-  if (int rc = thermal_view_ok(who, thermal)) return rc;
-  return update_groups_linear_impl(who, c, n_node, coord, n_group, groups, n_mat, E, nu, disp, strain, stress, qforce, ms_kernel, thermal);
+  if (!c || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  return update_groups_driver<1>(who, c, n_node, coord, n_group, groups, n_mat, E, nu, thermal, disp, strain, stress, qforce, ms_kernel);
 }
 
-// fstr_ass_load.f90:287-428 for the solid types: every element's TLOAD vector added to load_inout (3 * n_node, host).  The
-// kernels are the update kernels with TH = 2, one group after another on one stream; elements that share a node add with fp64
-// atomics, so the sum is reproducible to rounding, not bit for bit.
 extern "C" int fx_thermal_load_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                                       int32_t n_mat, const double *E, const double *nu, const fx_thermal_view *thermal,
                                       double *load_inout, float *ms_kernel) {
   const char *who = "fx_thermal_load_groups";
-  if (!c || !load_inout) { g_fx_error = "fx_thermal_load_groups: null argument"; return FX_ERROR_RUNTIME; }
-  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, E && nu)) return rc;
-  if (int rc = thermal_view_ok(who, thermal)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  DevScratch tmp;
-  GroupUploads up;
-  ThermalDev td;
-  double *d_coord = nullptr, *d_q = nullptr;
-  int32_t *d_err = nullptr;
-  if (tmp.alloc(&d_coord, (size_t)3 * n_node) || tmp.alloc(&d_q, (size_t)3 * n_node) || tmp.alloc(&d_err, 1)) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(d_coord, coord, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_q, load_inout, (size_t)3 * n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-  if (int rc = upload_groups(c, tmp, n_group, groups, n_mat, E, nu, up)) return rc;
-  if (upload_thermal(c, tmp, n_node, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  for (int32_t g = 0; g < n_group; g++) {
-    const fx_elem_group &G = groups[g];
-    if (G.n_elem < 1) continue;
-    launch_update_linear_th<2>(c, G.etype, G.elemopt, G.n_elem, d_coord, up.conn[g], up.D11, up.D12, up.D44, up.emat[g],
-                               up.emat[g] ? up.mtab : nullptr, nullptr, nullptr, nullptr, d_q, d_err, td);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  int32_t herr = 0;
-  std::vector<double> out((size_t)3 * n_node);  // the caller's vector changes only when everything went well
-  HIP_TRY(hipMemcpyAsync(out.data(), d_q, (size_t)3 * n_node * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  if (ms_kernel) *ms_kernel = ms;
-  if (herr) { g_fx_error = "PIVOT ERROR in the incompatible-mode block of an element (TLOAD_C3D8IC, calInverse)"; return FX_ERROR_RUNTIME; }
-  memcpy(load_inout, out.data(), out.size() * 8);
-  return 0;
+  if (!c || !load_inout) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  return update_groups_driver<2>(who, c, n_node, coord, n_group, groups, n_mat, E, nu, thermal, nullptr, nullptr, nullptr, load_inout,
+                                 ms_kernel);
+}
+
+// The single-type entry points: one group.
+extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
+                                     const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
+                                     const double **stress, double *qforce, float *ms_kernel) {
+  const char *who = "fx_update_c3d8_linear";
+  if (!c || !mesh || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  const fx_elem_group G = {361, elemopt, mesh->n_elem, mesh->conn, elem_mat};
+  return update_groups_driver<0>(who, c, mesh->n_node, mesh->coord, 1, &G, n_mat, E, nu, nullptr, disp, strain, stress, qforce, ms_kernel);
+}
+
+extern "C" int fx_update_c3_linear(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
+                                   const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
+                                   const double **stress, double *qforce, float *ms_kernel) {
+  const char *who = "fx_update_c3_linear";
+  if (!c || !mesh || !disp) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  if (!c3_linear_type(etype)) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_update_c3d8_linear)");
+  const fx_elem_group G = {etype, 0, mesh->n_elem, mesh->conn, elem_mat};
+  return update_groups_driver<0>(who, c, mesh->n_node, mesh->coord, 1, &G, n_mat, E, nu, nullptr, disp, strain, stress, qforce, ms_kernel);
 }

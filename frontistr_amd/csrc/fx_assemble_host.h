@@ -1,4 +1,4 @@
-// Host entry points of the assembly side (included at the end of fistr_hip.hip).
+// Host helpers of the assembly side (included at the end of fistr_hip.hip); the linear entry points are in fx_assemble_groups.h.
 #pragma once
 #include <cstdarg>
 
@@ -312,13 +312,6 @@ static int build_first_write(fx_context *c, const std::vector<FirstWriteGroup> &
   for (const FirstWriteGroup &g : groups) g.ec->first_write = *covered;
   return 0;
 }
-// the map of one colouring with its own first-write flags, made once (the single-type entry points, fx_nl_init_c3)
-static int ensure_scatter_map_flagged(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, int32_t etype) {
-  if (ec.pos) return 0;
-  if (ensure_scatter_map(c, ec, n_elem, d_conn, etype)) return FX_ERROR_RUNTIME;
-  bool covered;
-  return build_first_write(c, {{&ec, d_conn}}, &covered);
-}
 // Moves the elements that name a node twice out of the colour lists (order, off) into their own list (dups, dup_off), colour by
 // colour, each list keeping the colour order; an empty dup_off: there are none.  k_add_elem_blocks adds them after the colours.
 static bool names_a_node_twice(const int32_t *en, int nn = 8) {
@@ -446,7 +439,8 @@ static void launch_assemble(fx_context *c, int32_t etype, int elemopt, int32_t n
 }
 
 // A tetrahedron, wedge or 20-node hexahedron that names a node twice is degenerate (the reference stops in getJacobian or
-// assembles a singular element): refused, never assembled.
+// assembles a singular element): refused, never assembled.  For the single-type set-up of the nonlinear loop (nl_init_common);
+// the linear entry points and fx_nl_init_groups go through check_groups.
 // One parallel pass with the node-id range check; the lowest offending element is named.
 static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int nn) {
   int32_t first_bad = INT32_MAX, first_dup = INT32_MAX;  // 0-based elements
@@ -507,125 +501,8 @@ static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const do
   return 0;
 }
 
-// one element type over the whole mesh (launch_assemble), cached colouring c->asm_colors
-static int assemble_c3d8_common(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int32_t n_mat, const double *Es,
-                                const double *nus, const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
-                                const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble,
-                                int32_t etype = 361) {
-  HIP_TRY(hipSetDevice(c->device));
-  const int nn = c3_nodes(etype);
-  const char *who = etype == 361 ? "fx_assemble_c3d8" : "fx_assemble_c3";
-  if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
-  if (mesh->n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
-  if (etype == 361 && (elemopt < 1 || elemopt > 3)) return fx_fail(who, FX_ERROR_UNSUPPORTED, "elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)");
-  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_assemble_c3d8)");
-  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;  // (361: its checks stay in the colouring)
-  DevScratch tmp;
-  double *d_coord = nullptr;
-  int32_t *d_conn = nullptr, *d_err = nullptr;
-  if (tmp.alloc(&d_coord, (size_t)3 * mesh->n_node) || tmp.alloc(&d_conn, (size_t)nn * mesh->n_elem) || tmp.alloc(&d_err, 1))
-    return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(d_coord, mesh->coord, (size_t)3 * mesh->n_node * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)nn * mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-  if (ensure_elem_colors(c, c->asm_colors, mesh->n_elem, mesh->conn, mesh->n_node, nn, etype) ||
-      ensure_scatter_map_flagged(c, c->asm_colors, mesh->n_elem, d_conn, etype))
-    return FX_ERROR_RUNTIME;  // both cached per (profile, mesh, element type)
-  double D11 = 0.0, D12 = 0.0, D44 = 0.0;
-  int32_t *d_emat = nullptr;
-  double *d_mtab = nullptr;
-  if (n_mat > 0) {  // several sections: per-element material id + a (D11, D12, D44) table
-    std::vector<double> tab((size_t)3 * n_mat);
-    for (int32_t k = 0; k < n_mat; k++) elastic_constants(Es[k], nus[k], tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]);
-    for (int32_t e = 0; e < mesh->n_elem; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) {
-        g_fx_error = etype == 361 ? "fx_assemble_c3d8_sections: material id out of range" : "fx_assemble_c3: material id out of range";
-        return FX_ERROR_RUNTIME;
-      }
-    if (tmp.alloc(&d_emat, (size_t)mesh->n_elem) || tmp.alloc(&d_mtab, tab.size())) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(d_emat, elem_mat, (size_t)mesh->n_elem * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_mtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // tab is a host temporary
-  } else {
-    elastic_constants(E, nu, D11, D12, D44);
-  }
-  double *d_dupk = nullptr;  // element matrices of the collapsed elements
-  if (!c->asm_colors.dup_off.empty() && tmp.alloc(&d_dupk, (size_t)576 * c->asm_colors.dup_off.back())) return FX_ERROR_RUNTIME;
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  // first-write scatter: every block is stored before it is added to, no clearing
-  if (!(c->asm_colors.first_write && c->asm_colors.pos && !c->asm_colors.offsets.empty()) && mat_clear(c)) return FX_ERROR_RUNTIME;
-  launch_assemble(c, etype, elemopt, mesh->n_elem, d_coord, d_conn, D11, D12, D44, nullptr, d_err, d_emat, d_mtab, &c->asm_colors, d_dupk);
-  HIP_TRY(hipGetLastError());
-  if (int rc = load_and_bc(c, tmp, who, load, n_bc, bc_node, bc_dof, bc_val)) return rc;
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  int32_t herr = 0;  // the streaming (BELL) layouts re-gather these values on next use (ensure_solver)
-  HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  if (ms_assemble) *ms_assemble = ms;
-  if (int rc = assembly_error(herr)) return rc;
-  c->have_values = true;
-  c->bell_valid = false;   // the preconditioner is refreshed by the flags / recycle policy of the next solve, not here
-  return 0;
-}
-
-extern "C" int fx_assemble_c3d8(fx_context *c, const fx_mesh_view *mesh, double E, double nu, int elemopt, const double *load,
-                                int32_t n_bc, const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val,
-                                float *ms_assemble) {
-  return assemble_c3d8_common(c, mesh, E, nu, 0, nullptr, nullptr, nullptr, elemopt, load, n_bc, bc_node, bc_dof, bc_val,
-                              ms_assemble);
-}
-
-extern "C" int fx_assemble_c3d8_sections(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
-                                         const int32_t *elem_mat, int elemopt, const double *load, int32_t n_bc,
-                                         const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val,
-                                         float *ms_assemble) {
-  if (n_mat < 1 || !E || !nu || !elem_mat) { g_fx_error = "fx_assemble_c3d8_sections: materials missing"; return FX_ERROR_RUNTIME; }
-  return assemble_c3d8_common(c, mesh, 0.0, 0.0, n_mat, E, nu, elem_mat, elemopt, load, n_bc, bc_node, bc_dof, bc_val,
-                              ms_assemble);
-}
-
-extern "C" int fx_element_stiffness_c3d8(fx_context *c, int elemopt, const double *ecoord, double E, double nu, double *stiff) {
-  HIP_TRY(hipSetDevice(c->device));
-  DevScratch tmp;
-  double *d_coord = nullptr, *d_k = nullptr;
-  int32_t *d_conn = nullptr, *d_err = nullptr;
-  if (tmp.alloc(&d_coord, 24) || tmp.alloc(&d_conn, 8) || tmp.alloc(&d_k, 576) || tmp.alloc(&d_err, 1)) return FX_ERROR_RUNTIME;
-  const int32_t conn[8] = {1, 2, 3, 4, 5, 6, 7, 8};
-  HIP_TRY(hipMemcpy(d_coord, ecoord, 24 * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_conn, conn, 32, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_err, 0, 4));
-  double D11, D12, D44;
-  elastic_constants(E, nu, D11, D12, D44);
-  if (elemopt < 1 || elemopt > 3) { g_fx_error = "elemopt must be 1, 2 or 3"; return FX_ERROR_UNSUPPORTED; }
-  launch_assemble(c, 361, elemopt, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(stiff, d_k, 576 * 8, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// ---- tetrahedra, wedges, 20-node hexahedra (TYPE=341, 342, 351, 352, 362): fx_assemble_c3, fx_element_stiffness_c3 ------------------------------------------------
-extern "C" int fx_assemble_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
-                              const double *nu, const int32_t *elem_mat, const double *load, int32_t n_bc, const int32_t *bc_node,
-                              const int32_t *bc_dof, const double *bc_val, float *ms_assemble) {
-  if (!c || !mesh) { g_fx_error = "fx_assemble_c3: null argument"; return FX_ERROR_RUNTIME; }
-  if (!c3_linear_type(etype)) {
-    g_fx_error = "fx_assemble_c3: " FX_C3_UNSUPPORTED "fx_assemble_c3d8)";
-    return FX_ERROR_UNSUPPORTED;
-  }
-  if (n_mat < 1 || !E || !nu) { g_fx_error = "fx_assemble_c3: materials missing"; return FX_ERROR_RUNTIME; }
-  if (n_mat > 1 && !elem_mat) { g_fx_error = "fx_assemble_c3: several materials need elem_mat"; return FX_ERROR_RUNTIME; }
-  if (!elem_mat)
-    return assemble_c3d8_common(c, mesh, E[0], nu[0], 0, nullptr, nullptr, nullptr, 0, load, n_bc, bc_node, bc_dof, bc_val,
-                                ms_assemble, etype);
-  return assemble_c3d8_common(c, mesh, 0.0, 0.0, n_mat, E, nu, elem_mat, 0, load, n_bc, bc_node, bc_dof, bc_val, ms_assemble, etype);
-}
-
-extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const double *ecoord, double E, double nu, double *stiff) {
-  if (!c || !ecoord || !stiff) { g_fx_error = "fx_element_stiffness_c3: null argument"; return FX_ERROR_RUNTIME; }
-  if (!c3_linear_type(etype)) { g_fx_error = "fx_element_stiffness_c3: etype must be 341, 342, 351, 352 or 362"; return FX_ERROR_UNSUPPORTED; }
+// One element's stiffness through the device kernel (tests): etype 361 with elemopt 1..3, or an STF_C3 type.
+static int element_stiffness(fx_context *c, int32_t etype, int elemopt, const double *ecoord, double E, double nu, double *stiff) {
   HIP_TRY(hipSetDevice(c->device));
   const int nn = c3_nodes(etype), w = 3 * nn;
   DevScratch tmp;
@@ -639,9 +516,21 @@ extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const doubl
   HIP_TRY(hipMemset(d_err, 0, 4));
   double D11, D12, D44;
   elastic_constants(E, nu, D11, D12, D44);
-  launch_assemble(c, etype, 0, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
+  launch_assemble(c, etype, elemopt, 1, d_coord, d_conn, D11, D12, D44, d_k, d_err, nullptr, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(stiff, d_k, (size_t)w * w * 8, hipMemcpyDeviceToHost));
   return 0;
+}
+
+extern "C" int fx_element_stiffness_c3d8(fx_context *c, int elemopt, const double *ecoord, double E, double nu, double *stiff) {
+  if (!c || !ecoord || !stiff) { g_fx_error = "fx_element_stiffness_c3d8: null argument"; return FX_ERROR_RUNTIME; }
+  if (elemopt < 1 || elemopt > 3) { g_fx_error = "fx_element_stiffness_c3d8: elemopt must be 1, 2 or 3"; return FX_ERROR_UNSUPPORTED; }
+  return element_stiffness(c, 361, elemopt, ecoord, E, nu, stiff);
+}
+
+extern "C" int fx_element_stiffness_c3(fx_context *c, int32_t etype, const double *ecoord, double E, double nu, double *stiff) {
+  if (!c || !ecoord || !stiff) { g_fx_error = "fx_element_stiffness_c3: null argument"; return FX_ERROR_RUNTIME; }
+  if (!c3_linear_type(etype)) { g_fx_error = "fx_element_stiffness_c3: etype must be 341, 342, 351, 352 or 362"; return FX_ERROR_UNSUPPORTED; }
+  return element_stiffness(c, etype, 0, ecoord, E, nu, stiff);
 }

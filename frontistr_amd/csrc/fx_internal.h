@@ -203,12 +203,23 @@ struct ElemColors {
                                     // the coloured scatter stores the first contribution to a block and the matrix is not cleared first
 };
 
-// fx_assemble_groups with more than one group: one ElemColors per group (by position in the call), and the first-write flags of
+// The one cache of the linear assembly (fx_assemble_c3d8, _sections, fx_assemble_c3 and fx_assemble_groups all run the group
+// driver; a single-type call is one group): one ElemColors per group (by position in the call), and the first-write flags of
 // their maps in the launch order of ALL groups (group after group, colour after colour).
 struct AsmGroups {
   std::vector<ElemColors> ec;
   uint64_t flag_sig = 0;     // checksum of the (key, etype, n_elem) sequence the maps' first-write flags were made for; 0 = none
   bool first_write = false;  // the maps carry those flags and every block of the profile is covered: no clearing
+};
+
+// Pinned host staging of the results of the linear stress update (grown on demand, owned by the context): 2 x 6 nq doubles per
+// element would otherwise cross PCIe through pageable memory at a fraction of the link rate.  The pointers an update returns
+// are valid until the next update or prepare on the same context, or fx_destroy.
+struct UpdStage {
+  double *strain = nullptr, *stress = nullptr;
+  size_t cap = 0;     // doubles per array
+  std::thread maker;  // pinning 2.5 GB of host memory takes 0.3 s at 3.3M elements: the *_prepare entry points do it beside the solve
+  int make_err = 0;   // the maker's result: read only after the join (upd_stage_wait)
 };
 
 // One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
@@ -496,8 +507,8 @@ struct fx_context {
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_packed = nullptr, ev_halo = nullptr;
   NlDev nl;
-  ElemColors asm_colors;  // fx_assemble_c3d8
-  AsmGroups asm_groups;   // fx_assemble_groups (several groups)
+  AsmGroups asm_groups;   // the linear assembly entry points
+  UpdStage upd_stage;     // the linear stress update entry points
   void *nn = nullptr;  // NnDev (fx_nn_host.h): systems with NDOF != 3
   const void *host_D = nullptr, *host_AL = nullptr, *host_AU = nullptr;  // the caller's arrays of the last value upload (fx_solve)
   // timing

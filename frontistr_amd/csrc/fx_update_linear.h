@@ -288,47 +288,6 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
   }
 }
 
-// Pinned host staging of the results (grown on demand, kept with the context): 2 x 48 doubles per element would otherwise cross
-// PCIe through pageable memory at a fraction of the link rate.
-struct UpdStage {
-  double *strain = nullptr, *stress = nullptr;
-  size_t cap = 0;  // doubles per array
-  std::thread maker;  // pinning 2.5 GB of host memory takes 0.3 s at 3.3M elements: fx_update_c3d8_linear_prepare does it beside the solve
-  bool making = false;
-  int make_err = 0;
-  ~UpdStage() { if (maker.joinable()) maker.join(); }  // a process that ends before using what it asked for
-};
-static UpdStage g_upd_stage;
-
-static void upd_stage_wait() {
-  if (g_upd_stage.making) { g_upd_stage.maker.join(); g_upd_stage.making = false; }
-}
-static int upd_stage_make(int device, size_t doubles) {  // (re)allocates both arrays; on the calling thread
-  if (hipSetDevice(device) != hipSuccess) return 1;
-  if (g_upd_stage.strain) (void)hipHostFree(g_upd_stage.strain);
-  if (g_upd_stage.stress) (void)hipHostFree(g_upd_stage.stress);
-  g_upd_stage.strain = g_upd_stage.stress = nullptr;
-  g_upd_stage.cap = 0;
-  if (hipHostMalloc((void **)&g_upd_stage.strain, doubles * 8, hipHostMallocDefault) != hipSuccess) return 1;
-  if (hipHostMalloc((void **)&g_upd_stage.stress, doubles * 8, hipHostMallocDefault) != hipSuccess) return 1;
-  g_upd_stage.cap = doubles;
-  return 0;
-}
-
-// Optional: start pinning the host staging of fx_update_c3d8_linear for a mesh of n_elem elements on a helper thread and return at
-// once (a caller that knows a stress update will follow the solve -- the fistr1 binding after fstr_StiffMatrix -- hides the 0.3 s).
-extern "C" int fx_update_c3d8_linear_prepare(fx_context *c, int32_t n_elem) {
-  if (!c || n_elem < 1) { g_fx_error = "fx_update_c3d8_linear_prepare: bad argument"; return FX_ERROR_RUNTIME; }
-  upd_stage_wait();
-  if (g_upd_stage.cap >= (size_t)48 * n_elem) return 0;
-  const int device = c->device;
-  const size_t doubles = (size_t)48 * n_elem;
-  g_upd_stage.making = true;
-  g_upd_stage.make_err = 0;
-  g_upd_stage.maker = std::thread([device, doubles] { g_upd_stage.make_err = upd_stage_make(device, doubles); });
-  return 0;
-}
-
 // One group's update kernel: 361 (elemopt 1..3) k_update_c3d8_linear, 341 / 342 k_update_tet, 351 / 352 / 362 k_update_c3.
 // TH = 0: no temperature; 1: the thermal branch of the update; 2: the thermal load vector added to d_q (fx_thermal.h).
 template <int TH>
@@ -352,16 +311,6 @@ static void launch_update_linear_th(fx_context *c, int32_t etype, int elemopt, i
   hipLaunchKernelGGL(kern, dim3((unsigned)((ne + FXU_EPB - 1) / FXU_EPB)), dim3(FXU_BS), 0, c->stream, ne, d_coord, d_conn, D11, D12, D44,
                      d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err, th);
 }
-static void launch_update_linear(fx_context *c, int32_t etype, int elemopt, int32_t ne, const double *d_coord, const int32_t *d_conn,
-                                 double D11, double D12, double D44, const int32_t *d_emat, const double *d_mtab,
-                                 const double *d_disp, double *d_strain, double *d_stress, double *d_q, int32_t *d_err,
-                                 const ThermalDev *th = nullptr) {
-  if (th)
-    launch_update_linear_th<1>(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err, *th);
-  else
-    launch_update_linear_th<0>(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err,
-                               ThermalDev{nullptr, nullptr, nullptr, 0.0});
-}
 
 // The caller's temperatures and expansion coefficients on the device.  `who` has checked the view (thermal_view_ok).
 static int upload_thermal(fx_context *c, DevScratch &tmp, int32_t n_node, int32_t n_mat, const fx_thermal_view *tv, ThermalDev &td) {
@@ -378,106 +327,4 @@ static int thermal_view_ok(const char *who, const fx_thermal_view *tv) {
   if (!tv->temp || !tv->temp0) return fx_fail(who, FX_ERROR_RUNTIME, "temperature array missing");
   if (!tv->alpha) return fx_fail(who, FX_ERROR_RUNTIME, "expansion coefficients missing");
   return 0;
-}
-
-// fstr_UpdateNewton of a linear static analysis (see the header of this file).  mesh: coordinates + connectivity (host); n_mat
-// materials (E, nu), elem_mat 1-based per element (NULL with one material); elemopt 1 IC, 2 B-bar, 3 FI; disp = total
-// displacement unode + dunode (3 * n_node, host).  Out: *strain, *stress = pinned host arrays owned by the library, valid until
-// the next call ([n_elem][8][6], the reference's gausses(1:8)%strain(1:6) / %stress(1:6)); qforce (3 * n_node, host, caller's).
-// etype 361 (elemopt 1..3, 8 quadrature points) through k_update_c3d8_linear; 341 / 342 (1 / 4 points) through k_update_tet;
-// 351 / 352 / 362 (2 / 9 / 27 points) through k_update_c3.
-// Results: [n_elem][nq][6] in the pinned staging.
-static int update_linear_common(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
-                                const double *nu, const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
-                                const double **stress, double *qforce, float *ms_kernel, const fx_thermal_view *thermal = nullptr) {
-  HIP_TRY(hipSetDevice(c->device));
-  const bool hex = etype == 361;
-  const char *who = thermal ? "fx_update_groups_linear_thermal" : (hex ? "fx_update_c3d8_linear" : "fx_update_c3_linear");
-  if (!mesh || !E || !nu || !disp || n_mat < 1) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  if (hex && (elemopt < 1 || elemopt > 3)) return fx_fail(who, FX_ERROR_UNSUPPORTED, "elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)");
-  if (!hex && !c3_linear_type(etype)) return fx_fail(who, FX_ERROR_UNSUPPORTED, FX_C3_UNSUPPORTED "fx_update_c3d8_linear)");
-  const int32_t ne = mesh->n_elem, nn = mesh->n_node;
-  const int enn = c3_nodes(etype), nq = c3_points(etype);
-  const size_t per_elem = (size_t)6 * nq;  // doubles of strain (and of stress) per element
-  if (ne < 1 || nn < 1) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
-  if (hex) {
-    for (int64_t k = 0; k < (int64_t)enn * ne; k++)
-      if (mesh->conn[k] < 1 || mesh->conn[k] > nn) return fx_fail(who, FX_ERROR_RUNTIME, "node id out of range");
-  } else if (refuse_degenerate_tets(who, mesh, enn)) {
-    return FX_ERROR_RUNTIME;
-  }
-  PhaseTimer pt("update linear");
-  DevScratch tmp;
-  double *d_coord = nullptr, *d_disp = nullptr, *d_strain = nullptr, *d_stress = nullptr, *d_q = nullptr, *d_mtab = nullptr;
-  int32_t *d_conn = nullptr, *d_emat = nullptr, *d_err = nullptr;
-  if (tmp.alloc(&d_coord, (size_t)3 * nn) || tmp.alloc(&d_disp, (size_t)3 * nn) || tmp.alloc(&d_q, (size_t)3 * nn) ||
-      tmp.alloc(&d_conn, (size_t)enn * ne) || tmp.alloc(&d_strain, per_elem * ne) || tmp.alloc(&d_stress, per_elem * ne) ||
-      tmp.alloc(&d_err, 1))
-    return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemcpyAsync(d_coord, mesh->coord, (size_t)3 * nn * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_conn, mesh->conn, (size_t)enn * ne * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_disp, disp, (size_t)3 * nn * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(d_q, 0, (size_t)3 * nn * 8, c->stream));
-  HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-  double D11 = 0.0, D12 = 0.0, D44 = 0.0;
-  std::vector<double> tab((size_t)3 * n_mat);
-  for (int32_t k = 0; k < n_mat; k++) elastic_constants(E[k], nu[k], tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]);
-  if (n_mat > 1 || elem_mat) {
-    if (!elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "several materials need elem_mat");
-    for (int32_t e = 0; e < ne; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) return fx_fail(who, FX_ERROR_RUNTIME, "material id out of range");
-    if (tmp.alloc(&d_emat, (size_t)ne) || tmp.alloc(&d_mtab, tab.size())) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(d_emat, elem_mat, (size_t)ne * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_mtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-  } else {
-    D11 = tab[0]; D12 = tab[1]; D44 = tab[2];
-  }
-  ThermalDev td;
-  if (thermal && upload_thermal(c, tmp, nn, n_mat, thermal, td)) return FX_ERROR_RUNTIME;
-  if (pt.on) HIP_TRY(hipStreamSynchronize(c->stream));
-  pt.lap("device buffers + uploads");
-  upd_stage_wait();
-  if (g_upd_stage.make_err || g_upd_stage.cap < per_elem * ne) {
-    g_upd_stage.make_err = 0;
-    if (upd_stage_make(c->device, per_elem * ne)) { (void)hipGetLastError(); return fx_fail(who, FX_ERROR_RUNTIME, "cannot pin the host staging"); }
-  }
-  pt.lap("pinned staging");
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  launch_update_linear(c, etype, elemopt, ne, d_coord, d_conn, D11, D12, D44, d_emat, d_mtab, d_disp, d_strain, d_stress, d_q, d_err,
-                       thermal ? &td : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  int32_t herr = 0;
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.strain, d_strain, per_elem * ne * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(g_upd_stage.stress, d_stress, per_elem * ne * 8, hipMemcpyDeviceToHost, c->stream));
-  if (qforce) HIP_TRY(hipMemcpyAsync(qforce, d_q, (size_t)3 * nn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  pt.lap("kernel + downloads");
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  if (ms_kernel) *ms_kernel = ms;
-  if (herr) { g_fx_error = "PIVOT ERROR in the incompatible-mode block of an element (UpdateST_C3D8IC, calInverse)"; return FX_ERROR_RUNTIME; }
-  if (strain) *strain = g_upd_stage.strain;
-  if (stress) *stress = g_upd_stage.stress;
-  return 0;
-}
-
-extern "C" int fx_update_c3d8_linear(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
-                                     const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
-                                     const double **stress, double *qforce, float *ms_kernel) {
-  return update_linear_common(c, mesh, 361, n_mat, E, nu, elem_mat, elemopt, disp, strain, stress, qforce, ms_kernel);
-}
-
-// The same for a group of tetrahedra, wedges or 20-node hexahedra (etype 341, 342, 351, 352 or 362; UPDATE_C3): [n_elem][nq][6]
-// with nq = 1, 4, 2, 9, 27.
-extern "C" int fx_update_c3_linear(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
-                                   const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
-                                   const double **stress, double *qforce, float *ms_kernel) {
-  if (!c) { g_fx_error = "fx_update_c3_linear: null argument"; return FX_ERROR_RUNTIME; }
-  if (!c3_linear_type(etype)) {
-    g_fx_error = "fx_update_c3_linear: " FX_C3_UNSUPPORTED "fx_update_c3d8_linear)";
-    return FX_ERROR_UNSUPPORTED;
-  }
-  return update_linear_common(c, mesh, etype, n_mat, E, nu, elem_mat, 3, disp, strain, stress, qforce, ms_kernel);
 }

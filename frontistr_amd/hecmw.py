@@ -188,6 +188,26 @@ _C3_NODES = {341: 4, 342: 10, 351: 6, 352: 15, 362: 20}      # nodes and quadrat
 _C3_POINTS = {341: 1, 342: 4, 351: 2, 352: 9, 362: 27}
 
 
+def _bc_arrays(bc, load):
+    """(bc_node, bc_dof, bc_val, load) as the assembly entry points take them: bc = (nodes, dofs, values) or None."""
+    bn, bd, bv = ((), (), ()) if bc is None else bc
+    return (np.ascontiguousarray(bn, dtype=np.int32), np.ascontiguousarray(bd, dtype=np.int32),
+            np.ascontiguousarray(bv, dtype=np.float64), None if load is None else np.ascontiguousarray(load, dtype=np.float64))
+
+
+def _material_arrays(E, nu, elem_mat=None):
+    """(E[], nu[], elem_mat[] or None): scalars become one-entry tables; elem_mat is 1-based per element."""
+    return (np.atleast_1d(np.asarray(E, dtype=np.float64)).copy(), np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy(),
+            None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32))
+
+
+def _staged(p, n_elem, nq):
+    """A copy (n_elem, nq, 6) of one result in the context's pinned staging, which the next update on the context overwrites."""
+    if n_elem == 0:
+        return np.zeros((0, nq, 6))
+    return np.ctypeslib.as_array(p, shape=(6 * nq * n_elem,)).reshape(-1, nq, 6).copy()
+
+
 class SolverContext:
     """Device state the reference keeps in module-level `save` variables."""
 
@@ -411,18 +431,10 @@ class SolverContext:
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
         mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
-        if bc is None:
-            bn = np.zeros(0, dtype=np.int32); bd = np.zeros(0, dtype=np.int32); bv = np.zeros(0)
-        else:
-            bn = np.ascontiguousarray(bc[0], dtype=np.int32)
-            bd = np.ascontiguousarray(bc[1], dtype=np.int32)
-            bv = np.ascontiguousarray(bc[2], dtype=np.float64)
-        load = None if load is None else np.ascontiguousarray(load, dtype=np.float64)
+        bn, bd, bv, load = _bc_arrays(bc, load)
         ms = C.c_float(0)
         if sections is not None:
-            Es = np.ascontiguousarray(sections[0], dtype=np.float64)
-            nus = np.ascontiguousarray(sections[1], dtype=np.float64)
-            em = np.ascontiguousarray(sections[2], dtype=np.int32)
+            Es, nus, em = _material_arrays(*sections)
             _chk(lib().fx_assemble_c3d8_sections(self.h, C.byref(mv), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), int(elemopt),
                                                  _ptr(load), int(bn.size), _ptr(bn), _ptr(bd), _ptr(bv), C.byref(ms)))
             return ms.value
@@ -437,19 +449,14 @@ class SolverContext:
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
         disp = np.ascontiguousarray(disp, dtype=np.float64)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
-        em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        Es, nus, em = _material_arrays(E, nu, elem_mat)
         mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
         ps, pt = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
         qf = np.zeros(3 * coord.shape[0])
         ms = C.c_float(0)
         _chk(lib().fx_update_c3d8_linear(self.h, C.byref(mv), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), int(elemopt), _ptr(disp),
                                          C.byref(ps), C.byref(pt), _ptr(qf), C.byref(ms)))
-        n = 48 * conn.shape[0]
-        strain = np.ctypeslib.as_array(ps, shape=(n,)).reshape(-1, 8, 6).copy()      # the library's pinned staging: copy out
-        stress = np.ctypeslib.as_array(pt, shape=(n,)).reshape(-1, 8, 6).copy()
-        return strain, stress, qf, ms.value
+        return _staged(ps, conn.shape[0], 8), _staged(pt, conn.shape[0], 8), qf, ms.value
 
     def element_stiffness(self, elemopt, ecoord, E, nu):
         ec = np.ascontiguousarray(ecoord, dtype=np.float64).reshape(8, 3)
@@ -463,17 +470,9 @@ class SolverContext:
         per-material arrays with elem_mat (1-based per element).  Returns the kernel milliseconds."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
-        em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        Es, nus, em = _material_arrays(E, nu, elem_mat)
         mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
-        if bc is None:
-            bn = np.zeros(0, dtype=np.int32); bd = np.zeros(0, dtype=np.int32); bv = np.zeros(0)
-        else:
-            bn = np.ascontiguousarray(bc[0], dtype=np.int32)
-            bd = np.ascontiguousarray(bc[1], dtype=np.int32)
-            bv = np.ascontiguousarray(bc[2], dtype=np.float64)
-        load = None if load is None else np.ascontiguousarray(load, dtype=np.float64)
+        bn, bd, bv, load = _bc_arrays(bc, load)
         ms = C.c_float(0)
         _chk(lib().fx_assemble_c3(self.h, C.byref(mv), int(etype), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), _ptr(load),
                                   int(bn.size), _ptr(bn), _ptr(bd), _ptr(bv), C.byref(ms)))
@@ -486,9 +485,7 @@ class SolverContext:
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         conn = np.ascontiguousarray(conn, dtype=np.int32)
         disp = np.ascontiguousarray(disp, dtype=np.float64)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
-        em = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        Es, nus, em = _material_arrays(E, nu, elem_mat)
         mv = _MeshView(coord.shape[0], conn.shape[0], _ptr(coord), _ptr(conn))
         ps, pt = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
         qf = np.zeros(3 * coord.shape[0])
@@ -496,10 +493,7 @@ class SolverContext:
         _chk(lib().fx_update_c3_linear(self.h, C.byref(mv), int(etype), int(Es.size), _ptr(Es), _ptr(nus), _ptr(em), _ptr(disp),
                                        C.byref(ps), C.byref(pt), _ptr(qf), C.byref(ms)))
         nq = _C3_POINTS.get(int(etype), 1)
-        n = 6 * nq * conn.shape[0]
-        strain = np.ctypeslib.as_array(ps, shape=(n,)).reshape(-1, nq, 6).copy()    # the library's pinned staging: copy out
-        stress = np.ctypeslib.as_array(pt, shape=(n,)).reshape(-1, nq, 6).copy()
-        return strain, stress, qf, ms.value
+        return _staged(ps, conn.shape[0], nq), _staged(pt, conn.shape[0], nq), qf, ms.value
 
     def element_stiffness_c3(self, etype, ecoord, E, nu):
         """One element's (3 nn, 3 nn) stiffness through the device kernel (fx_element_stiffness_c3): etype 341, 342, 351, 352
@@ -531,16 +525,9 @@ class SolverContext:
         all into the one resident matrix; E, nu scalars, or per-material arrays with every group's elem_mat (1-based).
         Returns the kernel milliseconds."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        Es, nus, _ = _material_arrays(E, nu)
         tab, keep = self._group_table(groups)
-        if bc is None:
-            bn = np.zeros(0, dtype=np.int32); bd = np.zeros(0, dtype=np.int32); bv = np.zeros(0)
-        else:
-            bn = np.ascontiguousarray(bc[0], dtype=np.int32)
-            bd = np.ascontiguousarray(bc[1], dtype=np.int32)
-            bv = np.ascontiguousarray(bc[2], dtype=np.float64)
-        load = None if load is None else np.ascontiguousarray(load, dtype=np.float64)
+        bn, bd, bv, load = _bc_arrays(bc, load)
         ms = C.c_float(0)
         _chk(lib().fx_assemble_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, int(Es.size), _ptr(Es), _ptr(nus),
                                       _ptr(load), int(bn.size), _ptr(bn), _ptr(bd), _ptr(bv), C.byref(ms)))
@@ -560,8 +547,7 @@ class SolverContext:
         (3 * n_node, zeros when None).  groups, E, nu as assemble_groups; thermal = (temp, temp0, ref_temp, alpha).  Returns
         (the vector, kernel ms); ``load`` itself is not changed."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        Es, nus, _ = _material_arrays(E, nu)
         tab, keep = self._group_table(groups)
         tv, keep_t = self._thermal_view(thermal)
         out = np.zeros(3 * coord.shape[0]) if load is None else np.array(load, dtype=np.float64).ravel()
@@ -587,8 +573,7 @@ class SolverContext:
         Returns ([strain per group (n_elem, nq, 6)], [stress per group], qforce (3 * n_node) summed over the groups, kernel ms)."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         disp = np.ascontiguousarray(disp, dtype=np.float64)
-        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).copy()
-        nus = np.atleast_1d(np.asarray(nu, dtype=np.float64)).copy()
+        Es, nus, _ = _material_arrays(E, nu)
         tab, keep = self._group_table(groups)
         ng = len(groups)
         ps, pt = (C.POINTER(C.c_double) * max(ng, 1))(), (C.POINTER(C.c_double) * max(ng, 1))()
@@ -602,15 +587,9 @@ class SolverContext:
             _chk(lib().fx_update_groups_linear_thermal(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es),
                                                        _ptr(nus), C.byref(tv), _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
             del keep_t
-        strain, stress = [], []
-        for g in range(ng):
-            nq = 8 if tab[g].etype == 361 else _C3_POINTS[tab[g].etype]
-            n = 6 * nq * tab[g].n_elem
-            if n == 0:
-                strain.append(np.zeros((0, nq, 6))); stress.append(np.zeros((0, nq, 6)))
-                continue
-            strain.append(np.ctypeslib.as_array(ps[g], shape=(n,)).reshape(-1, nq, 6).copy())   # pinned staging: copy out
-            stress.append(np.ctypeslib.as_array(pt[g], shape=(n,)).reshape(-1, nq, 6).copy())
+        nqs = [8 if tab[g].etype == 361 else _C3_POINTS[tab[g].etype] for g in range(ng)]
+        strain = [_staged(ps[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
+        stress = [_staged(pt[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
         del keep
         return strain, stress, qf, ms.value
 

@@ -258,13 +258,14 @@ int fx_assemble_c3d8_sections(fx_context *ctx, const fx_mesh_view *mesh, int32_t
 /* fstr_UpdateNewton of a LINEAR static analysis (`!SOLUTION, TYPE=STATIC`; fistr1/src/analysis/static/fstr_Update.f90:25-293) for
  * one TYPE=361 group of isotropic ELASTIC materials: UpdateST_C3D8IC (static_LIB_3dIC.f90:220-455, elemopt 1), Update_C3D8Bbar
  * (static_LIB_C3D8.f90:203-547, elemopt 2) or UPDATE_C3 (static_LIB_3d.f90:516-837, elemopt 3) per element, small strain.
- * disp = total displacement unode + dunode (3*n_node).  *strain, *stress: pinned host arrays OWNED BY THE LIBRARY, valid until the
- * next call, [n_elem][8][6] = gausses(1:8)%strain(1:6) / %stress(1:6) of every element; qforce (3*n_node, caller's, may be NULL) =
+ * disp = total displacement unode + dunode (3*n_node).  *strain, *stress: pinned host arrays OWNED BY THE CONTEXT, valid until the
+ * next update or prepare ON THE SAME CONTEXT or fx_destroy (other contexts have their own staging), [n_elem][8][6] = gausses(1:8)%strain(1:6) / %stress(1:6) of every element; qforce (3*n_node, caller's, may be NULL) =
  * fstrSOLID%QFORCE before its halo update.  n_mat materials, elem_mat 1-based per element (NULL with one material). */
 int fx_update_c3d8_linear(fx_context *ctx, const fx_mesh_view *mesh, int32_t n_mat, const double *E, const double *nu,
                           const int32_t *elem_mat, int elemopt, const double *disp, const double **strain,
                           const double **stress, double *qforce, float *ms_kernel);
-/* Optional: start pinning the host staging of fx_update_c3d8_linear for n_elem elements on a helper thread and return at once. */
+/* Optional: start pinning the context's host staging of fx_update_c3d8_linear for n_elem elements on a helper thread and return
+ * at once.  Pointers that an earlier update on this context returned are no longer valid after it. */
 int fx_update_c3d8_linear_prepare(fx_context *ctx, int32_t n_elem);
 /* One element stiffness through the device kernel (tests): ecoord 8x3, stiff 24x24 row-major. */
 int fx_element_stiffness_c3d8(fx_context *ctx, int elemopt, const double *ecoord, double E, double nu,
@@ -283,7 +284,7 @@ int fx_assemble_c3(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int
                    const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble);
 /* fstr_UpdateNewton of a linear static analysis for one group of the same types: UPDATE_C3 (static_LIB_3d.f90:516-837), small
  * strain.  As fx_update_c3d8_linear, with *strain, *stress [n_elem][nq][6] (nq = the type's quadrature points: 1, 4, 2, 9,
- * 27) in the library's pinned staging, valid until the next call. */
+ * 27) in the context's pinned staging, valid until the next update or prepare on the same context or fx_destroy. */
 int fx_update_c3_linear(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const double *E,
                         const double *nu, const int32_t *elem_mat, const double *disp, const double **strain,
                         const double **stress, double *qforce, float *ms_kernel);
@@ -304,15 +305,17 @@ typedef struct fx_elem_group {
 /* All groups into the one resident matrix: cleared (or first-written) once, group after group in the order given, each group
  * colour by colour (no atomics, bitwise reproducible); `load` and the boundary conditions once after the last group
  * (hecmw_mat_ass_bc, matrix/hecmw_mat_ass.f90:292).  The colouring and the position map are kept per group and re-used by the
- * next call with the same groups.  With ONE group the result is bit for bit that of fx_assemble_c3d8_sections / fx_assemble_c3.
+ * next call with the same groups.  fx_assemble_c3d8, fx_assemble_c3d8_sections and fx_assemble_c3 are this call with ONE group:
+ * the same driver, the same argument checks (messages name the entry point called) and the same one cache per context, so
+ * alternating different group sets on one context colours and maps again each time.
  * An unknown etype in any group: FX_ERROR_UNSUPPORTED; n_group < 1, missing materials, a material or node id out of range, a
  * degenerate element of a type other than 361 (named with its group and element): FX_ERROR_RUNTIME.  Nothing is assembled then. */
 int fx_assemble_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                        int32_t n_mat, const double *E, const double *nu, const double *load, int32_t n_bc,
                        const int32_t *bc_node, const int32_t *bc_dof, const double *bc_val, float *ms_assemble);
 /* fstr_UpdateNewton's element loop (fstr_Update.f90:73-264) over the same groups.  strain[g], stress[g] (n_group pointers each,
- * the caller's arrays of pointers): group g's [n_elem][nq(etype)][6] in the library's pinned staging, valid until the next
- * call; qforce (3*n_node, may be NULL) summed over all groups. */
+ * the caller's arrays of pointers): group g's [n_elem][nq(etype)][6] in the context's pinned staging, valid until the next
+ * update or prepare on the same context or fx_destroy; qforce (3*n_node, may be NULL) summed over all groups. */
 int fx_update_groups_linear(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                             int32_t n_mat, const double *E, const double *nu, const double *disp, const double **strain,
                             const double **stress, double *qforce, float *ms_kernel);
@@ -339,7 +342,7 @@ int fx_thermal_load_groups(fx_context *ctx, int32_t n_node, const double *coord,
                            double *load_inout, float *ms_kernel);
 /* fx_update_groups_linear with the routines' thermal branches: stored strain = the total strain, stress = D (strain - EPSTH),
  * qforce from that stress; the IC element also subtracts its TLOAD_C3D8IC vector (static_LIB_3dIC.f90:337-342).  Same pinned
- * staging and results layout; one group runs the single-type kernels.  With temp == temp0 == ref_temp everywhere the strain and
+ * staging (valid until the next update or prepare on the same context or fx_destroy) and results layout.  With temp == temp0 == ref_temp everywhere the strain and
  * stress are those of fx_update_groups_linear. */
 int fx_update_groups_linear_thermal(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group,
                                     const fx_elem_group *groups, int32_t n_mat, const double *E, const double *nu,

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Bitwise A/B of the nonlinear element kernels between two builds of libfistr_hip.so (a refactor must not move a bit).
+"""Bitwise A/B of the element kernels' results between two builds of libfistr_hip.so (a refactor must not move a bit).
 
-    ab_nl_bitwise.py --dump OUT.npz [--lib PATH]     run the cases below in this process, write every output
-    ab_nl_bitwise.py --compare A.npz B.npz           per array: equal bit for bit, or the first difference; exit 1 on any
+    ab_nl_bitwise.py --dump OUT.npz [--lib PATH]            run the nonlinear cases below in this process, write every output
+    ab_nl_bitwise.py --dump-linear OUT.npz [--lib PATH]     the same for the linear case set at the end of this text
+    ab_nl_bitwise.py --compare A.npz B.npz                  per array: equal bit for bit, or the first difference; exit 1 on any
 
 Not a test: the second build (the parent commit's) is not in the repository.  Run --dump once with each library, each in a fresh
 process (a few seconds), then --compare.
@@ -14,7 +15,16 @@ Cases, on the small distorted meshes of the GPU tests (hyper_ref.gpu_mesh: a han
   tetrahedra, linear and quadratic) with the same two sections.
 Outputs per case: element tangents before the first update and after it (the latch), the per-element internal forces of the update,
 the state after the update and after fx_nl_commit, and D / AL / AU of the coloured scatter (fx_nl_stiffness_at, fx_download_matrix)
-before and after the update.  Nodal QFORCE and the FX_ASM_ATOMIC scatter are sums of fp64 atomics in no fixed order: not compared."""
+before and after the update.  Nodal QFORCE and the FX_ASM_ATOMIC scatter are sums of fp64 atomics in no fixed order: not compared.
+
+Linear case set (the host path of the linear static analysis), on the small distorted meshes of test_gpu_mixed_assembly.py:
+  every type through its single-type entry points, with one material and with two sections -- 361 with elemopt 1, 2, 3 and with
+  a collapsed hexahedron --, and the two three-type mixed meshes through fx_assemble_groups / fx_update_groups_linear, one
+  material and three sections.
+Outputs per case: D / AL / AU / B after assembly without and with load and boundary conditions, strain and stress of the update
+without and with a thermal view; per type the element stiffness.  A refused call is recorded by its return code.  Run it under
+the default, FX_ASM_FIRST=0 and FX_ASM_MAP=0, each in its own process (the switches are read once).  QFORCE and the thermal load
+vector are atomic sums: not compared."""
 import os
 import sys
 
@@ -144,6 +154,103 @@ def dump(path):
     return 0
 
 
+def dump_linear(path):
+    from frontistr_amd import hecmw as hip
+    from frontistr_amd.mesh import CubeMesh, MixedMesh, mesh_groups, solid_mesh
+    assert not os.environ.get("FX_ASM_ATOMIC"), "the atomic scatter has no fixed order"
+    out = {}
+
+    def record(name, call):
+        """call() -> {key: array}; a refusal is recorded by its code"""
+        try:
+            for k, v in call().items():
+                out["%s/%s" % (name, k)] = np.array(v)
+        except hip.HecmwSolverError as e:
+            out["%s/refused" % name] = np.array([e.code])
+
+    def case(name, m, groups, Es, nus, single):
+        """single: the group goes through the single-type entry points"""
+        et, conn, eo, em = groups[0]
+        hm = hip.hecmwST_local_mesh(n_node=m.n_node)
+        if single:
+            hm.nn_elem = conn.shape[1]
+            hm.elem_node_item = conn.ravel()
+            mat = hip.hecmw_mat_con(hm, hip.hecmwST_matrix())
+        else:
+            mat = hip.hecmw_mat_con_groups(hm, hip.hecmwST_matrix(), groups)
+        ctx = hip.SolverContext()
+        ctx.upload(mat, what=hip.FX_UP_PROFILE)
+
+        def assemble(load, bc):
+            if not single:
+                ctx.assemble_groups(m.coord, groups, Es, nus, load=load, bc=bc)
+            elif et == 361:
+                ctx.assemble_c3d8(m.coord, conn, Es[0], nus[0], elemopt=eo, load=load, bc=bc,
+                                  sections=None if em is None else (Es, nus, em))
+            else:
+                ctx.assemble_c3(m.coord, conn, et, Es, nus, load=load, bc=bc, elem_mat=em)
+            ctx.download_matrix(mat)
+            return {k: getattr(mat, k) for k in ("D", "AL", "AU", "B")}
+
+        def update(thermal):
+            if thermal is not None or not single:
+                s, t, _, _ = ctx.update_groups_linear(m.coord, groups, Es, nus, u, thermal=thermal)
+            elif et == 361:
+                s, t = ctx.update_c3d8_linear(m.coord, conn, Es, nus, u, elemopt=eo, elem_mat=em)[:2]
+                s, t = [s], [t]
+            else:
+                s, t = ctx.update_c3_linear(m.coord, conn, et, Es, nus, u, elem_mat=em)[:2]
+                s, t = [s], [t]
+            res = {"strain%d" % g: v for g, v in enumerate(s)}
+            res.update({"stress%d" % g: v for g, v in enumerate(t)})
+            return res
+
+        rng = np.random.default_rng(11)
+        u = 1e-3 * rng.standard_normal(3 * m.n_node)
+        temp, temp0 = 20.0 + 30.0 * rng.random(m.n_node), 20.0 + 5.0 * rng.random(m.n_node)
+        record(name + "/assemble", lambda: assemble(None, None))
+        record(name + "/assemble_load_bc", lambda: assemble(m.load(), m.dirichlet()))
+        record(name + "/assemble_again", lambda: assemble(None, None))
+        record(name + "/update", lambda: update(None))
+        record(name + "/update_thermal", lambda: update((temp, temp0, 20.0, 1.2e-5 * (1.0 + np.arange(len(Es))))))
+        ctx.close()
+
+    one = {361: lambda: CubeMesh(4, skew=0.1), 341: lambda: solid_mesh(3, 341, skew=0.1),
+           342: lambda: solid_mesh(2, 342, skew=0.1, curve=0.04), 351: lambda: solid_mesh(3, 351, skew=0.1),
+           352: lambda: solid_mesh(2, 352, skew=0.1, curve=0.04), 362: lambda: solid_mesh(2, 362, skew=0.1, curve=0.04)}
+    E1, NU1 = np.array([210000.0]), np.array([0.3])
+    ES, NUS = np.array([210000.0, 70000.0, 150000.0]), np.array([0.3, 0.33, 0.25])
+    for et in ETYPES:
+        m = one[et]()
+        variants = [("", m.conn)]
+        if et == 361:
+            c = m.conn.copy()
+            c[3, 3], c[3, 7] = c[3, 0], c[3, 4]
+            variants.append(("_collapsed", c))
+        for tag, conn in variants:
+            for eo in ((1, 2, 3) if et == 361 else (1,)):
+                em = (1 + np.arange(m.n_elem) % 2).astype(np.int32)
+                name = "t%d%s%s" % (et, tag, "_elemopt%d" % eo if et == 361 else "")
+                case(name + "_one_material", m, [(et, conn, eo, None)], E1, NU1, True)
+                case(name + "_two_sections", m, [(et, conn, eo, em)], ES[:2], NUS[:2], True)
+        ctx = hip.SolverContext()
+        ec = m.coord[m.conn[1] - 1]
+        for eo in ((1, 2, 3) if et == 361 else (1,)):
+            out["t%d_elemopt%d/element_stiffness" % (et, eo)] = (ctx.element_stiffness(eo, ec, 210000.0, 0.3) if et == 361 else
+                                                                 ctx.element_stiffness_c3(et, ec, 210000.0, 0.3))
+        ctx.close()
+    for order in (1, 2):
+        m = MixedMesh(2, order=order, skew=0.1, curve=0.04 if order == 2 else 0.0)
+        case("mixed_order%d_one_material" % order, m, m.groups, E1, NU1, False)
+        em = (1 + np.arange(m.n_elem) % 3).astype(np.int32)
+        case("mixed_order%d_three_sections" % order, m, m.groups_with(elemopt=2, elem_mat=em), ES, NUS, False)
+    np.savez(path, **out)
+    print("%d arrays of %d cases written to %s (library %s; FX_ASM_FIRST=%s FX_ASM_MAP=%s)" % (
+        len(out), len({k.split("/")[0] for k in out}), path, hip.LIBPATH, os.environ.get("FX_ASM_FIRST", "-"),
+        os.environ.get("FX_ASM_MAP", "-")))
+    return 0
+
+
 if __name__ == "__main__":
     from _libarg import take_lib
     take_lib()
@@ -152,4 +259,6 @@ if __name__ == "__main__":
         sys.exit(compare(args[1], args[2]))
     if len(args) == 2 and args[0] == "--dump":
         sys.exit(dump(args[1]))
+    if len(args) == 2 and args[0] == "--dump-linear":
+        sys.exit(dump_linear(args[1]))
     sys.exit(__doc__)

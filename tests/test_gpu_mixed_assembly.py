@@ -11,8 +11,11 @@ are read once per process, so each non-default path runs in a fresh child; the p
 tests); the group order permuted; two assemblies bit for bit, also after another mesh was assembled in between (the per-group
 colour / map cache); one group through assemble_groups bit for bit the single-type entry point, for each of the six types; a
 collapsed 361 element inside a mixed mesh; a degenerate wedge and an unknown type refused with the matrix of the previous
-assembly untouched; the stress update to 1e-11; CG + SSOR and CG + ILU(0) solves of the device-assembled mixed system against
+assembly untouched; the single-type entry points run the same group driver: their calls and multi-group calls alternate on one
+context (one cache) bit for bit, they refuse a bad node id before anything is uploaded, and the pinned staging of the stress
+update belongs to its context; the stress update to 1e-11; CG + SSOR and CG + ILU(0) solves of the device-assembled mixed system against
 the dense solve of the restated one."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -286,6 +289,115 @@ def test_refusals_leave_the_previous_matrix_untouched():
     ctx.close()
     for k in before:
         assert np.array_equal(before[k], again[k]), k
+
+
+def _fresh(hip, m, groups, call):
+    """D / AL / AU / B of call(ctx) on a new context holding the profile of `groups`."""
+    mat = M.profile(hip, m.n_node, groups)
+    ctx = hip.SolverContext()
+    ctx.upload(mat, what=hip.FX_UP_PROFILE)
+    call(ctx)
+    out = _arrays(ctx, mat)
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("collapsed", [False, True])
+def test_single_type_and_group_calls_share_one_cache_without_stale_flags(collapsed):
+    """assemble_c3d8 with the hexahedra alone, assemble_groups with all three groups, the hexahedra alone again, all on the
+    profile of the mixed mesh: every call re-colours and re-maps the one cache, and none inherits the other's first-write flags
+    (the hexahedra alone do not cover the profile: cleared; the three groups do: first-write, unless a hexahedron is collapsed)."""
+    from frontistr_amd import hecmw as hip
+    m = MESHES["m1_n2"]()
+    conns = [c.copy() for c in m.conns]
+    eo = 1
+    if collapsed:
+        conns[0][1, 3], conns[0][1, 7] = conns[0][1, 0], conns[0][1, 4]
+        eo = 3
+    groups = [(et, c, eo, None) for et, c in zip(m.etypes, conns)]
+    assert groups[0][0] == 361
+    load, bc = m.load(), bc_of(m)
+    hexes = lambda ctx: ctx.assemble_c3d8(m.coord, conns[0], E, NU, elemopt=eo, load=load, bc=bc)
+    mixed = lambda ctx: ctx.assemble_groups(m.coord, groups, E, NU, load=load, bc=bc)
+    mat = M.profile(hip, m.n_node, groups)
+    ctx = hip.SolverContext()
+    ctx.upload(mat, what=hip.FX_UP_PROFILE)
+    got = []
+    for call in (hexes, mixed, hexes):
+        call(ctx)
+        got.append(_arrays(ctx, mat))
+    ctx.close()
+    want_hexes, want_mixed = _fresh(hip, m, groups, hexes), _fresh(hip, m, groups, mixed)
+    for k in ("D", "AL", "AU", "B"):
+        assert np.array_equal(got[0][k], got[2][k]), k
+        assert np.array_equal(got[0][k], want_hexes[k]), k
+        assert np.array_equal(got[1][k], want_mixed[k]), k
+    assert not np.array_equal(got[0]["D"], got[1]["D"])
+
+
+def test_single_type_entries_refuse_a_bad_node_id_before_anything_is_uploaded():
+    from frontistr_amd import hecmw as hip
+    m = CubeMesh(3, skew=0.1)
+    hm = hip.hecmwST_local_mesh(n_node=m.n_node)
+    hm.elem_node_item = m.conn.ravel()
+    mat = hip.hecmw_mat_con(hm, hip.hecmwST_matrix())
+    ctx = hip.SolverContext()
+    ctx.upload(mat, what=hip.FX_UP_PROFILE)
+    ctx.assemble_c3d8(m.coord, m.conn, E, NU, elemopt=1, load=m.load(), bc=m.dirichlet())
+    before = _arrays(ctx, mat)
+    oob = m.conn.copy()
+    oob[5, 2] = m.n_node + 1
+    with pytest.raises(hip.HecmwSolverError) as e:
+        ctx.assemble_c3d8(m.coord, oob, E, NU, elemopt=1)
+    assert e.value.code == FX_ERROR_RUNTIME and "node id" in str(e.value) and "fx_assemble_c3d8:" in str(e.value)
+    after = _arrays(ctx, mat)
+    for k in ("D", "AL", "AU", "B"):
+        assert np.array_equal(before[k], after[k]), k
+    with pytest.raises(hip.HecmwSolverError) as e:
+        ctx.update_c3d8_linear(m.coord, oob, E, NU, np.zeros(m.ndof), elemopt=1)
+    assert e.value.code == FX_ERROR_RUNTIME and "node id" in str(e.value) and "fx_update_c3d8_linear:" in str(e.value)
+    ctx.close()
+
+
+def _update_c3d8_raw(hip, ctx, coord, conn, u):
+    """fx_update_c3d8_linear (IC) itself: the library's pointers into the context's pinned staging, not copies."""
+    mv = hip._MeshView(coord.shape[0], conn.shape[0], hip._ptr(coord), hip._ptr(conn))
+    Es, nus = np.array([E]), np.array([NU])
+    ps, pt = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+    hip._chk(hip.lib().fx_update_c3d8_linear(ctx.h, C.byref(mv), 1, hip._ptr(Es), hip._ptr(nus), None, 1, hip._ptr(u), C.byref(ps),
+                                             C.byref(pt), None, None))
+    n = 48 * conn.shape[0]
+    return np.ctypeslib.as_array(ps, shape=(n,)), np.ctypeslib.as_array(pt, shape=(n,))
+
+
+def test_update_staging_belongs_to_its_context():
+    """Context B pins a larger staging (prepare + update) after context A's update: A's pointers still read A's values, B's
+    read B's; after B is destroyed A updates again into the same values."""
+    from frontistr_amd import hecmw as hip
+    small, big = CubeMesh(2, skew=0.1), CubeMesh(3, skew=0.1)
+    coord_a, conn_a = np.ascontiguousarray(small.coord), np.ascontiguousarray(small.conn[:2], dtype=np.int32)   # two elements
+    coord_b, conn_b = np.ascontiguousarray(big.coord), np.ascontiguousarray(big.conn, dtype=np.int32)
+    ua = 1e-3 * np.random.default_rng(3).standard_normal(3 * small.n_node)
+    ub = 1e-3 * np.random.default_rng(4).standard_normal(3 * big.n_node)
+    ref = hip.SolverContext()
+    want_b = ref.update_c3d8_linear(coord_b, conn_b, E, NU, ub, elemopt=1)[:2]
+    ref.close()
+    a, b = hip.SolverContext(), hip.SolverContext()
+    sa, ta = _update_c3d8_raw(hip, a, coord_a, conn_a, ua)
+    keep_s, keep_t = sa.copy(), ta.copy()
+    assert np.abs(keep_s).max() > 0 and np.abs(keep_t).max() > 0
+    hip._chk(hip.lib().fx_update_c3d8_linear_prepare(b.h, int(conn_b.shape[0])))
+    sb, tb = _update_c3d8_raw(hip, b, coord_b, conn_b, ub)
+    assert sa.ctypes.data != sb.ctypes.data and ta.ctypes.data != tb.ctypes.data
+    assert np.array_equal(sa, keep_s) and np.array_equal(ta, keep_t)
+    assert np.array_equal(sb, want_b[0].ravel()) and np.array_equal(tb, want_b[1].ravel())
+    del sb, tb
+    b.close()
+    assert np.array_equal(sa, keep_s) and np.array_equal(ta, keep_t)
+    sa2, ta2 = _update_c3d8_raw(hip, a, coord_a, conn_a, ua)
+    assert np.array_equal(sa2, keep_s) and np.array_equal(ta2, keep_t)
+    del sa, ta, sa2, ta2
+    a.close()
 
 
 @pytest.mark.parametrize("name", ["m1_n5", "m2_n2", "m2_n2_renum"])
