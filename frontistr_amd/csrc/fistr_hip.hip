@@ -17,6 +17,7 @@
 #include "fx_assemble_c3.h"
 #include "fx_kernels.h"
 #include "fx_nonlinear.h"
+#include "fx_nonlinear_fbar.h"
 #include "fx_nonlinear_tet.h"
 #include "fx_nonlinear_c3.h"
 

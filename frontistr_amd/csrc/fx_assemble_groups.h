@@ -44,12 +44,13 @@ static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group
 // What the linear entry points and fx_nl_init_groups refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
 // material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
 static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                        int32_t n_mat, bool have_mats) {
+                        int32_t n_mat, bool have_mats, bool nonlinear = false) {
   if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
   for (int32_t g = 0; g < n_group; g++) {
     if (c3_nodes(groups[g].etype) == 0)
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)",
                          (int)g + 1, (int)groups[g].etype);
+    if (nonlinear) continue;  // fx_nl_init_groups names what it serves of 361 itself
     if (groups[g].etype == 361 && (groups[g].elemopt < 1 || groups[g].elemopt > 3))
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
   }

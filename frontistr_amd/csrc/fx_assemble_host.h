@@ -212,6 +212,9 @@ static int assembly_error(int32_t herr) {
   if (herr == 3) { g_fx_error = "Math Error in Mohr-Coulomb calculation (|sin 3 theta| > 1, Elastoplastic.f90:85, :338, :474)"; return FX_ERROR_RUNTIME; }
   if (herr == 4) { g_fx_error = "Math error in return mapping (Elastoplastic.f90:496, :541)"; return FX_ERROR_RUNTIME; }
   if (herr == 5) { g_fx_error = "Jacobi iteration unable to converge (eigen3, utilities.f90:200)"; return FX_ERROR_RUNTIME; }
+  // the `stop` statements of the F-bar hexahedron (FX_FERR_*, fx_nonlinear_fbar.h)
+  if (herr == 6) { g_fx_error = "Error in Update_C3D8Fbar: too small element volume (static_LIB_Fbar.f90:121, :456)"; return FX_ERROR_RUNTIME; }
+  if (herr == 7) { g_fx_error = "Error in Update_C3D8Fbar: too small average jacob (static_LIB_Fbar.f90:115, :450)"; return FX_ERROR_RUNTIME; }
   return 0;
 }
 // hecmw_mat_clear (fstr_StiffMatrix.f90:40)

@@ -226,7 +226,8 @@ struct UpdStage {
 // conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
 constexpr int NL_GROUPS = 7;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
 struct NlPart {
-  int32_t etype = 361;                // 361 (B-bar), 341, 342, 351, 352 or 362
+  int32_t etype = 361;                // 361 (B-bar, or F-bar: fbar), 341, 342, 351, 352 or 362
+  bool fbar = false;                  // a 361 part of F-bar elements (elemopt 4): k_nl_stiffness_fbar / k_nl_update_fbar
   int nn = 8, nq = 8;                 // its nodes and quadrature points per element
   int32_t n_elem = 0;
   int64_t elem_off = 0, pt_off = 0;   // elements / quadrature points of the parts before this one
@@ -247,6 +248,7 @@ struct NlDev {
   std::vector<NlPart> parts;          // in the order given; the per-point arrays and the element outputs hold them one after the other
   bool first_write = false;           // every part's map carries first-write flags in the launch order of ALL parts and every block is covered: no clearing
   bool has_yield = false;             // a Mohr-Coulomb or Drucker-Prager section: the stress update reports through the error word too
+  bool has_fbar = false;              // an F-bar part: so does its stress update (`too small element volume`, `too small average jacob`)
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material
   std::vector<NlMat> h_mats;

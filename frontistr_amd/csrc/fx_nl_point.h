@@ -1,5 +1,5 @@
 // Point functions of the nonlinear element kernels: what does not depend on the element family a quadrature point
-// belongs to.  The three families (fx_nonlinear.h: 361 B-bar; fx_nonlinear_tet.h: 341 / 342; fx_nonlinear_c3.h: 351 / 352 / 362) keep
+// belongs to.  The families (fx_nonlinear.h: 361 B-bar; fx_nonlinear_fbar.h: 361 F-bar; fx_nonlinear_tet.h: 341 / 342; fx_nonlinear_c3.h: 351 / 352 / 362) keep
 // their own lane mappings, staging and their own text of the tangent and update sequences; shared are:
 //
 //   nl_point_matrix    material matrix of a point: MatlMatrix with its latch minus GEOMAT_C3, as STF_C3D8Bbar

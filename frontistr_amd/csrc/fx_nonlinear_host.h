@@ -82,6 +82,7 @@ static int nl_check_materials(const char *who, int32_t n_mat, const fx_material_
 struct NlPartIn {
   int32_t etype, n_elem;
   const int32_t *conn, *elem_mat;  // elem_mat: null with one material
+  bool fbar = false;               // 361: F-bar (elemopt 4), not B-bar
 };
 
 // Element lists of one part: grouped by the NLGEOM flag of the element's material, hyperelastic ones apart (one kernel instantiation
@@ -144,6 +145,8 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
   for (size_t i = 0; i < in.size(); i++) {
     NlPart &p = n.parts[i];
     p.etype = in[i].etype; p.nn = c3_nodes(p.etype); p.nq = c3_points(p.etype);
+    p.fbar = p.etype == 361 && in[i].fbar;
+    n.has_fbar |= p.fbar;
     p.n_elem = in[i].n_elem;
     p.elem_off = n.n_elem; p.pt_off = n.n_pt; p.k_off = n.n_k; p.qf_off = n.n_qf;
     if ((int64_t)n.n_elem + p.n_elem > INT32_MAX) { g_fx_error = "fx_nl_init: more than 2^31 - 1 elements"; return FX_ERROR_RUNTIME; }
@@ -231,7 +234,7 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
 // fstr_solid / tGaussStatus set-up for one group of one type (fstr_setup.f90:325-400, fstr_init_gauss mechgauss.f90:37-71): zero
 // state, zero displacement.
 static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                          const int32_t *elem_mat, int32_t etype, const char *who) {
+                          const int32_t *elem_mat, int32_t etype, const char *who, bool fbar = false) {
   HIP_TRY(hipSetDevice(c->device));
   const int nn = c3_nodes(etype);
   if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
@@ -245,7 +248,7 @@ static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat
     for (int32_t e = 0; e < mesh->n_elem; e++)
       if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
   if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;
-  return nl_init_parts(c, mesh->n_node, mesh->coord, {{etype, mesh->n_elem, mesh->conn, n_mat > 1 ? elem_mat : nullptr}}, n_mat, mats);
+  return nl_init_parts(c, mesh->n_node, mesh->coord, {{etype, mesh->n_elem, mesh->conn, n_mat > 1 ? elem_mat : nullptr, fbar}}, n_mat, mats);
 }
 
 extern "C" int fx_nl_init(fx_context *c, const fx_mesh_view *mesh, const fx_material_view *mat) {
@@ -285,28 +288,42 @@ extern "C" int fx_nl_init_type(fx_context *c, const fx_mesh_view *mesh, int32_t 
 }
 
 // The same context for a mesh of several solid element types (fstr_StiffMatrix.f90:43-212 and fstr_Update.f90:73-264 loop over
-// hecMESH%elem_type_item; a group is one entry of that loop).  One material table serves all groups.
+// hecMESH%elem_type_item; a group is one entry of that loop).  One material table serves all groups.  A 361 group is B-bar
+// (elemopt 2) or F-bar (elemopt 4, fx_nonlinear_fbar.h: INFINITE and TOTALLAG materials only); part g launches the family its
+// elemopt names, everything else of a part -- lists, colours, history, outputs -- is the same for both.
 extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                                  int32_t n_mat, const fx_material_view *mats) {
   const char *who = "fx_nl_init_groups";
   if (!c) { g_fx_error = "fx_nl_init_groups: null argument"; return FX_ERROR_RUNTIME; }
-  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, mats != nullptr)) return rc;
-  for (int32_t g = 0; g < n_group; g++)
-    if (groups[g].etype == 361 && groups[g].elemopt != 2)
+  if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, mats != nullptr, true)) return rc;
+  for (int32_t g = 0; g < n_group; g++) {
+    const fx_elem_group &G = groups[g];
+    if (G.etype != 361) continue;
+    if (G.elemopt != 2 && G.elemopt != 4)
       return fx_fail(who, FX_ERROR_UNSUPPORTED,
-                     "group %d: elemopt %d of TYPE=361; the nonlinear loop serves 361 with elemopt 2 (B-bar) only", (int)g + 1,
-                     (int)groups[g].elemopt);
+                     "group %d: elemopt %d of TYPE=361; the nonlinear loop serves 361 with elemopt 2 (B-bar) and 4 (F-bar) only", (int)g + 1,
+                     (int)G.elemopt);
+    if (G.elemopt != 4) continue;
+    // Update_C3D8Fbar's UPDATELAG branch reads a local array it never assigned (static_LIB_Fbar.f90:600-602): nothing to be equal to
+    for (int32_t e = 0; e < G.n_elem; e++)
+      if (mats[n_mat > 1 ? G.elem_mat[e] - 1 : 0].nlgeom == 2)
+        return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                       "group %d: an F-bar element (elemopt 4) with an UPDATELAG material (nlgeom 2), element %d; F-bar is served for "
+                       "INFINITE and TOTALLAG", (int)g + 1, (int)e + 1);
+  }
   HIP_TRY(hipSetDevice(c->device));
   if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
   if (n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
   if (int e = nl_check_materials(who, n_mat, mats)) return e;
   std::vector<NlPartIn> in;
   for (int32_t g = 0; g < n_group; g++)
-    if (groups[g].n_elem > 0) in.push_back({groups[g].etype, groups[g].n_elem, groups[g].conn, n_mat > 1 ? groups[g].elem_mat : nullptr});
+    if (groups[g].n_elem > 0)
+      in.push_back({groups[g].etype, groups[g].n_elem, groups[g].conn, n_mat > 1 ? groups[g].elem_mat : nullptr,
+                    groups[g].etype == 361 && groups[g].elemopt == 4});
   if (in.empty()) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
   if (in.size() == 1) {  // the single-type context
     const fx_mesh_view mesh = {n_node, in[0].n_elem, coord, in[0].conn};
-    return nl_init_common(c, &mesh, n_mat, mats, in[0].elem_mat, in[0].etype, who);
+    return nl_init_common(c, &mesh, n_mat, mats, in[0].elem_mat, in[0].etype, who, in[0].fbar);
   }
   return nl_init_parts(c, n_node, coord, in, n_mat, mats);
 }
@@ -329,7 +346,7 @@ static void for_each_nl_group(F &&f) {
 template <int ETYPE, int G, bool UPDATE>
 static constexpr auto nl_c3_kernel() {
   if constexpr (UPDATE) {
-    if constexpr (ETYPE == 361) return k_nl_update<G>;
+    if constexpr (ETYPE == 361) return k_nl_update<G>;  // (an F-bar part: nl_fbar_update_kernel)
     else if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
     else return k_nl_update_c3<ETYPE, G>;
   } else {
@@ -342,6 +359,8 @@ template <int ETYPE>
 static constexpr int NL_UPDATE_EPB = ETYPE == 361 ? FXN_EPB : C3El<ETYPE>::UEPB;  // elements per workgroup of the update kernel
 template <int ETYPE>
 static constexpr int NL_UPDATE_BLOCK = ETYPE == 361 ? FXN_BLOCK : C3El<ETYPE>::BS;
+// The groups the F-bar kernels are instantiated for: no UPDATELAG (fx_nl_init_groups refuses it, so such a list is empty)
+static constexpr bool nl_fbar_group(int G) { return nl_group_flag(G) != 2; }
 // A part's block of the per-point arrays
 struct NlPartState {
   double *stress, *strain, *stress_bak, *strain_bak, *plstrain, *fstat;
@@ -371,8 +390,15 @@ template <int ETYPE, int G>
 static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
   const NlPartState s = nl_part_state(n, p);
+  auto kern = nl_c3_kernel<ETYPE, G, true>();
+  if constexpr (ETYPE == 361) {  // same arguments, block and elements per workgroup
+    if (p.fbar) {
+      if constexpr (nl_fbar_group(G)) kern = k_nl_update_fbar<G>;
+      else return;
+    }
+  }
   auto launch = [&](const int32_t *list, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, true>()), dim3((unsigned)((e1 - e0 + NL_UPDATE_EPB<ETYPE> - 1) / NL_UPDATE_EPB<ETYPE>)),
+    hipLaunchKernelGGL(kern, dim3((unsigned)((e1 - e0 + NL_UPDATE_EPB<ETYPE> - 1) / NL_UPDATE_EPB<ETYPE>)),
                        dim3(NL_UPDATE_BLOCK<ETYPE>), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, s.stress, s.strain,
                        s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats,
                        (const int32_t *)p.emat, n.err);
@@ -393,9 +419,16 @@ static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Ko
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
   const NlPartState s = nl_part_state(n, p);
+  // the part's family: the two kernels take the same arguments and differ in their workgroup
+  auto kern = k_nl_stiffness<G>;
+  int epb = FXN_EPB, block = FXN_BLOCK;
+  if (p.fbar) {
+    if constexpr (nl_fbar_group(G)) { kern = k_nl_stiffness_fbar<G>; epb = FXF_EPB; block = FXF_BLOCK; }
+    else return;
+  }
   // element matrices out, or atomics: the group's colours in one launch
-  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, FXN_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((k_nl_stiffness<G>), grid, dim3(FXN_BLOCK), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch,
+  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, epb, [&](dim3 grid, int32_t e0, int32_t e1) {
+    hipLaunchKernelGGL(kern, grid, dim3(block), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch,
                        s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
                        (const int32_t *)p.colors.order, e0, (const int32_t *)p.colors.pos, p.scatter_atomic ? 1 : 0,
                        (const NlMat *)n.mats, (const int32_t *)p.emat, 0, (const double *)s.strain);
@@ -405,7 +438,7 @@ static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Ko
   const std::vector<int32_t> &doff = p.dup_off[G];
   if (doff.empty()) return;
   const int32_t d0 = doff.front(), d1 = doff.back();
-  hipLaunchKernelGGL((k_nl_stiffness<G>), dim3((d1 - d0 + FXN_EPB - 1) / FXN_EPB), dim3(FXN_BLOCK), 0, c->stream, d1, n.coord, p.conn,
+  hipLaunchKernelGGL(kern, dim3((d1 - d0 + epb - 1) / epb), dim3(block), 0, c->stream, d1, n.coord, p.conn,
                      n.unode, n.dunode, n.mat, n.latch, s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
                      Kout ? Kout : dup_k, n.err, (const int32_t *)p.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
                      (const int32_t *)p.emat, Kout ? 0 : 1, (const double *)s.strain);
@@ -447,14 +480,14 @@ static void nl_launch_update(fx_context *c, double *qf_out) {  // qf_out: the el
       });
     });
 }
-// The stress update of a context with a Mohr-Coulomb / Drucker-Prager section reports the reference's `stop` statements through the
-// error word: cleared before the launches, read after them (one 4-byte copy; contexts without such a section skip both).
+// The stress update of a context with a Mohr-Coulomb / Drucker-Prager section or an F-bar part reports the reference's `stop`
+// statements through the error word: cleared before the launches, read after them (one 4-byte copy; other contexts skip both).
 static int nl_update_err_clear(fx_context *c) {
-  if (c->nl.has_yield) HIP_TRY(hipMemsetAsync(c->nl.err, 0, 4, c->stream));
+  if (c->nl.has_yield || c->nl.has_fbar) HIP_TRY(hipMemsetAsync(c->nl.err, 0, 4, c->stream));
   return 0;
 }
 static int nl_update_err_check(fx_context *c) {
-  if (!c->nl.has_yield) return 0;
+  if (!c->nl.has_yield && !c->nl.has_fbar) return 0;
   int32_t herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, c->nl.err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

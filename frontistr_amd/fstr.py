@@ -13,7 +13,8 @@
     fstr_Newton          fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
 
-for one TYPE=361 B-bar group, or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
+for one TYPE=361 B-bar or F-bar group (fstr_solid(..., elemopt=2 | 4); F-bar: `!SECTION, FORM361=FBAR`, INFINITE and TOTALLAG materials),
+or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
 (fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3), or a mesh of several groups of these types
 (fstr_solid(ctx, coord, None, materials, groups=[...]): fx_nl_init_groups),
 with one isotropic (elastic; Mises, Mohr-Coulomb or Drucker-Prager elastoplastic: tMaterial.mohr_coulomb / .drucker_prager; or
@@ -121,14 +122,15 @@ class fstr_solid:
     NODES = {361: 8, 341: 4, 342: 10, 351: 6, 352: 15, 362: 20}     # nodes per element
     POINTS = {361: 8, 341: 1, 342: 4, 351: 2, 352: 9, 362: 27}      # quadrature points per element (NumOfQuadPoints)
 
-    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361, groups=None):
+    def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361, groups=None, elemopt=2):
         """material: one tMaterial, or a list of them with elem_mat (1-based material id per element = the section's
         material, hecMESH%section_ID -> fstrSOLID%materials).  etype: 361 (B-bar), 341 / 342 (fx_nl_init_c3), or 351 / 352 / 362
-        (fx_nl_init_type with the row length of hecMESH_conn).
+        (fx_nl_init_type with the row length of hecMESH_conn).  elemopt (etype 361 only): 2 B-bar, 4 F-bar; any value but 2 goes
+        through fx_nl_init_groups with one group, which makes the same single-type context and refuses what is not served.
 
         A mesh of several solid element types (fx_nl_init_groups): hecMESH_conn = None and groups = [(etype, conn, elemopt,
         elem_mat), ...], the tuples of SolverContext.assemble_groups / mesh.mesh_groups; a 361 group is B-bar (elemopt 2, also
-        taken when left out or None), elem_mat of every group is 1-based into the one list ``material``.  The state arrays and
+        taken when left out or None) or F-bar (elemopt 4), elem_mat of every group is 1-based into the one list ``material``.  The state arrays and
         the element outputs are then flat, the groups one after the other (point_offsets, elem_offsets; group_slices cuts them
         into per-group views)."""
         self.ctx = ctx
@@ -145,6 +147,17 @@ class fstr_solid:
         self.conn = np.ascontiguousarray(hecMESH_conn, dtype=np.int32)
         self.n_elem = self.conn.shape[0]
         self._set_parts([(self.etype, self.n_elem)])
+        if self.etype == 361 and int(elemopt) != 2:
+            mats = list(material) if isinstance(material, (list, tuple)) else [material]
+            self.elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+            if len(mats) > 1 and (self.elem_mat is None or self.elem_mat.shape != (self.n_elem,)):
+                raise ValueError("elem_mat: one material id per element")
+            tab, keep = hecmw.SolverContext._group_table([(361, self.conn, int(elemopt), self.elem_mat)])
+            views = [m.view() for m in mats]
+            arr = (_MaterialView * len(views))(*views)
+            _chk(lib().fx_nl_init_groups(ctx.h, self.n_node, _ptr(self.coord), 1, tab, len(views), arr))
+            del keep
+            return
         mv = hecmw._MeshView(self.n_node, self.n_elem, _ptr(self.coord), _ptr(self.conn))
         if self.etype != 361:
             mats = list(material) if isinstance(material, (list, tuple)) else [material]

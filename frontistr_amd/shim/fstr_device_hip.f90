@@ -45,6 +45,7 @@ module fstr_device_hip
   integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or a type of STF_C3 / UPDATE_C3 (fx_nl_init_type)
   integer, save :: nl_nq = 8                       ! its quadrature points per element
   logical, save :: nl_mixed = .false.              ! several of the six solid types (HECMW_GPU_NL_MIXED=1): fx_nl_init_groups
+  logical, save :: nl_fbar = .false.               ! the 361 sections are F-bar, all of them (HECMW_GPU_NL_FBAR=1): fx_nl_init_groups with elemopt 4
   integer, allocatable, save :: el_nq(:), el_p0(:) ! per element: its type's quadrature points, and the points of the elements before it
   integer, save :: n_pt = 0                        ! quadrature points of the mesh: the per-point arrays are flat over them, in hecMESH's element order
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
@@ -80,7 +81,7 @@ contains
     character(len=8) :: env
     character(len=3) :: tname
     character(len=64) :: tnames
-    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype
+    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype, n_bbar, n_fbar
     integer(c_int32_t) :: et
     logical :: opted
     if (decided) then
@@ -134,8 +135,20 @@ contains
     ! (automatic incrementation, `!AUTOINC_PARAM`: fstr_cutback_save / _load roll the device's copy of the history back with the
     !  host's, shim/fstr_Cutback_hip.f90 -> fsd_cutback.  A run continued from a restart file: the history read from the file is what
     !  fsd_init pushes to the device at the first fstr_StiffMatrix, after fstr_read_restart, fstr_solve_NLGEOM.f90:70-76.)
+    ! the formulation of the 361 elements: B-bar, or -- with HECMW_GPU_NL_FBAR=1 -- F-bar (`!SECTION, FORM361=FBAR`), the same for all
+    ! of them: a mesh with sections of both keeps the host loops, as does any IC or FI section
+    n_bbar = 0
+    n_fbar = 0
     do i = 1, hecMESH%section%n_sect
-      if (lin_etype == 361 .and. .not. nl_mixed .and. fstrSOLID%sections(i)%elemopt361 /= kel361BBAR) return
+      if (lin_etype == 361 .and. .not. nl_mixed) then
+        if (fstrSOLID%sections(i)%elemopt361 == kel361BBAR) then
+          n_bbar = n_bbar + 1
+        else if (fstrSOLID%sections(i)%elemopt361 == kel361FBAR) then
+          n_fbar = n_fbar + 1
+        else
+          return
+        endif
+      endif
       if (hecMESH%section%sect_orien_ID(i) > 0) return
     enddo
     if (nl_mixed) then      ! the node count per element, checked per type range; B-bar for the sections of the 361 elements
@@ -146,7 +159,13 @@ contains
         do icel = hecMESH%elem_type_index(itype-1) + 1, hecMESH%elem_type_index(itype)
           if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
           if (et == 361) then
-            if (fstrSOLID%sections(hecMESH%section_ID(icel))%elemopt361 /= kel361BBAR) return
+            if (fstrSOLID%sections(hecMESH%section_ID(icel))%elemopt361 == kel361BBAR) then
+              n_bbar = n_bbar + 1
+            else if (fstrSOLID%sections(hecMESH%section_ID(icel))%elemopt361 == kel361FBAR) then
+              n_fbar = n_fbar + 1
+            else
+              return
+            endif
           endif
           cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
           if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
@@ -157,6 +176,20 @@ contains
         if (hecMESH%elem_node_index(icel) - hecMESH%elem_node_index(icel-1) /= nn) return
         cid = hecMESH%section%sect_mat_ID_item(hecMESH%section_ID(icel))
         if (.not. associated(fstrSOLID%elements(icel)%gausses(1)%pMaterial, fstrSOLID%materials(cid))) return
+      enddo
+    endif
+    nl_fbar = n_fbar > 0
+    if (nl_fbar) then
+      ! F-bar decks opt in: no end-to-end time against the host loops is on record (DESIGN.md section 7)
+      if (n_bbar > 0) return
+      if (hecMESH%PETOT > 1) return
+      call get_environment_variable('HECMW_GPU_NL_FBAR', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+      ! Update_C3D8Fbar's UPDATELAG branch reads a local array it never assigned (static_LIB_Fbar.f90:600-602): no material of an
+      ! F-bar section may be UPDATELAG (`!ELASTIC, CAUCHY`, the default of `!PLASTIC`)
+      do icel = 1, hecMESH%n_elem
+        if (hecMESH%elem_type(icel) /= 361) cycle
+        if (fstrSOLID%elements(icel)%gausses(1)%pMaterial%nlgeom_flag == UPDATELAG) return
       enddo
     endif
     n_hyper = 0
@@ -196,6 +229,7 @@ contains
       enddo
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//trim(tnames)//'); '// &
         'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+      if (nl_fbar .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: the TYPE=361 sections are F-bar (HECMW_GPU_NL_FBAR=1)'
       if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
       if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
       return
@@ -208,8 +242,13 @@ contains
       if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
       return
     endif
-    if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
-      'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+    if (nl_fbar) then
+      if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 F-bar); '// &
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+    else
+      if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+    endif
     if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
     if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
   end function fsd_eligible
@@ -543,12 +582,13 @@ contains
     if (allocated(el_nq)) deallocate(el_nq, el_p0)
     allocate(el_nq(n_elem), el_p0(n_elem))
     el_nq = nl_nq
-    if (nl_mixed) then      ! elem_node_item holds the elements type by type: a group is a pointer into it (and into emat), B-bar for 361
+    if (nl_mixed .or. nl_fbar) then      ! elem_node_item holds the elements type by type: a group is a pointer into it (and into emat); 361: B-bar, or F-bar
       allocate(groups(hecMESH%n_elem_type))
       do itype = 1, hecMESH%n_elem_type
         first = hecMESH%elem_type_index(itype-1) + 1
         groups(itype)%etype = int(hecMESH%elem_type_item(itype), c_int32_t)
         groups(itype)%elemopt = 2
+        if (nl_fbar) groups(itype)%elemopt = 4
         groups(itype)%n_elem = int(hecMESH%elem_type_index(itype) - hecMESH%elem_type_index(itype-1), c_int32_t)
         groups(itype)%conn = c_null_ptr
         groups(itype)%elem_mat = c_null_ptr
@@ -566,7 +606,7 @@ contains
       el_p0(icel) = n_pt
       n_pt = n_pt + el_nq(icel)
     enddo
-    if (nl_mixed) then
+    if (nl_mixed .or. nl_fbar) then      ! (a single-type F-bar mesh: one group, which makes the single-type context)
       ierr = fx_nl_init_groups(ctx, int(hecMESH%n_node, c_int32_t), hecMESH%node, int(size(groups), c_int32_t), groups, &
                                int(nmat, c_int32_t), mats)
       if (ierr /= 0) call fsd_fail('fx_nl_init_groups')

@@ -297,7 +297,7 @@ int fx_element_stiffness_c3(fx_context *ctx, int32_t etype, const double *ecoord
  * may differ in elemopt. */
 typedef struct fx_elem_group {
   int32_t etype;           /* 361, 341, 342, 351, 352, 362 */
-  int32_t elemopt;         /* 361 only: 1 IC, 2 B-bar, 3 FI; ignored otherwise */
+  int32_t elemopt;         /* 361 only: 1 IC, 2 B-bar, 3 FI, and for fx_nl_init_groups alone 4 F-bar; ignored otherwise */
   int32_t n_elem;
   const int32_t *conn;     /* nn(etype) * n_elem, 1-based */
   const int32_t *elem_mat; /* 1-based per element, may be NULL with one material */
@@ -431,9 +431,18 @@ int fx_nl_init_type(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, in
  * group with its own colouring: no atomics, two fx_nl_stiffness calls on the same state give bitwise equal D / AL / AU.  Collapsed
  * hexahedra of a 361 group are served as in fx_nl_init.  With ONE non-empty group the context and all it computes are bit for
  * bit those of fx_nl_init_sections / fx_nl_init_type.
- * Refused, the previous context untouched: an unknown etype, or elemopt 1 / 3 on a 361 group (named): FX_ERROR_UNSUPPORTED, as
+ * A 361 group is B-bar (elemopt 2) or F-bar (elemopt 4: !SECTION, FORM361=FBAR; STF_C3D8Fbar / Update_C3D8Fbar,
+ * static_LIB_Fbar.f90:26-769, in their INFINITE and TOTALLAG branches, with every material kind the loop has under those flags);
+ * groups of either formulation and of the other five types may share one context.  Layouts, colouring, latch, snapshot, commit
+ * and the state views are the same for both.  The two `stop` statements of the F-bar routines (`too small element volume`,
+ * |V0| <= 1e-12, and `too small average jacob`) come back from fx_nl_stiffness* / fx_nl_update* / fx_nl_element_* as
+ * FX_ERROR_RUNTIME with that text.  F-bar with an UPDATELAG material is refused: Update_C3D8Fbar's UPDATELAG branch builds `rot`
+ * from the local array Fbar (:600-602), which only the TOTALLAG branch assigns (:556), so the reference defines no result there.
+ * Refused, the previous context untouched: an unknown etype, an elemopt other than 2 and 4 on a 361 group (1 IC and 3 FI among
+ * them; named), an F-bar group with an element whose material has nlgeom 2 (group and element named): FX_ERROR_UNSUPPORTED, as
  * are the materials fx_nl_init* refuse; n_group < 1, no element at all, missing materials, a material or node id out of range, a
- * degenerate element of a type other than 361 (named with group and element): FX_ERROR_RUNTIME. */
+ * degenerate element of a type other than 361 (named with group and element): FX_ERROR_RUNTIME.
+ * fx_nl_init and fx_nl_init_sections stay B-bar; the linear entry points (fx_assemble_groups, ...) keep refusing elemopt 4. */
 int fx_nl_init_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                       int32_t n_mat, const fx_material_view *mats);
 /* fstr_Newton :63-68 + fstr_ass_load: dunode = 0, GL (3*NP, may be NULL), B = GL - QFORCE. */

@@ -32,6 +32,8 @@ NLSTATIC decks of the STF_C3 types and of the mixed cube (--etype 341|342|351|35
                                                              the first plastic update every tangent is the elastic one, the sub-steps take 10
                                                              to 40 Newton iterations to CONVERG = 1e-3, and what the linear solves leave
                                                              unconverged stays in the printed stresses (2e-4 of 1.5 at 1e-8).
+--form361 FI|BBAR|IC|FBAR (TYPE=361 cubes, linear or NLSTATIC): `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320), and the
+same for SECNUM=2 with --two-sections; without it the program's default (IC in a linear analysis, B-bar under NLSTATIC).
 --thermal (with --linear): a thermal-stress deck.  `!REFTEMP 20`, `!INITIAL CONDITION, TYPE=TEMPERATURE` (ALL, 25) in the mesh file,
 `!TEMPERATURE` on the node groups FIX (35) and TOP (120) -- every other node keeps the initial condition's, so the temperature
 varies inside the elements -- and `!EXPANSION_COEFF` 1.2e-5 for MAT1, 2.3e-5 for MAT2."""
@@ -43,9 +45,11 @@ import numpy as np
 linear = "--linear" in sys.argv      # !SOLUTION, TYPE=STATIC: bench.py's workload (z = 0 clamped, unit load in x on every top node, E = 210000, nu = 0.3)
 if linear:
     sys.argv.remove("--linear")
-form361 = None                       # --form361 FI|BBAR|IC: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's (IC)
+form361 = None                       # --form361 FI|BBAR|IC|FBAR: `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320); default: the program's
 if "--form361" in sys.argv:
     k = sys.argv.index("--form361"); form361 = sys.argv[k + 1]; del sys.argv[k:k + 2]
+    if form361 not in ("FI", "BBAR", "IC", "FBAR"):
+        sys.exit("--form361 takes FI, BBAR, IC or FBAR")
 etype = 361                          # --etype 341|342|351|352|362: tetrahedra, wedges, 20-node hexahedra
 if "--etype" in sys.argv:
     k = sys.argv.index("--etype"); etype = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
@@ -132,6 +136,7 @@ with open(os.path.join(d, "cube.msh"), "w") as fh:
             fh.write("!NGROUP, NGRP=%s\n" % name)
             np.savetxt(fh, ids.reshape(-1, 1), fmt=" %d")
         fh.write("!END\n")
+SECTIONS = "".join("!SECTION, SECNUM=%d, FORM361=%s\n" % (s, form361) for s in ((1, 2) if two else (1,))) if form361 else ""
 if linear:
     with open(os.path.join(d, "cube.cnt"), "w") as fh:
         fh.write("""!VERSION
@@ -153,7 +158,7 @@ if linear:
 """ % ("!REFTEMP\n 20.0\n" if thermal else "", "!TEMPERATURE\n FIX, 35.0\n TOP, 120.0\n" if thermal else "",
        "!EXPANSION_COEFF\n 1.2e-5\n" if thermal else "",
        ("!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n" + ("!EXPANSION_COEFF\n 2.3e-5\n" if thermal else "")) if two else "",
-       "!SECTION, SECNUM=1, FORM361=%s\n" % form361 if form361 else "", method, precond))
+       SECTIONS, method, precond))
 # MAT1 of the NLSTATIC deck.  multilinear / bilinear: Mises, updated Lagrange (the default of !PLASTIC); elastic_tl: total Lagrange
 # (the default of !ELASTIC under NLSTATIC); elastic_ul: `!ELASTIC, CAUCHY`, updated Lagrange.  --two-sections: MAT2 is ELASTIC (total Lagrange).
 NL_MATERIALS = {
@@ -195,13 +200,13 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
 !STEP, SUBSTEPS=%d, CONVERG=1.0e-3
  BOUNDARY, 1
 !MATERIAL, NAME=MAT1
-%s%s!RESTART, FREQUENCY=100000
+%s%s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  5000, 1
  %s, 1.0, 0.0
 !END
 """ % (strain * n, 0.2 * strain * n, nsub, NL_MATERIALS[nlmat],
-       MAT2 if two else "", method, precond, "1.0e-12" if yieldf else "1.0e-8"))
+       MAT2 if two else "", SECTIONS, method, precond, "1.0e-12" if yieldf else "1.0e-8"))
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
