@@ -41,7 +41,7 @@ static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group
   return 0;
 }
 
-// What the linear entry points and fx_nl_init_groups refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
+// What the linear entry points and the nonlinear set-up (nl_init_driver) refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
 // material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
 static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
                         int32_t n_mat, bool have_mats, bool nonlinear = false) {
@@ -50,7 +50,7 @@ static int check_groups(const char *who, int32_t n_node, const double *coord, in
     if (c3_nodes(groups[g].etype) == 0)
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)",
                          (int)g + 1, (int)groups[g].etype);
-    if (nonlinear) continue;  // fx_nl_init_groups names what it serves of 361 itself
+    if (nonlinear) continue;  // nl_init_driver names what it serves of 361 itself
     if (groups[g].etype == 361 && (groups[g].elemopt < 1 || groups[g].elemopt > 3))
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
   }

@@ -441,34 +441,22 @@ static void launch_assemble(fx_context *c, int32_t etype, int elemopt, int32_t n
   });
 }
 
-// A tetrahedron, wedge or 20-node hexahedron that names a node twice is degenerate (the reference stops in getJacobian or
-// assembles a singular element): refused, never assembled.  For the single-type set-up of the nonlinear loop (nl_init_common);
-// the linear entry points and fx_nl_init_groups go through check_groups.
-// One parallel pass with the node-id range check; the lowest offending element is named.
-static int refuse_degenerate_tets(const char *who, const fx_mesh_view *mesh, int nn) {
-  int32_t first_bad = INT32_MAX, first_dup = INT32_MAX;  // 0-based elements
-  parallel_for(mesh->n_elem, [&](int64_t a, int64_t b) {
-    int32_t bad = INT32_MAX, dup = INT32_MAX;
-    for (int64_t e = a; e < b && bad == INT32_MAX && dup == INT32_MAX; e++) {
-      const int32_t *en = mesh->conn + (size_t)nn * e;
-      for (int x = 0; x < nn; x++)
-        if (en[x] < 1 || en[x] > mesh->n_node) bad = (int32_t)e;
-      if (bad == INT32_MAX && names_a_node_twice(en, nn)) dup = (int32_t)e;
-    }
-    __atomic_fetch_min(&first_bad, bad, __ATOMIC_RELAXED);
-    __atomic_fetch_min(&first_dup, dup, __ATOMIC_RELAXED);
-  });
-  static thread_local char msg[160];
-  if (first_bad != INT32_MAX) {
-    snprintf(msg, sizeof msg, "%s: node id out of range (element %d)", who, (int)first_bad + 1);
-    g_fx_error = msg;
-    return FX_ERROR_RUNTIME;
-  }
-  if (first_dup != INT32_MAX) {
-    snprintf(msg, sizeof msg, "%s: element %d names a node twice (a degenerate element)", who, (int)first_dup + 1);
-    g_fx_error = msg;
-    return FX_ERROR_RUNTIME;
-  }
+// hecmw_mat_ass_bc (hecmw_mat_ass.f90:292-429) for n_bc prescribed dofs whose lists (node, dof, value) are on the device: column
+// times value moved to B, row and column zeroed, unit diagonal, B = value.  d_flag (3*NP bytes) and d_bcv (3*NP doubles) are
+// cleared and then hold the marks and values of the listed dofs; with n_bc == 0 that is all.
+static int bc_eliminate(fx_context *c, int32_t n_bc, const int32_t *d_node, const int32_t *d_dof, const double *d_val, uint8_t *d_flag,
+                        double *d_bcv) {
+  DevCSR &A = c->A;
+  HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
+  HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
+  if (n_bc < 1) return 0;
+  hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, d_node, d_dof, d_val, d_flag, d_bcv);
+  const dim3 g((A.NP + 255) / 256);
+  hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B,
+                     d_flag, d_bcv);
+  hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B,
+                     d_flag, d_bcv);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -488,18 +476,10 @@ static int load_and_bc(fx_context *c, DevScratch &tmp, const char *who, const do
       return FX_ERROR_RUNTIME;
     for (int32_t k = 0; k < n_bc; k++)
       if (bc_node[k] < 1 || bc_node[k] > A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "BC node id out of range");
-    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
-    HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
     HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_dof, bc_dof, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_val, bc_val, (size_t)n_bc * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, d_node, d_dof, d_val, d_flag, d_bcv);
-    const dim3 g((A.NP + 255) / 256);
-    hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                       A.B, d_flag, d_bcv);
-    hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                       A.B, d_flag, d_bcv);
-    HIP_TRY(hipGetLastError());
+    if (bc_eliminate(c, n_bc, d_node, d_dof, d_val, d_flag, d_bcv)) return FX_ERROR_RUNTIME;
   }
   return 0;
 }

@@ -241,6 +241,21 @@ struct NlPart {
   int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
 };
 
+// tGaussStatus (mechgauss.f90:13-22), flat over (element, quadrature point): the seven per-point arrays of the context, or one
+// part's block of them (nl_part_state)
+struct NlPartState {
+  double *stress = nullptr, *strain = nullptr, *stress_bak = nullptr, *strain_bak = nullptr;  // 6 per point
+  double *plstrain = nullptr, *fstat = nullptr;                                               // 1 per point
+  int32_t *istat = nullptr;
+};
+// f(bytes per point, that array of every struct given) for the seven, in this order; true: an f returned non-zero and the rest
+// was not visited.  A new piece of history is one member above and one term here.
+template <class F, class... S>
+static bool for_each_point_array(F &&f, S &...s) {
+  return f((size_t)48, s.stress...) || f((size_t)48, s.strain...) || f((size_t)48, s.stress_bak...) || f((size_t)48, s.strain_bak...) ||
+         f((size_t)8, s.plstrain...) || f((size_t)8, s.fstat...) || f((size_t)4, s.istat...);
+}
+
 // The context of the nonlinear static loop: element groups (parts) of the six solid types over one set of nodes, materials and
 // per-point arrays.  fx_nl_init / _sections / _c3 / _type make the one-part case, fx_nl_init_groups any number of parts.
 struct NlDev {
@@ -259,10 +274,7 @@ struct NlDev {
   NlMat mat = {};
   double *tab = nullptr;
   double *coord = nullptr;
-  // tGaussStatus (mechgauss.f90:13-22), flat over (element, quadrature point)
-  double *stress = nullptr, *strain = nullptr, *stress_bak = nullptr, *strain_bak = nullptr;  // 6 per point
-  double *plstrain = nullptr, *fstat = nullptr;                                               // 1 per point
-  int32_t *istat = nullptr;
+  NlPartState st;                     // the per-point arrays of all parts
   double *unode = nullptr, *dunode = nullptr, *qforce = nullptr, *GL = nullptr;  // 3*NP
   uint8_t *bc_flag = nullptr;   // prescribed dofs of the current step (3*NP)
   double *bc_val = nullptr;     // their values (3*NP)
@@ -275,8 +287,7 @@ struct NlDev {
   int latch = 0;  // MatlMatrix's saved `flag` (calMatMatrix.f90:39): set by the first elastoplastic stress update
   // fstr_cutback_save / _load (fstr_Cutback.f90:108-198): a device-side copy of the quadrature-point history to roll back to when a
   // sub-step of an automatic incrementation does not converge (fx_nl_snapshot); allocated at the first save
-  double *bk_stress = nullptr, *bk_strain = nullptr, *bk_stress_bak = nullptr, *bk_strain_bak = nullptr, *bk_plstrain = nullptr, *bk_fstat = nullptr;
-  int32_t *bk_istat = nullptr;
+  NlPartState bk;
   bool bk_valid = false;
 };
 

@@ -9,56 +9,52 @@ static void nl_free(fx_context *c) {
     dev_free(p.conn); dev_free(p.emat);
     elem_colors_free(p.colors);
   }
-  dev_free(n.stress); dev_free(n.strain); dev_free(n.stress_bak); dev_free(n.strain_bak);
-  dev_free(n.plstrain); dev_free(n.fstat); dev_free(n.istat);
+  for (NlPartState *s : {&n.st, &n.bk})
+    for_each_point_array([](size_t, auto *&a) { dev_free(a); return 0; }, *s);
   dev_free(n.unode); dev_free(n.dunode); dev_free(n.qforce); dev_free(n.GL);
   dev_free(n.bc_flag); dev_free(n.bc_val); dev_free(n.bc_node); dev_free(n.bc_dof); dev_free(n.bc_v); dev_free(n.err);
   dev_free(n.mats);
-  dev_free(n.bk_stress); dev_free(n.bk_strain); dev_free(n.bk_stress_bak); dev_free(n.bk_strain_bak);
-  dev_free(n.bk_plstrain); dev_free(n.bk_fstat); dev_free(n.bk_istat);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
   n = NlDev();
 }
 
 // What the device loop serves of one material; everything else is refused by name
-static int nl_check_material(const fx_material_view *mat) {
+static int nl_check_material(const char *who, const fx_material_view *mat) {
   if (mat->plastic == FX_MAT_MOONEY || mat->plastic == FX_MAT_ARRUDA) {  // E, nu, harden, tab are not read
     if (mat->nlgeom != 1)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
                      "a hyperelastic material needs nlgeom = 1 (TOTALLAG): under UPDATELAG (CAUCHY) the reference multiplies the "
                      "hyperelastic tangent with the strain increment, a different algorithm that is not on the device");
     if (mat->plconst[2] == 0.0)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "hyperelastic material with plconst[2] = 0: cannot deal with incompressible material");
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "hyperelastic material with plconst[2] = 0: cannot deal with incompressible material");
     if (mat->plastic == FX_MAT_ARRUDA && mat->plconst[1] == 0.0)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Arruda-Boyce material with plconst[1] = 0 (locking stretch lambda_m)");
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "Arruda-Boyce material with plconst[1] = 0 (locking stretch lambda_m)");
     return 0;
   }
   if (mat->plastic < 0 || mat->plastic > FX_MAT_DRUCKER)
-    return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+    return fx_fail(who, FX_ERROR_UNSUPPORTED,
                    "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce, 4 Mohr-Coulomb, 5 Drucker-Prager", (int)mat->plastic);
   if (mat->plastic == FX_MAT_MOHR || mat->plastic == FX_MAT_DRUCKER) {  // fstr_ctrl_material.f90:451-469: linear hardening, no table
     if (mat->harden != 0 || mat->nlgeom < 0 || mat->nlgeom > 2)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED,
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
                      "a Mohr-Coulomb / Drucker-Prager material has harden = 0 (the card forces linear hardening) and nlgeom 0, 1 or 2");
     // the constants at which BackwardEuler would stop with `Math error in return mapping` (Elastoplastic.f90:496, :541)
     if (mat->plastic == FX_MAT_MOHR && cos(mat->plconst[2]) == 0.0)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Mohr-Coulomb material with cos(phi) = 0 (plconst[2] is the friction angle in radians)");
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "Mohr-Coulomb material with cos(phi) = 0 (plconst[2] is the friction angle in radians)");
     if (mat->plastic == FX_MAT_DRUCKER && mat->plconst4 == 0.0)
-      return fx_fail("fx_nl_init", FX_ERROR_UNSUPPORTED, "Drucker-Prager material with xi = 0 (plconst4)");
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "Drucker-Prager material with xi = 0 (plconst4)");
     return 0;
   }
-  if (mat->harden < 0 || mat->harden > 3 || mat->nlgeom < 0 || mat->nlgeom > 2) {
-    g_fx_error = "fx_nl_init: only Mises yield with BILINEAR/MULTILINEAR/SWIFT/RAMBERG-OSGOOD hardening is on the hot path";
-    return FX_ERROR_UNSUPPORTED;
-  }
-  if (mat->plastic && mat->harden == 1 && (mat->ntab < 1 || !mat->tab)) { g_fx_error = "fx_nl_init: MULTILINEAR hardening needs a table"; return FX_ERROR_RUNTIME; }
+  if (mat->harden < 0 || mat->harden > 3 || mat->nlgeom < 0 || mat->nlgeom > 2)
+    return fx_fail(who, FX_ERROR_UNSUPPORTED, "only Mises yield with BILINEAR/MULTILINEAR/SWIFT/RAMBERG-OSGOOD hardening is on the hot path");
+  if (mat->plastic && mat->harden == 1 && (mat->ntab < 1 || !mat->tab)) return fx_fail(who, FX_ERROR_RUNTIME, "MULTILINEAR hardening needs a table");
   return 0;
 }
 
 // nl_check_material for every material, and the refusal of an elastoplastic beside a hyperelastic one, over the whole context
 static int nl_check_materials(const char *who, int32_t n_mat, const fx_material_view *mats) {
   for (int32_t k = 0; k < n_mat; k++)
-    if (int e = nl_check_material(&mats[k])) return e;
+    if (int e = nl_check_material(who, &mats[k])) return e;
   // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
   // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
   bool mises = false, hyper = false, yield = false;
@@ -84,6 +80,10 @@ struct NlPartIn {
   const int32_t *conn, *elem_mat;  // elem_mat: null with one material
   bool fbar = false;               // 361: F-bar (elemopt 4), not B-bar
 };
+
+static int nl_alloc_point_arrays(NlPartState &s, size_t npt) {
+  return for_each_point_array([&](size_t b, auto *&a) { return dev_alloc(&a, npt * b / sizeof(*a)); }, s);
+}
 
 // Element lists of one part: grouped by the NLGEOM flag of the element's material, hyperelastic ones apart (one kernel instantiation
 // per group), inside a group colour by colour (fx_order.cpp: color_elements) for the atomic-free scatter
@@ -135,7 +135,7 @@ static int nl_part_lists(fx_context *c, NlPart &p, const NlPartIn &in, int32_t n
   return 0;
 }
 
-// The context for checked parts (none empty) and checked materials: the single-type entry points pass one part
+// The context for checked parts (none empty) and checked materials (nl_init_driver)
 static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, const std::vector<NlPartIn> &in, int32_t n_mat,
                          const fx_material_view *mats) {
   nl_free(c);
@@ -156,9 +156,7 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
     n.n_qf += (size_t)3 * p.nn * p.n_elem;
   }
   const size_t np3 = (size_t)3 * c->A.NP, npt = (size_t)n.n_pt;
-  if (dev_alloc(&n.coord, np3) || dev_alloc(&n.stress, 6 * npt) || dev_alloc(&n.strain, 6 * npt) ||
-      dev_alloc(&n.stress_bak, 6 * npt) || dev_alloc(&n.strain_bak, 6 * npt) || dev_alloc(&n.plstrain, npt) ||
-      dev_alloc(&n.fstat, npt) || dev_alloc(&n.istat, npt) || dev_alloc(&n.unode, np3) || dev_alloc(&n.dunode, np3) ||
+  if (dev_alloc(&n.coord, np3) || nl_alloc_point_arrays(n.st, npt) || dev_alloc(&n.unode, np3) || dev_alloc(&n.dunode, np3) ||
       dev_alloc(&n.qforce, np3) || dev_alloc(&n.GL, np3) || dev_alloc(&n.bc_flag, np3) || dev_alloc(&n.bc_val, np3) ||
       dev_alloc(&n.err, 1))
     return FX_ERROR_RUNTIME;
@@ -220,9 +218,8 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
   }
   // otherwise unflagged maps in every part and the matrix is cleared once: never both uncleared and unflagged
   if (flags && build_first_write(c, fw, &n.first_write)) return FX_ERROR_RUNTIME;
-  for (double *p : {n.stress, n.strain, n.stress_bak, n.strain_bak}) HIP_TRY(hipMemsetAsync(p, 0, 6 * npt * 8, c->stream));
-  for (double *p : {n.plstrain, n.fstat}) HIP_TRY(hipMemsetAsync(p, 0, npt * 8, c->stream));
-  HIP_TRY(hipMemsetAsync(n.istat, 0, npt * 4, c->stream));
+  if (for_each_point_array([&](size_t b, void *a) { HIP_TRY(hipMemsetAsync(a, 0, npt * b, c->stream)); return 0; }, n.st))
+    return FX_ERROR_RUNTIME;
   for (double *p : {n.unode, n.dunode, n.qforce, n.GL, n.bc_val}) HIP_TRY(hipMemsetAsync(p, 0, np3 * 8, c->stream));
   HIP_TRY(hipMemsetAsync(n.bc_flag, 0, np3, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -231,70 +228,12 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
   return 0;
 }
 
-// fstr_solid / tGaussStatus set-up for one group of one type (fstr_setup.f90:325-400, fstr_init_gauss mechgauss.f90:37-71): zero
-// state, zero displacement.
-static int nl_init_common(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                          const int32_t *elem_mat, int32_t etype, const char *who, bool fbar = false) {
-  HIP_TRY(hipSetDevice(c->device));
-  const int nn = c3_nodes(etype);
-  if (!c->have_profile) { g_fx_error = "fx_nl_init: upload the profile first (fx_upload FX_UP_PROFILE)"; return FX_ERROR_RUNTIME; }
-  if (mesh->n_node != c->A.NP) { g_fx_error = "fx_nl_init: mesh/profile size mismatch"; return FX_ERROR_RUNTIME; }
-  if (n_mat < 1 || !mats || (n_mat > 1 && !elem_mat)) { g_fx_error = "fx_nl_init: materials missing"; return FX_ERROR_RUNTIME; }
-  if (int e = nl_check_materials(who, n_mat, mats)) return e;
-  if (mesh->n_elem < 1 || mesh->n_node < 1) { g_fx_error = "fx_nl_init: empty mesh"; return FX_ERROR_RUNTIME; }
-  for (int64_t k = 0; k < (int64_t)nn * mesh->n_elem; k++)
-    if (mesh->conn[k] < 1 || mesh->conn[k] > mesh->n_node) { g_fx_error = "fx_nl_init: node id out of range"; return FX_ERROR_RUNTIME; }
-  if (n_mat > 1)
-    for (int32_t e = 0; e < mesh->n_elem; e++)
-      if (elem_mat[e] < 1 || elem_mat[e] > n_mat) { g_fx_error = "fx_nl_init_sections: material id out of range"; return FX_ERROR_RUNTIME; }
-  if (etype != 361 && refuse_degenerate_tets(who, mesh, nn)) return FX_ERROR_RUNTIME;
-  return nl_init_parts(c, mesh->n_node, mesh->coord, {{etype, mesh->n_elem, mesh->conn, n_mat > 1 ? elem_mat : nullptr, fbar}}, n_mat, mats);
-}
-
-extern "C" int fx_nl_init(fx_context *c, const fx_mesh_view *mesh, const fx_material_view *mat) {
-  return nl_init_common(c, mesh, 1, mat, nullptr, 361, "fx_nl_init");
-}
-
-// Several sections (hecMESH%section_ID -> fstrSOLID%materials, fstr_setup.f90:325-400): elem_mat[e] in 1..n_mat.  The materials may
-// carry different NLGEOM flags (an elastic TOTALLAG part next to an elastoplastic UPDATELAG part).
-extern "C" int fx_nl_init_sections(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
-                                   const int32_t *elem_mat) {
-  return nl_init_common(c, mesh, n_mat, mats, elem_mat, 361, "fx_nl_init_sections");
-}
-
-// The same context for a mesh of tetrahedra, etype 341 or 342 (STF_C3 / UPDATE_C3, fx_nonlinear_tet.h): n_mat materials,
-// elem_mat[e] in 1..n_mat (may be NULL with one material).  Every other fx_nl_* entry point works on either context.
-extern "C" int fx_nl_init_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const fx_material_view *mats,
-                             const int32_t *elem_mat) {
-  if (etype != 341 && etype != 342) {
-    g_fx_error = "fx_nl_init_c3: the nonlinear loop covers TYPE=341 and 342 (361 through fx_nl_init / fx_nl_init_sections)";
-    return FX_ERROR_UNSUPPORTED;
-  }
-  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype, "fx_nl_init_c3");
-}
-
-// The same for any of the five types STF_C3 / UPDATE_C3 serve: 341, 342 (fx_nonlinear_tet.h), 351, 352, 362 (fx_nonlinear_c3.h).
-// fx_mesh_view carries no nodes-per-element, so the caller states it: nn_elem is the row length of mesh->conn, and a type whose
-// node count it is not is refused before anything reads the connectivity.
-extern "C" int fx_nl_init_type(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t nn_elem, int32_t n_mat,
-                               const fx_material_view *mats, const int32_t *elem_mat) {
-  if (!c3_linear_type(etype))
-    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED,
-                   "TYPE=%d: the STF_C3 nonlinear loop covers 341, 342, 351, 352 and 362 (361 through fx_nl_init / fx_nl_init_sections)", (int)etype);
-  if (nn_elem != c3_nodes(etype))
-    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED, "TYPE=%d has %d nodes per element, the connectivity has %d", (int)etype,
-                   c3_nodes(etype), (int)nn_elem);
-  return nl_init_common(c, mesh, n_mat, mats, n_mat > 1 ? elem_mat : nullptr, etype, "fx_nl_init_type");
-}
-
-// The same context for a mesh of several solid element types (fstr_StiffMatrix.f90:43-212 and fstr_Update.f90:73-264 loop over
-// hecMESH%elem_type_item; a group is one entry of that loop).  One material table serves all groups.  A 361 group is B-bar
-// (elemopt 2) or F-bar (elemopt 4, fx_nonlinear_fbar.h: INFINITE and TOTALLAG materials only); part g launches the family its
-// elemopt names, everything else of a part -- lists, colours, history, outputs -- is the same for both.
-extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                                 int32_t n_mat, const fx_material_view *mats) {
-  const char *who = "fx_nl_init_groups";
-  if (!c) { g_fx_error = "fx_nl_init_groups: null argument"; return FX_ERROR_RUNTIME; }
+// The one set-up of the nonlinear context, for every fx_nl_init* entry point (`who`: the one called).  fstr_solid / tGaussStatus
+// set-up (fstr_setup.f90:325-400, fstr_init_gauss mechgauss.f90:37-71) over the groups of fstr_StiffMatrix's and fstr_Update's
+// loops over hecMESH%elem_type_item: zero state, zero displacement.  Everything is refused before nl_init_parts frees the
+// context that is there.
+static int nl_init_driver(fx_context *c, const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                          int32_t n_mat, const fx_material_view *mats) {
   if (int rc = check_groups(who, n_node, coord, n_group, groups, n_mat, mats != nullptr, true)) return rc;
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
@@ -311,7 +250,6 @@ extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *co
                        "group %d: an F-bar element (elemopt 4) with an UPDATELAG material (nlgeom 2), element %d; F-bar is served for "
                        "INFINITE and TOTALLAG", (int)g + 1, (int)e + 1);
   }
-  HIP_TRY(hipSetDevice(c->device));
   if (!c->have_profile) return fx_fail(who, FX_ERROR_RUNTIME, "upload the profile first (fx_upload FX_UP_PROFILE)");
   if (n_node != c->A.NP) return fx_fail(who, FX_ERROR_RUNTIME, "mesh/profile size mismatch");
   if (int e = nl_check_materials(who, n_mat, mats)) return e;
@@ -321,11 +259,58 @@ extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *co
       in.push_back({groups[g].etype, groups[g].n_elem, groups[g].conn, n_mat > 1 ? groups[g].elem_mat : nullptr,
                     groups[g].etype == 361 && groups[g].elemopt == 4});
   if (in.empty()) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
-  if (in.size() == 1) {  // the single-type context
-    const fx_mesh_view mesh = {n_node, in[0].n_elem, coord, in[0].conn};
-    return nl_init_common(c, &mesh, n_mat, mats, in[0].elem_mat, in[0].etype, who, in[0].fbar);
-  }
+  HIP_TRY(hipSetDevice(c->device));
   return nl_init_parts(c, n_node, coord, in, n_mat, mats);
+}
+// The single-type entry points: the mesh as one group (361: B-bar).  With one material elem_mat is not read, whatever it holds.
+static int nl_init_mesh(fx_context *c, const char *who, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat,
+                        const fx_material_view *mats, const int32_t *elem_mat) {
+  if (!c || !mesh) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
+  const fx_elem_group g = {etype, 2, mesh->n_elem, mesh->conn, n_mat > 1 ? elem_mat : nullptr};
+  return nl_init_driver(c, who, mesh->n_node, mesh->coord, 1, &g, n_mat, mats);
+}
+
+extern "C" int fx_nl_init(fx_context *c, const fx_mesh_view *mesh, const fx_material_view *mat) {
+  return nl_init_mesh(c, "fx_nl_init", mesh, 361, 1, mat, nullptr);
+}
+
+// Several sections (hecMESH%section_ID -> fstrSOLID%materials, fstr_setup.f90:325-400): elem_mat[e] in 1..n_mat.  The materials may
+// carry different NLGEOM flags (an elastic TOTALLAG part next to an elastoplastic UPDATELAG part).
+extern "C" int fx_nl_init_sections(fx_context *c, const fx_mesh_view *mesh, int32_t n_mat, const fx_material_view *mats,
+                                   const int32_t *elem_mat) {
+  return nl_init_mesh(c, "fx_nl_init_sections", mesh, 361, n_mat, mats, elem_mat);
+}
+
+// The same context for a mesh of tetrahedra, etype 341 or 342 (STF_C3 / UPDATE_C3, fx_nonlinear_tet.h): n_mat materials,
+// elem_mat[e] in 1..n_mat (may be NULL with one material).  Every other fx_nl_* entry point works on either context.
+extern "C" int fx_nl_init_c3(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat, const fx_material_view *mats,
+                             const int32_t *elem_mat) {
+  if (etype != 341 && etype != 342)
+    return fx_fail("fx_nl_init_c3", FX_ERROR_UNSUPPORTED, "the nonlinear loop covers TYPE=341 and 342 (361 through fx_nl_init / fx_nl_init_sections)");
+  return nl_init_mesh(c, "fx_nl_init_c3", mesh, etype, n_mat, mats, elem_mat);
+}
+
+// The same for any of the five types STF_C3 / UPDATE_C3 serve: 341, 342 (fx_nonlinear_tet.h), 351, 352, 362 (fx_nonlinear_c3.h).
+// fx_mesh_view carries no nodes-per-element, so the caller states it: nn_elem is the row length of mesh->conn, and a type whose
+// node count it is not is refused before anything reads the connectivity.
+extern "C" int fx_nl_init_type(fx_context *c, const fx_mesh_view *mesh, int32_t etype, int32_t nn_elem, int32_t n_mat,
+                               const fx_material_view *mats, const int32_t *elem_mat) {
+  if (!c3_linear_type(etype))
+    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED,
+                   "TYPE=%d: the STF_C3 nonlinear loop covers 341, 342, 351, 352 and 362 (361 through fx_nl_init / fx_nl_init_sections)", (int)etype);
+  if (nn_elem != c3_nodes(etype))
+    return fx_fail("fx_nl_init_type", FX_ERROR_UNSUPPORTED, "TYPE=%d has %d nodes per element, the connectivity has %d", (int)etype,
+                   c3_nodes(etype), (int)nn_elem);
+  return nl_init_mesh(c, "fx_nl_init_type", mesh, etype, n_mat, mats, elem_mat);
+}
+
+// The same context for a mesh of several solid element types.  One material table serves all groups.  A 361 group is B-bar
+// (elemopt 2) or F-bar (elemopt 4, fx_nonlinear_fbar.h: INFINITE and TOTALLAG materials only); part g launches the family its
+// elemopt names, everything else of a part -- lists, colours, history, outputs -- is the same for both.
+extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                 int32_t n_mat, const fx_material_view *mats) {
+  if (!c) return fx_fail("fx_nl_init_groups", FX_ERROR_RUNTIME, "null argument");
+  return nl_init_driver(c, "fx_nl_init_groups", n_node, coord, n_group, groups, n_mat, mats);
 }
 
 #define NL_READY(name)                                                                              \
@@ -341,133 +326,120 @@ template <class F>
 static void for_each_nl_group(F &&f) {
   for_each_nl_group(f, std::make_integer_sequence<int, NL_GROUPS>());
 }
-// The element kernel of one type and group: k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362, and for the stress
-// update, whose three kernels take the same arguments, k_nl_update of 361 (its tangent has a launcher of its own)
+// The element kernel of one type and group: k_nl_* of 361 (B-bar), k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362.
+// The three tangents take the same arguments but for one int of 361's, the three updates the same arguments.
 template <int ETYPE, int G, bool UPDATE>
 static constexpr auto nl_c3_kernel() {
   if constexpr (UPDATE) {
-    if constexpr (ETYPE == 361) return k_nl_update<G>;  // (an F-bar part: nl_fbar_update_kernel)
+    if constexpr (ETYPE == 361) return k_nl_update<G>;
     else if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
     else return k_nl_update_c3<ETYPE, G>;
   } else {
-    static_assert(ETYPE != 361, "k_nl_stiffness<G>: nl_launch_stiffness_group");
-    if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G>;
+    if constexpr (ETYPE == 361) return k_nl_stiffness<G>;
+    else if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G>;
     else return k_nl_stiffness_c3<ETYPE, G>;
   }
 }
-template <int ETYPE>
-static constexpr int NL_UPDATE_EPB = ETYPE == 361 ? FXN_EPB : C3El<ETYPE>::UEPB;  // elements per workgroup of the update kernel
-template <int ETYPE>
-static constexpr int NL_UPDATE_BLOCK = ETYPE == 361 ? FXN_BLOCK : C3El<ETYPE>::BS;
-// The groups the F-bar kernels are instantiated for: no UPDATELAG (fx_nl_init_groups refuses it, so such a list is empty)
+// The groups the F-bar kernels are instantiated for: no UPDATELAG (nl_init_driver refuses it, so such a list is empty)
 static constexpr bool nl_fbar_group(int G) { return nl_group_flag(G) != 2; }
-// A part's block of the per-point arrays
-struct NlPartState {
-  double *stress, *strain, *stress_bak, *strain_bak, *plstrain, *fstat;
-  int32_t *istat;
+// What one group of a part launches: the kernel of its type (null: nothing to launch), elements per workgroup and workgroup size.
+// An F-bar part takes the F-bar kernels, which have the arguments of 361's and, for the tangent, a workgroup of their own.
+template <int ETYPE, int G, bool UPDATE>
+struct NlKernel {
+  decltype(nl_c3_kernel<ETYPE, G, UPDATE>()) kern = nl_c3_kernel<ETYPE, G, UPDATE>();
+  int epb = ETYPE != 361 ? (UPDATE ? C3El<ETYPE>::UEPB : C3El<ETYPE>::EPB) : FXN_EPB;
+  int block = ETYPE != 361 ? C3El<ETYPE>::BS : FXN_BLOCK;
+  explicit NlKernel(const NlPart &p) {
+    if constexpr (ETYPE == 361) {
+      if (!p.fbar) return;
+      if constexpr (!nl_fbar_group(G)) kern = nullptr;
+      else if constexpr (UPDATE) kern = k_nl_update_fbar<G>;
+      else { kern = k_nl_stiffness_fbar<G>; epb = FXF_EPB; block = FXF_BLOCK; }
+    }
+  }
 };
+// A part's block of the per-point arrays
 static NlPartState nl_part_state(const NlDev &n, const NlPart &p) {
-  const int64_t o = p.pt_off;
-  return {n.stress + 6 * o, n.strain + 6 * o, n.stress_bak + 6 * o, n.strain_bak + 6 * o, n.plstrain + o, n.fstat + o, n.istat + o};
+  NlPartState s = n.st;
+  for_each_point_array([&](size_t b, auto *&a) { a += (int64_t)(b / sizeof(*a)) * p.pt_off; return 0; }, s);
+  return s;
 }
-// Kout / qf_out: the part's block of the element outputs, or null
+template <int ETYPE>
+static constexpr size_t NL_KE = (size_t)(3 * C3El<ETYPE>::NN) * (3 * C3El<ETYPE>::NN);  // doubles of one element matrix
+// The tangent of one group of a part of any of the six types.  Kout: the part's block of the element matrices, or null (scatter);
+// dup_k (361, scatter): room for the element matrices of the part's collapsed elements
 template <int ETYPE, int G>
-static void nl_launch_stiffness_c3_group(fx_context *c, const NlPart &p, double *Kout) {
+static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Kout, double *dup_k) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
   const NlPartState s = nl_part_state(n, p);
-  using El = C3El<ETYPE>;
+  const NlKernel<ETYPE, G, false> k(p);
+  if (!k.kern) return;
+  auto launch = [&](dim3 grid, int32_t e0, int32_t e1, double *K, const int32_t *list, const int32_t *pos, int atomic, int k_by_pos) {
+    auto go = [&](auto... tail) {
+      hipLaunchKernelGGL(k.kern, grid, dim3(k.block), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch, s.stress,
+                         s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, K, n.err, list, e0, pos, atomic,
+                         (const NlMat *)n.mats, (const int32_t *)p.emat, tail...);
+    };
+    if constexpr (ETYPE == 361) go(k_by_pos, (const double *)s.strain);  // 361's own argument: K by position in the list
+    else go((const double *)s.strain);
+  };
   // element matrices out, or atomics: the group's colours in one launch
-  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, El::EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL((nl_c3_kernel<ETYPE, G, false>()), grid, dim3(El::BS), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch, s.stress, s.fstat,
-                       s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err, (const int32_t *)p.colors.order, e0,
-                       (const int32_t *)p.colors.pos, p.scatter_atomic ? 1 : 0, (const NlMat *)n.mats, (const int32_t *)p.emat,
-                       (const double *)s.strain);
+  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, k.epb, [&](dim3 grid, int32_t e0, int32_t e1) {
+    launch(grid, e0, e1, Kout, p.colors.order, p.colors.pos, p.scatter_atomic ? 1 : 0, 0);
   });
+  if constexpr (ETYPE == 361) {  // the collapsed elements of the group: only 361 has them, the other types refuse them at init
+    // their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter -- added colour
+    // by colour (k_add_elem_blocks)
+    const std::vector<int32_t> &doff = p.dup_off[G];
+    if (doff.empty()) return;
+    const int32_t d0 = doff.front(), d1 = doff.back();
+    launch(dim3((d1 - d0 + k.epb - 1) / k.epb), d0, d1, Kout ? Kout : dup_k, p.colors.dup, nullptr, 0, Kout ? 0 : 1);
+    if (Kout) return;
+    for_colour_ranges(doff, false, 64, [&](dim3 grid, int32_t p0, int32_t p1) {
+      hipLaunchKernelGGL(k_add_elem_blocks, grid, dim3(64), 0, c->stream, p0, p1, (const int32_t *)p.colors.dup, (const double *)dup_k,
+                         (const int32_t *)p.conn, (const int32_t *)p.colors.pos, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
+    });
+  }
 }
 // The stress update of one group of a part of any of the six types
 template <int ETYPE, int G>
 static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
   const NlPartState s = nl_part_state(n, p);
-  auto kern = nl_c3_kernel<ETYPE, G, true>();
-  if constexpr (ETYPE == 361) {  // same arguments, block and elements per workgroup
-    if (p.fbar) {
-      if constexpr (nl_fbar_group(G)) kern = k_nl_update_fbar<G>;
-      else return;
-    }
-  }
+  const NlKernel<ETYPE, G, true> k(p);
+  if (!k.kern) return;
   auto launch = [&](const int32_t *list, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)((e1 - e0 + NL_UPDATE_EPB<ETYPE> - 1) / NL_UPDATE_EPB<ETYPE>)),
-                       dim3(NL_UPDATE_BLOCK<ETYPE>), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, s.stress, s.strain,
-                       s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out, list, e0, (const NlMat *)n.mats,
-                       (const int32_t *)p.emat, n.err);
+    hipLaunchKernelGGL(k.kern, dim3((unsigned)((e1 - e0 + k.epb - 1) / k.epb)), dim3(k.block), 0, c->stream, e1, n.coord, p.conn, n.unode,
+                       n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out,
+                       list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
   };
   const std::vector<int32_t> &off = p.grp_off[G];
   // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
   // force is scattered with atomics either way
   if (!off.empty() && off.back() > off.front())
     launch((off.front() == 0 && off.back() == p.n_elem) ? nullptr : p.colors.order, off.front(), off.back());
-  if constexpr (ETYPE == 361) {  // the collapsed elements of the group: only 361 has them, the other types refuse them at init
+  if constexpr (ETYPE == 361) {  // the collapsed elements of the group
     const std::vector<int32_t> &doff = p.dup_off[G];
     if (!doff.empty()) launch(p.colors.dup, doff.front(), doff.back());
   }
 }
-
-template <int G>
-static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Kout, double *dup_k) {
-  NlDev &n = c->nl;
-  const DevCSR &A = c->A;
-  const NlPartState s = nl_part_state(n, p);
-  // the part's family: the two kernels take the same arguments and differ in their workgroup
-  auto kern = k_nl_stiffness<G>;
-  int epb = FXN_EPB, block = FXN_BLOCK;
-  if (p.fbar) {
-    if constexpr (nl_fbar_group(G)) { kern = k_nl_stiffness_fbar<G>; epb = FXF_EPB; block = FXF_BLOCK; }
-    else return;
-  }
-  // element matrices out, or atomics: the group's colours in one launch
-  for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, epb, [&](dim3 grid, int32_t e0, int32_t e1) {
-    hipLaunchKernelGGL(kern, grid, dim3(block), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch,
-                       s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, Kout, n.err,
-                       (const int32_t *)p.colors.order, e0, (const int32_t *)p.colors.pos, p.scatter_atomic ? 1 : 0,
-                       (const NlMat *)n.mats, (const int32_t *)p.emat, 0, (const double *)s.strain);
-  });
-  // collapsed elements: their element matrices (into Kout by element id, or dup_k by position in colors.dup), then -- for the scatter --
-  // added colour by colour (k_add_elem_blocks)
-  const std::vector<int32_t> &doff = p.dup_off[G];
-  if (doff.empty()) return;
-  const int32_t d0 = doff.front(), d1 = doff.back();
-  hipLaunchKernelGGL(kern, dim3((d1 - d0 + epb - 1) / epb), dim3(block), 0, c->stream, d1, n.coord, p.conn,
-                     n.unode, n.dunode, n.mat, n.latch, s.stress, s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU,
-                     Kout ? Kout : dup_k, n.err, (const int32_t *)p.colors.dup, d0, (const int32_t *)nullptr, 0, (const NlMat *)n.mats,
-                     (const int32_t *)p.emat, Kout ? 0 : 1, (const double *)s.strain);
-  if (Kout) return;
-  for (size_t k = 0; k + 1 < doff.size(); k++)
-    if (doff[k + 1] > doff[k])
-      hipLaunchKernelGGL(k_add_elem_blocks, dim3((doff[k + 1] - doff[k] + 63) / 64), dim3(64), 0, c->stream, doff[k], doff[k + 1],
-                         (const int32_t *)p.colors.dup, (const double *)dup_k, (const int32_t *)p.conn, (const int32_t *)p.colors.pos,
-                         A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, n.err);
-}
-// Part after part, NLGEOM group after group, colour after colour on one stream; Kout: the element matrices of all parts one after the other
-static int nl_launch_stiffness(fx_context *c, double *Kout) {  // one kernel instantiation per type and group present
+// Part after part, NLGEOM group after group, colour after colour on one stream: one kernel instantiation per type and group present
+static int nl_launch_stiffness(fx_context *c, double *Kout) {  // Kout: the element matrices of all parts one after the other, or null
   DevScratch tmp;
   double *dup_k = nullptr;
   size_t n_dup = 0;
   for (const NlPart &p : c->nl.parts) n_dup += (size_t)p.n_dup;
-  if (!Kout && n_dup > 0 && tmp.alloc(&dup_k, (size_t)576 * n_dup)) return FX_ERROR_RUNTIME;
-  size_t dup_at = 0;
+  if (!Kout && n_dup > 0 && tmp.alloc(&dup_k, NL_KE<361> * n_dup)) return FX_ERROR_RUNTIME;
+  size_t dup_at = 0;  // collapsed elements of the parts before this one (361 parts alone have any)
   for (const NlPart &p : c->nl.parts) {
-    double *K = Kout ? Kout + p.k_off : nullptr;
-    if (p.etype != 361) {
-      with_c3_type(p.etype, [&](auto t) {
-        for_each_nl_group([&](auto g) { nl_launch_stiffness_c3_group<decltype(t)::value, decltype(g)::value>(c, p, K); });
+    with_solid_type(p.etype, [&](auto t) {
+      for_each_nl_group([&](auto g) {
+        nl_launch_stiffness_group<decltype(t)::value, decltype(g)::value>(c, p, Kout ? Kout + p.k_off : nullptr,
+                                                                          dup_k ? dup_k + NL_KE<361> * dup_at : nullptr);
       });
-      continue;
-    }
-    double *dk = dup_k ? dup_k + (size_t)576 * dup_at : nullptr;
+    });
     dup_at += (size_t)p.n_dup;
-    for_each_nl_group([&](auto g) { nl_launch_stiffness_group<decltype(g)::value>(c, p, K, dk); });
   }
   if (dup_k) HIP_TRY(hipStreamSynchronize(c->stream));  // dup_k is freed on return
   return 0;
@@ -493,6 +465,18 @@ static int nl_update_err_check(fx_context *c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   return assembly_error(herr);
 }
+// fstr_UpdateNewton's element loop for the three update entry points: error word, launches (`launched`, if given, is recorded
+// behind them), the reference's `stop`s, and MatlMatrix's saved flag -- an update that stopped sets no latch.
+static int nl_run_update(fx_context *c, double *qf_out, hipEvent_t launched = nullptr) {
+  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
+  nl_launch_update(c, qf_out);
+  HIP_TRY(hipGetLastError());
+  if (launched) HIP_TRY(hipEventRecord(launched, c->stream));
+  if (int rc = nl_update_err_check(c)) return rc;
+  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45); the flag is the process's, whichever section set it
+  for (const NlMat &m : c->nl.h_mats) if (m.plastic) c->nl.latch = 1;
+  return 0;
+}
 
 // fstr_StiffMatrix + fstr_AddBC (fstr_StiffMatrix.f90:18-212, fstr_AddBC.f90:17-190): tangent of the current
 // state (u = unode + dunode) into the resident D/AL/AU, then Dirichlet elimination with the given increments
@@ -510,8 +494,6 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
   if (!n.first_write && mat_clear(c)) return FX_ERROR_RUNTIME;
   if (nl_launch_stiffness(c, nullptr)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(n.bc_flag, 0, (size_t)3 * A.NP, c->stream));
-  HIP_TRY(hipMemsetAsync(n.bc_val, 0, (size_t)3 * A.NP * 8, c->stream));
   n.n_bc = n_bc;
   if (n_bc > 0) {
     if (n_bc > n.bc_cap) {
@@ -522,14 +504,8 @@ extern "C" int fx_nl_stiffness(fx_context *c, int32_t n_bc, const int32_t *bc_no
     HIP_TRY(hipMemcpyAsync(n.bc_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(n.bc_dof, bc_dof, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(n.bc_v, bc_val, (size_t)n_bc * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, n.bc_node, n.bc_dof, n.bc_v, n.bc_flag, n.bc_val);
-    const dim3 g((A.NP + 255) / 256);
-    hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B,
-                       n.bc_flag, n.bc_val);
-    hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B,
-                       n.bc_flag, n.bc_val);
-    HIP_TRY(hipGetLastError());
   }
+  if (bc_eliminate(c, n_bc, n.bc_node, n.bc_dof, n.bc_v, n.bc_flag, n.bc_val)) return FX_ERROR_RUNTIME;  // no dof: the flags are cleared
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, n.err, 4, hipMemcpyDeviceToHost, c->stream));
@@ -587,12 +563,7 @@ extern "C" int fx_nl_update(fx_context *c, double out[4], float *ms_update) {
   hipLaunchKernelGGL(k_axpy_plain, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, 1.0, c->A.X, n.dunode);
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   HIP_TRY(hipMemsetAsync(n.qforce, 0, (size_t)np3 * 8, c->stream));
-  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
-  nl_launch_update(c, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  if (int rc = nl_update_err_check(c)) return rc;
-  for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45); the flag is the process's, whichever section set it
+  if (int rc = nl_run_update(c, nullptr, c->ev1)) return rc;
   if (nl_halo_natural(c, n.qforce)) return FX_ERROR_RUNTIME;
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, n.GL, n.qforce, n.bc_flag, c->A.B);
   HIP_TRY(hipGetLastError());
@@ -630,13 +601,7 @@ extern "C" int fx_nl_update_at(fx_context *c, const double *dunode, double *qfor
   if (dunode) HIP_TRY(hipMemcpyAsync(n.dunode, dunode, np3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   HIP_TRY(hipMemsetAsync(n.qforce, 0, np3, c->stream));
-  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
-  nl_launch_update(c, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  if (int rc = nl_update_err_check(c)) return rc;
-  if (n.mat.plastic) n.latch = 1;  // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45)
-  for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;
+  if (int rc = nl_run_update(c, nullptr, c->ev1)) return rc;
   if (qforce) HIP_TRY(hipMemcpyAsync(qforce, n.qforce, np3, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (ms_update) HIP_TRY(hipEventElapsedTime(ms_update, c->ev0, c->ev1));
@@ -659,16 +624,10 @@ extern "C" int fx_mat_ass_bc(fx_context *c, int32_t n_bc, const int32_t *bc_node
   if (tmp.alloc(&d_flag, (size_t)3 * A.NP) || tmp.alloc(&d_bcv, (size_t)3 * A.NP) || tmp.alloc(&d_node, (size_t)n_bc) ||
       tmp.alloc(&d_dof, (size_t)n_bc) || tmp.alloc(&d_val, (size_t)n_bc))
     return FX_ERROR_RUNTIME;
-  HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)3 * A.NP, c->stream));
-  HIP_TRY(hipMemsetAsync(d_bcv, 0, (size_t)3 * A.NP * 8, c->stream));
   HIP_TRY(hipMemcpyAsync(d_node, bc_node, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_dof, bc_dof, (size_t)n_bc * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_val, bc_val, (size_t)n_bc * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_bc_mark, dim3((n_bc + 255) / 256), dim3(256), 0, c->stream, n_bc, d_node, d_dof, d_val, d_flag, d_bcv);
-  const dim3 g((A.NP + 255) / 256);
-  hipLaunchKernelGGL((k_bc_apply<1>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B, d_flag, d_bcv);
-  hipLaunchKernelGGL((k_bc_apply<2>), g, dim3(256), 0, c->stream, A.NP, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, A.B, d_flag, d_bcv);
-  HIP_TRY(hipGetLastError());
+  if (bc_eliminate(c, n_bc, d_node, d_dof, d_val, d_flag, d_bcv)) return FX_ERROR_RUNTIME;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->bell_valid = false;  // the streaming layouts re-gather the values on next use
   return 0;
@@ -699,21 +658,13 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
   NL_READY("fx_nl_snapshot");
   NlDev &n = c->nl;
   const size_t npt = (size_t)n.n_pt;
-  if (!n.bk_stress) {
-    if (load) { g_fx_error = "fx_nl_snapshot: nothing was saved"; return FX_ERROR_RUNTIME; }
-    if (dev_alloc(&n.bk_stress, 6 * npt) || dev_alloc(&n.bk_strain, 6 * npt) || dev_alloc(&n.bk_stress_bak, 6 * npt) ||
-        dev_alloc(&n.bk_strain_bak, 6 * npt) || dev_alloc(&n.bk_plstrain, npt) || dev_alloc(&n.bk_fstat, npt) || dev_alloc(&n.bk_istat, npt))
-      return FX_ERROR_RUNTIME;
-  }
   if (load && !n.bk_valid) { g_fx_error = "fx_nl_snapshot: nothing was saved"; return FX_ERROR_RUNTIME; }
-  struct { void *live; void *bk; size_t bytes; } f[] = {
-      {n.stress, n.bk_stress, 6 * npt * 8}, {n.strain, n.bk_strain, 6 * npt * 8}, {n.stress_bak, n.bk_stress_bak, 6 * npt * 8},
-      {n.strain_bak, n.bk_strain_bak, 6 * npt * 8}, {n.plstrain, n.bk_plstrain, npt * 8}, {n.fstat, n.bk_fstat, npt * 8},
-      {n.istat, n.bk_istat, npt * 4}};
-  for (auto &e : f) {
-    if (load) HIP_TRY(hipMemcpyAsync(e.live, e.bk, e.bytes, hipMemcpyDeviceToDevice, c->stream));
-    else HIP_TRY(hipMemcpyAsync(e.bk, e.live, e.bytes, hipMemcpyDeviceToDevice, c->stream));
-  }
+  if (!n.bk.stress && nl_alloc_point_arrays(n.bk, npt)) return FX_ERROR_RUNTIME;
+  if (for_each_point_array([&](size_t b, void *live, void *bk) {
+        HIP_TRY(hipMemcpyAsync(load ? live : bk, load ? bk : live, npt * b, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+      }, n.st, n.bk))
+    return FX_ERROR_RUNTIME;
   HIP_TRY(hipStreamSynchronize(c->stream));
   n.bk_valid = true;
   return 0;
@@ -722,15 +673,13 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
 static int nl_copy_state(fx_context *c, const fx_nl_state_view *s, bool to_device) {
   NlDev &n = c->nl;
   const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)n.n_pt;
-  struct { void *h; void *d; size_t bytes; } f[] = {
-      {s->stress, n.stress, 6 * npt * 8}, {s->strain, n.strain, 6 * npt * 8}, {s->stress_bak, n.stress_bak, 6 * npt * 8},
-      {s->strain_bak, n.strain_bak, 6 * npt * 8}, {s->plstrain, n.plstrain, npt * 8}, {s->fstat, n.fstat, npt * 8},
-      {s->istat, n.istat, npt * 4}, {s->unode, n.unode, np3}, {s->dunode, n.dunode, np3}, {s->qforce, n.qforce, np3}};
-  for (auto &e : f) {
-    if (!e.h) continue;
-    if (to_device) HIP_TRY(hipMemcpyAsync(e.d, e.h, e.bytes, hipMemcpyHostToDevice, c->stream));
-    else HIP_TRY(hipMemcpyAsync(e.h, e.d, e.bytes, hipMemcpyDeviceToHost, c->stream));
-  }
+  auto copy = [&](size_t bytes, void *h, void *d) {  // a null host array is skipped
+    if (h) HIP_TRY(hipMemcpyAsync(to_device ? d : h, to_device ? h : d, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, c->stream));
+    return 0;
+  };
+  if (for_each_point_array([&](size_t b, void *h, void *d) { return copy(npt * b, h, d); }, *s, n.st) || copy(np3, s->unode, n.unode) ||
+      copy(np3, s->dunode, n.dunode) || copy(np3, s->qforce, n.qforce))
+    return FX_ERROR_RUNTIME;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -769,11 +718,7 @@ extern "C" int fx_nl_element_update(fx_context *c, double *qf) {
   double *d = nullptr;
   const size_t nqf = n.n_qf;
   if (tmp.alloc(&d, nqf)) return FX_ERROR_RUNTIME;
-  if (nl_update_err_clear(c)) return FX_ERROR_RUNTIME;
-  nl_launch_update(c, d);
-  HIP_TRY(hipGetLastError());
-  if (int rc = nl_update_err_check(c)) return rc;  // as fx_nl_update: an update that stopped sets no latch
-  for (const NlMat &m : n.h_mats) if (m.plastic) n.latch = 1;
+  if (int rc = nl_run_update(c, d)) return rc;
   HIP_TRY(hipMemcpyAsync(qf, d, nqf * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

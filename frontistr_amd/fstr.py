@@ -147,41 +147,33 @@ class fstr_solid:
         self.conn = np.ascontiguousarray(hecMESH_conn, dtype=np.int32)
         self.n_elem = self.conn.shape[0]
         self._set_parts([(self.etype, self.n_elem)])
-        if self.etype == 361 and int(elemopt) != 2:
-            mats = list(material) if isinstance(material, (list, tuple)) else [material]
-            self.elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
-            if len(mats) > 1 and (self.elem_mat is None or self.elem_mat.shape != (self.n_elem,)):
-                raise ValueError("elem_mat: one material id per element")
-            tab, keep = hecmw.SolverContext._group_table([(361, self.conn, int(elemopt), self.elem_mat)])
-            views = [m.view() for m in mats]
-            arr = (_MaterialView * len(views))(*views)
-            _chk(lib().fx_nl_init_groups(ctx.h, self.n_node, _ptr(self.coord), 1, tab, len(views), arr))
-            del keep
-            return
+        mats, arr, self.elem_mat = self._materials(material, elem_mat, self.n_elem)
         mv = hecmw._MeshView(self.n_node, self.n_elem, _ptr(self.coord), _ptr(self.conn))
-        if self.etype != 361:
-            mats = list(material) if isinstance(material, (list, tuple)) else [material]
-            views = [m.view() for m in mats]
-            arr = (_MaterialView * len(views))(*views)
-            self.elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
-            if len(views) > 1 and (self.elem_mat is None or self.elem_mat.shape != (self.n_elem,)):
-                raise ValueError("elem_mat: one material id per element")
-            if self.etype in (351, 352, 362):
-                nn_elem = self.conn.shape[1] if self.conn.ndim == 2 else 0
-                _chk(lib().fx_nl_init_type(ctx.h, C.byref(mv), self.etype, nn_elem, len(views), arr, _ptr(self.elem_mat)))
-            else:
-                _chk(lib().fx_nl_init_c3(ctx.h, C.byref(mv), self.etype, len(views), arr, _ptr(self.elem_mat)))
-            return
-        if isinstance(material, (list, tuple)):
-            views = [m.view() for m in material]
-            arr = (_MaterialView * len(views))(*views)
-            self.elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-            if self.elem_mat.shape != (self.n_elem,):
-                raise ValueError("elem_mat: one material id per element")
-            _chk(lib().fx_nl_init_sections(ctx.h, C.byref(mv), len(views), arr, _ptr(self.elem_mat)))
-            return
-        m = material.view()
-        _chk(lib().fx_nl_init(ctx.h, C.byref(mv), C.byref(m)))
+        head, tail = (ctx.h, C.byref(mv)), (len(mats), arr, _ptr(self.elem_mat))
+        if self.etype == 361 and int(elemopt) != 2:
+            tab, keep = hecmw.SolverContext._group_table([(361, self.conn, int(elemopt), self.elem_mat)])
+            _chk(lib().fx_nl_init_groups(ctx.h, self.n_node, _ptr(self.coord), 1, tab, len(mats), arr))
+            del keep
+        elif self.etype in (351, 352, 362):
+            nn_elem = self.conn.shape[1] if self.conn.ndim == 2 else 0
+            _chk(lib().fx_nl_init_type(*head, self.etype, nn_elem, *tail))
+        elif self.etype != 361:
+            _chk(lib().fx_nl_init_c3(*head, self.etype, *tail))
+        elif isinstance(material, (list, tuple)):
+            _chk(lib().fx_nl_init_sections(*head, *tail))
+        else:
+            _chk(lib().fx_nl_init(*head, arr))
+
+    @staticmethod
+    def _materials(material, elem_mat=None, n_elem=None):
+        """(mats, the _MaterialView array the entry points take, elem_mat as int32 or None).  n_elem given (one group): several
+        materials need one id per element."""
+        mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        arr = (_MaterialView * len(mats))(*[m.view() for m in mats])
+        elem_mat = None if elem_mat is None else np.ascontiguousarray(elem_mat, dtype=np.int32)
+        if n_elem is not None and len(mats) > 1 and (elem_mat is None or elem_mat.shape != (n_elem,)):
+            raise ValueError("elem_mat: one material id per element")
+        return mats, arr, elem_mat
 
     def _set_parts(self, parts):
         """parts: [(etype, n_elem)] in the context's order -> the offsets of the flat layouts (fx_nl_init_groups)."""
@@ -194,16 +186,14 @@ class fstr_solid:
         self.n_point = int(self.point_offsets[-1])
 
     def _init_groups(self, groups, material):
-        mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        mats, arr, _ = self._materials(material)
         groups = [(g[0], g[1], 2 if len(g) < 3 or g[2] is None else g[2], g[3] if len(g) > 3 else None) for g in groups]
         tab, keep = hecmw.SolverContext._group_table(groups)
         self.groups = groups
         self.etype = self.nn = self.nq = self.conn = None       # no single type: see parts
         self._set_parts([(tab[g].etype, tab[g].n_elem) for g in range(len(groups))])
         self.n_elem = int(self.elem_offsets[-1])
-        views = [m.view() for m in mats]
-        arr = (_MaterialView * len(views))(*views)
-        _chk(lib().fx_nl_init_groups(self.ctx.h, self.n_node, _ptr(self.coord), len(groups), tab, len(views), arr))
+        _chk(lib().fx_nl_init_groups(self.ctx.h, self.n_node, _ptr(self.coord), len(groups), tab, len(mats), arr))
         del keep
 
     def group_slices(self, name, array):

@@ -394,7 +394,11 @@ typedef struct fx_nl_state_view { /* host arrays, any may be NULL (skipped).  tG
   double *unode, *dunode, *qforce;                    /* 3*NP: fstrSOLID%unode, %dunode, %QFORCE */
   int32_t latch; /* MatlMatrix's saved flag (calMatMatrix.f90:39); set_state: <0 leaves it */
 } fx_nl_state_view;
-/* fstr_solid / gauss-point set-up (zero state).  Needs a profile (fx_upload FX_UP_PROFILE). */
+/* fstr_solid / gauss-point set-up (zero state).  Needs a profile (fx_upload FX_UP_PROFILE).
+ * fx_nl_init, _sections, _c3 and _type check what is their own (the types they take, nn_elem, null arguments) and hand the mesh as
+ * ONE group (361: B-bar) to the set-up that fx_nl_init_groups runs: the same checks in the same order, every message under the
+ * name of the entry point called, group and element named ("group 1, element N: ..."), and nothing of the context that was there
+ * is touched by a call that is refused.  With n_mat == 1 elem_mat is not read. */
 int fx_nl_init(fx_context *ctx, const fx_mesh_view *mesh, const fx_material_view *mat);
 /* The same for a group whose elements belong to several sections / materials: elem_mat[e] in 1..n_mat selects mats[m-1]
  * (hecMESH%section_ID -> fstrSOLID%materials, fstr_setup.f90:325-400; every tGaussStatus%pMaterial points at its section's
@@ -429,8 +433,8 @@ int fx_nl_init_type(fx_context *ctx, const fx_mesh_view *mesh, int32_t etype, in
  * elastoplastic beside a hyperelastic material are the context's: the first elastoplastic stress update in ANY group latches the
  * tangents of EVERY group.  The scatter runs group after group, NLGEOM flag after flag, colour after colour on one stream, each
  * group with its own colouring: no atomics, two fx_nl_stiffness calls on the same state give bitwise equal D / AL / AU.  Collapsed
- * hexahedra of a 361 group are served as in fx_nl_init.  With ONE non-empty group the context and all it computes are bit for
- * bit those of fx_nl_init_sections / fx_nl_init_type.
+ * hexahedra of a 361 group are served as in fx_nl_init.  The single-type entry points are this call with one group, so with ONE
+ * non-empty group the context and all it computes are bit for bit those of fx_nl_init_sections / fx_nl_init_c3 / fx_nl_init_type.
  * A 361 group is B-bar (elemopt 2) or F-bar (elemopt 4: !SECTION, FORM361=FBAR; STF_C3D8Fbar / Update_C3D8Fbar,
  * static_LIB_Fbar.f90:26-769, in their INFINITE and TOTALLAG branches, with every material kind the loop has under those flags);
  * groups of either formulation and of the other five types may share one context.  Layouts, colouring, latch, snapshot, commit

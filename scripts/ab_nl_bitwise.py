@@ -12,7 +12,10 @@ Cases, on the small distorted meshes of the GPU tests (hyper_ref.gpu_mesh: a han
   every type 361, 341, 342, 351, 352, 362 x group 0..6 -- ELASTIC and Mises for each NLGEOM flag, Mooney-Rivlin (group 3),
   Drucker-Prager and Mohr-Coulomb for each flag (yield_ref.gpu_case: points on both sides of the surface) --,
   a two-section context per type (Mises UPDATELAG beside ELASTIC TOTALLAG), and two fx_nl_init_groups contexts (hexahedra + wedges +
-  tetrahedra, linear and quadratic) with the same two sections.
+  tetrahedra, linear and quadratic) with the same two sections;
+  F-bar (elemopt 4): one-group contexts for groups 0, 1 and 3 (ELASTIC INFINITE, ELASTIC TOTALLAG, Mooney-Rivlin), and one context of
+  an F-bar, a B-bar and a wedge group with two sections (Mises TOTALLAG beside ELASTIC INFINITE);
+  a 361 two-section context in which two hexahedra name a node twice (the collapsed-element tail of both launchers).
 Outputs per case: element tangents before the first update and after it (the latch), the per-element internal forces of the update,
 the state after the update and after fx_nl_commit, and D / AL / AU of the coloured scatter (fx_nl_stiffness_at, fx_download_matrix)
 before and after the update.  Nodal QFORCE and the FX_ASM_ATOMIC scatter are sums of fp64 atomics in no fixed order: not compared.
@@ -87,7 +90,7 @@ def dump(path):
         """groups: [(etype, conn, elemopt, elem_mat)]; one group: the single-type context"""
         hm = hip.hecmwST_local_mesh(n_node=mesh.n_node)
         if len(groups) == 1:
-            et, conn, _, em = groups[0]
+            et, conn, eo, em = groups[0]
             hm.nn_elem = conn.shape[1]
             hm.elem_node_item = conn.ravel()
             hecMAT = hip.hecmw_mat_con(hm, hip.hecmwST_matrix())
@@ -97,7 +100,7 @@ def dump(path):
         ctx.upload(hecMAT, what=hip.FX_UP_PROFILE)
         fm = [fmat(x) for x in mats]
         if len(groups) == 1:
-            solid = fstr.fstr_solid(ctx, mesh.coord, conn, fm if len(fm) > 1 else fm[0], elem_mat=em, etype=et)
+            solid = fstr.fstr_solid(ctx, mesh.coord, conn, fm if len(fm) > 1 else fm[0], elem_mat=em, etype=et, elemopt=eo)
         else:
             solid = fstr.fstr_solid(ctx, mesh.coord, None, fm, groups=groups)
         solid.set_state(dict(st or {}, unode=unode, dunode=dunode), latch=0)
@@ -123,8 +126,8 @@ def dump(path):
         state("after_commit")
         ctx.close()
 
-    def single(name, etype, mesh, mats, em, unode=None, dunode=None, history=True):
-        groups = [(etype, mesh.conn, 2, em)]
+    def single(name, etype, mesh, mats, em, unode=None, dunode=None, history=True, elemopt=2):
+        groups = [(etype, mesh.conn, elemopt, em)]
         if unode is None:
             unode, dunode, st = M.random_case(mesh, groups, mats, 17, history=history)
         else:
@@ -149,6 +152,23 @@ def dump(path):
         mats = [mises(M.UPDATELAG), Material(70000.0, 0.33, nlgeom=M.TOTALLAG)]
         mesh, groups, unode, dunode, st = M.gpu_case("n3", order, "mesh_order", mats, True)
         run("groups_order%d_two_sections" % order, mesh, groups, mats, unode, dunode, st)
+    mesh = H.gpu_mesh(361)
+    for g, mat in ((0, Material(E0, NU0, nlgeom=M.INFINITE)), (1, Material(E0, NU0, nlgeom=M.TOTALLAG)), (3, H.TEST_MATERIALS["mooney"]())):
+        unode, dunode = H.random_displacement(mesh.coord, 17, H.GPU_AMP)
+        single("t361_fbar_group%d" % g, 361, mesh, [mat], None, unode, dunode, elemopt=4)
+    mats = [mises(M.TOTALLAG), Material(70000.0, 0.33, nlgeom=M.INFINITE)]
+    mixed = M._mesh("n3", 1)
+    hexes, wedges = mixed.groups_with(2, (1 + (np.arange(mixed.n_elem) * 7 // 3) % 2).astype(np.int32))[:2]
+    assert hexes[0] == 361 and wedges[0] == 351
+    groups = [(361, np.ascontiguousarray(hexes[1][:2]), 4, np.ascontiguousarray(hexes[3][:2])),
+              (361, np.ascontiguousarray(hexes[1][2:]), 2, np.ascontiguousarray(hexes[3][2:])), wedges]
+    run("groups_fbar_bbar_wedges", mixed, groups, mats, *M.random_case(mixed, groups, mats, 17))
+    conn = mesh.conn.copy()
+    conn[0, 7], conn[0, 6] = conn[0, 4], conn[0, 5]      # a second collapsed hexahedron beside the mesh's own
+    assert sum(len(set(c)) < 8 for c in conn.tolist()) == 2
+    groups = [(361, conn, 2, (1 + (np.arange(mesh.n_elem) * 7 // 3) % 2).astype(np.int32))]
+    mats = [mises(M.UPDATELAG), Material(70000.0, 0.33, nlgeom=M.TOTALLAG)]
+    run("t361_two_collapsed_two_sections", mesh, groups, mats, *M.random_case(mesh, groups, mats, 17))
     np.savez(path, **out)
     print("%d arrays of %d cases written to %s (library %s)" % (len(out), len({k.split("/")[0] for k in out}), path, hip.LIBPATH))
     return 0

@@ -326,21 +326,29 @@ def _state_and_matrix(hip, ctx, hecMAT, solid, st, unode, dunode, bc):
     return out
 
 
-@pytest.mark.parametrize("etype", [361, 352, 341])
+@pytest.mark.parametrize("etype", [361, 352, 341, "361_collapsed"])
 def test_one_group_is_the_single_type_context_bitwise(hip, oracle, etype):
     """fx_nl_init_groups with one group (also: with empty groups around it) against fx_nl_init_sections (361) / fx_nl_init_type /
-    fx_nl_init_c3 on the same mesh, two sections: every number equal bit for bit."""
+    fx_nl_init_c3 on the same mesh, two sections: every number equal bit for bit.  361_collapsed: two of the hexahedra, one of
+    each section, name two nodes twice (the collapsed-element tail of the tangent and update launchers, with its own room for
+    the element matrices)."""
     from frontistr_amd import fstr
     from frontistr_amd.mesh import CubeMesh, solid_mesh
+    collapsed, etype = etype == "361_collapsed", 361 if etype == "361_collapsed" else etype
     m = CubeMesh(3, skew=0.1) if etype == 361 else solid_mesh(2, etype, skew=0.1)
     mats, _ = materials("two_sections", M.UPDATELAG)
     em = (1 + (np.arange(m.n_elem) * 7 // 3) % 2).astype(np.int32)
-    groups = [(etype, m.conn, 2, em)]
+    conn = m.conn.copy()
+    if collapsed:
+        hexes = [4, 18]
+        assert em[4] != em[18]
+        conn[hexes, 7], conn[hexes, 6] = conn[hexes, 4], conn[hexes, 5]      # the edge 7-8 onto the edge 5-6: a wedge
+    groups = [(etype, conn, 2, em)]
     unode, dunode, st = M.random_case(m, groups, mats, 5)
     bc = m.dirichlet()
     hm = hip.hecmwST_local_mesh(n_node=m.n_node)
-    hm.nn_elem = m.conn.shape[1]
-    hm.elem_node_item = m.conn.ravel()
+    hm.nn_elem = conn.shape[1]
+    hm.elem_node_item = conn.ravel()
     res = []
     empty = (342, np.zeros((0, 10), dtype=np.int32), 2, np.zeros(0, dtype=np.int32))
     for how in ("single", "groups", "groups_with_empty"):
@@ -349,7 +357,7 @@ def test_one_group_is_the_single_type_context_bitwise(hip, oracle, etype):
         ctx.upload(hecMAT, what=hip.FX_UP_PROFILE)
         fm = [_fmat(x) for x in mats]
         if how == "single":
-            solid = fstr.fstr_solid(ctx, m.coord, m.conn, fm, elem_mat=em, etype=etype)
+            solid = fstr.fstr_solid(ctx, m.coord, conn, fm, elem_mat=em, etype=etype)
         else:
             solid = fstr.fstr_solid(ctx, m.coord, None, fm, groups=groups if how == "groups" else [empty] + groups + [empty])
         res.append(_state_and_matrix(hip, ctx, hecMAT, solid, st, unode, dunode, bc))
