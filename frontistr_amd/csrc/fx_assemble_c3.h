@@ -184,7 +184,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_update_c3(int32_t n_elem, c
       double eps[6], sg[6];
       small_strain(gu, eps);
       if (TH) {
-        const double e = thermal_eps(th.alpha[elem_mat ? elem_mat[elem] - 1 : 0], tc, t0, th.ref_temp);
+        double e;
+        if (TH == 2 && th.tab_idx) {  // tables (the nonlinear loop's load, the only caller with any): the coefficients and D at this point's temperatures
+          double alp, alp0, E, nu;
+          if (thermal_coefficients(th, elem_mat ? elem_mat[elem] - 1 : 0, tc, t0, alp, alp0, E, nu)) elastic_constants(E, nu, D11, D12, D44);
+          e = thermal_eps(alp, alp0, tc, t0, th.ref_temp);
+        } else {
+          e = thermal_eps(th.alpha[elem_mat ? elem_mat[elem] - 1 : 0], tc, t0, th.ref_temp);
+        }
         double em[6] = {e, e, e, 0.0, 0.0, 0.0};
         if (TH == 1) {
 #pragma unroll

@@ -289,6 +289,22 @@ struct NlDev {
   // sub-step of an automatic incrementation does not converge (fx_nl_snapshot); allocated at the first save
   NlPartState bk;
   bool bk_valid = false;
+  // Thermal strain (fx_nl_set_thermal; NlThermalDev of fx_nl_point.h is made from these).  Off: every pointer null, and the
+  // launchers take the instantiations without the switch.
+  struct Thermal {
+    bool on = false;
+    bool elastic_tab = false;         // some material has an E(T), nu(T) table: the tangent kernels' thermal variant is launched
+    bool any_tab = false;             // some material has a table of either kind: the thermal load looks them up at the point
+    double ref_temp = 0.0;
+    double *temp = nullptr, *last_temp = nullptr, *temp_init = nullptr, *last_temp_bk = nullptr;  // NP each
+    double *alpha = nullptr;          // n_mat
+    double *tabs = nullptr;           // the tables of all materials, one after the other
+    double *xc = nullptr;             // 3 NP: coord + unode, the configuration the thermal load is taken on (nl_thermal_load)
+    double *mtab = nullptr;           // n_mat x (D11, D12, D44) of the constants E, nu: what the thermal-load kernels take per material
+    double D0[3] = {0.0, 0.0, 0.0};   // material 1's, the kernels' by-value arguments
+    bool bk_valid = false;            // last_temp_bk holds a saved last_temp of THIS thermal set-up
+    int32_t *tab_idx = nullptr;       // per material: offset and rows of its alpha table (alpha, T), offset and rows of its elastic table (E, nu, T)
+  } th;
 };
 
 // TIMELOG (hecmw_solver_Iterative.f90:192-208): device time of the three phases the reference reports -- solver/matvec

@@ -98,6 +98,42 @@ __device__ __forceinline__ void nl_backward_euler(const NlMat &m, double (&s)[6]
   }
 }
 
+// Thermal strain of one quadrature point of the update routines (Update_C3D8Bbar static_LIB_C3D8.f90:309-344, UPDATE_C3
+// static_LIB_3d.f90:602-637, Update_C3D8Fbar static_LIB_Fbar.f90:487-522), the compile-time switch TH of the four update kernels:
+// ttc = H . temperature, tt0 = H . last_temp for an elastoplastic element and H . initial condition for any other
+// (fstr_Update.f90:92-102), EPSTH(1:3) = alp (ttc - ref_temp) - alp0 (tt0 - ref_temp) with MC_THEMOEXP at ttc and at tt0.  Where
+// the material has an MC_ISOELASTIC table, m.E and m.nu become its values at ttc: MatlMatrix(..., ttc, isEp) and
+// BackwardEuler(..., ttc) read them from there.  node(j): id of the element's node j (1-based), H(j): its shape function at the point.
+template <int NN, class Node, class Shape>
+__device__ __forceinline__ double nl_thermal_point(const ThermalDev &th, NlMat &m, int mid, Node &&node, Shape &&H) {
+  const double *t0n = m.plastic ? th.temp0 : th.temp_init;
+  double ttc = 0.0, tt0 = 0.0;
+#pragma unroll
+  for (int j = 0; j < NN; j++) {
+    const double h = H(j);
+    const int32_t nd = node(j) - 1;
+    ttc += h * th.temp[nd];
+    tt0 += h * t0n[nd];
+  }
+  double alp, alp0;
+  thermal_coefficients(th, mid, ttc, tt0, alp, alp0, m.E, m.nu);
+  return thermal_eps(alp, alp0, ttc, tt0, th.ref_temp);
+}
+// The tangent kernels' share of it (TH, launched only where a material has an MC_ISOELASTIC table): MatlMatrix's E, nu at
+// tt = H . temperature (fstr_StiffMatrix.f90:72-73)
+template <int NN, class Node, class Shape>
+__device__ __forceinline__ void nl_thermal_matrix(const ThermalDev &th, NlMat &m, int mid, Node &&node, Shape &&H) {
+  const int32_t *ix = th.tab_idx + 4 * mid;
+  if (ix[3] < 1) return;
+  double ttc = 0.0;
+#pragma unroll
+  for (int j = 0; j < NN; j++) ttc += H(j) * th.temp[node(j) - 1];
+  double en[2];
+  thermal_table<2>(th.tabs + ix[2], ix[3], ttc, en);
+  m.E = en[0];
+  m.nu = en[1];
+}
+
 // symmetric 6x6 in 21 entries, row-major upper triangle: index of (i,j), i<=j
 __device__ __forceinline__ constexpr int sym21(int i, int j) { return (i <= j) ? (i * (13 - i)) / 2 + (j - i) : (j * (13 - j)) / 2 + (i - j); }
 

@@ -56,7 +56,8 @@ __device__ __forceinline__ void hex8_gderiv(const double (&ec)[8][3], double xi,
 
 __device__ __forceinline__ double bcast8(double v, int src) { return __shfl(v, src, 8); }
 
-template <int G>
+// TH: MatlMatrix with E, nu at the point's temperature (nl_thermal_matrix, fx_nl_point.h); th is read by TH = 1 alone.
+template <int G, int TH = 0>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, const double *__restrict__ coord,
                                                             const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                             const double *__restrict__ dunode, NlMat m, int latch,
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                            int kout_pos, const double *__restrict__ strain) {
+                                                            int kout_pos, const double *__restrict__ strain, ThermalDev th) {
   constexpr int NLGEOM = nl_group_flag(G);
   // positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one colour (no shared node),
   // scattered without atomics, see k_assemble_c3d8.  mats / emat: several sections, element e uses mats[emat[e] - 1].
@@ -126,6 +127,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 #pragma unroll
       for (int k = 0; k < 21; k++) Dsh[21 * lane8 + k] = Dm[k];
     } else {
+      if constexpr (TH != 0)
+        nl_thermal_matrix<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return nod[j]; }, [&](int j) { return hex8_shape_func(j, xi, et, ze); });
       nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr);
     }
 #pragma unroll
@@ -257,7 +260,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
 }
 
 // Update_C3D8Bbar + scatter of the internal force.  qf_out (tests): per-element qf[24] instead of the scatter.
-template <int G>
+// TH: the routine's thermal branch (nl_thermal_point, fx_nl_point.h); th is read by TH = 1 alone.
+template <int G, int TH = 0>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const double *__restrict__ coord,
                                                          const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                          const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
                                                          double *__restrict__ qforce, double *__restrict__ qf_out,
                                                          const int32_t *__restrict__ elem_list, int32_t e0,
                                                          const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                         int32_t *__restrict__ err) {
+                                                         int32_t *__restrict__ err, ThermalDev th) {
   // positions [e0, n_elem) of elem_list: the elements of this group; mats / emat: several sections
   constexpr int NLGEOM = nl_group_flag(G);
   const int LX = threadIdx.x & 7;
@@ -327,6 +331,12 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
   double de[6];
   small_strain(g, de);
   de[0] += dvol; de[1] += dvol; de[2] += dvol;
+  double eth = 0.0;  // EPSTH(1:3), subtracted before the Green-Lagrange terms (:359)
+  if constexpr (TH != 0) {
+    eth = nl_thermal_point<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return nod[j]; },
+                              [&](int j) { return hex8_shape_func(j, xi, et, ze); });
+    de[0] -= eth; de[1] -= eth; de[2] -= eth;
+  }
   if (NLGEOM == 1) {  // Green-Lagrange strain :378-388
 #pragma unroll
     for (int c = 0; c < 3; c++) de[c] += 0.5 * (g[0][c] * g[0][c] + g[1][c] * g[1][c] + g[2][c] * g[2][c]);
@@ -374,6 +384,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
 #pragma unroll
     for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
   }
+  if constexpr (TH != 0) { eg[0] += eth; eg[1] += eth; eg[2] += eth; }  // the stored strain is the total one (:363, :389-401, :412)
   if (G != 3 && m.plastic) {
     int32_t ist = istat[gp];
     double fs = fstat[gp];

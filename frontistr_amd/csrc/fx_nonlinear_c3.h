@@ -29,7 +29,8 @@
 #include "fx_nl_point.h"
 
 // Arguments as k_nl_stiffness_tet.
-template <int ETYPE, int G>
+// TH: MatlMatrix with E, nu at the point's temperature (nl_thermal_matrix, fx_nl_point.h); th is read by TH = 1 alone.
+template <int ETYPE, int G, int TH = 0>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_elem, const double *__restrict__ coord,
                                                            const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                            const double *__restrict__ dunode, NlMat m, int latch,
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
                                                            const int32_t *__restrict__ elem_list, int32_t e0,
                                                            const int32_t *__restrict__ pos_map, int atomic,
                                                            const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                           const double *__restrict__ strain) {
+                                                           const double *__restrict__ strain, ThermalDev th) {
   using El = C3El<ETYPE>;
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = El::NN, NQ = El::NQ, EPB = El::EPB, LPE = El::LPE, NB = El::NB;
@@ -82,6 +83,12 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
         for (int i = 0; i < 6; i++) E[i] = strain[gp * 6 + i];
         hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
       } else {
+        if constexpr (TH != 0) {
+          double xi, et, ze, w;
+          c3_gauss<ETYPE>(q, xi, et, ze, w);
+          nl_thermal_matrix<NN>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return conn[(size_t)NN * elem + j]; },
+                                [&](int j) { return c3_shape_func<ETYPE>(j, xi, et, ze); });
+        }
         // (inside `if (active)`: only lanes that own a real point get here, so err needs no `active ?` guard as in k_nl_stiffness)
         nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm, err);
       }
@@ -165,7 +172,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_c3(int32_t n_e
 }
 
 // UPDATE_C3 + scatter of the internal force.  Arguments as k_nl_update_tet; state arrays [elem][NQ][.].
-template <int ETYPE, int G>
+// TH: the routine's thermal branch (nl_thermal_point, fx_nl_point.h); th is read by TH = 1 alone.
+template <int ETYPE, int G, int TH = 0>
 __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem, const double *__restrict__ coord,
                                                         const int32_t *__restrict__ conn, const double *__restrict__ unode,
                                                         const double *__restrict__ dunode, NlMat m, double *__restrict__ stress,
@@ -175,7 +183,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
                                                         double *__restrict__ qforce, double *__restrict__ qf_out,
                                                         const int32_t *__restrict__ elem_list, int32_t e0,
                                                         const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                        int32_t *__restrict__ err) {
+                                                        int32_t *__restrict__ err, ThermalDev th) {
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ, LPE = C3El<ETYPE>::ULPE, EPB = C3El<ETYPE>::UEPB;
   constexpr int NF = NLGEOM == 1 ? 9 : 1;
@@ -209,6 +217,14 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
       }
       double de[6];
       small_strain(gu, de);
+      double eth = 0.0;  // EPSTH(1:3), subtracted before the Green-Lagrange terms (:653)
+      if constexpr (TH != 0) {
+        double xi, et, ze, w;
+        c3_gauss<ETYPE>(g, xi, et, ze, w);
+        eth = nl_thermal_point<NN>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return conn[(size_t)NN * elem + j]; },
+                                   [&](int j) { return c3_shape_func<ETYPE>(j, xi, et, ze); });
+        de[0] -= eth; de[1] -= eth; de[2] -= eth;
+      }
       if (NLGEOM == 1) {  // Green-Lagrange strain (:671-679)
 #pragma unroll
         for (int c = 0; c < 3; c++) de[c] += 0.5 * (gu[0][c] * gu[0][c] + gu[1][c] * gu[1][c] + gu[2][c] * gu[2][c]);
@@ -254,6 +270,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_c3(int32_t n_elem
 #pragma unroll
         for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
       }
+      if constexpr (TH != 0) { eg[0] += eth; eg[1] += eth; eg[2] += eth; }  // the stored strain is the total one (:657, :683-694, :707)
       if (G != 3 && m.plastic) {
         int32_t ist = istat[gp];
         double fs = fstat[gp];

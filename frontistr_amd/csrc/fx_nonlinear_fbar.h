@@ -106,7 +106,8 @@ __device__ __forceinline__ void fbar_node_B(const double *g, const double *Z, co
 template <int NLGEOM>
 __device__ __forceinline__ constexpr int fbar_lds_doubles() { return NLGEOM == 1 ? 8 * (24 + 21 + 24 + FXF_PT) + 24 + 2 : 8 * (24 + 21 + 1) + 24 + 2; }
 
-template <int G>
+// TH: MatlMatrix with E, nu at the point's temperature (nl_thermal_matrix, fx_nl_point.h); th is read by TH = 1 alone.
+template <int G, int TH = 0>
 __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
     int32_t n_elem, const double *__restrict__ coord, const int32_t *__restrict__ conn, const double *__restrict__ unode,
     const double *__restrict__ dunode, NlMat m, int latch, const double *__restrict__ stress, const double *__restrict__ fstat,
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
     const int32_t *__restrict__ indexU, const int32_t *__restrict__ itemU, double *__restrict__ D, double *__restrict__ AL,
     double *__restrict__ AU, double *__restrict__ Kout, int32_t *__restrict__ err, const int32_t *__restrict__ elem_list, int32_t e0,
     const int32_t *__restrict__ pos_map, int atomic, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat, int kout_pos,
-    const double *__restrict__ strain) {
+    const double *__restrict__ strain, ThermalDev th) {
   // arguments and element lists as k_nl_stiffness
   constexpr int NLGEOM = nl_group_flag(G);
   static_assert(NLGEOM != 2, "F-bar: INFINITE and TOTALLAG only");
@@ -191,6 +192,9 @@ __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
       for (int i = 0; i < 6; i++) E[i] = strain[((size_t)8 * elem + lane8) * 6 + i];
       hyper_tangent(nl_hyper_kind(m), m.pl, E, Dm);
     } else {
+      if constexpr (TH != 0)
+        nl_thermal_matrix<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return conn[(size_t)8 * elem + j]; },
+                             [&](int j) { return hex8_shape_func(j, xi, et, ze); });
       nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0,
                                          m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr);
     }
@@ -394,14 +398,15 @@ __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
 }
 
 // Update_C3D8Fbar + scatter of the internal force; arguments as k_nl_update.  All of it is per point, in registers: no LDS.
-template <int G>
+// TH: the routine's thermal branch (nl_thermal_point, fx_nl_point.h); th is read by TH = 1 alone.
+template <int G, int TH = 0>
 __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
     int32_t n_elem, const double *__restrict__ coord, const int32_t *__restrict__ conn, const double *__restrict__ unode,
     const double *__restrict__ dunode, NlMat m, double *__restrict__ stress, double *__restrict__ strain,
     const double *__restrict__ stress_bak, const double *__restrict__ strain_bak, const double *__restrict__ plstrain,
     double *__restrict__ fstat, int32_t *__restrict__ istat, double *__restrict__ qforce, double *__restrict__ qf_out,
     const int32_t *__restrict__ elem_list, int32_t e0, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-    int32_t *__restrict__ err) {
+    int32_t *__restrict__ err, ThermalDev th) {
   constexpr int NLGEOM = nl_group_flag(G);
   static_assert(NLGEOM != 2, "F-bar: INFINITE and TOTALLAG only");
   const int LX = threadIdx.x & 7;
@@ -456,7 +461,12 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
     for (int d = 0; d < 3; d++) gave[j][d] = g1[j][d];
   double Jr, inv;
   fbar_averages(wg, jacob * wg, gave, Jr, inv, active ? err : nullptr);
-  double de[6], Fl[9], cr[6], J2 = 1.0;
+  double de[6], Fl[9], cr[6], J2 = 1.0, eth = 0.0;
+  // EPSTH(1:3): subtracted from the strain of either branch where the routine does it (:542, :565) -- in the TOTALLAG branch
+  // before the strain enters B2 of the internal force (:720-725)
+  if constexpr (TH != 0)
+    eth = nl_thermal_point<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return nod[j]; },
+                              [&](int j) { return hex8_shape_func(j, xi, et, ze); });
   if (NLGEOM == 0) {  // :532-541
     double dvol = 0.0;
 #pragma unroll
@@ -469,6 +479,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
     dvol = (dvol - (g[0][0] + g[1][1] + g[2][2])) / 3.0;
     small_strain(g, de);
     de[0] += dvol; de[1] += dvol; de[2] += dvol;
+    if constexpr (TH != 0) { de[0] -= eth; de[1] -= eth; de[2] -= eth; }
 #pragma unroll
     for (int i = 0; i < 9; i++) Fl[i] = 0.0;
 #pragma unroll
@@ -477,6 +488,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
     const double Jl = Jr * pow(jacob, -1.0 / 3.0);
     double Fb[9];
     fbar_strain(Jl, g, Fb, de);
+    if constexpr (TH != 0) { de[0] -= eth; de[1] -= eth; de[2] -= eth; }
     J2 = Jl * Jl;
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -502,7 +514,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
   }
   if (active) {
 #pragma unroll
-    for (int i = 0; i < 6; i++) { stress[gp * 6 + i] = sg[i]; strain[gp * 6 + i] = de[i]; }
+    for (int i = 0; i < 6; i++) { stress[gp * 6 + i] = sg[i]; strain[gp * 6 + i] = TH != 0 && i < 3 ? de[i] + eth : de[i]; }
   }
   // ---- internal force of this point (:661-765); WG is taken before gderiv1 is formed (:674): the reference configuration's
   double qf[24];

@@ -2,6 +2,21 @@
 // fstr_Newton (fstr_solve_NonLinear.f90:29-167) either side of the linear solve, on resident state.
 #pragma once
 
+static void nl_thermal_free(NlDev::Thermal &t) {
+  dev_free(t.temp); dev_free(t.last_temp); dev_free(t.temp_init); dev_free(t.last_temp_bk);
+  dev_free(t.alpha); dev_free(t.tabs); dev_free(t.tab_idx); dev_free(t.mtab); dev_free(t.xc);
+  t = NlDev::Thermal();
+}
+// The kernels' view of the context's thermal data (all null while thermal is off: the TH = 0 instantiations do not read it)
+static ThermalDev nl_thermal_dev(const NlDev &n) {
+  const NlDev::Thermal &t = n.th;
+  ThermalDev d{t.temp, t.last_temp, t.alpha, t.ref_temp};
+  d.tabs = t.tabs;
+  d.tab_idx = t.any_tab ? t.tab_idx : nullptr;
+  d.temp_init = t.temp_init;
+  return d;
+}
+
 static void nl_free(fx_context *c) {
   NlDev &n = c->nl;
   dev_free(n.tab); dev_free(n.coord);
@@ -15,6 +30,7 @@ static void nl_free(fx_context *c) {
   dev_free(n.bc_flag); dev_free(n.bc_val); dev_free(n.bc_node); dev_free(n.bc_dof); dev_free(n.bc_v); dev_free(n.err);
   dev_free(n.mats);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
+  nl_thermal_free(n.th);
   n = NlDev();
 }
 
@@ -328,33 +344,35 @@ static void for_each_nl_group(F &&f) {
 }
 // The element kernel of one type and group: k_nl_* of 361 (B-bar), k_nl_*_tet for the tetrahedra, k_nl_*_c3 for 351 / 352 / 362.
 // The three tangents take the same arguments but for one int of 361's, the three updates the same arguments.
-template <int ETYPE, int G, bool UPDATE>
+// TH: the thermal variant (fx_nl_set_thermal).  The update kernels take it whenever thermal is on, the tangent kernels only where a
+// material has an elastic table; a context without thermal strain launches the TH = 0 instantiations, the kernels it always had.
+template <int ETYPE, int G, bool UPDATE, int TH>
 static constexpr auto nl_c3_kernel() {
   if constexpr (UPDATE) {
-    if constexpr (ETYPE == 361) return k_nl_update<G>;
-    else if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G>;
-    else return k_nl_update_c3<ETYPE, G>;
+    if constexpr (ETYPE == 361) return k_nl_update<G, TH>;
+    else if constexpr (C3El<ETYPE>::TET) return k_nl_update_tet<ETYPE, G, TH>;
+    else return k_nl_update_c3<ETYPE, G, TH>;
   } else {
-    if constexpr (ETYPE == 361) return k_nl_stiffness<G>;
-    else if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G>;
-    else return k_nl_stiffness_c3<ETYPE, G>;
+    if constexpr (ETYPE == 361) return k_nl_stiffness<G, TH>;
+    else if constexpr (C3El<ETYPE>::TET) return k_nl_stiffness_tet<ETYPE, G, TH>;
+    else return k_nl_stiffness_c3<ETYPE, G, TH>;
   }
 }
 // The groups the F-bar kernels are instantiated for: no UPDATELAG (nl_init_driver refuses it, so such a list is empty)
 static constexpr bool nl_fbar_group(int G) { return nl_group_flag(G) != 2; }
 // What one group of a part launches: the kernel of its type (null: nothing to launch), elements per workgroup and workgroup size.
 // An F-bar part takes the F-bar kernels, which have the arguments of 361's and, for the tangent, a workgroup of their own.
-template <int ETYPE, int G, bool UPDATE>
+template <int ETYPE, int G, bool UPDATE, int TH>
 struct NlKernel {
-  decltype(nl_c3_kernel<ETYPE, G, UPDATE>()) kern = nl_c3_kernel<ETYPE, G, UPDATE>();
+  decltype(nl_c3_kernel<ETYPE, G, UPDATE, TH>()) kern = nl_c3_kernel<ETYPE, G, UPDATE, TH>();
   int epb = ETYPE != 361 ? (UPDATE ? C3El<ETYPE>::UEPB : C3El<ETYPE>::EPB) : FXN_EPB;
   int block = ETYPE != 361 ? C3El<ETYPE>::BS : FXN_BLOCK;
   explicit NlKernel(const NlPart &p) {
     if constexpr (ETYPE == 361) {
       if (!p.fbar) return;
       if constexpr (!nl_fbar_group(G)) kern = nullptr;
-      else if constexpr (UPDATE) kern = k_nl_update_fbar<G>;
-      else { kern = k_nl_stiffness_fbar<G>; epb = FXF_EPB; block = FXF_BLOCK; }
+      else if constexpr (UPDATE) kern = k_nl_update_fbar<G, TH>;
+      else { kern = k_nl_stiffness_fbar<G, TH>; epb = FXF_EPB; block = FXF_BLOCK; }
     }
   }
 };
@@ -368,21 +386,22 @@ template <int ETYPE>
 static constexpr size_t NL_KE = (size_t)(3 * C3El<ETYPE>::NN) * (3 * C3El<ETYPE>::NN);  // doubles of one element matrix
 // The tangent of one group of a part of any of the six types.  Kout: the part's block of the element matrices, or null (scatter);
 // dup_k (361, scatter): room for the element matrices of the part's collapsed elements
-template <int ETYPE, int G>
+template <int ETYPE, int G, int TH>
 static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Kout, double *dup_k) {
   NlDev &n = c->nl;
   const DevCSR &A = c->A;
   const NlPartState s = nl_part_state(n, p);
-  const NlKernel<ETYPE, G, false> k(p);
+  const NlKernel<ETYPE, G, false, TH> k(p);
   if (!k.kern) return;
+  const ThermalDev th = nl_thermal_dev(n);
   auto launch = [&](dim3 grid, int32_t e0, int32_t e1, double *K, const int32_t *list, const int32_t *pos, int atomic, int k_by_pos) {
     auto go = [&](auto... tail) {
       hipLaunchKernelGGL(k.kern, grid, dim3(k.block), 0, c->stream, e1, n.coord, p.conn, n.unode, n.dunode, n.mat, n.latch, s.stress,
                          s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, K, n.err, list, e0, pos, atomic,
                          (const NlMat *)n.mats, (const int32_t *)p.emat, tail...);
     };
-    if constexpr (ETYPE == 361) go(k_by_pos, (const double *)s.strain);  // 361's own argument: K by position in the list
-    else go((const double *)s.strain);
+    if constexpr (ETYPE == 361) go(k_by_pos, (const double *)s.strain, th);  // 361's own argument: K by position in the list
+    else go((const double *)s.strain, th);
   };
   // element matrices out, or atomics: the group's colours in one launch
   for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, k.epb, [&](dim3 grid, int32_t e0, int32_t e1) {
@@ -403,16 +422,17 @@ static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Ko
   }
 }
 // The stress update of one group of a part of any of the six types
-template <int ETYPE, int G>
+template <int ETYPE, int G, int TH>
 static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_out) {
   NlDev &n = c->nl;
   const NlPartState s = nl_part_state(n, p);
-  const NlKernel<ETYPE, G, true> k(p);
+  const NlKernel<ETYPE, G, true, TH> k(p);
   if (!k.kern) return;
+  const ThermalDev th = nl_thermal_dev(n);
   auto launch = [&](const int32_t *list, int32_t e0, int32_t e1) {
     hipLaunchKernelGGL(k.kern, dim3((unsigned)((e1 - e0 + k.epb - 1) / k.epb)), dim3(k.block), 0, c->stream, e1, n.coord, p.conn, n.unode,
                        n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out,
-                       list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err);
+                       list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err, th);
   };
   const std::vector<int32_t> &off = p.grp_off[G];
   // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
@@ -435,8 +455,10 @@ static int nl_launch_stiffness(fx_context *c, double *Kout) {  // Kout: the elem
   for (const NlPart &p : c->nl.parts) {
     with_solid_type(p.etype, [&](auto t) {
       for_each_nl_group([&](auto g) {
-        nl_launch_stiffness_group<decltype(t)::value, decltype(g)::value>(c, p, Kout ? Kout + p.k_off : nullptr,
-                                                                          dup_k ? dup_k + NL_KE<361> * dup_at : nullptr);
+        constexpr int ET = decltype(t)::value, G = decltype(g)::value;
+        double *const K = Kout ? Kout + p.k_off : nullptr, *const dk = dup_k ? dup_k + NL_KE<361> * dup_at : nullptr;
+        if (c->nl.th.on && c->nl.th.elastic_tab) nl_launch_stiffness_group<ET, G, 1>(c, p, K, dk);
+        else nl_launch_stiffness_group<ET, G, 0>(c, p, K, dk);
       });
     });
     dup_at += (size_t)p.n_dup;
@@ -448,7 +470,9 @@ static void nl_launch_update(fx_context *c, double *qf_out) {  // qf_out: the el
   for (const NlPart &p : c->nl.parts)
     with_solid_type(p.etype, [&](auto t) {
       for_each_nl_group([&](auto g) {
-        nl_launch_update_group<decltype(t)::value, decltype(g)::value>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
+        constexpr int ET = decltype(t)::value, G = decltype(g)::value;
+        if (c->nl.th.on) nl_launch_update_group<ET, G, 1>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
+        else nl_launch_update_group<ET, G, 0>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
       });
     });
 }
@@ -538,6 +562,24 @@ static int nl_halo_natural(fx_context *c, double *v) {  // hecmw_update_3_R on a
   return 0;
 }
 
+// The thermal load of fstr_ass_load.f90:287-428 added to the resident right-hand side: the TLOAD vector of every element on the
+// current configuration node + unode (:316-320) with TEMP0 = last_temp whatever the material (:307), through the thermal-load
+// kernels of the linear path (fx_thermal.h, TH = 2).  Every 361 part is B-bar here, F-bar included (:391-398).  The kernels take
+// the elastic matrix of the material's E, nu (or of its table at the point): a hyperelastic material, which has neither, adds nothing.
+static int nl_thermal_load(fx_context *c) {
+  NlDev &n = c->nl;
+  const size_t np3 = (size_t)3 * c->A.NP;
+  double *xc = n.th.xc;
+  HIP_TRY(hipMemcpyAsync(xc, n.coord, np3 * 8, hipMemcpyDeviceToDevice, c->stream));
+  hipLaunchKernelGGL(k_axpy_plain, dim3(grid_for((int64_t)np3)), dim3(256), 0, c->stream, (int64_t)np3, 1.0, n.unode, xc);
+  const ThermalDev th = nl_thermal_dev(n);
+  for (const NlPart &p : n.parts)
+    launch_update_linear_th<2>(c, p.etype, 2, p.n_elem, xc, p.conn, n.th.D0[0], n.th.D0[1], n.th.D0[2], p.emat, p.emat ? n.th.mtab : nullptr, nullptr,
+                               nullptr, nullptr, c->A.B, n.err, th);
+  HIP_TRY(hipGetLastError());
+  return 0;  // (on the context's stream: fx_nl_begin_substep synchronises)
+}
+
 // Start of a substep (fstr_Newton :63-68, fstr_ass_load.f90:64-91,:273): dunode = 0, GL = load at the end of the
 // increment (host, 3*NP, may be NULL = no nodal load), B = GL - QFORCE.
 extern "C" int fx_nl_begin_substep(fx_context *c, const double *GL) {
@@ -550,6 +592,8 @@ extern "C" int fx_nl_begin_substep(fx_context *c, const double *GL) {
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for((int64_t)np3)), dim3(256), 0, c->stream, (int64_t)np3, n.GL, n.qforce,
                      (const uint8_t *)nullptr, c->A.B);
   HIP_TRY(hipGetLastError());
+  if (n.th.on)
+    if (int rc = nl_thermal_load(c)) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -645,6 +689,8 @@ extern "C" int fx_nl_commit(fx_context *c) {
     hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat.plastic, s.fstat, s.plstrain,
                        s.stress, s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
   }
+  if (n.th.on)  // last_temp = temperature (fstr_Update.f90:308-312)
+    HIP_TRY(hipMemcpyAsync(n.th.last_temp, n.th.temp, (size_t)c->A.NP * 8, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -659,12 +705,21 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
   NlDev &n = c->nl;
   const size_t npt = (size_t)n.n_pt;
   if (load && !n.bk_valid) { g_fx_error = "fx_nl_snapshot: nothing was saved"; return FX_ERROR_RUNTIME; }
+  // a save from before fx_nl_set_thermal (or before a repeated one) holds no last_temp of this set-up: nothing is restored then
+  if (load && n.th.on && !n.th.bk_valid)
+    return fx_fail("fx_nl_snapshot", FX_ERROR_RUNTIME, "the saved state holds no last_temp: fx_nl_set_thermal was called after the save");
   if (!n.bk.stress && nl_alloc_point_arrays(n.bk, npt)) return FX_ERROR_RUNTIME;
   if (for_each_point_array([&](size_t b, void *live, void *bk) {
         HIP_TRY(hipMemcpyAsync(load ? live : bk, load ? bk : live, npt * b, hipMemcpyDeviceToDevice, c->stream));
         return 0;
       }, n.st, n.bk))
     return FX_ERROR_RUNTIME;
+  if (n.th.on) {  // last_temp travels with the history (fstr_Cutback.f90:127, :173)
+    if (!n.th.last_temp_bk && dev_alloc(&n.th.last_temp_bk, (size_t)c->A.NP)) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(load ? n.th.last_temp : n.th.last_temp_bk, load ? n.th.last_temp_bk : n.th.last_temp, (size_t)c->A.NP * 8,
+                           hipMemcpyDeviceToDevice, c->stream));
+    if (!load) n.th.bk_valid = true;
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   n.bk_valid = true;
   return 0;
@@ -692,6 +747,95 @@ extern "C" int fx_nl_set_state(fx_context *c, const fx_nl_state_view *s) {
   NL_READY("fx_nl_set_state");
   if (s->latch >= 0) c->nl.latch = s->latch ? 1 : 0;
   return nl_copy_state(c, s, true);
+}
+
+// ---- thermal strain (see the header): the context's temperatures, expansion coefficients and tables
+extern "C" int fx_nl_set_thermal(fx_context *c, const fx_nl_thermal_view *v) {
+  const char *who = "fx_nl_set_thermal";
+  NL_READY("fx_nl_set_thermal");
+  NlDev &n = c->nl;
+  if (!v) { nl_thermal_free(n.th); return 0; }
+  if (!v->alpha) return fx_fail(who, FX_ERROR_RUNTIME, "expansion coefficients missing");
+  // everything is checked, and the new data is on the device, before the context changes
+  std::vector<double> tabs;
+  std::vector<int32_t> idx((size_t)4 * n.n_mat, 0);
+  NlDev::Thermal t;
+  for (int32_t k = 0; k < n.n_mat; k++) {
+    const double *tab[2] = {v->alpha_tab ? v->alpha_tab[k] : nullptr, v->elastic_tab ? v->elastic_tab[k] : nullptr};
+    for (int w = 0; w < 2; w++) {
+      if (!tab[w]) continue;
+      const int32_t *nrows = w == 0 ? v->alpha_rows : v->elastic_rows;
+      const int nc = w == 0 ? 2 : 3, rows = nrows ? nrows[k] : 0;
+      if (rows < 1) return fx_fail(who, FX_ERROR_RUNTIME, "material %d: a table with %d rows", (int)k + 1, rows);
+      if (w == 1 && n.h_mats[k].group == 3)
+        return fx_fail(who, FX_ERROR_UNSUPPORTED, "material %d: an elastic table on a hyperelastic material, which reads no E, nu", (int)k + 1);
+      for (int r = 1; r < rows; r++)
+        if (!(tab[w][nc * r + nc - 1] > tab[w][nc * (r - 1) + nc - 1]))
+          return fx_fail(who, FX_ERROR_UNSUPPORTED, "material %d: the temperatures of the %s table are not strictly ascending (row %d)",
+                         (int)k + 1, w == 0 ? "expansion" : "elastic", r + 1);
+      idx[4 * k + 2 * w] = (int32_t)tabs.size();
+      idx[4 * k + 2 * w + 1] = rows;
+      tabs.insert(tabs.end(), tab[w], tab[w] + (size_t)nc * rows);
+      t.any_tab = true;
+      t.elastic_tab |= w == 1;
+    }
+  }
+  // the elastic matrices of the constants, for the thermal-load kernels (nl_thermal_load); a hyperelastic material has none
+  std::vector<double> mtab((size_t)3 * n.n_mat);
+  for (int32_t k = 0; k < n.n_mat; k++) {
+    const bool hyper = n.h_mats[k].group == 3;
+    elastic_constants(hyper ? 0.0 : n.h_mats[k].E, hyper ? 0.0 : n.h_mats[k].nu, mtab[3 * k], mtab[3 * k + 1], mtab[3 * k + 2]);
+  }
+  for (int i = 0; i < 3; i++) t.D0[i] = mtab[i];
+  const size_t np = (size_t)c->A.NP;
+  if (dev_alloc(&t.mtab, mtab.size()) || dev_alloc(&t.xc, 3 * np) || dev_alloc(&t.temp, np) || dev_alloc(&t.last_temp, np) || dev_alloc(&t.temp_init, np) || dev_alloc(&t.alpha, (size_t)n.n_mat) ||
+      dev_alloc(&t.tabs, std::max<size_t>(tabs.size(), 1)) || dev_alloc(&t.tab_idx, idx.size())) {
+    nl_thermal_free(t);
+    return FX_ERROR_RUNTIME;
+  }
+  const std::vector<double> ref(v->temp_init ? 0 : np, v->ref_temp);
+  auto up = [&]() {
+    if (v->temp_init) HIP_TRY(hipMemcpyAsync(t.temp_init, v->temp_init, np * 8, hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(hipMemsetAsync(t.temp_init, 0, np * 8, c->stream));
+    // last_temp = the initial condition (fstr_solve_NLGEOM.f90:53-57), or 0 (fstr_setup.f90:788)
+    HIP_TRY(hipMemcpyAsync(t.last_temp, t.temp_init, np * 8, hipMemcpyDeviceToDevice, c->stream));
+    // the temperature until fx_nl_set_temperature gives one: the initial condition, or without one REF_TEMP (fstr_setup.f90:780)
+    if (v->temp_init) HIP_TRY(hipMemcpyAsync(t.temp, t.temp_init, np * 8, hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(hipMemcpyAsync(t.temp, ref.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t.alpha, v->alpha, (size_t)n.n_mat * 8, hipMemcpyHostToDevice, c->stream));
+    if (!tabs.empty()) HIP_TRY(hipMemcpyAsync(t.tabs, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t.tab_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t.mtab, mtab.data(), mtab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // tabs and idx are host temporaries
+    return 0;
+  };
+  if (int rc = up()) { nl_thermal_free(t); return rc; }
+  t.on = true;
+  t.ref_temp = v->ref_temp;
+  nl_thermal_free(n.th);
+  n.th = t;
+  return 0;
+}
+#define NL_THERMAL_ON(name)                                                                                  \
+  NL_READY(name);                                                                                            \
+  if (!c->nl.th.on) return fx_fail(name, FX_ERROR_RUNTIME, "thermal strain is off: call fx_nl_set_thermal first"); \
+  if (!temp) return fx_fail(name, FX_ERROR_RUNTIME, "temperature array missing")
+static int nl_copy_temp(fx_context *c, void *dst, const void *src, hipMemcpyKind kind) {
+  HIP_TRY(hipMemcpyAsync(dst, src, (size_t)c->A.NP * 8, kind, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int fx_nl_set_temperature(fx_context *c, const double *temp) {
+  NL_THERMAL_ON("fx_nl_set_temperature");
+  return nl_copy_temp(c, c->nl.th.temp, temp, hipMemcpyHostToDevice);
+}
+extern "C" int fx_nl_get_last_temp(fx_context *c, double *temp) {
+  NL_THERMAL_ON("fx_nl_get_last_temp");
+  return nl_copy_temp(c, temp, c->nl.th.last_temp, hipMemcpyDeviceToHost);
+}
+extern "C" int fx_nl_set_last_temp(fx_context *c, const double *temp) {
+  NL_THERMAL_ON("fx_nl_set_last_temp");
+  return nl_copy_temp(c, c->nl.th.last_temp, temp, hipMemcpyHostToDevice);
 }
 
 // Element-level outputs of the two kernels (tests): tangents ke (per element 3 nn x 3 nn row-major) of the current state

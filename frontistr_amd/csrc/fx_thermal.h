@@ -18,6 +18,13 @@
 struct ThermalDev {
   const double *temp, *temp0, *alpha;
   double ref_temp;
+  // The nonlinear loop alone (fx_nl_set_thermal; null in a linear static analysis).  tabs: the temperature tables of all materials
+  // in one array; tab_idx[4 m ..]: offset and rows of material m's MC_THEMOEXP table (rows alpha, T), offset and rows of its
+  // MC_ISOELASTIC table (rows E, nu, T); rows = 0: no table, the constant holds.  temp_init: the initial condition, the TEMP0 of
+  // an element whose material is not elastoplastic (fstr_Update.f90:93-99); temp0 is then last_temp.
+  const double *tabs = nullptr;
+  const int32_t *tab_idx = nullptr;
+  const double *temp_init = nullptr;
 };
 
 // (two rounded products, never one product fused into the subtraction: equal temperatures give exactly zero)
@@ -25,6 +32,59 @@ __device__ __forceinline__ double thermal_eps(double alp, double tempc, double t
 #pragma clang fp contract(off)
   const double now = alp * (tempc - ref_temp), then = alp * (temp0 - ref_temp);
   return now - then;
+}
+// the same with each temperature's own coefficient: MC_THEMOEXP fetched at TEMPC and at TEMP0 (static_LIB_3d.f90:610-636)
+__device__ __forceinline__ double thermal_eps(double alp, double alp0, double tempc, double temp0, double ref_temp) {
+#pragma clang fp contract(off)
+  const double now = alp * (tempc - ref_temp), then = alp0 * (temp0 - ref_temp);
+  return now - then;
+}
+
+// fetch_TableData on a table with one dependency (ttable.f90:282-354): n rows of NV values and the temperature, ascending.  Below
+// the first row the first row, at or above the last row the last, in between the blend of rows i and i + 1 for T_i <= a < T_i+1.
+template <int NV>
+__device__ __forceinline__ void thermal_table(const double *t, int n, double a, double (&out)[NV]) {
+  constexpr int NC = NV + 1;
+  const double *last = t + (size_t)NC * (n - 1);
+#pragma unroll
+  for (int v = 0; v < NV; v++) out[v] = last[v];
+  if (n == 1 || a >= last[NV]) return;
+  if (a < t[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) out[v] = t[v];
+    return;
+  }
+  for (int i = 0; i < n - 1; i++) {
+    const double *r0 = t + (size_t)NC * i, *r1 = r0 + NC;
+    if (a >= r0[NV] && a < r1[NV]) {
+      const double lambda = (a - r0[NV]) / (r1[NV] - r0[NV]);
+#pragma unroll
+      for (int v = 0; v < NV; v++) out[v] = (1.0 - lambda) * r0[v] + lambda * r1[v];
+      return;
+    }
+  }
+}
+// What a point of material `mid` (0-based) takes from the temperature: alp at TEMPC, alp0 at TEMP0 and, where the material has an
+// MC_ISOELASTIC table, E and nu at TEMPC (MatlMatrix's temperature argument, calElasticMatrix).  Without tables: the constant
+// coefficient twice, E and nu untouched.  Returns whether E and nu were replaced.
+__device__ __forceinline__ bool thermal_coefficients(const ThermalDev &th, int mid, double tempc, double temp0, double &alp, double &alp0,
+                                                     double &E, double &nu) {
+  alp = alp0 = th.alpha[mid];
+  if (!th.tab_idx) return false;
+  const int32_t *ix = th.tab_idx + 4 * mid;
+  if (ix[1] > 0) {
+    double o[1];
+    thermal_table<1>(th.tabs + ix[0], ix[1], tempc, o);
+    alp = o[0];
+    thermal_table<1>(th.tabs + ix[0], ix[1], temp0, o);
+    alp0 = o[0];
+  }
+  if (ix[3] < 1) return false;
+  double en[2];
+  thermal_table<2>(th.tabs + ix[2], ix[3], tempc, en);
+  E = en[0];
+  nu = en[1];
+  return true;
 }
 
 // ShapeFunc_hex8n (hex8n.f90), node order of TYPE=361

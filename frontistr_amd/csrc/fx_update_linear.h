@@ -67,7 +67,22 @@ __global__ __launch_bounds__(FXU_BS) void k_update_c3d8_linear(int32_t n_elem, c
       tc += h * th.temp[nod[j] - 1];
       t0 += h * th.temp0[nod[j] - 1];
     }
-    eth[0] = eth[1] = eth[2] = thermal_eps(alp, tc, t0, th.ref_temp);
+    if (TH == 2 && th.tab_idx) {  // tables (the nonlinear loop's load, the only caller with any): the coefficients and D at the POINT's temperatures (C3D8.f90:652-674)
+      double pc = tc, p0 = t0, E, nu, a1, a0;
+      if (centre) {
+        pc = p0 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const double h = hex8_shape_func(j, xi, et, ze);
+          pc += h * th.temp[nod[j] - 1];
+          p0 += h * th.temp0[nod[j] - 1];
+        }
+      }
+      if (thermal_coefficients(th, elem_mat ? elem_mat[elem] - 1 : 0, pc, p0, a1, a0, E, nu)) elastic_constants(E, nu, D11, D12, D44);
+      eth[0] = eth[1] = eth[2] = thermal_eps(a1, a0, tc, t0, th.ref_temp);
+    } else {
+      eth[0] = eth[1] = eth[2] = thermal_eps(alp, tc, t0, th.ref_temp);
+    }
   }
   double det, inv[3][3], gd[11][3];
   double c0[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // IC: det0 * inverse Jacobian at the centre (3dIC.f90:268-270)

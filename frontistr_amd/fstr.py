@@ -46,12 +46,24 @@ class _StateView(C.Structure):
                                           "istat", "unode", "dunode", "qforce")] + [("latch", C.c_int32)]
 
 
+class _NlThermalView(C.Structure):
+    _fields_ = [("ref_temp", C.c_double), ("temp_init", C.c_void_p), ("alpha", C.c_void_p), ("alpha_tab", C.c_void_p),
+                ("alpha_rows", C.c_void_p), ("elastic_tab", C.c_void_p), ("elastic_rows", C.c_void_p)]
+
+
 class tMaterial:
     """!ELASTIC E, nu; optional !PLASTIC, YIELD=MISES, HARDEN=<harden> with `plconst` (BILINEAR: yield0, H;
     SWIFT / RAMBERG-OSGOOD: the three constants) or `table` rows (yield stress, plastic strain) for MULTILINEAR.
     nlgeom_flag defaults to UPDATELAG as !PLASTIC does (KIRCHHOFF -> TOTALLAG, INFINITE -> INFINITE).
     Hyperelastic materials come from the named constructors neohooke / mooney_rivlin / arruda_boyce; they default to TOTALLAG, the
-    only flag the device loop serves for them.  Mohr-Coulomb and Drucker-Prager materials come from mohr_coulomb / drucker_prager."""
+    only flag the device loop serves for them.  Mohr-Coulomb and Drucker-Prager materials come from mohr_coulomb / drucker_prager.
+    Thermal strain (fstr_solid.set_thermal): ``expansion`` is !EXPANSION_COEFF's constant; ``expansion_table`` (rows alpha, T) and
+    ``elastic_table`` (rows E, nu, T) are the DEPENDENCIES=1 forms of !EXPANSION_COEFF and !ELASTIC, ascending in T.  They are
+    attributes: set them on the material before fstr_solid.set_thermal."""
+
+    expansion = 0.0
+    expansion_table = None
+    elastic_table = None
 
     def __init__(self, E, nu, plastic=False, harden=BILINEAR, plconst=(0.0, 0.0, 0.0), table=None, nlgeom_flag=UPDATELAG):
         self.E, self.nu, self.plastic, self.harden = float(E), float(nu), bool(plastic), int(harden)
@@ -214,9 +226,59 @@ class fstr_solid:
                 raise ValueError("group_slices: %r is no per-point or per-element array" % (name,))
         return out
 
+    # ---- thermal strain (fx_nl_set_thermal)
+    thermal = False
+
+    def set_thermal(self, ref_temp, temp_init=None):
+        """Switch the thermal branches of the update routines on: !REFTEMP, the initial condition (n_node, None = 0; last_temp
+        starts from it) and every material's expansion / expansion_table / elastic_table.  ref_temp = None switches them off."""
+        if ref_temp is None:
+            _chk(lib().fx_nl_set_thermal(self.ctx.h, None))
+            self.thermal = False
+            return
+        mats = list(self.material) if isinstance(self.material, (list, tuple)) else [self.material]
+        t0 = None if temp_init is None else np.ascontiguousarray(temp_init, dtype=np.float64)
+        if t0 is not None and t0.shape != (self.n_node,):
+            raise ValueError("temp_init: one temperature per node")
+        alpha = np.array([float(m.expansion) for m in mats])
+
+        def tables(name, ncol):
+            tabs = [None if getattr(m, name) is None else np.ascontiguousarray(getattr(m, name), dtype=np.float64).reshape(-1, ncol)
+                    for m in mats]
+            if all(t is None for t in tabs):
+                return None, None, tabs
+            ptrs = (C.c_void_p * len(mats))(*[None if t is None else t.ctypes.data for t in tabs])
+            rows = np.array([0 if t is None else t.shape[0] for t in tabs], dtype=np.int32)
+            return ptrs, rows, tabs
+
+        ap, ar, akeep = tables("expansion_table", 2)
+        ep, er, ekeep = tables("elastic_table", 3)
+        v = _NlThermalView(float(ref_temp), _ptr(t0), _ptr(alpha), None if ap is None else C.cast(ap, C.c_void_p), _ptr(ar),
+                           None if ep is None else C.cast(ep, C.c_void_p), _ptr(er))
+        _chk(lib().fx_nl_set_thermal(self.ctx.h, C.byref(v)))
+        del akeep, ekeep
+        self.thermal = True
+        self._temperature = np.full(self.n_node, float(ref_temp)) if t0 is None else t0.copy()
+
+    def temperature_at_step_start(self):
+        """temp_bak of fstr_solve_NLGEOM.f90:92: the temperature last set, or what set_thermal left (the initial condition, or
+        ref_temp without one)"""
+        return self._temperature.copy()
+
+    def set_temperature(self, temp):
+        """fstrSOLID%temperature (n_node) of the coming sub-step or call."""
+        t = None if temp is None else np.ascontiguousarray(temp, dtype=np.float64)
+        if t is not None and t.shape != (self.n_node,):
+            raise ValueError("temperature: one value per node")
+        _chk(lib().fx_nl_set_temperature(self.ctx.h, _ptr(t)))
+        self._temperature = t.copy()
+
     # ---- state transfer (tests, restart, output)
     def get_state(self, names=("stress", "strain", "stress_bak", "strain_bak", "plstrain", "fstat", "istat",
                                "unode", "dunode", "qforce")):
+        """``last_temp`` may be named too (thermal strain on); it is not among the defaults."""
+        want_last = "last_temp" in names
+        names = tuple(k for k in names if k != "last_temp")
         ne, nn, q = self.n_elem, self.n_node, self.nq
         if self.etype is None:      # several groups: flat, the groups one after the other
             p6, p1 = (self.n_point, 6), (self.n_point,)
@@ -229,6 +291,9 @@ class fstr_solid:
         v = _StateView(*[_ptr(out.get(k)) for k in shapes], 0)
         _chk(lib().fx_nl_get_state(self.ctx.h, C.byref(v)))
         out["latch"] = int(v.latch)
+        if want_last:
+            out["last_temp"] = np.zeros(nn)
+            _chk(lib().fx_nl_get_last_temp(self.ctx.h, _ptr(out["last_temp"])))
         return out
 
     def set_state(self, state, latch=-1):
@@ -239,6 +304,8 @@ class fstr_solid:
                 arrs[k] = np.ascontiguousarray(state[k], dtype=np.int32 if k == "istat" else np.float64)
         v = _StateView(*[_ptr(arrs.get(k)) for k in keys], int(latch))
         _chk(lib().fx_nl_set_state(self.ctx.h, C.byref(v)))
+        if state.get("last_temp") is not None:
+            _chk(lib().fx_nl_set_last_temp(self.ctx.h, _ptr(np.ascontiguousarray(state["last_temp"], dtype=np.float64))))
 
     def element_tangents(self):
         ke = np.zeros(int(self.tangent_offsets[-1])) if self.etype is None else np.zeros((self.n_elem, 3 * self.nn, 3 * self.nn))
@@ -290,9 +357,12 @@ def fstr_cutback_load(fstrSOLID):
     _chk(lib().fx_nl_snapshot(fstrSOLID.ctx.h, 1))
 
 
-def fstr_Newton(fstrSOLID, hecMAT, factor, bc, cload, max_iter, converg, commit_unconverged=False):
+def fstr_Newton(fstrSOLID, hecMAT, factor, bc, cload, max_iter, converg, commit_unconverged=False, temperature=None):
     """One substep of fstr_Newton.  factor = (FACTOR(1), FACTOR(2)); bc / cload are the values at load factor 1.
+    temperature: fstrSOLID%temperature of this sub-step (fstr_solid.set_thermal first); None keeps the one last set.
     Returns (converged, log) with log rows (iter, solver iterations, solver code, |B|, |X|, |QFORCE|, |dunode|)."""
+    if temperature is not None:
+        fstrSOLID.set_temperature(temperature)
     bn, bd, bv = _bc_arrays(bc)
     cl = None if cload is None else np.ascontiguousarray(cload, dtype=np.float64)
     log = np.zeros((max_iter, 7))
@@ -313,12 +383,23 @@ def fstr_set_step_control(fstrSOLID, maxres=1.0e10, is_linear=False):
     _chk(lib().fx_nl_set_step_control(fstrSOLID.ctx.h, C.c_double(maxres), int(is_linear)))
 
 
-def fstr_solve_NLGEOM(fstrSOLID, hecMAT, bc, cload, substeps, max_iter, converg, commit_unconverged=True):
+def fstr_solve_NLGEOM(fstrSOLID, hecMAT, bc, cload, substeps, max_iter, converg, commit_unconverged=True, temperature=None):
     """The sub-step loop of fstr_solve_NLGEOM with the default linear load-factor ramp (table_nlsta without
-    amplitude).  Returns the concatenated Newton log with the substep number in front."""
+    amplitude).  temperature: the nodal temperature at load factor 1 (fstr_solid.set_thermal first), ramped as
+    fstr_ass_load.f90:291-300 ramps it from temp_bak, the temperature at the start of the step (fstr_solve_NLGEOM.f90:92) -- in
+    a first step the initial condition given to set_thermal or, without one, ref_temp (fstr_setup.f90:780):
+    temperature(sub) = temp_bak + (temperature - temp_bak) * factor; and as the program calls fstr_UpdateState at the start of
+    the step (:96), last_temp starts the step as that temperature.  Returns the concatenated Newton log with the substep number
+    in front."""
     logs = []
+    if temperature is not None:
+        temperature = np.asarray(temperature, dtype=np.float64)
+        temp_bak = fstrSOLID.temperature_at_step_start()
+        fstrSOLID.set_temperature(temp_bak)
+        fstr_UpdateState(fstrSOLID)
     for sub in range(1, substeps + 1):
+        tsub = None if temperature is None else temp_bak + (temperature - temp_bak) * (sub / substeps)
         ok, log = fstr_Newton(fstrSOLID, hecMAT, ((sub - 1) / substeps, sub / substeps), bc, cload, max_iter, converg,
-                              commit_unconverged)
+                              commit_unconverged, temperature=tsub)
         logs.append(np.concatenate([np.full((log.shape[0], 1), float(sub)), log], axis=1))
     return np.concatenate(logs, axis=0)

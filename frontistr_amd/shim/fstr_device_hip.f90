@@ -45,10 +45,15 @@ module fstr_device_hip
   integer(c_int32_t), save :: nl_etype = 361       ! nonlinear loop: 361 (B-bar), or a type of STF_C3 / UPDATE_C3 (fx_nl_init_type)
   integer, save :: nl_nq = 8                       ! its quadrature points per element
   logical, save :: nl_mixed = .false.              ! several of the six solid types (HECMW_GPU_NL_MIXED=1): fx_nl_init_groups
+  logical, save :: nl_thermal = .false.            ! an NLGEOM deck with temperatures on the device (HECMW_GPU_NL_THERMAL=1): fx_nl_set_thermal
   logical, save :: nl_fbar = .false.               ! the 361 sections are F-bar, all of them (HECMW_GPU_NL_FBAR=1): fx_nl_init_groups with elemopt 4
   integer, allocatable, save :: el_nq(:), el_p0(:) ! per element: its type's quadrature points, and the points of the elements before it
   integer, save :: n_pt = 0                        ! quadrature points of the mesh: the per-point arrays are flat over them, in hecMESH's element order
   real(c_double), allocatable, target, save :: tabs(:,:,:)       ! (2, ntab_max, n_mat): the MC_YIELD tables handed to the library
+  ! what fx_nl_set_thermal was given (HECMW_GPU_NL_THERMAL=1): M_EXAPNSION, the MC_THEMOEXP / MC_ISOELASTIC tables, the initial condition
+  real(c_double), allocatable, target, save :: th_alpha(:), th_atab(:,:,:), th_etab(:,:,:), th_init(:)
+  integer(c_int32_t), allocatable, target, save :: th_arows(:), th_erows(:)
+  type(c_ptr), allocatable, target, save :: th_aptr(:), th_eptr(:)
   real(c_double), allocatable, target, save :: b6(:,:)
   integer(c_int32_t), allocatable, target, save :: bi(:)
 
@@ -83,7 +88,8 @@ contains
     character(len=64) :: tnames
     integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype, n_bbar, n_fbar
     integer(c_int32_t) :: et
-    logical :: opted
+    logical :: opted, th
+    character(len=9) :: tail
     if (decided) then
       fsd_eligible = eligible
       return
@@ -126,7 +132,18 @@ contains
     nn = 8
     if (lin_etype /= 361) nn = c3_type_nodes(lin_etype)
     if (hecMESH%mpc%n_mpc > 0) return
-    if (fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0) return
+    ! temperatures (`!TEMPERATURE`, also READRESULT: the array is made on the host): opt-in, one process, isotropic expansion, no
+    ! temperature column in a yield table; the section orientations are refused below for every deck
+    th = fstrSOLID%TEMP_ngrp_tot > 0 .or. fstrSOLID%TEMP_irres > 0
+    if (th) then
+      call get_environment_variable('HECMW_GPU_NL_THERMAL', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+      if (hecMESH%PETOT > 1) return
+      do i = 1, size(fstrSOLID%materials)
+        if (fstrSOLID%materials(i)%mtype == -1) cycle
+        if (.not. thermal_material_covered(fstrSOLID%materials(i))) return
+      enddo
+    endif
     if (fstrSOLID%SPRING_ngrp_tot > 0) return
     if (associated(fstrSOLID%contacts)) then
       if (size(fstrSOLID%contacts) > 0) return
@@ -217,6 +234,9 @@ contains
     endif
     eligible = .true.
     fsd_eligible = .true.
+    nl_thermal = th
+    tail = ''
+    if (th) tail = ', thermal'
     nl_etype = lin_etype
     nl_nq = 8
     if (nl_etype /= 361) nl_nq = c3_type_points(nl_etype)
@@ -228,7 +248,7 @@ contains
         tnames = trim(tnames)//'+'//tname
       enddo
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//trim(tnames)//'); '// &
-        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'//trim(tail)
       if (nl_fbar .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: the TYPE=361 sections are F-bar (HECMW_GPU_NL_FBAR=1)'
       if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
       if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
@@ -237,17 +257,17 @@ contains
     if (nl_etype /= 361) then
       write(tname, '(i3)') nl_etype
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE='//tname//'); '// &
-        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'//trim(tail)
       if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
       if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
       return
     endif
     if (nl_fbar) then
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 F-bar); '// &
-        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'//trim(tail)
     else
       if (hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: stiffness assembly and stress update on the device (TYPE=361 B-bar); '// &
-        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'
+        'HECMW_GPU_ASSEMBLY=0 keeps them on the host'//trim(tail)
     endif
     if (n_hyper > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: hyperelastic materials on the device (HECMW_GPU_NL_HYPER=1)'
     if (n_yield > 0 .and. hecMESH%my_rank == 0) write(*,'(a)') '### libfistr_hip: Mohr-Coulomb / Drucker-Prager materials on the device (HECMW_GPU_NL_YIELD=1)'
@@ -501,6 +521,96 @@ contains
     endif
   end function material_covered
 
+  !> What the device's thermal strain serves of a material: isotropic expansion (no MC_ORTHOEXP), MC_THEMOEXP and MC_ISOELASTIC
+  !> constant or with one dependency, and no temperature column in MC_YIELD
+  logical function thermal_material_covered(m)
+    type(tMaterial), intent(in) :: m
+    type(DICT_DATA), pointer :: tbl
+    logical :: miss
+    thermal_material_covered = .false.
+    if (fetch_TableRow(MC_ORTHOEXP, m%dict) > 0) return
+    call fetch_Table(MC_THEMOEXP, m%dict, tbl, miss)
+    if (.not. miss) then
+      if (tbl%ndepends > 1) return
+    endif
+    call fetch_Table(MC_ISOELASTIC, m%dict, tbl, miss)
+    if (.not. miss) then
+      if (tbl%ndepends > 1) return
+      if (tbl%ndepends == 1 .and. is_hyperelastic(m%mtype)) return
+    endif
+    call fetch_Table(MC_YIELD, m%dict, tbl, miss)
+    if (.not. miss) then
+      if (isElastoplastic(m%mtype) .and. getHardenType(m%mtype) == 1) then
+        if (tbl%ndepends > 1) return      ! MULTILINEAR: (yield stress, plastic strain) and nothing more
+      else if (tbl%ndepends > 0) then
+        return
+      endif
+    endif
+    thermal_material_covered = .true.
+  end function thermal_material_covered
+
+  !> fx_nl_set_thermal from M_EXAPNSION, MC_THEMOEXP, MC_ISOELASTIC, ref_temp and the initial condition; last_temp as the host has it
+  subroutine fsd_init_thermal(ctx, hecMESH, fstrSOLID)
+    type(c_ptr), intent(in) :: ctx
+    type(hecmwST_local_mesh), intent(in) :: hecMESH
+    type(fstr_solid), intent(inout), target :: fstrSOLID
+    type(fx_nl_thermal_view) :: tv
+    type(DICT_DATA), pointer :: tbl
+    logical :: miss
+    integer(c_int) :: ierr
+    integer :: i, j, nmat, nrow
+    nmat = size(fstrSOLID%materials)
+    nrow = 1
+    do i = 1, nmat
+      if (fstrSOLID%materials(i)%mtype == -1) cycle
+      nrow = max(nrow, fetch_TableRow(MC_THEMOEXP, fstrSOLID%materials(i)%dict), fetch_TableRow(MC_ISOELASTIC, fstrSOLID%materials(i)%dict))
+    enddo
+    if (allocated(th_alpha)) deallocate(th_alpha, th_atab, th_etab, th_arows, th_erows, th_aptr, th_eptr, th_init)
+    allocate(th_alpha(nmat), th_atab(2, nrow, nmat), th_etab(3, nrow, nmat), th_arows(nmat), th_erows(nmat), th_aptr(nmat), th_eptr(nmat), &
+             th_init(hecMESH%n_node))
+    th_alpha = 0.d0; th_arows = 0; th_erows = 0
+    do i = 1, nmat
+      th_aptr(i) = c_null_ptr; th_eptr(i) = c_null_ptr
+      if (fstrSOLID%materials(i)%mtype == -1) cycle
+      th_alpha(i) = fstrSOLID%materials(i)%variables(M_EXAPNSION)
+      call fetch_Table(MC_THEMOEXP, fstrSOLID%materials(i)%dict, tbl, miss)      ! rows (alpha, T) as the reference holds them
+      if (.not. miss) then
+        if (tbl%ndepends == 1) then
+          th_arows(i) = tbl%tbrow
+          th_atab(1:2, 1:tbl%tbrow, i) = tbl%tbval(1:2, 1:tbl%tbrow)
+          th_aptr(i) = c_loc(th_atab(1, 1, i))
+        else
+          th_alpha(i) = tbl%tbval(1, 1)
+        endif
+      endif
+      call fetch_Table(MC_ISOELASTIC, fstrSOLID%materials(i)%dict, tbl, miss)    ! rows (E, nu, T)
+      if (.not. miss) then
+        if (tbl%ndepends == 1) then
+          th_erows(i) = tbl%tbrow
+          th_etab(1:3, 1:tbl%tbrow, i) = tbl%tbval(1:3, 1:tbl%tbrow)
+          th_eptr(i) = c_loc(th_etab(1, 1, i))
+        endif
+      endif
+    enddo
+    tv%ref_temp = REF_TEMP
+    tv%temp_init = c_null_ptr
+    if (hecMESH%hecmw_flag_initcon == 1) then      ! tt0 of fstr_Update.f90:97-98
+      do j = 1, hecMESH%n_node
+        th_init(j) = hecMESH%node_init_val_item(j)
+      enddo
+      tv%temp_init = c_loc(th_init(1))
+    endif
+    tv%alpha = c_loc(th_alpha(1))
+    tv%alpha_tab = c_loc(th_aptr(1)); tv%alpha_rows = c_loc(th_arows(1))
+    tv%elastic_tab = c_loc(th_eptr(1)); tv%elastic_rows = c_loc(th_erows(1))
+    ierr = fx_nl_set_thermal(ctx, tv)
+    if (ierr /= 0) call fsd_fail('fx_nl_set_thermal')
+    ierr = fx_nl_set_last_temp(ctx, fstrSOLID%last_temp)      ! (fstr_UpdateState at the start of the step has already run)
+    if (ierr /= 0) call fsd_fail('fx_nl_set_last_temp')
+    ierr = fx_nl_set_temperature(ctx, fstrSOLID%temperature)
+    if (ierr /= 0) call fsd_fail('fx_nl_set_temperature')
+  end subroutine fsd_init_thermal
+
   logical function is_hyperelastic(mtype)
     integer, intent(in) :: mtype
     is_hyperelastic = (mtype == NEOHOOKE .or. mtype == MOONEYRIVLIN .or. mtype == ARRUDABOYCE)
@@ -619,6 +729,7 @@ contains
       if (ierr /= 0) call fsd_fail('fx_nl_init_type')
     endif
     deallocate(mats, emat)
+    if (nl_thermal) call fsd_init_thermal(ctx, hecMESH, fstrSOLID)
     if (allocated(b6)) deallocate(b6, bi)
     allocate(b6(6, n_pt), bi(n_pt))
     call fsd_push_state(ctx, fstrSOLID)
@@ -724,6 +835,10 @@ contains
       return
     endif
     if (.not. ready) call fsd_init(hecMESH, hecMAT, fstrSOLID)
+    if (nl_thermal) then      ! fstrSOLID%temperature of this call (fstr_StiffMatrix.f90:72-73)
+      ierr = fx_nl_set_temperature(fxb_context(hecMESH), fstrSOLID%temperature)
+      if (ierr /= 0) call fsd_fail('fx_nl_set_temperature')
+    endif
     ierr = fx_nl_stiffness_at(fxb_context(hecMESH), fstrSOLID%unode, fstrSOLID%dunode, ms)
     if (ierr /= 0) call fsd_fail('fx_nl_stiffness_at')
     fxb_matrix_on_device = .true.       ! from here to the solve: hecmw_mat_ass_bc records, hecmw_solve uses the resident matrix
@@ -740,6 +855,10 @@ contains
     if (.not. ready) then
       if (lin_ready) fsd_update_newton = fsd_update_newton_linear(hecMESH, fstrSOLID)
       return
+    endif
+    if (nl_thermal) then      ! tt of fstr_Update.f90:101; the device's last_temp follows the host's through fx_nl_commit
+      ierr = fx_nl_set_temperature(fxb_context(hecMESH), fstrSOLID%temperature)
+      if (ierr /= 0) call fsd_fail('fx_nl_set_temperature')
     endif
     ierr = fx_nl_update_at(fxb_context(hecMESH), fstrSOLID%dunode, fstrSOLID%QFORCE, ms)
     if (ierr /= 0) call fsd_fail('fx_nl_update_at')
@@ -890,6 +1009,9 @@ contains
     ctx = fxb_context(hecMESH)
     ierr = fx_nl_commit(ctx)      ! unode += dunode is the host's (fstr_Newton :156-158); the device does the same on its copy
     if (ierr /= 0) call fsd_fail('fx_nl_commit')
+    if (associated(fstrSOLID%temperature)) then      ! the host's copy too (fstr_Update.f90:308-312): fstr_ass_load reads it for the thermal load
+      fstrSOLID%last_temp(1:hecMESH%n_node) = fstrSOLID%temperature(1:hecMESH%n_node)
+    endif
     allocate(s6(6, n_pt), pl(n_pt), fs(n_pt))
     sv%stress = c_loc(s6(1,1)); sv%strain = c_loc(b6(1,1)); sv%stress_bak = c_null_ptr; sv%strain_bak = c_null_ptr
     sv%plstrain = c_loc(pl(1)); sv%fstat = c_loc(fs(1)); sv%istat = c_loc(bi(1))

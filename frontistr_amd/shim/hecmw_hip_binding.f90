@@ -22,11 +22,16 @@ module hecmw_hip_binding
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
   public :: fx_mesh_view, fx_material_view, fx_nl_state_view, fx_elem_group
   public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_init_type, fx_nl_init_groups, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
-            fx_nl_set_state, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
+            fx_nl_set_state, fx_nl_thermal_view, fx_nl_set_thermal, fx_nl_set_temperature, fx_nl_set_last_temp, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
             fx_assemble_c3, fx_update_c3_linear, fx_assemble_groups, fx_update_groups_linear, fx_update_groups_linear_prepare
   public :: fxb_values_owner, fxb_values_addr
   public :: fxb_matrix_on_device, fxb_defer_bc, fxb_solve_device_matrix, FX_UP_PROFILE
   public :: fxb_context, fxb_views, fxb_ensure_transport, fxb_error_text, fxb_on_gpu_path, fx_get_stats
+
+  type, bind(C) :: fx_nl_thermal_view      ! include/fistr_hip.h: thermal strain in the nonlinear static loop
+    real(c_double) :: ref_temp
+    type(c_ptr) :: temp_init, alpha, alpha_tab, alpha_rows, elastic_tab, elastic_rows
+  end type fx_nl_thermal_view
 
   type, bind(C) :: fx_matrix_view
     integer(c_int32_t) :: N, NP, NPL, NPU, NDOF
@@ -242,6 +247,21 @@ module hecmw_hip_binding
       real(c_double) :: dunode(*), qforce(*)
       real(c_float) :: ms
     end function fx_nl_update_at
+    integer(c_int) function fx_nl_set_thermal(ctx, thermal) bind(C, name='fx_nl_set_thermal')
+      import :: c_int, c_ptr, fx_nl_thermal_view
+      type(c_ptr), value :: ctx
+      type(fx_nl_thermal_view) :: thermal
+    end function fx_nl_set_thermal
+    integer(c_int) function fx_nl_set_temperature(ctx, temp) bind(C, name='fx_nl_set_temperature')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx
+      real(c_double) :: temp(*)
+    end function fx_nl_set_temperature
+    integer(c_int) function fx_nl_set_last_temp(ctx, temp) bind(C, name='fx_nl_set_last_temp')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx
+      real(c_double) :: temp(*)
+    end function fx_nl_set_last_temp
     integer(c_int) function fx_nl_commit(ctx) bind(C, name='fx_nl_commit')
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx

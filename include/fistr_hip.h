@@ -498,6 +498,41 @@ int fx_newton_substep(fx_context *ctx, double factor0, double factor1, int32_t n
  * (.not. fstrPR%nlgeom, :50-51, :107): one pass without a convergence test. */
 int fx_nl_set_step_control(fx_context *ctx, double maxres, int is_linear);
 
+/* ---- thermal strain in the nonlinear static loop (!TEMPERATURE in an NLSTATIC deck) ----
+ * The thermal branches of Update_C3D8Bbar (static_LIB_C3D8.f90:309-455), UPDATE_C3 (static_LIB_3d.f90:602-757) and Update_C3D8Fbar
+ * (static_LIB_Fbar.f90:487-651): EPSTH(1:3) = alp (ttc - ref_temp) - alp0 (tt0 - ref_temp) with ttc = H . temperature and
+ * tt0 = H . last_temp for an element of an elastoplastic material, H . temp_init for every other (fstr_Update.f90:92-102).
+ * Isotropic expansion: one constant per material (M_EXAPNSION) or a table over temperature (MC_THEMOEXP); E and nu constant or a
+ * table over temperature (MC_ISOELASTIC).  A table has one dependency, rows in ascending temperature, and is looked up as
+ * fetch_TableData does (ttable.f90:282-354).  Not served: MC_ORTHOEXP, section orientation, a temperature column in the yield
+ * table, NORTON and viscoelastic materials.
+ *
+ * fx_nl_set_thermal: after any fx_nl_init*.  Sets last_temp = temp_init (fstr_solve_NLGEOM.f90:53-57) and the temperature to temp_init
+ *   or, without one, to ref_temp (fstr_setup.f90:780) until fx_nl_set_temperature gives another, and switches the thermal
+ *   variants of the element kernels on; thermal = NULL switches them off again.  FX_ERROR_UNSUPPORTED, context untouched: a table
+ *   whose temperatures are not strictly ascending, an elastic_tab on a hyperelastic material.
+ * fx_nl_set_temperature: fstrSOLID%temperature (n_node) of the coming sub-step or call; NULL while thermal is on: FX_ERROR_RUNTIME.
+ * With thermal on, fx_nl_stiffness* / fx_nl_update* / fx_nl_element_* read that temperature; fx_nl_commit copies it to last_temp
+ * (fstr_UpdateState, fstr_Update.f90:308-312); fx_nl_snapshot saves and restores last_temp with the point history
+ * (fstr_Cutback.f90:127, :173); fx_nl_begin_substep and fx_newton_substep add the thermal load of fstr_ass_load.f90:287-428 to
+ * the first right-hand side: TLOAD_C3D8Bbar for every 361 element whatever its formulation, TLOAD_C3 for the other types, on
+ * coord + unode with TEMP0 = last_temp for every element.  (Elements of a hyperelastic material add no thermal load: the vector only
+ * steers the first correction of a sub-step.)  fx_nl_stiffness_at / fx_nl_update_at add no load. */
+typedef struct fx_nl_thermal_view {
+  double ref_temp;            /* !REFTEMP */
+  const double *temp_init;    /* n_node: !INITIAL CONDITION, TYPE=TEMPERATURE; NULL = 0 */
+  const double *alpha;        /* n_mat: M_EXAPNSION */
+  const double *const *alpha_tab;   /* NULL, or n_mat pointers (each may be NULL): rows (alpha, T) */
+  const int32_t *alpha_rows;        /* rows of each alpha_tab (read where alpha_tab[m] is not NULL) */
+  const double *const *elastic_tab; /* NULL, or n_mat pointers (each may be NULL): rows (E, nu, T) */
+  const int32_t *elastic_rows;
+} fx_nl_thermal_view;
+int fx_nl_set_thermal(fx_context *ctx, const fx_nl_thermal_view *thermal);
+int fx_nl_set_temperature(fx_context *ctx, const double *temp);
+/* last_temp (n_node), for tests and restart; FX_ERROR_RUNTIME while thermal is off */
+int fx_nl_get_last_temp(fx_context *ctx, double *last_temp);
+int fx_nl_set_last_temp(fx_context *ctx, const double *last_temp);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------- */
 /* 128-byte ncclUniqueId made by rank 0 and broadcast by the host side
  * (torch.distributed / MPI); then every rank calls fx_comm_init. */
