@@ -8,7 +8,9 @@ fallbacks; the refusals; the device error word.
 
 Meshes: hyper_ref.gpu_mesh (distorted, at 361 with a collapsed hexahedron so that the `dup` path runs).  Tolerance: the project's
 nonlinear 1e-11 of the largest entry of the compared array; tests/test_yield_ref.py shows that the inputs (yield_ref.gpu_case)
-determine the restated numbers to 1e-12 on that scale and keep every point off every branch edge; istat is compared exactly."""
+determine the restated numbers to 1e-12 on that scale and keep every point off every branch edge; istat is compared exactly.  The
+edges themselves -- ties of principal stresses, |f| beside tol, the `dlambda < 0` reset, the apex, sin 3 theta = +-1 -- are run by
+tests/test_gpu_point_edges.py on trial stresses chosen to the bit (tests/point_ref.py, tests/test_point_ref.py)."""
 import json
 import os
 import subprocess

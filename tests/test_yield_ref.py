@@ -15,6 +15,8 @@ program, and the conditions under which the GPU comparisons at 1e-11 mean someth
     | |f| - tol | >= 10 tol, no return through the `dlambda < 0` reset, and for Mohr-Coulomb |sin 3 theta| <= 0.95 (trial and
     returned stress) with principal stresses separated by 1e-6 of the largest; at least a quarter of the points plastic and a tenth
     elastic.  No point is left out.
+    (These inputs stay off the edges on purpose.  The edges are run separately, on trial stresses that sit exactly on them, where
+    the branch is the same in every arithmetic: tests/point_ref.py holds the cases, tests/test_point_ref.py their conditions.)
 """
 import json
 import os

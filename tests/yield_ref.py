@@ -65,8 +65,9 @@ def is_yield(mat):
 
 
 # ---- lib/utilities/utilities.f90 ------------------------------------------------------------------------------------------------------
-def eigen3(tensor):
-    """eigen3 :107-201 -> eigval (3), princ (3, 3) with the principal vectors as columns.  Only the upper triangle of btens is read."""
+def eigen3(tensor, info=None):
+    """eigen3 :107-201 -> eigval (3), princ (3, 3) with the principal vectors as columns.  Only the upper triangle of btens is read.
+    info (a dict, optional) receives the number of rotations made and of those skipped because the off-diagonal term is negligible."""
     t = np.asarray(tensor)
     dt = t.dtype
     n = dt.type
@@ -77,6 +78,8 @@ def eigen3(tensor):
     b[2, 0] = b[0, 2] = t[5]
     princ = np.eye(3, dtype=dt)
     ev = np.array([b[0, 0], b[1, 1], b[2, 2]], dtype=dt)
+    if info is not None:
+        info.update(rotated=0, skipped=0)
     for _ in range(50):
         fsum = abs(b[0, 1]) + abs(b[0, 2]) + abs(b[1, 2])
         if fsum < n(1.0e-10):
@@ -84,7 +87,10 @@ def eigen3(tensor):
         for ip in range(2):
             for iq in range(ip + 1, 3):
                 od = n(100) * abs(b[ip, iq])
-                if od + abs(ev[ip]) != abs(ev[ip]) and od + abs(ev[iq]) != abs(ev[iq]):
+                rotate = od + abs(ev[ip]) != abs(ev[ip]) and od + abs(ev[iq]) != abs(ev[iq])
+                if info is not None:
+                    info["rotated" if rotate else "skipped"] += 1
+                if rotate:
                     hd = ev[iq] - ev[ip]
                     if abs(hd) + od == abs(hd):
                         tt = b[ip, iq] / hd
@@ -158,9 +164,16 @@ def cal_yield_func(mat, stress, pstrain):
     return np.sqrt(J2) + p3 * J1 - eqvs * p4
 
 
-def backward_euler(mat, stress, plstrain, istat, fstat1, info=None):
+def backward_euler(mat, stress, plstrain, istat, fstat1, info=None, *, maxiter=MAXITER, first_of_ties=True, mm_rule=True,
+                   reset_istat=0, exits_write_fstat=False, zeroing=True):
     """BackwardEuler :351-561, yield types 1 and 2 -> (stress, istat, fstat(1)).  info (a dict, optional) receives what the margin
-    checks read: f of the trial stress, whether the return ended through the `dlambda < 0` reset, sin 3 theta and the principal stresses."""
+    checks read: f of the trial stress, whether the return ended through the `dlambda < 0` reset, sin 3 theta and the principal
+    stresses; the exit taken (`band`: |f| < tol, `elastic`: f < 0, `reset`, `converged`, `exhausted`: the loop ran out), the number of
+    iterations begun, and maxp / minp / mm (0-based) of the Mohr-Coulomb return.
+    The keyword parameters default to what the reference does; any other value is a deliberately wrong point function, for the
+    check that the edge cases of tests/point_ref.py tell the two apart: maxiter (:361); first_of_ties (maxloc / minloc :481-482, False:
+    the last of ties); mm_rule (:483-485, False: the index that is neither maxp nor minp); reset_istat (:497 / :542 set 0);
+    exits_write_fstat (:386-393 leave fstat alone, True: they store plstrain); zeroing (:476-478)."""
     s = np.array(stress)
     dt = s.dtype
     n = dt.type
@@ -168,11 +181,12 @@ def backward_euler(mat, stress, plstrain, istat, fstat1, info=None):
     plstrain = n(plstrain)
     f = cal_yield_func(mat, s, plstrain)
     if info is not None:
-        info.update(f=float(f), reset=False)
-    if abs(f) < n(TOL):
-        return s, 1, fstat1
-    if f < 0:
-        return s, 0, fstat1
+        info.update(f=float(f), reset=False, iterations=0)
+    if abs(f) < n(TOL) or f < 0:
+        ist = 1 if abs(f) < n(TOL) else 0
+        if info is not None:
+            info["exit"] = "band" if ist else "elastic"
+        return s, ist, (plstrain if exits_write_fstat else fstat1)
     istat = 1
     J1 = (s[0] + s[1] + s[2]) / n(3)                      # :402, the MEAN stress from here on
     d = np.array([s[0] - J1, s[1] - J1, s[2] - J1, s[3], s[4], s[5]], dtype=dt)
@@ -180,37 +194,43 @@ def backward_euler(mat, stress, plstrain, istat, fstat1, info=None):
     G = E / (n(2) * (n(1) + nu))
     K = E / (n(3) * (n(1) - n(2) * nu))
     dlambda, pstrain = n(0), plstrain
+    how, it = "exhausted", 0
     if mat.kind == MOHR:
         J3 = _j3(d)
         if info is not None:
             info["sin3"] = float(sin3theta(J2, J3))
         sita = _lode(J2, J3)
         sf, cf, ss = np.sin(p3), np.cos(p3), np.sin(sita)
-        s[np.abs(s) < n(1.0e-10)] = n(0)                  # :476-478
-        prn, prj = eigen3(s)
-        if info is not None:
-            info["principal"] = [float(v) for v in prn]
-        maxp, minp = int(np.argmax(prn)), int(np.argmin(prn))      # the first of ties, as maxloc / minloc
+        if zeroing:
+            s[np.abs(s) < n(1.0e-10)] = n(0)              # :476-478
+        prn, prj = eigen3(s, info)
+        if first_of_ties:
+            maxp, minp = int(np.argmax(prn)), int(np.argmin(prn))  # the first of ties, as maxloc / minloc
+        else:
+            maxp, minp = 2 - int(np.argmax(prn[::-1])), 2 - int(np.argmin(prn[::-1]))
         mm = 0
         if maxp == 0 or minp == 0:
             mm = 1
         if maxp == 1 or minp == 1:
             mm = 2
+        if not mm_rule and maxp != minp:
+            mm = 3 - maxp - minp
+        if info is not None:
+            info.update(principal=[float(v) for v in prn], maxp=maxp, minp=minp, mm=mm)
         smax, smin = prn[maxp], prn[minp]
         stiff = n(4) * G * (n(1) + sf * ss / n(3)) + n(4) * K * sf * ss
-        for _ in range(MAXITER):
+        for it in range(1, maxiter + 1):
             dd = stiff + n(4) * Hd * cf * cf                # H at the sub-step's first plastic strain (:488-490; linear law: a constant)
             dlambda = dlambda + f / dd
             if n(2) * dlambda * cf < 0:
                 if cf == 0:
                     raise MathError("Math error in return mapping")
-                dlambda, istat = n(0), 0
-                if info is not None:
-                    info["reset"] = True
+                dlambda, istat, how = n(0), reset_istat, "reset"
                 break
             yd = c + Hd * (pstrain + n(2) * dlambda * cf)
             f = smax - smin + (smax + smin) * sf - stiff * dlambda - n(2) * yd * cf
             if abs(f) < n(TOL):
+                how = "converged"
                 break
         pstrain = pstrain + n(2) * dlambda * cf
         prn[maxp] = prn[maxp] - (n(2) * G * (n(1) + sf / n(3)) + n(2) * K * sf) * dlambda
@@ -220,24 +240,25 @@ def backward_euler(mat, stress, plstrain, istat, fstat1, info=None):
         s = np.array([m[0, 0], m[1, 1], m[2, 2], m[0, 1], m[1, 2], m[2, 0]], dtype=dt)
     else:
         yd = np.sqrt(J2)                                   # cal_equivalent_stress :158-159
-        for _ in range(MAXITER):
+        for it in range(1, maxiter + 1):
             dd = G + K * p3 * p3 + Hd * p4 * p4
             dlambda = dlambda + f / dd
             if p4 * dlambda < 0:
                 if p4 == 0:
                     raise MathError("Math error in return mapping")
-                dlambda, istat = n(0), 0
-                if info is not None:
-                    info["reset"] = True
+                dlambda, istat, how = n(0), reset_istat, "reset"
                 break
             f = c + Hd * (pstrain + p4 * dlambda)
             f = yd - G * dlambda + p3 * (J1 - K * p3 * dlambda) - p4 * f
             if abs(f) < n(TOL) * n(TOL):
+                how = "converged"
                 break
         pstrain = pstrain + p4 * dlambda
         d = (n(1) - G * dlambda / yd) * d
         J1 = J1 - K * p3 * dlambda
         s = np.array([d[0] + J1, d[1] + J1, d[2] + J1, d[3], d[4], d[5]], dtype=dt)
+    if info is not None:
+        info.update(reset=how == "reset", exit=how, iterations=it, residual=float(f))
     return s, istat, pstrain
 
 
