@@ -215,6 +215,8 @@ static int assembly_error(int32_t herr) {
   // the `stop` statements of the F-bar hexahedron (FX_FERR_*, fx_nonlinear_fbar.h)
   if (herr == 6) { g_fx_error = "Error in Update_C3D8Fbar: too small element volume (static_LIB_Fbar.f90:121, :456)"; return FX_ERROR_RUNTIME; }
   if (herr == 7) { g_fx_error = "Error in Update_C3D8Fbar: too small average jacob (static_LIB_Fbar.f90:115, :450)"; return FX_ERROR_RUNTIME; }
+  // the creep iteration of a NORTON point (FX_CERR_CREEP, fx_visco.h)
+  if (herr == 8) { g_fx_error = "creep: the iteration of update_iso_creep on the consistency parameter did not end within 100 passes or left the finite numbers (creep.f90:185-195; the reference's loop has no bound)"; return FX_ERROR_RUNTIME; }
   return 0;
 }
 // hecmw_mat_clear (fstr_StiffMatrix.f90:40)

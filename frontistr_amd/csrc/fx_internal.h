@@ -177,7 +177,10 @@ struct NlMat {
   int32_t plastic;          // non-zero: elastoplastic (state history, the latch) -- 1 Mises, FX_MAT_MOHR, FX_MAT_DRUCKER; 0: ELASTIC and hyperelastic
   int32_t harden;           // Mises: hardening law 0..3 (0 for the other two yield functions); group 3: the kind, FX_MAT_MOONEY or FX_MAT_ARRUDA
   int32_t group;            // compile-time group of the element kernels: 0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic (total Lagrange),
-                            // 4..6: the three flags again for Mohr-Coulomb / Drucker-Prager (nl_group_flag, nl_group_yield)
+                            // 4..6: the three flags again for Mohr-Coulomb / Drucker-Prager (nl_group_flag, nl_group_yield),
+                            // 7, 8: INFINITE / TOTALLAG of a viscoelastic material (fx_visco.h: there pl = mu_0, gfac, tincr and
+                            // tab = ntab rows (exp_n, dq_n), rewritten by fx_nl_set_time), 9: UPDATELAG of a NORTON material
+                            // (pl = aa, n, tincr, rewritten by fx_nl_set_time)
   int32_t ntab;
   const double *tab;  // device, ntab rows (yield stress, plastic strain)
   double pl4;         // M_PLCONST4: xi of Drucker-Prager
@@ -224,7 +227,7 @@ struct UpdStage {
 
 // One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
 // conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
-constexpr int NL_GROUPS = 7;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
+constexpr int NL_GROUPS = 10;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
 struct NlPart {
   int32_t etype = 361;                // 361 (B-bar, or F-bar: fbar), 341, 342, 351, 352 or 362
   bool fbar = false;                  // a 361 part of F-bar elements (elemopt 4): k_nl_stiffness_fbar / k_nl_update_fbar
@@ -235,7 +238,7 @@ struct NlPart {
   int32_t *conn = nullptr;            // device, nn * n_elem
   int32_t *emat = nullptr;            // device, 1-based material id per element; null with one material
   ElemColors colors;                  // order: elements grouped by NLGEOM flag, then by colour; pos: scatter position map
-  std::vector<int32_t> grp_off[NL_GROUPS];  // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager): positions of its colours in order (+ end)
+  std::vector<int32_t> grp_off[NL_GROUPS];  // per group (0 INFINITE, 1 TOTALLAG, 2 UPDATELAG, 3 hyperelastic, 4..6 Mohr-Coulomb / Drucker-Prager, 7, 8 viscoelastic, 9 NORTON): positions of its colours in order (+ end)
   std::vector<int32_t> dup_off[NL_GROUPS];  // per group: its collapsed elements' colours in colors.dup (+ end); empty = none
   bool scatter_atomic = false;        // colouring failed (a node in more than 64 elements) or FX_ASM_ATOMIC=1: one range per group, fp64 atomics
   int32_t n_dup = 0;                  // collapsed elements taken out of the colours (colors.dup)
@@ -263,6 +266,7 @@ struct NlDev {
   std::vector<NlPart> parts;          // in the order given; the per-point arrays and the element outputs hold them one after the other
   bool first_write = false;           // every part's map carries first-write flags in the launch order of ALL parts and every block is covered: no clearing
   bool has_yield = false;             // a Mohr-Coulomb or Drucker-Prager section: the stress update reports through the error word too
+  bool has_creep = false;             // a NORTON section: so does its creep iteration (FX_CERR_CREEP)
   bool has_fbar = false;              // an F-bar part: so does its stress update (`too small element volume`, `too small average jacob`)
   int32_t n_mat = 1;
   NlMat *mats = nullptr;              // device, n_mat entries (several sections); null with one material
@@ -285,6 +289,14 @@ struct NlDev {
   double maxres = 1.0e10;  // step_ctrl%maxres (m_step.f90:78): Newton gives up when rres exceeds it
   bool is_linear = false;   // fstr_Newton's isLinear: one pass, no convergence test
   int latch = 0;  // MatlMatrix's saved `flag` (calMatMatrix.f90:39): set by the first elastoplastic stress update
+  // Time of the coming sub-step or call (fx_nl_set_time): ctime and tincr as fstr_Newton hands them to fstr_StiffMatrix,
+  // fstr_UpdateNewton and fstr_UpdateState (fstr_solve_NonLinear.f90:74, :100, :162); (0, 0) after every fx_nl_init*
+  double time = 0.0, tincr = 0.0;
+  // History of the viscoelastic and NORTON points (fx_visco.h), allocated only where such a material is present: hist_w components per point,
+  // component-major over all points of the context (hist[k * n_pt + p]); hist_bk: fx_nl_snapshot's copy
+  int32_t hist_w = 0;
+  double *hist = nullptr, *hist_bk = nullptr;
+  std::vector<std::vector<double>> prony;  // per material: its rows (g, tau) as given, or (A, n, m) of a NORTON material; empty for another kind
   // fstr_cutback_save / _load (fstr_Cutback.f90:108-198): a device-side copy of the quadrature-point history to roll back to when a
   // sub-step of an automatic incrementation does not converge (fx_nl_snapshot); allocated at the first save
   NlPartState bk;

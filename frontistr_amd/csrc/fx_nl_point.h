@@ -9,11 +9,13 @@
 //                      STF_C3 (static_LIB_3d.f90:120-199)
 //   nl_node_B          strain-displacement block of one node (B-bar correction and BL1 included)
 // with MatlMatrix (calMatMatrix.f90:28-113), calElastoPlasticMatrix (Elastoplastic.f90:16-117), BackwardEuler (:351-558), the
-// hardening laws and the table lookups underneath.  Hyperelastic points: fx_hyperelastic.h; Mohr-Coulomb / Drucker-Prager: fx_yield.h.
+// hardening laws and the table lookups underneath.  Hyperelastic points: fx_hyperelastic.h; Mohr-Coulomb / Drucker-Prager: fx_yield.h;
+// viscoelastic points: fx_visco.h.
 #pragma once
 #include "fx_assemble.h"
 #include "fx_hyperelastic.h"
 #include "fx_yield.h"
+#include "fx_visco.h"
 
 // `real(x)` of a double-precision x without KIND: default real.  UPDATE_C3's UPDATELAG branch rounds the stress increment so
 // (static_LIB_3d.f90:718); Update_C3D8Bbar does not.
@@ -70,7 +72,7 @@ __device__ __forceinline__ double nl_harden_coeff(const NlMat &m, double p) {
 template <int Y = 0>
 __device__ __forceinline__ void nl_backward_euler(const NlMat &m, double (&s)[6], double plstrain, int32_t &istat, double &fstat1,
                                                   int32_t *err = nullptr) {
-  if constexpr (Y != 0) {
+  if constexpr (Y == 1) {
     yield_backward_euler(m.plastic, m.E, m.nu, m.pl[0], m.pl[1], m.pl[2], m.pl4, s, plstrain, istat, fstat1, err);
   } else {
     const double tol = 1.0e-3;
@@ -138,12 +140,16 @@ __device__ __forceinline__ void nl_thermal_matrix(const ThermalDev &th, NlMat &m
 __device__ __forceinline__ constexpr int sym21(int i, int j) { return (i <= j) ? (i * (13 - i)) / 2 + (j - i) : (j * (13 - j)) / 2 + (i - j); }
 
 // material matrix of one quadrature point, as STF_C3D8Bbar (:90-101) and STF_C3 (static_LIB_3d.f90:108-119) use it: MatlMatrix with
-// the latch, minus GEOMAT_C3 for the updated-Lagrange flag.  Y != 0: the flow vector of Mohr-Coulomb / Drucker-Prager (fx_yield.h).
+// the latch, minus GEOMAT_C3 for the updated-Lagrange flag.  Y == 1: the flow vector of Mohr-Coulomb / Drucker-Prager (fx_yield.h);
+// Y == 2: calViscoelasticMatrix (fx_visco.h), which MatlMatrix takes before it looks at the latch.  Y == 3: NORTON -- iso_creep
+// (calMatMatrix.f90:100-107) while the latch is clear, with gauss%plstrain in `creep_dg`; the elastic matrix at dtime == 0, at an
+// all-zero stress (creep.f90:40) and, as for every material but the viscoelastic one, once the latch is set.
 template <int Y = 0>
 __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int flag, const double (&s)[6], int istat, double fstat1,
-                                                double (&Dm)[21], int32_t *err = nullptr) {
+                                                double (&Dm)[21], int32_t *err = nullptr, double creep_dg = 0.0) {
   double D11, D12, D44;
-  elastic_constants(m.E, m.nu, D11, D12, D44);
+  if constexpr (Y == 2) visco_constants(m, D11, D12, D44);
+  else elastic_constants(m.E, m.nu, D11, D12, D44);
 #pragma unroll
   for (int k = 0; k < 21; k++) Dm[k] = 0.0;
   Dm[sym21(0, 0)] = D11; Dm[sym21(1, 1)] = D11; Dm[sym21(2, 2)] = D11;
@@ -155,7 +161,7 @@ __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int f
     const double J2 = 0.5 * (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + (dv[3] * dv[3] + dv[4] * dv[4] + dv[5] * dv[5]);
     double a[6];
     bool flow = true;
-    if constexpr (Y != 0) {
+    if constexpr (Y == 1) {
       flow = yield_flow_vector(m.plastic, m.pl[2], dv, J2, a, err);
     } else {
       const double q = 2.0 * sqrt(J2), r3 = sqrt(3.0);
@@ -174,6 +180,10 @@ __device__ __forceinline__ void nl_point_matrix(const NlMat &m, int latch, int f
 #pragma unroll
         for (int j = i; j < 6; j++) Dm[sym21(i, j)] -= da[i] * da[j] / dum;
     }
+  }
+  if constexpr (Y == 3) {
+    if (!latch && m.pl[2] != 0.0 && !(s[0] == 0.0 && s[1] == 0.0 && s[2] == 0.0 && s[3] == 0.0 && s[4] == 0.0 && s[5] == 0.0))
+      norton_tangent(m, s, creep_dg, Dm);
   }
   if (flag == 2) {  // GEOMAT_C3
     Dm[sym21(0, 0)] -= 2.0 * s[0]; Dm[sym21(0, 3)] -= s[3]; Dm[sym21(0, 5)] -= s[5];
@@ -210,8 +220,11 @@ __device__ __forceinline__ void nl_node_B(const double *g, const double *h, cons
 // Groups 4, 5, 6: the three flags again for a Mohr-Coulomb or Drucker-Prager material (fx_yield.h; which of the two is a run-time
 // branch on NlMat::plastic).  The yield family is a compile-time parameter so that the instantiations 0..3 stay what they were:
 // k_nl_stiffness<1> sits at 512 VGPRs with scratch and has no register to give to another branch.  NL_GROUPS (fx_internal.h) counts them.
-__device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : (G >= 4 ? G - 4 : G); }
-__device__ __forceinline__ constexpr int nl_group_yield(int G) { return G >= 4 ? 1 : 0; }
+// Groups 7, 8: INFINITE and TOTALLAG for a viscoelastic material (fx_visco.h), compile-time for the same reason; nl_group_yield
+// names the point functions of a group: 0 ELASTIC / Mises, 1 Mohr-Coulomb / Drucker-Prager, 2 viscoelastic, 3 NORTON.
+// Group 9: UPDATELAG for a NORTON material.
+__host__ __device__ __forceinline__ constexpr int nl_group_flag(int G) { return G == 3 ? 1 : (G >= 7 ? G - 7 : (G >= 4 ? G - 4 : G)); }
+__device__ __forceinline__ constexpr int nl_group_yield(int G) { return G == 9 ? 3 : (G >= 7 ? 2 : (G >= 4 ? 1 : 0)); }
 
 // One quadrature point's share of the 3x3 block (a, b) of STF_C3's element matrix, added to K: Ba^T D Bb w with BL0 (+ BL1 for
 // TOTALLAG, static_LIB_3d.f90:120-162) and, for NLGEOM != 0, the initial-stress matrix BN^T S BN (:170-199), which is

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                            int kout_pos, const double *__restrict__ strain, ThermalDev th) {
+                                                            int kout_pos, const double *__restrict__ strain, ThermalDev th, NlHist hs) {
   constexpr int NLGEOM = nl_group_flag(G);
   // positions [e0, n_elem) of elem_list: elements of one NLGEOM group; atomic == 0: they are of one colour (no shared node),
   // scattered without atomics, see k_assemble_c3d8.  mats / emat: several sections, element e uses mats[emat[e] - 1].
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_stiffness(int32_t n_elem, cons
     } else {
       if constexpr (TH != 0)
         nl_thermal_matrix<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return nod[j]; }, [&](int j) { return hex8_shape_func(j, xi, et, ze); });
-      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr);
+      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0, m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr, nl_group_creep(G) ? hs.plstrain[(size_t)8 * elem + lane8] : 0.0);
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) F[k] = 0.0;
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
                                                          double *__restrict__ qforce, double *__restrict__ qf_out,
                                                          const int32_t *__restrict__ elem_list, int32_t e0,
                                                          const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                         int32_t *__restrict__ err, ThermalDev th) {
+                                                         int32_t *__restrict__ err, ThermalDev th, NlHist hs) {
   // positions [e0, n_elem) of elem_list: the elements of this group; mats / emat: several sections
   constexpr int NLGEOM = nl_group_flag(G);
   const int LX = threadIdx.x & 7;
@@ -347,6 +347,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
   double ds[6];
   if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:387-390)
     hyper_stress(nl_hyper_kind(m), m.pl, de, ds);
+  } else if constexpr (nl_group_visco(G)) {  // StressUpdate -> UpdateViscoelastic under tincr /= 0, else matmul(D, dstrain)
+    nl_visco_stress<NLGEOM>(m, de, hs, (size_t)8 * elem + LX, active, ds);
   } else {
     double D11, D12, D44;
     elastic_constants(m.E, m.nu, D11, D12, D44);
@@ -385,6 +387,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update(int32_t n_elem, const d
     for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
   }
   if constexpr (TH != 0) { eg[0] += eth; eg[1] += eth; eg[2] += eth; }  // the stored strain is the total one (:363, :389-401, :412)
+  if constexpr (nl_group_creep(G)) nl_creep_stress(m, sg, hs, fstat, gp, active, active ? err : nullptr);  // NORTON behind the UPDATELAG stress
   if (G != 3 && m.plastic) {
     int32_t ist = istat[gp];
     double fs = fstat[gp];

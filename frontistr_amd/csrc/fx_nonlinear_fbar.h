@@ -115,7 +115,7 @@ __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
     const int32_t *__restrict__ indexU, const int32_t *__restrict__ itemU, double *__restrict__ D, double *__restrict__ AL,
     double *__restrict__ AU, double *__restrict__ Kout, int32_t *__restrict__ err, const int32_t *__restrict__ elem_list, int32_t e0,
     const int32_t *__restrict__ pos_map, int atomic, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat, int kout_pos,
-    const double *__restrict__ strain, ThermalDev th) {
+    const double *__restrict__ strain, ThermalDev th, NlHist hs) {
   // arguments and element lists as k_nl_stiffness
   constexpr int NLGEOM = nl_group_flag(G);
   static_assert(NLGEOM != 2, "F-bar: INFINITE and TOTALLAG only");
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(FXF_BLOCK) void k_nl_stiffness_fbar(
         nl_thermal_matrix<8>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return conn[(size_t)8 * elem + j]; },
                              [&](int j) { return hex8_shape_func(j, xi, et, ze); });
       nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[(size_t)8 * elem + lane8] : 0,
-                                         m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr);
+                                         m.plastic ? fstat[(size_t)8 * elem + lane8] : 0.0, Dm, active ? err : nullptr, nl_group_creep(G) ? hs.plstrain[(size_t)8 * elem + lane8] : 0.0);
     }
 #pragma unroll
     for (int k = 0; k < 21; k++) dsh[21 * lane8 + k] = Dm[k];
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
     const double *__restrict__ stress_bak, const double *__restrict__ strain_bak, const double *__restrict__ plstrain,
     double *__restrict__ fstat, int32_t *__restrict__ istat, double *__restrict__ qforce, double *__restrict__ qf_out,
     const int32_t *__restrict__ elem_list, int32_t e0, const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-    int32_t *__restrict__ err, ThermalDev th) {
+    int32_t *__restrict__ err, ThermalDev th, NlHist hs) {
   constexpr int NLGEOM = nl_group_flag(G);
   static_assert(NLGEOM != 2, "F-bar: INFINITE and TOTALLAG only");
   const int LX = threadIdx.x & 7;
@@ -500,6 +500,8 @@ __global__ __launch_bounds__(FXN_BLOCK) void k_nl_update_fbar(
   double sg[6];
   if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:567-570)
     hyper_stress(nl_hyper_kind(m), m.pl, de, sg);
+  } else if constexpr (nl_group_visco(G)) {  // StressUpdate -> UpdateViscoelastic under tincr /= 0, else matmul(D, dstrain)
+    nl_visco_stress<NLGEOM>(m, de, hs, (size_t)8 * elem + LX, active, sg);
   } else {
     double D11, D12, D44;
     elastic_constants(m.E, m.nu, D11, D12, D44);

@@ -28,7 +28,7 @@ static void nl_free(fx_context *c) {
     for_each_point_array([](size_t, auto *&a) { dev_free(a); return 0; }, *s);
   dev_free(n.unode); dev_free(n.dunode); dev_free(n.qforce); dev_free(n.GL);
   dev_free(n.bc_flag); dev_free(n.bc_val); dev_free(n.bc_node); dev_free(n.bc_dof); dev_free(n.bc_v); dev_free(n.err);
-  dev_free(n.mats);
+  dev_free(n.mats); dev_free(n.hist); dev_free(n.hist_bk);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
   nl_thermal_free(n.th);
   n = NlDev();
@@ -47,9 +47,34 @@ static int nl_check_material(const char *who, const fx_material_view *mat) {
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "Arruda-Boyce material with plconst[1] = 0 (locking stretch lambda_m)");
     return 0;
   }
+  if (mat->plastic == FX_MAT_VISCO) {  // harden, plconst are not read; tab / ntab: the Prony rows (g, tau)
+    if (mat->nlgeom != 0 && mat->nlgeom != 1)
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                     "a viscoelastic material has nlgeom 0 (INFINITE) or 1 (TOTALLAG): the card reaches no other flag "
+                     "(fstr_ctrl_material.f90:277-279), and UPDATELAG is not on the device");
+    if (mat->ntab < 1 || !mat->tab) return fx_fail(who, FX_ERROR_RUNTIME, "a viscoelastic material needs at least one Prony row (g, tau)");
+    for (int32_t r = 0; r < mat->ntab; r++)
+      if (mat->tab[2 * r + 1] == 0.0)
+        return fx_fail(who, FX_ERROR_UNSUPPORTED, "viscoelastic material: Prony row %d has tau = 0 (dt / tau is formed for every row)", (int)r + 1);
+    return 0;
+  }
+  if (mat->plastic == FX_MAT_NORTON) {  // harden, tab are not read; plconst = A, n, m
+    // TOTALLAG (KIRCHHOFF): the update routines hand StressUpdate the point's STORED stress and never D . strain
+    // (static_LIB_3d.f90:685-692), so a point that starts a VISCO step at zero stress divides 0 by 0 in update_iso_creep's loop,
+    // which has no exit then; INFINITE is not reachable from the card and has no NORTON branch at all
+    if (!(mat->plconst[2] > -1.0))
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "NORTON material with m = %g: the law divides by m + 1 and takes time**(m + 1) (creep.f90:66), m must be above -1",
+                     mat->plconst[2]);
+    if (mat->nlgeom != 2)
+      return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                     "a NORTON material needs nlgeom = 2 (UPDATELAG, the default of !CREEP): under TOTALLAG the reference relaxes the "
+                     "stored stress instead of the trial one, which defines no usable result, and INFINITE has no creep branch");
+    return 0;
+  }
   if (mat->plastic < 0 || mat->plastic > FX_MAT_DRUCKER)
     return fx_fail(who, FX_ERROR_UNSUPPORTED,
-                   "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce, 4 Mohr-Coulomb, 5 Drucker-Prager", (int)mat->plastic);
+                   "material kind %d: 0 ELASTIC, 1 Mises, 2 Neo-Hooke / Mooney-Rivlin, 3 Arruda-Boyce, 4 Mohr-Coulomb, 5 Drucker-Prager, "
+                   "7 viscoelastic, 8 NORTON", (int)mat->plastic);
   if (mat->plastic == FX_MAT_MOHR || mat->plastic == FX_MAT_DRUCKER) {  // fstr_ctrl_material.f90:451-469: linear hardening, no table
     if (mat->harden != 0 || mat->nlgeom < 0 || mat->nlgeom > 2)
       return fx_fail(who, FX_ERROR_UNSUPPORTED,
@@ -73,8 +98,9 @@ static int nl_check_materials(const char *who, int32_t n_mat, const fx_material_
     if (int e = nl_check_material(who, &mats[k])) return e;
   // MatlMatrix's saved flag (calMatMatrix.f90:39-62): after the first plastic update EVERY material goes to calElasticMatrix, which
   // for a hyperelastic one reads a Young's modulus and a Poisson's ratio that were never set
-  bool mises = false, hyper = false, yield = false;
+  bool mises = false, hyper = false, yield = false, creep = false;
   for (int32_t k = 0; k < n_mat; k++) {
+    creep |= mats[k].plastic == FX_MAT_NORTON;
     mises |= mats[k].plastic == 1;
     hyper |= mats[k].plastic == FX_MAT_MOONEY || mats[k].plastic == FX_MAT_ARRUDA;
     yield |= mats[k].plastic == FX_MAT_MOHR || mats[k].plastic == FX_MAT_DRUCKER;
@@ -83,6 +109,11 @@ static int nl_check_materials(const char *who, int32_t n_mat, const fx_material_
     return fx_fail(who, FX_ERROR_UNSUPPORTED,
                    "a Mises and a hyperelastic material in one context: after the first plastic update the reference takes the elastic "
                    "matrix of every material, which a hyperelastic one does not define");
+  if (creep && hyper)
+    return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                   "a NORTON and a hyperelastic material in one context: the first stress update of a NORTON element sets MatlMatrix's "
+                   "saved flag (static_LIB_3d.f90:595), after which the reference takes the elastic matrix of every material, which a "
+                   "hyperelastic one does not define");
   if (yield && hyper)
     return fx_fail(who, FX_ERROR_UNSUPPORTED,
                    "a Mohr-Coulomb / Drucker-Prager and a hyperelastic material in one context: after the first plastic update the "
@@ -96,6 +127,56 @@ struct NlPartIn {
   const int32_t *conn, *elem_mat;  // elem_mat: null with one material
   bool fbar = false;               // 361: F-bar (elemopt 4), not B-bar
 };
+
+// The factors of a viscoelastic material that depend on it and the time increment alone, as calViscoelasticMatrix (:143-161) and
+// UpdateViscoelastic (:249-265) form them per point: rows (exp_n, dq_n) into `rows`, mu_0 -> pl[0], gfac -> pl[1], dt -> pl[2]
+static void nl_visco_factors(const std::vector<double> &prony, double dt, NlMat &m, std::vector<double> &rows) {
+  const size_t nrow = prony.size() / 2;
+  rows.assign(2 * nrow, 0.0);
+  double mu_0 = 0.0, gfac = 0.0;
+  for (size_t r = 0; r < nrow; r++) {
+    const double mu_n = prony[2 * r], dtau = dt / prony[2 * r + 1], exp_n = exp(-dtau);
+    const double dq_n = mu_n * visco_hvisc(dtau, exp_n);
+    gfac = gfac + dq_n;
+    mu_0 = mu_0 + mu_n;
+    rows[2 * r] = exp_n;
+    rows[2 * r + 1] = dq_n;
+  }
+  mu_0 = 1.0 - mu_0;
+  gfac = gfac + mu_0;
+  m.pl[0] = mu_0; m.pl[1] = gfac; m.pl[2] = dt;
+}
+// The time of the coming sub-step into the context and the materials the kernels take (`who`: the entry point called).  A NORTON
+// material forms ttime**(m + 1): a negative time or increment is refused before anything changes, with the reason, instead of
+// travelling to every point as a NaN that the creep iteration's error word would report afterwards.
+static int nl_apply_time(fx_context *c, const char *who, double time, double tincr) {
+  NlDev &n = c->nl;
+  if (n.has_creep && !(time >= 0.0 && tincr >= 0.0))
+    return fx_fail(who, FX_ERROR_RUNTIME, "time %g, tincr %g: a NORTON material takes powers of the time (creep.f90:66), both must be >= 0 and finite",
+                   time, tincr);
+  n.time = time; n.tincr = tincr;
+  if (n.hist_w == 0) return 0;
+  std::vector<std::vector<double>> tables((size_t)n.n_mat);  // alive until the one synchronisation below
+  bool copied = false;
+  for (int32_t k = 0; k < n.n_mat; k++) {
+    if (n.prony[k].empty()) continue;
+    std::vector<double> &rows = tables[k];
+    if (nl_group_creep(n.h_mats[k].group)) {  // creep.f90:66, :165
+      const double A = n.prony[k][0], xm = n.prony[k][2];
+      n.h_mats[k].pl[0] = A * (pow(time + tincr, xm + 1.0) - pow(time, xm + 1.0)) / (xm + 1.0);
+      n.h_mats[k].pl[1] = n.prony[k][1];
+      n.h_mats[k].pl[2] = tincr;
+      continue;
+    }
+    nl_visco_factors(n.prony[k], tincr, n.h_mats[k], rows);
+    HIP_TRY(hipMemcpyAsync(n.tabs[k], rows.data(), rows.size() * 8, hipMemcpyHostToDevice, c->stream));
+    copied = true;
+  }
+  n.mat = n.h_mats[0];
+  if (n.mats) HIP_TRY(hipMemcpyAsync(n.mats, n.h_mats.data(), (size_t)n.n_mat * sizeof(NlMat), hipMemcpyHostToDevice, c->stream));
+  if (copied || n.mats) HIP_TRY(hipStreamSynchronize(c->stream));  // with one NORTON material everything travels by value
+  return 0;
+}
 
 static int nl_alloc_point_arrays(NlPartState &s, size_t npt) {
   return for_each_point_array([&](size_t b, auto *&a) { return dev_alloc(&a, npt * b / sizeof(*a)); }, s);
@@ -185,6 +266,7 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
   }
   // materials: one NlMat per section, hardening tables on the device
   n.h_mats.resize((size_t)n_mat);
+  n.prony.assign((size_t)n_mat, std::vector<double>());
   for (int32_t k = 0; k < n_mat; k++) {
     const fx_material_view &mv = mats[k];
     double *tab = nullptr;
@@ -201,7 +283,23 @@ static int nl_init_parts(fx_context *c, int32_t n_node, const double *coord, con
       m.plastic = mv.plastic; m.harden = 0; m.group = 4 + mv.nlgeom; m.ntab = 0; m.pl4 = mv.plconst4;
       n.has_yield = true;
     }
+    if (mv.plastic == FX_MAT_VISCO) {  // groups 7, 8: its own tangent and stress, fstatus(1 : 12 nrow + 6) in n.hist, no latch
+      m.plastic = 0; m.harden = 0; m.group = 7 + mv.nlgeom;
+      n.prony[k].assign(mv.tab, mv.tab + (size_t)2 * mv.ntab);
+      n.hist_w = std::max(n.hist_w, 12 * mv.ntab + 6);
+    }
+    if (mv.plastic == FX_MAT_NORTON) {  // group 9: plstrain, fstatus(1), fstatus(2); sets the latch
+      m.plastic = 0; m.harden = 0; m.group = 9; m.ntab = 0;
+      n.prony[k].assign(mv.plconst, mv.plconst + 3);
+      n.hist_w = std::max(n.hist_w, 2);
+      n.has_creep = true;
+    }
     m.tab = tab;
+  }
+  if (n.hist_w > 0) {
+    if (dev_alloc(&n.hist, (size_t)n.hist_w * npt)) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemsetAsync(n.hist, 0, (size_t)n.hist_w * npt * 8, c->stream));
+    if (int rc = nl_apply_time(c, "fx_nl_init", 0.0, 0.0)) return rc;  // the device tables hold (exp_n, dq_n), not the card's rows
   }
   n.mat = n.h_mats[0];
   n.tab = nullptr;
@@ -360,6 +458,9 @@ static constexpr auto nl_c3_kernel() {
 }
 // The groups the F-bar kernels are instantiated for: no UPDATELAG (nl_init_driver refuses it, so such a list is empty)
 static constexpr bool nl_fbar_group(int G) { return nl_group_flag(G) != 2; }
+// The groups that have thermal variants (TH = 1): fx_nl_set_thermal refuses a context with a viscoelastic or NORTON material, so
+// groups 7..9 are instantiated without them
+static constexpr bool nl_thermal_group(int G) { return !nl_group_visco(G) && !nl_group_creep(G); }
 // What one group of a part launches: the kernel of its type (null: nothing to launch), elements per workgroup and workgroup size.
 // An F-bar part takes the F-bar kernels, which have the arguments of 361's and, for the tangent, a workgroup of their own.
 template <int ETYPE, int G, bool UPDATE, int TH>
@@ -376,6 +477,10 @@ struct NlKernel {
     }
   }
 };
+// A part's block of the viscoelastic history
+static NlHist nl_part_hist(const NlDev &n, const NlPart &p) {
+  return NlHist{n.hist ? n.hist + p.pt_off : nullptr, n.n_pt, n.st.plstrain + p.pt_off};
+}
 // A part's block of the per-point arrays
 static NlPartState nl_part_state(const NlDev &n, const NlPart &p) {
   NlPartState s = n.st;
@@ -400,8 +505,8 @@ static void nl_launch_stiffness_group(fx_context *c, const NlPart &p, double *Ko
                          s.fstat, s.istat, A.indexL, A.itemL, A.indexU, A.itemU, A.D, A.AL, A.AU, K, n.err, list, e0, pos, atomic,
                          (const NlMat *)n.mats, (const int32_t *)p.emat, tail...);
     };
-    if constexpr (ETYPE == 361) go(k_by_pos, (const double *)s.strain, th);  // 361's own argument: K by position in the list
-    else go((const double *)s.strain, th);
+    if constexpr (ETYPE == 361) go(k_by_pos, (const double *)s.strain, th, nl_part_hist(n, p));  // 361's own argument: K by position in the list
+    else go((const double *)s.strain, th, nl_part_hist(n, p));
   };
   // element matrices out, or atomics: the group's colours in one launch
   for_colour_ranges(p.grp_off[G], Kout || p.scatter_atomic, k.epb, [&](dim3 grid, int32_t e0, int32_t e1) {
@@ -432,7 +537,7 @@ static void nl_launch_update_group(fx_context *c, const NlPart &p, double *qf_ou
   auto launch = [&](const int32_t *list, int32_t e0, int32_t e1) {
     hipLaunchKernelGGL(k.kern, dim3((unsigned)((e1 - e0 + k.epb - 1) / k.epb)), dim3(k.block), 0, c->stream, e1, n.coord, p.conn, n.unode,
                        n.dunode, n.mat, s.stress, s.strain, s.stress_bak, s.strain_bak, s.plstrain, s.fstat, s.istat, n.qforce, qf_out,
-                       list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err, th);
+                       list, e0, (const NlMat *)n.mats, (const int32_t *)p.emat, n.err, th, nl_part_hist(n, p));
   };
   const std::vector<int32_t> &off = p.grp_off[G];
   // a group that holds every element of the part is walked in the elements' own order (contiguous history arrays); the internal
@@ -457,8 +562,10 @@ static int nl_launch_stiffness(fx_context *c, double *Kout) {  // Kout: the elem
       for_each_nl_group([&](auto g) {
         constexpr int ET = decltype(t)::value, G = decltype(g)::value;
         double *const K = Kout ? Kout + p.k_off : nullptr, *const dk = dup_k ? dup_k + NL_KE<361> * dup_at : nullptr;
-        if (c->nl.th.on && c->nl.th.elastic_tab) nl_launch_stiffness_group<ET, G, 1>(c, p, K, dk);
-        else nl_launch_stiffness_group<ET, G, 0>(c, p, K, dk);
+        if constexpr (nl_thermal_group(G)) {
+          if (c->nl.th.on && c->nl.th.elastic_tab) { nl_launch_stiffness_group<ET, G, 1>(c, p, K, dk); return; }
+        }
+        nl_launch_stiffness_group<ET, G, 0>(c, p, K, dk);
       });
     });
     dup_at += (size_t)p.n_dup;
@@ -471,19 +578,21 @@ static void nl_launch_update(fx_context *c, double *qf_out) {  // qf_out: the el
     with_solid_type(p.etype, [&](auto t) {
       for_each_nl_group([&](auto g) {
         constexpr int ET = decltype(t)::value, G = decltype(g)::value;
-        if (c->nl.th.on) nl_launch_update_group<ET, G, 1>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
-        else nl_launch_update_group<ET, G, 0>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
+        if constexpr (nl_thermal_group(G)) {
+          if (c->nl.th.on) { nl_launch_update_group<ET, G, 1>(c, p, qf_out ? qf_out + p.qf_off : nullptr); return; }
+        }
+        nl_launch_update_group<ET, G, 0>(c, p, qf_out ? qf_out + p.qf_off : nullptr);
       });
     });
 }
-// The stress update of a context with a Mohr-Coulomb / Drucker-Prager section or an F-bar part reports the reference's `stop`
+// The stress update of a context with a Mohr-Coulomb / Drucker-Prager or NORTON section or an F-bar part reports the reference's `stop`
 // statements through the error word: cleared before the launches, read after them (one 4-byte copy; other contexts skip both).
 static int nl_update_err_clear(fx_context *c) {
-  if (c->nl.has_yield || c->nl.has_fbar) HIP_TRY(hipMemsetAsync(c->nl.err, 0, 4, c->stream));
+  if (c->nl.has_yield || c->nl.has_fbar || c->nl.has_creep) HIP_TRY(hipMemsetAsync(c->nl.err, 0, 4, c->stream));
   return 0;
 }
 static int nl_update_err_check(fx_context *c) {
-  if (!c->nl.has_yield && !c->nl.has_fbar) return 0;
+  if (!c->nl.has_yield && !c->nl.has_fbar && !c->nl.has_creep) return 0;
   int32_t herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, c->nl.err, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -498,7 +607,8 @@ static int nl_run_update(fx_context *c, double *qf_out, hipEvent_t launched = nu
   if (launched) HIP_TRY(hipEventRecord(launched, c->stream));
   if (int rc = nl_update_err_check(c)) return rc;
   // MatlMatrix(..., isEp=1) has now been called (calMatMatrix.f90:43-45); the flag is the process's, whichever section set it
-  for (const NlMat &m : c->nl.h_mats) if (m.plastic) c->nl.latch = 1;
+  // (the update routines set isEp for a NORTON element too, whatever tincr is: static_LIB_3d.f90:595)
+  for (const NlMat &m : c->nl.h_mats) if (m.plastic || nl_group_creep(m.group)) c->nl.latch = 1;
   return 0;
 }
 
@@ -688,6 +798,9 @@ extern "C" int fx_nl_commit(fx_context *c) {
     const int64_t npt = (int64_t)p.nq * p.n_elem;
     hipLaunchKernelGGL(k_nl_commit, dim3(grid_for(6 * npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat.plastic, s.fstat, s.plstrain,
                        s.stress, s.strain, s.stress_bak, s.strain_bak, (const NlMat *)n.mats, (const int32_t *)p.emat);
+    if (n.hist && n.tincr > 0.0)  // updateViscoElasticState under `tincr > 0.d0` (fstr_Update.f90:333-337)
+      hipLaunchKernelGGL(k_nl_commit_visco, dim3(grid_for(npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat, (const NlMat *)n.mats,
+                         (const int32_t *)p.emat, (const double *)s.strain, nl_part_hist(n, p));
   }
   if (n.th.on)  // last_temp = temperature (fstr_Update.f90:308-312)
     HIP_TRY(hipMemcpyAsync(n.th.last_temp, n.th.temp, (size_t)c->A.NP * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -714,6 +827,11 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
         return 0;
       }, n.st, n.bk))
     return FX_ERROR_RUNTIME;
+  if (n.hist) {  // fstatus(:) of the viscoelastic points (fstr_copy_gauss)
+    const size_t nh = (size_t)n.hist_w * npt;
+    if (!n.hist_bk && dev_alloc(&n.hist_bk, nh)) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(load ? n.hist : n.hist_bk, load ? n.hist_bk : n.hist, nh * 8, hipMemcpyDeviceToDevice, c->stream));
+  }
   if (n.th.on) {  // last_temp travels with the history (fstr_Cutback.f90:127, :173)
     if (!n.th.last_temp_bk && dev_alloc(&n.th.last_temp_bk, (size_t)c->A.NP)) return FX_ERROR_RUNTIME;
     HIP_TRY(hipMemcpyAsync(load ? n.th.last_temp : n.th.last_temp_bk, load ? n.th.last_temp_bk : n.th.last_temp, (size_t)c->A.NP * 8,
@@ -725,6 +843,7 @@ extern "C" int fx_nl_snapshot(fx_context *c, int load) {
   return 0;
 }
 
+static int nl_creep_fstat(fx_context *c, int to_fstat);
 static int nl_copy_state(fx_context *c, const fx_nl_state_view *s, bool to_device) {
   NlDev &n = c->nl;
   const size_t np3 = (size_t)3 * c->A.NP * 8, npt = (size_t)n.n_pt;
@@ -735,6 +854,8 @@ static int nl_copy_state(fx_context *c, const fx_nl_state_view *s, bool to_devic
   if (for_each_point_array([&](size_t b, void *h, void *d) { return copy(npt * b, h, d); }, *s, n.st) || copy(np3, s->unode, n.unode) ||
       copy(np3, s->dunode, n.dunode) || copy(np3, s->qforce, n.qforce))
     return FX_ERROR_RUNTIME;
+  if (to_device && s->fstat)
+    if (int rc = nl_creep_fstat(c, 0)) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -756,6 +877,10 @@ extern "C" int fx_nl_set_thermal(fx_context *c, const fx_nl_thermal_view *v) {
   NlDev &n = c->nl;
   if (!v) { nl_thermal_free(n.th); return 0; }
   if (!v->alpha) return fx_fail(who, FX_ERROR_RUNTIME, "expansion coefficients missing");
+  if (n.hist_w > 0)
+    return fx_fail(who, FX_ERROR_UNSUPPORTED,
+                   "the context holds a viscoelastic or NORTON material: their thermal branches (the WLF / Arrhenius shift of !TRS, "
+                   "the temperature tables inside UpdateViscoelastic, iso_creep and update_iso_creep) are not on the device");
   // everything is checked, and the new data is on the device, before the context changes
   std::vector<double> tabs;
   std::vector<int32_t> idx((size_t)4 * n.n_mat, 0);
@@ -836,6 +961,56 @@ extern "C" int fx_nl_get_last_temp(fx_context *c, double *temp) {
 extern "C" int fx_nl_set_last_temp(fx_context *c, const double *temp) {
   NL_THERMAL_ON("fx_nl_set_last_temp");
   return nl_copy_temp(c, c->nl.th.last_temp, temp, hipMemcpyHostToDevice);
+}
+
+// ---- time-dependent materials (see the header)
+extern "C" int fx_nl_set_time(fx_context *c, double time, double tincr) {
+  NL_READY("fx_nl_set_time");
+  return nl_apply_time(c, "fx_nl_set_time", time, tincr);
+}
+// fstatus(1) of the NORTON points is in the context's fstat array and in component 0 of the history: after a transfer into one, the other
+static int nl_creep_fstat(fx_context *c, int to_fstat) {
+  NlDev &n = c->nl;
+  if (!n.has_creep) return 0;
+  for (const NlPart &p : n.parts) {
+    const int64_t npt = (int64_t)p.nq * p.n_elem;
+    hipLaunchKernelGGL(k_nl_creep_fstat, dim3(grid_for(npt)), dim3(256), 0, c->stream, npt, p.nq, n.mat, (const NlMat *)n.mats,
+                       (const int32_t *)p.emat, n.st.fstat + p.pt_off, nl_part_hist(n, p), to_fstat);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// fstatus(1..W) of every point, [point][W] on the host side; the device keeps it component-major (fx_visco.h)
+static int nl_copy_history(fx_context *c, const char *who, double *hist, int32_t *width, bool to_device) {
+  NlDev &n = c->nl;
+  if (width) *width = n.hist_w;
+  if (!hist || n.hist_w == 0) return 0;
+  const size_t npt = (size_t)n.n_pt, W = (size_t)n.hist_w;
+  std::vector<double> t(W * npt);
+  if (to_device) {
+    for (size_t p = 0; p < npt; p++)
+      for (size_t k = 0; k < W; k++) t[k * npt + p] = hist[p * W + k];
+    HIP_TRY(hipMemcpyAsync(n.hist, t.data(), t.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = nl_creep_fstat(c, 1)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  HIP_TRY(hipMemcpyAsync(t.data(), n.hist, t.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t p = 0; p < npt; p++)
+    for (size_t k = 0; k < W; k++) hist[p * W + k] = t[k * npt + p];
+  return 0;
+}
+extern "C" int fx_nl_get_history(fx_context *c, double *hist, int32_t *width) {
+  NL_READY("fx_nl_get_history");
+  return nl_copy_history(c, "fx_nl_get_history", hist, width, false);
+}
+extern "C" int fx_nl_set_history(fx_context *c, const double *hist, int32_t width) {
+  NL_READY("fx_nl_set_history");
+  if (width != c->nl.hist_w)
+    return fx_fail("fx_nl_set_history", FX_ERROR_RUNTIME, "width %d, the context's history has %d components per point", (int)width,
+                   (int)c->nl.hist_w);
+  return nl_copy_history(c, "fx_nl_set_history", const_cast<double *>(hist), nullptr, true);
 }
 
 // Element-level outputs of the two kernels (tests): tangents ke (per element 3 nn x 3 nn row-major) of the current state

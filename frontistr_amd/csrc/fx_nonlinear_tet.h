@@ -46,7 +46,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
                                                             const int32_t *__restrict__ elem_list, int32_t e0,
                                                             const int32_t *__restrict__ pos_map, int atomic,
                                                             const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                            const double *__restrict__ strain, ThermalDev th) {
+                                                            const double *__restrict__ strain, ThermalDev th, NlHist hs) {
   using El = C3El<ETYPE>;
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = El::NN, NQ = El::NQ, EPB = El::EPB, LPE = El::LPE, NB = El::NB;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_stiffness_tet(int32_t n_
         nl_thermal_matrix<NN>(th, m, mats ? emat[elem] - 1 : 0, [&](int j) { return conn[(size_t)NN * elem + j]; },
                               [&](int j) { return c3_shape_func<ETYPE>(j, xi, et, ze); });
       // (inside `if (active && k < NQ)`: only lanes that own a real point get here, so err needs no `active ?` guard)
-      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm, err);
+      nl_point_matrix<nl_group_yield(G)>(m, latch, NLGEOM, S, m.plastic ? istat[gp] : 0, m.plastic ? fstat[gp] : 0.0, Dm, err, nl_group_creep(G) ? hs.plstrain[gp] : 0.0);
     }
 #pragma unroll
     for (int i = 0; i < 21; i++) Dsh[el][k][i] = Dm[i];
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
                                                              double *__restrict__ qforce, double *__restrict__ qf_out,
                                                              const int32_t *__restrict__ elem_list, int32_t e0,
                                                              const NlMat *__restrict__ mats, const int32_t *__restrict__ emat,
-                                                             int32_t *__restrict__ err, ThermalDev th) {
+                                                             int32_t *__restrict__ err, ThermalDev th, NlHist hs) {
   constexpr int NLGEOM = nl_group_flag(G);
   constexpr int NN = C3El<ETYPE>::NN, NQ = C3El<ETYPE>::NQ;
   const int64_t t = (int64_t)blockIdx.x * C3El<ETYPE>::BS + threadIdx.x;
@@ -225,6 +225,8 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
   double ds[6];
   if (G == 3) {  // StressUpdate: 2nd Piola-Kirchhoff stress from the total strain (:681-684)
     hyper_stress(nl_hyper_kind(m), m.pl, de, ds);
+  } else if constexpr (nl_group_visco(G)) {  // StressUpdate -> UpdateViscoelastic under tincr /= 0, else matmul(D, dstrain)
+    nl_visco_stress<NLGEOM>(m, de, hs, (size_t)NQ * elem + g, active, ds);
   } else {
     double D11, D12, D44;
     elastic_constants(m.E, m.nu, D11, D12, D44);
@@ -260,6 +262,7 @@ __global__ __launch_bounds__(C3El<ETYPE>::BS) void k_nl_update_tet(int32_t n_ele
     for (int i = 0; i < 6; i++) { sg[i] = ds[i]; eg[i] = de[i]; }
   }
   if constexpr (TH != 0) { eg[0] += eth; eg[1] += eth; eg[2] += eth; }  // the stored strain is the total one (:657, :683-694, :707)
+  if constexpr (nl_group_creep(G)) nl_creep_stress(m, sg, hs, fstat, gp, active, active ? err : nullptr);  // NORTON behind the UPDATELAG stress
   if (G != 3 && m.plastic) {
     int32_t ist = active ? istat[gp] : 0;      // idle lanes read no state another workgroup may be writing
     double fs = active ? fstat[gp] : 0.0;

@@ -17,8 +17,9 @@ for one TYPE=361 B-bar or F-bar group (fstr_solid(..., elemopt=2 | 4); F-bar: `!
 or one group of tetrahedra TYPE=341 / 342, wedges TYPE=351 / 352 or 20-node hexahedra TYPE=362
 (fstr_solid(..., etype=341 | 342 | 351 | 352 | 362): STF_C3 / UPDATE_C3), or a mesh of several groups of these types
 (fstr_solid(ctx, coord, None, materials, groups=[...]): fx_nl_init_groups),
-with one isotropic (elastic; Mises, Mohr-Coulomb or Drucker-Prager elastoplastic: tMaterial.mohr_coulomb / .drucker_prager; or
-hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce) material per section.  Everything is resident on the GPU; there is NO CPU
+with one isotropic (elastic; Mises, Mohr-Coulomb or Drucker-Prager elastoplastic: tMaterial.mohr_coulomb / .drucker_prager;
+hyperelastic: tMaterial.neohooke / .mooney_rivlin / .arruda_boyce; viscoelastic: tMaterial.viscoelastic; or NORTON creep:
+tMaterial.norton) material per section.  Everything is resident on the GPU; there is NO CPU
 fallback.
 """
 import ctypes as C
@@ -32,6 +33,8 @@ INFINITE, TOTALLAG, UPDATELAG = 0, 1, 2
 BILINEAR, MULTILINEAR, SWIFT, RAMBERG_OSGOOD = 0, 1, 2, 3
 ELASTIC, MISES, MOONEYRIVLIN, ARRUDABOYCE = 0, 1, 2, 3      # fx_material_view::plastic, the material kind (NEOHOOKE is MOONEYRIVLIN with C01 = 0)
 MOHRCOULOMB, DRUCKERPRAGER = 4, 5                           # !PLASTIC, YIELD=MOHR-COULOMB | DRUCKER-PRAGER
+VISCOELASTIC = 7                                            # !VISCOELASTIC: table = the Prony rows (g, tau)
+NORTON = 8                                                  # !CREEP, TYPE=NORTON: plconst = A, n, m
 _PLASTICITY_PI = 3.14159265358979                           # fstr_ctrl_get_PLASTICITY's own PI (fstr_ctrl_material.f90:355)
 
 
@@ -120,6 +123,22 @@ class tMaterial:
         m.plconst4 = float(xi)
         return m
 
+    @classmethod
+    def viscoelastic(cls, E, nu, prony, nlgeom_flag=TOTALLAG):
+        """!ELASTIC E, nu with !VISCOELASTIC: ``prony`` rows (g_n, tau_n), one per term.  The card's flag is TOTALLAG, or INFINITE
+        with its INFINITE parameter (fstr_ctrl_material.f90:277-279).  Time-dependent: fstr_solid.set_time / the tincr arguments."""
+        m = cls(E, nu, table=prony, nlgeom_flag=nlgeom_flag)
+        m.kind = VISCOELASTIC
+        return m
+
+    @classmethod
+    def norton(cls, E, nu, A, n, m, nlgeom_flag=UPDATELAG):
+        """!ELASTIC E, nu with !CREEP, TYPE=NORTON: A, n, m of the law  d(eps_cr)/dt = A q**n t**m.  The card's flag is UPDATELAG
+        (TOTALLAG with KIRCHHOFF, which the device loop refuses; fstr_ctrl_material.f90:502-504).  Time-dependent."""
+        mat = cls(E, nu, plconst=(A, n, m), nlgeom_flag=nlgeom_flag)
+        mat.kind = NORTON
+        return mat
+
     def view(self):
         kind = self.kind if self.kind >= MOONEYRIVLIN else int(self.plastic)
         v = _MaterialView(self.E, self.nu, kind, self.harden, self.nlgeom_flag, self.table.shape[0],
@@ -146,6 +165,7 @@ class fstr_solid:
         the element outputs are then flat, the groups one after the other (point_offsets, elem_offsets; group_slices cuts them
         into per-group views)."""
         self.ctx = ctx
+        self._timed = False         # set_time has been called: a later STATIC step sets tincr = 0 again
         self.coord = np.ascontiguousarray(hecMESH_coord, dtype=np.float64)
         self.material = material
         self.n_node = self.coord.shape[0]
@@ -273,6 +293,29 @@ class fstr_solid:
         _chk(lib().fx_nl_set_temperature(self.ctx.h, _ptr(t)))
         self._temperature = t.copy()
 
+    # ---- time (fx_nl_set_time) and the history of time-dependent materials
+    def set_time(self, time, tincr):
+        """ctime and tincr of the coming sub-step or call (fstr_solve_NonLinear.f90:74, :100, :162); (0, 0) after construction."""
+        _chk(lib().fx_nl_set_time(self.ctx.h, C.c_double(time), C.c_double(tincr)))
+        self._timed = True
+
+    def history_width(self):
+        w = C.c_int32(0)
+        _chk(lib().fx_nl_get_history(self.ctx.h, None, C.byref(w)))
+        return int(w.value)
+
+    def get_history(self):
+        """fstatus(1..W) of every point, (n_point, W); W = 0 without a time-dependent material."""
+        w = self.history_width()
+        out = np.zeros((self.n_point, w))
+        if w:
+            _chk(lib().fx_nl_get_history(self.ctx.h, _ptr(out), None))
+        return out
+
+    def set_history(self, hist):
+        h = np.ascontiguousarray(hist, dtype=np.float64).reshape(self.n_point, -1)
+        _chk(lib().fx_nl_set_history(self.ctx.h, _ptr(h) if h.size else None, int(h.shape[1])))
+
     # ---- state transfer (tests, restart, output)
     def get_state(self, names=("stress", "strain", "stress_bak", "strain_bak", "plstrain", "fstat", "istat",
                                "unode", "dunode", "qforce")):
@@ -357,12 +400,16 @@ def fstr_cutback_load(fstrSOLID):
     _chk(lib().fx_nl_snapshot(fstrSOLID.ctx.h, 1))
 
 
-def fstr_Newton(fstrSOLID, hecMAT, factor, bc, cload, max_iter, converg, commit_unconverged=False, temperature=None):
+def fstr_Newton(fstrSOLID, hecMAT, factor, bc, cload, max_iter, converg, commit_unconverged=False, temperature=None,
+                time=None, tincr=None):
     """One substep of fstr_Newton.  factor = (FACTOR(1), FACTOR(2)); bc / cload are the values at load factor 1.
     temperature: fstrSOLID%temperature of this sub-step (fstr_solid.set_thermal first); None keeps the one last set.
+    time, tincr: ctime and tincr of this sub-step (fstr_solid.set_time); both None keeps what was last set.
     Returns (converged, log) with log rows (iter, solver iterations, solver code, |B|, |X|, |QFORCE|, |dunode|)."""
     if temperature is not None:
         fstrSOLID.set_temperature(temperature)
+    if time is not None or tincr is not None:
+        fstrSOLID.set_time(0.0 if time is None else time, 0.0 if tincr is None else tincr)
     bn, bd, bv = _bc_arrays(bc)
     cl = None if cload is None else np.ascontiguousarray(cload, dtype=np.float64)
     log = np.zeros((max_iter, 7))
@@ -383,13 +430,21 @@ def fstr_set_step_control(fstrSOLID, maxres=1.0e10, is_linear=False):
     _chk(lib().fx_nl_set_step_control(fstrSOLID.ctx.h, C.c_double(maxres), int(is_linear)))
 
 
-def fstr_solve_NLGEOM(fstrSOLID, hecMAT, bc, cload, substeps, max_iter, converg, commit_unconverged=True, temperature=None):
+def fstr_solve_NLGEOM(fstrSOLID, hecMAT, bc, cload, substeps, max_iter, converg, commit_unconverged=True, temperature=None,
+                      tincr=None, start_time=0.0, load_held=False):
     """The sub-step loop of fstr_solve_NLGEOM with the default linear load-factor ramp (table_nlsta without
     amplitude).  temperature: the nodal temperature at load factor 1 (fstr_solid.set_thermal first), ramped as
     fstr_ass_load.f90:291-300 ramps it from temp_bak, the temperature at the start of the step (fstr_solve_NLGEOM.f90:92) -- in
     a first step the initial condition given to set_thermal or, without one, ref_temp (fstr_setup.f90:780):
     temperature(sub) = temp_bak + (temperature - temp_bak) * factor; and as the program calls fstr_UpdateState at the start of
-    the step (:96), last_temp starts the step as that temperature.  Returns the concatenated Newton log with the substep number
+    the step (:96), last_temp starts the step as that temperature.  tincr: the time increment of every sub-step of a `!STEP,
+    TYPE=VISCO` step (None: a STATIC step, which sets tincr = 0 as fstr_Newton does for one, fstr_solve_NonLinear.f90:60-61, unless
+    the context holds no time yet); sub-step k runs at the time of its start, start_time + (k - 1) tincr
+    (fstr_solve_NLGEOM.f90:129-130: fstr_get_time() before fstr_proceed_time), which is what iso_creep and update_iso_creep document
+    for ttime.  In a VISCO step the prescribed displacements are not ramped: fstr_AddBC gives the first sub-step the whole value and
+    every later one nothing (fstr_AddBC.f90:44-47), while the nodal load follows the load factor as in a STATIC step -- or, with
+    load_held, stays whole in every sub-step, which is what fstr_ass_load does for a load group that was active in the step before
+    (fstr_ass_load.f90:69-70).  Returns the concatenated Newton log with the substep number
     in front."""
     logs = []
     if temperature is not None:
@@ -397,9 +452,20 @@ def fstr_solve_NLGEOM(fstrSOLID, hecMAT, bc, cload, substeps, max_iter, converg,
         temp_bak = fstrSOLID.temperature_at_step_start()
         fstrSOLID.set_temperature(temp_bak)
         fstr_UpdateState(fstrSOLID)
+    if tincr is None and fstrSOLID._timed:
+        fstrSOLID.set_time(start_time, 0.0)         # a STATIC step after a VISCO one
     for sub in range(1, substeps + 1):
         tsub = None if temperature is None else temp_bak + (temperature - temp_bak) * (sub / substeps)
-        ok, log = fstr_Newton(fstrSOLID, hecMAT, ((sub - 1) / substeps, sub / substeps), bc, cload, max_iter, converg,
-                              commit_unconverged, temperature=tsub)
+        f0, f1 = (sub - 1) / substeps, sub / substeps
+        bcs, cl = bc, cload
+        if tincr is not None:    # step and hold: fx_newton_substep forms bc * (factor1 - factor0) and cload * factor1, so factor (0, 1)
+            if bc is not None and sub > 1:
+                bcs = (bc[0], bc[1], np.zeros(len(bc[2])))
+            if cload is not None and not load_held:
+                cl = np.asarray(cload, dtype=np.float64) * f1
+            f0, f1 = 0.0, 1.0
+        ok, log = fstr_Newton(fstrSOLID, hecMAT, (f0, f1), bcs, cl, max_iter, converg,
+                              commit_unconverged, temperature=tsub,
+                              time=None if tincr is None else start_time + (sub - 1) * tincr, tincr=tincr)
         logs.append(np.concatenate([np.full((log.shape[0], 1), float(sub)), log], axis=1))
     return np.concatenate(logs, axis=0)

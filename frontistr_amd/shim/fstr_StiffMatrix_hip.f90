@@ -18,6 +18,7 @@ contains
     real(kind=kreal), intent(in) :: tincr
     real(kind=kreal) :: t0
     t0 = hecmw_Wtime()
+    call fsd_set_time(time, tincr)
     if (fsd_stiffness(hecMESH, hecMAT, fstrSOLID)) then        ! tangent assembled on the device; D / AL / AU of hecMAT are not touched
       call fsd_report('fstr_StiffMatrix on the device', hecmw_Wtime() - t0)
       return

@@ -23,6 +23,7 @@ contains
       return
     endif
     t0 = hecmw_Wtime()
+    call fsd_set_time(time, tincr)
     if (fsd_update_newton(hecMESH, fstrSOLID)) then
       call fsd_report('fstr_UpdateNewton on the device', hecmw_Wtime() - t0)
       return
@@ -37,7 +38,7 @@ contains
     real(kind=kreal) :: tincr
     real(kind=kreal) :: t0
     t0 = hecmw_Wtime()
-    if (fsd_update_state(hecMESH, fstrSOLID)) then
+    if (fsd_update_state(hecMESH, fstrSOLID, tincr)) then
       call fsd_report('fstr_UpdateState on the device', hecmw_Wtime() - t0)
       return
     endif

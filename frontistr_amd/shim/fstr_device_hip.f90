@@ -14,6 +14,8 @@
 !> increments (a cutback rolls the device's history back too, fsd_cutback); anything else runs the reference's own routines (kept,
 !> renamed, in the same binary).
 !> HECMW_GPU_ASSEMBLY=0 keeps the reference's element loops on the host for every deck; the tetrahedra are taken only with
+!> Viscoelastic (!VISCOELASTIC, INFINITE / TOTALLAG) and NORTON creep (!CREEP, UPDATELAG) materials go there with HECMW_GPU_NL_VISCO=1:
+!> ctime and tincr of every call reach the library through fx_nl_set_time, and the whole fstatus(:) of such points travels both ways.
 !> HECMW_GPU_NL_TET=1, the five STF_C3 types with HECMW_GPU_NL_C3=1 (opt-in until their end-to-end time against the host loops
 !> is on record).
 module fstr_device_hip
@@ -26,7 +28,7 @@ module fstr_device_hip
   use hecmw_hip_binding
   implicit none
   private
-  public :: fsd_stiffness, fsd_update_newton, fsd_update_state, fsd_active, fsd_report, fsd_cutback
+  public :: fsd_stiffness, fsd_update_newton, fsd_update_state, fsd_active, fsd_report, fsd_cutback, fsd_set_time
 
   logical, save :: decided = .false., eligible = .false., ready = .false.
   ! linear static decks: the stiffness loop (fx_assemble_c3d8_sections) and the stress update (fx_update_c3d8_linear)
@@ -46,6 +48,9 @@ module fstr_device_hip
   integer, save :: nl_nq = 8                       ! its quadrature points per element
   logical, save :: nl_mixed = .false.              ! several of the six solid types (HECMW_GPU_NL_MIXED=1): fx_nl_init_groups
   logical, save :: nl_thermal = .false.            ! an NLGEOM deck with temperatures on the device (HECMW_GPU_NL_THERMAL=1): fx_nl_set_thermal
+  logical, save :: nl_timed = .false.              ! viscoelastic or NORTON materials on the device (HECMW_GPU_NL_VISCO=1): fx_nl_set_time, the whole fstatus(:)
+  integer(c_int32_t), save :: nl_hw = 0            ! components of their history per point (fx_nl_get_history)
+  real(c_double), save :: nl_time = 0.d0, nl_tincr = 0.d0      ! ctime, tincr of the call in hand (fsd_set_time: the three forwarders)
   logical, save :: nl_fbar = .false.               ! the 361 sections are F-bar, all of them (HECMW_GPU_NL_FBAR=1): fx_nl_init_groups with elemopt 4
   integer, allocatable, save :: el_nq(:), el_p0(:) ! per element: its type's quadrature points, and the points of the elements before it
   integer, save :: n_pt = 0                        ! quadrature points of the mesh: the per-point arrays are flat over them, in hecMESH's element order
@@ -86,10 +91,10 @@ contains
     character(len=8) :: env
     character(len=3) :: tname
     character(len=64) :: tnames
-    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype, n_bbar, n_fbar
+    integer :: elen, estat, i, icel, cid, nn, n_hyper, n_mises, n_yield, itype, n_bbar, n_fbar, n_visco, n_creep
     integer(c_int32_t) :: et
     logical :: opted, th
-    character(len=9) :: tail
+    character(len=32) :: tail
     if (decided) then
       fsd_eligible = eligible
       return
@@ -212,9 +217,13 @@ contains
     n_hyper = 0
     n_mises = 0
     n_yield = 0
+    n_visco = 0
+    n_creep = 0
     do i = 1, size(fstrSOLID%materials)
       if (.not. material_covered(fstrSOLID%materials(i))) return
       if (is_hyperelastic(fstrSOLID%materials(i)%mtype)) n_hyper = n_hyper + 1
+      if (fstrSOLID%materials(i)%mtype == VISCOELASTIC) n_visco = n_visco + 1
+      if (fstrSOLID%materials(i)%mtype == NORTON) n_creep = n_creep + 1
       if (fstrSOLID%materials(i)%mtype /= -1 .and. isElastoplastic(fstrSOLID%materials(i)%mtype)) then
         n_mises = n_mises + 1      ! every elastoplastic material, whatever its yield function: what sets MatlMatrix's saved flag
         if (getYieldFunction(fstrSOLID%materials(i)%mtype) /= 0) n_yield = n_yield + 1
@@ -232,11 +241,24 @@ contains
       call get_environment_variable('HECMW_GPU_NL_HYPER', env, elen, estat)
       if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
     endif
+    if (n_visco + n_creep > 0) then
+      ! !VISCOELASTIC / !CREEP decks opt in: no end-to-end time against the host loops is on record (DESIGN.md section 7).  Any
+      ! temperature in the deck keeps the host loops (fx_nl_set_thermal refuses these materials), a NORTON material beside a
+      ! hyperelastic one too (its first stress update sets MatlMatrix's saved flag), and a decomposed mesh
+      if (th) return
+      if (n_creep > 0 .and. n_hyper > 0) return
+      if (hecMESH%PETOT > 1) return
+      call get_environment_variable('HECMW_GPU_NL_VISCO', env, elen, estat)
+      if (.not. (estat == 0 .and. elen > 0 .and. env(1:1) == '1')) return
+    endif
+    nl_timed = n_visco + n_creep > 0
     eligible = .true.
     fsd_eligible = .true.
     nl_thermal = th
     tail = ''
     if (th) tail = ', thermal'
+    if (n_visco > 0) tail = trim(tail)//', viscoelastic'
+    if (n_creep > 0) tail = trim(tail)//', creep'
     nl_etype = lin_etype
     nl_nq = 8
     if (nl_etype /= 361) nl_nq = c3_type_points(nl_etype)
@@ -489,6 +511,9 @@ contains
 
   logical function material_covered(m)
     type(tMaterial), intent(in) :: m
+    type(DICT_DATA), pointer :: tbl
+    logical :: ierr_l
+    integer :: k
     material_covered = .false.
     if (m%mtype == -1) then            ! a slot of fstrSOLID%materials no section refers to (initMaterial never ran): ignored
       material_covered = .true.
@@ -510,6 +535,27 @@ contains
       endif
       if (getYieldFunction(m%mtype) /= 0) return         ! Mises
       if (getHardenType(m%mtype) < 0 .or. getHardenType(m%mtype) > 3) return
+      material_covered = .true.
+    else if (m%mtype == VISCOELASTIC) then
+      ! the plain card only (a !TRS card makes the mtype VISCOELASTIC + 1 / + 2: host loops), INFINITE or TOTALLAG, no DEPENDENCIES
+      ! column, no relaxation time of zero
+      if (m%nlgeom_flag /= INFINITE .and. m%nlgeom_flag /= TOTALLAG) return
+      call fetch_Table(MC_VISCOELASTIC, m%dict, tbl, ierr_l)
+      if (ierr_l) return
+      ! (the card makes its table with ndepends = 1 whatever DEPENDENCIES says, fstr_ctrl_material.f90:302: a temperature column shows
+      ! as a third column)
+      if (tbl%tbcol /= 2 .or. tbl%tbrow < 1) return
+      do k = 1, tbl%tbrow
+        if (tbl%tbval(2, k) == 0.d0) return
+      enddo
+      material_covered = .true.
+    else if (m%mtype == NORTON) then
+      ! UPDATELAG (the card's default), no DEPENDENCIES, a time exponent above -1
+      if (m%nlgeom_flag /= UPDATELAG) return
+      call fetch_Table(MC_NORTON, m%dict, tbl, ierr_l)
+      if (ierr_l) return
+      if (tbl%ndepends /= 0 .or. tbl%tbrow /= 1) return
+      if (.not. (tbl%tbval(3, 1) > -1.d0)) return
       material_covered = .true.
     else if (is_hyperelastic(m%mtype)) then
       ! total Lagrange only (`CAUCHY` -> UPDATELAG is another algorithm in the reference).  A card with a DEPENDENCIES table never gets
@@ -649,6 +695,7 @@ contains
       if (isElastoplastic(fstrSOLID%materials(i)%mtype)) then
         if (getHardenType(fstrSOLID%materials(i)%mtype) == 1) ntmax = max(ntmax, fetch_TableRow(MC_YIELD, fstrSOLID%materials(i)%dict))
       endif
+      if (fstrSOLID%materials(i)%mtype == VISCOELASTIC) ntmax = max(ntmax, fetch_TableRow(MC_VISCOELASTIC, fstrSOLID%materials(i)%dict))
     enddo
     if (allocated(tabs)) deallocate(tabs)
     allocate(tabs(2, ntmax, nmat))
@@ -666,6 +713,21 @@ contains
         mats(i)%plconst(1) = fstrSOLID%materials(i)%variables(M_PLCONST1)
         mats(i)%plconst(2) = fstrSOLID%materials(i)%variables(M_PLCONST2)
         mats(i)%plconst(3) = fstrSOLID%materials(i)%variables(M_PLCONST3)
+      endif
+      if (fstrSOLID%materials(i)%mtype == VISCOELASTIC) then      ! kind 7: the Prony rows (g, tau) as the reference holds them
+        call fetch_Table(MC_VISCOELASTIC, fstrSOLID%materials(i)%dict, tbl, ierr_l)
+        if (ierr_l) call fsd_fail('MC_VISCOELASTIC table')
+        nt = tbl%tbrow
+        tabs(1:2, 1:nt, i) = tbl%tbval(1:2, 1:nt)
+        mats(i)%plastic = 7
+        mats(i)%ntab = nt
+        mats(i)%tab = c_loc(tabs(1, 1, i))
+      endif
+      if (fstrSOLID%materials(i)%mtype == NORTON) then            ! kind 8: A, n, m
+        call fetch_Table(MC_NORTON, fstrSOLID%materials(i)%dict, tbl, ierr_l)
+        if (ierr_l) call fsd_fail('MC_NORTON table')
+        mats(i)%plastic = 8
+        mats(i)%plconst(1:3) = tbl%tbval(1:3, 1)
       endif
       if (isElastoplastic(fstrSOLID%materials(i)%mtype)) then
         mats(i)%plastic = 1
@@ -730,6 +792,11 @@ contains
     endif
     deallocate(mats, emat)
     if (nl_thermal) call fsd_init_thermal(ctx, hecMESH, fstrSOLID)
+    nl_hw = 0
+    if (nl_timed) then
+      ierr = fx_nl_get_history(ctx, c_null_ptr, nl_hw)
+      if (ierr /= 0) call fsd_fail('fx_nl_get_history')
+    endif
     if (allocated(b6)) deallocate(b6, bi)
     allocate(b6(6, n_pt), bi(n_pt))
     call fsd_push_state(ctx, fstrSOLID)
@@ -767,7 +834,8 @@ contains
     type(fx_nl_state_view) :: sv
     integer(c_int) :: ierr
     integer :: icel, g, p
-    real(c_double), allocatable, target :: s6(:,:), sb6(:,:), e6b(:,:), pl(:), fs(:)
+    real(c_double), allocatable, target :: s6(:,:), sb6(:,:), e6b(:,:), pl(:), fs(:), hw(:,:)
+    integer :: nf
     allocate(s6(6, n_pt), sb6(6, n_pt), e6b(6, n_pt), pl(n_pt), fs(n_pt))
     bi = 0; fs = 0.d0
     do icel = 1, n_elem      ! every element with its own type's points, at the cumulative point offset
@@ -788,8 +856,42 @@ contains
     sv%latch = -1
     ierr = fx_nl_set_state(ctx, sv)
     if (ierr /= 0) call fsd_fail('fx_nl_set_state')
+    if (nl_hw > 0) then      ! the whole fstatus(:) of the viscoelastic and NORTON points, [point][nl_hw], zero behind a shorter one
+      allocate(hw(nl_hw, n_pt))
+      hw = 0.d0
+      do icel = 1, n_elem
+        if (.not. timed_mtype(fstrSOLID%elements(icel)%gausses(1)%pMaterial%mtype)) cycle
+        do g = 1, el_nq(icel)
+          nf = min(size(fstrSOLID%elements(icel)%gausses(g)%fstatus), int(nl_hw))
+          hw(1:nf, el_p0(icel) + g) = fstrSOLID%elements(icel)%gausses(g)%fstatus(1:nf)
+        enddo
+      enddo
+      ierr = fx_nl_set_history(ctx, c_loc(hw(1,1)), nl_hw)
+      if (ierr /= 0) call fsd_fail('fx_nl_set_history')
+      deallocate(hw)
+    endif
     deallocate(s6, sb6, e6b, pl, fs)
   end subroutine fsd_push_state
+
+  logical function timed_mtype(mtype)
+    integer, intent(in) :: mtype
+    timed_mtype = (mtype == VISCOELASTIC .or. mtype == NORTON)
+  end function timed_mtype
+
+  !> ctime and tincr of the call in hand, as fstr_Newton hands them to fstr_StiffMatrix and fstr_UpdateNewton (tincr = 0 in a STATIC step)
+  subroutine fsd_set_time(time, tincr)
+    real(kind=kreal), intent(in) :: time, tincr
+    nl_time = time
+    nl_tincr = tincr
+  end subroutine fsd_set_time
+
+  subroutine fsd_apply_time(ctx)
+    type(c_ptr), intent(in) :: ctx
+    integer(c_int) :: ierr
+    if (.not. nl_timed) return
+    ierr = fx_nl_set_time(ctx, nl_time, nl_tincr)
+    if (ierr /= 0) call fsd_fail('fx_nl_set_time')
+  end subroutine fsd_apply_time
 
   !> fstr_StiffMatrix on the device; .false. = not covered, the caller runs the reference's routine.
   logical function fsd_stiffness(hecMESH, hecMAT, fstrSOLID)
@@ -839,6 +941,7 @@ contains
       ierr = fx_nl_set_temperature(fxb_context(hecMESH), fstrSOLID%temperature)
       if (ierr /= 0) call fsd_fail('fx_nl_set_temperature')
     endif
+    call fsd_apply_time(fxb_context(hecMESH))
     ierr = fx_nl_stiffness_at(fxb_context(hecMESH), fstrSOLID%unode, fstrSOLID%dunode, ms)
     if (ierr /= 0) call fsd_fail('fx_nl_stiffness_at')
     fxb_matrix_on_device = .true.       ! from here to the solve: hecmw_mat_ass_bc records, hecmw_solve uses the resident matrix
@@ -860,6 +963,7 @@ contains
       ierr = fx_nl_set_temperature(fxb_context(hecMESH), fstrSOLID%temperature)
       if (ierr /= 0) call fsd_fail('fx_nl_set_temperature')
     endif
+    call fsd_apply_time(fxb_context(hecMESH))
     ierr = fx_nl_update_at(fxb_context(hecMESH), fstrSOLID%dunode, fstrSOLID%QFORCE, ms)
     if (ierr /= 0) call fsd_fail('fx_nl_update_at')
     call hecmw_update_3_R(hecMESH, fstrSOLID%QFORCE, hecMESH%n_node)
@@ -996,17 +1100,20 @@ contains
 
   !> fstr_UpdateState on the device, then the history comes back to fstrSOLID%elements (results, restart files and whatever else
   !> of fistr1 reads it) -- once per sub-step, not per Newton iteration.
-  logical function fsd_update_state(hecMESH, fstrSOLID)
+  logical function fsd_update_state(hecMESH, fstrSOLID, tincr)
     type(hecmwST_local_mesh), intent(in) :: hecMESH
     type(fstr_solid), intent(inout), target :: fstrSOLID
+    real(kind=kreal), intent(in) :: tincr      ! fstr_UpdateState's: the two state updates of the time-dependent materials run under tincr > 0
     type(fx_nl_state_view) :: sv
     type(c_ptr) :: ctx
     integer(c_int) :: ierr
-    integer :: icel, g, p
-    real(c_double), allocatable, target :: s6(:,:), pl(:), fs(:)
+    integer :: icel, g, p, nf
+    real(c_double), allocatable, target :: s6(:,:), pl(:), fs(:), hw(:,:)
     fsd_update_state = .false.
     if (.not. ready) return
     ctx = fxb_context(hecMESH)
+    nl_tincr = tincr
+    call fsd_apply_time(ctx)
     ierr = fx_nl_commit(ctx)      ! unode += dunode is the host's (fstr_Newton :156-158); the device does the same on its copy
     if (ierr /= 0) call fsd_fail('fx_nl_commit')
     if (associated(fstrSOLID%temperature)) then      ! the host's copy too (fstr_Update.f90:308-312): fstr_ass_load reads it for the thermal load
@@ -1031,6 +1138,19 @@ contains
         if (associated(fstrSOLID%elements(icel)%gausses(g)%fstatus)) fstrSOLID%elements(icel)%gausses(g)%fstatus(1) = fs(p)
       enddo
     enddo
+    if (nl_hw > 0) then      ! the whole fstatus(:) back: result output, restart files and the host's cutback copies read it
+      allocate(hw(nl_hw, n_pt))
+      ierr = fx_nl_get_history(ctx, c_loc(hw(1,1)), nl_hw)
+      if (ierr /= 0) call fsd_fail('fx_nl_get_history')
+      do icel = 1, n_elem
+        if (.not. timed_mtype(fstrSOLID%elements(icel)%gausses(1)%pMaterial%mtype)) cycle
+        do g = 1, el_nq(icel)
+          nf = min(size(fstrSOLID%elements(icel)%gausses(g)%fstatus), int(nl_hw))
+          fstrSOLID%elements(icel)%gausses(g)%fstatus(1:nf) = hw(1:nf, el_p0(icel) + g)
+        enddo
+      enddo
+      deallocate(hw)
+    endif
     deallocate(s6, pl, fs)
     fsd_update_state = .true.
   end function fsd_update_state

@@ -22,7 +22,7 @@ module hecmw_hip_binding
   ! device-side assembly / stress update driven by fistr1's own fstr_Newton (INTEGRATION.md section 5)
   public :: fx_mesh_view, fx_material_view, fx_nl_state_view, fx_elem_group
   public :: fx_upload, fx_solve_device_matrix, fx_nl_init_sections, fx_nl_init_c3, fx_nl_init_type, fx_nl_init_groups, fx_nl_stiffness_at, fx_nl_update_at, fx_nl_commit, fx_nl_get_state, &
-            fx_nl_set_state, fx_nl_thermal_view, fx_nl_set_thermal, fx_nl_set_temperature, fx_nl_set_last_temp, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, &
+            fx_nl_set_state, fx_nl_thermal_view, fx_nl_set_thermal, fx_nl_set_temperature, fx_nl_set_last_temp, fx_assemble_c3d8_sections, fx_update_c3d8_linear, fx_update_c3d8_linear_prepare, fx_nl_snapshot, fx_nl_set_time, fx_nl_get_history, fx_nl_set_history, &
             fx_assemble_c3, fx_update_c3_linear, fx_assemble_groups, fx_update_groups_linear, fx_update_groups_linear_prepare
   public :: fxb_values_owner, fxb_values_addr
   public :: fxb_matrix_on_device, fxb_defer_bc, fxb_solve_device_matrix, FX_UP_PROFILE
@@ -262,6 +262,21 @@ module hecmw_hip_binding
       type(c_ptr), value :: ctx
       real(c_double) :: temp(*)
     end function fx_nl_set_last_temp
+    integer(c_int) function fx_nl_set_time(ctx, time, tincr) bind(C, name='fx_nl_set_time')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx
+      real(c_double), value :: time, tincr
+    end function fx_nl_set_time
+    integer(c_int) function fx_nl_get_history(ctx, hist, width) bind(C, name='fx_nl_get_history')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: ctx, hist
+      integer(c_int32_t) :: width
+    end function fx_nl_get_history
+    integer(c_int) function fx_nl_set_history(ctx, hist, width) bind(C, name='fx_nl_set_history')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: ctx, hist
+      integer(c_int32_t), value :: width
+    end function fx_nl_set_history
     integer(c_int) function fx_nl_commit(ctx) bind(C, name='fx_nl_commit')
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx

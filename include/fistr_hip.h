@@ -370,21 +370,40 @@ int fx_update_groups_linear_thermal(fx_context *ctx, int32_t n_node, const doubl
  * M_PLCONST1..4 as fstr_ctrl_get_PLASTICITY leaves them (fstr_ctrl_material.f90:451-469).  Hardening is the linear law c + H p; harden
  * must be 0 (the card forces the digit), any of the three nlgeom flags is served.  Both are "plastic" for every piece of history
  * (plstrain, fstat, istat, commit, snapshot) and for the latch: after the first stress update every tangent is the elastic one.
- * Refused with FX_ERROR_UNSUPPORTED: cos(phi) == 0, xi == 0, harden != 0, a kind above 5, and kind 4 / 5 beside a hyperelastic
+ * Refused with FX_ERROR_UNSUPPORTED: cos(phi) == 0, xi == 0, harden != 0, kind 6 and any kind above 8, and kind 4 / 5 beside a hyperelastic
  * material (as Mises is); beside Mises or ELASTIC sections they are served.  The reference's `stop` statements of these branches --
  * `Math Error in Mohr-Coulomb calculation`, `Math error in return mapping`, `Jacobi iteration unable to converge` -- set the
  * context's device error word: fx_nl_stiffness, fx_nl_update, their _at forms and the element-level entry points then return
  * FX_ERROR_RUNTIME with that text.
- * plconst4 was appended at the end of the struct: every older member keeps its offset, the struct grew from 56 to 64 bytes. */
+ * plconst4 was appended at the end of the struct: every older member keeps its offset, the struct grew from 56 to 64 bytes.
+ *
+ * Viscoelastic materials (!VISCOELASTIC; Viscoelastic.f90, restated as written in csrc/fx_visco.h): kind 7 reads E, nu, nlgeom and
+ * tab / ntab as the Prony rows (g_n, tau_n), any number >= 1.  nlgeom is 0 (INFINITE) or 1 (TOTALLAG, the card's default), the two
+ * flags the card reaches (fstr_ctrl_material.f90:277-279); all six solid types and 361 F-bar; beside ELASTIC, Mises, Mohr-Coulomb /
+ * Drucker-Prager and hyperelastic sections.  The material is time-dependent: see fx_nl_set_time below.  MatlMatrix tests
+ * isViscoelastic before its saved flag (calMatMatrix.f90:51), so the latch neither changes this tangent nor is set by this material.
+ * Refused with FX_ERROR_UNSUPPORTED: nlgeom 2, a Prony row with tau == 0, and fx_nl_set_thermal on a context that holds the kind
+ * (the WLF / Arrhenius shift of !TRS and the temperature tables of the card stay out).
+ *
+ * NORTON creep (!CREEP, TYPE=NORTON; creep.f90, restated in csrc/fx_visco.h): kind 8 reads E, nu, nlgeom and plconst = A, n, m.
+ * nlgeom must be 2 (UPDATELAG, the card's default); the five STF_C3 types and 361 B-bar; beside ELASTIC, Mises, Mohr-Coulomb /
+ * Drucker-Prager and viscoelastic sections.  The update routines set isEp for a NORTON element (static_LIB_3d.f90:595): its first
+ * stress update sets the latch whatever tincr is, and iso_creep's tangent is taken only while the latch is clear.  The update writes
+ * gauss%plstrain = dg (the creep strain increment) and fstatus(1) = eqvs; fx_nl_commit adds plstrain to fstatus(2) under tincr > 0.
+ * Refused with FX_ERROR_UNSUPPORTED: nlgeom 0 or 1 (under TOTALLAG the reference relaxes the point's stored stress instead of the
+ * trial one, which defines no usable result), an F-bar group (UPDATELAG is refused there), kind 8 beside a hyperelastic material (the
+ * latch, as for Mises), a time exponent m <= -1 (the law divides by m + 1), fx_nl_set_thermal.  The iteration of update_iso_creep on dg has no bound in the reference (a purely
+ * hydrostatic non-zero stress never leaves it); here it ends after 100 passes or at a dg that is not finite, the point keeps its trial
+ * stress, and fx_nl_update* / fx_nl_element_update return FX_ERROR_RUNTIME with a text that names creep. */
 typedef struct fx_material_view { /* tMaterial after fstr_ctrl_get_ELASTICITY/_PLASTICITY (fstr_ctrl_material.f90:60-106, :341-480) */
   double E, nu;         /* M_YOUNGS, M_POISSON */
   int32_t plastic;      /* material kind.  0: mtype ELASTIC; 1: elastoplastic, Mises; 2: Neo-Hooke / Mooney-Rivlin; 3: Arruda-Boyce;
-                         * 4: elastoplastic, Mohr-Coulomb; 5: elastoplastic, Drucker-Prager */
+                         * 4: elastoplastic, Mohr-Coulomb; 5: elastoplastic, Drucker-Prager; 7: viscoelastic; 8: NORTON creep */
   int32_t harden;       /* fifth digit of mtype: 0 BILINEAR 1 MULTILINEAR 2 SWIFT 3 RAMBERG-OSGOOD */
   int32_t nlgeom;       /* nlgeom_flag: 0 INFINITE 1 TOTALLAG 2 UPDATELAG */
   int32_t ntab;         /* MULTILINEAR: rows of the MC_YIELD table */
   double plconst[3];    /* M_PLCONST1..3 */
-  const double *tab;    /* ntab rows (yield stress, plastic strain) */
+  const double *tab;    /* ntab rows (yield stress, plastic strain); kind 7: ntab Prony rows (g, tau) */
   double plconst4;      /* M_PLCONST4: xi of Drucker-Prager; not read for another kind */
 } fx_material_view;
 typedef struct fx_nl_state_view { /* host arrays, any may be NULL (skipped).  tGaussStatus members (mechgauss.f90:13-22) */
@@ -497,6 +516,26 @@ int fx_newton_substep(fx_context *ctx, double factor0, double factor1, int32_t n
  * |B|/|QFORCE| exceeds it (fstr_solve_NonLinear.f90:140-152, nothing committed); is_linear = fstr_Newton's isLinear
  * (.not. fstrPR%nlgeom, :50-51, :107): one pass without a convergence test. */
 int fx_nl_set_step_control(fx_context *ctx, double maxres, int is_linear);
+
+/* ---- time in the nonlinear static loop (time-dependent materials) ----
+ * fx_nl_set_time: ctime and tincr of the coming sub-step or call, as fstr_Newton hands them to fstr_StiffMatrix, fstr_UpdateNewton
+ *   and fstr_UpdateState (fstr_solve_NonLinear.f90:74, :100, :162; a `!STEP, TYPE=STATIC` step forces tincr = 0, :60-61).  The
+ *   default after any fx_nl_init* is (0, 0).  fx_nl_stiffness*, fx_nl_update*, fx_nl_element_*, fx_nl_commit and fx_newton_substep
+ *   read it.  With tincr == 0 a viscoelastic material computes what an ELASTIC one of the same flag computes
+ *   (calViscoelasticMatrix :108-115; the update routines call StressUpdate only under tincr /= 0, static_LIB_3d.f90:659, :685).
+ *   With tincr > 0 fx_nl_commit also runs updateViscoElasticState and updateViscoState (fstr_Update.f90:327-337).  NORTON reads
+ *   both numbers: aa = A ((time + tincr)**(m+1) - time**(m+1)) / (m+1) with time at the START of the increment (creep.f90:66, :165);
+ *   on a context with a NORTON material a negative or non-finite time or tincr is refused with FX_ERROR_RUNTIME, nothing changed.
+ * fx_nl_get_history / fx_nl_set_history: fstatus(1..W) of every point, hist[point][W] on the host side (points in the order of the
+ *   per-point arrays), W = the largest 12 nrow + 6 of the context's viscoelastic materials (Viscoelastic.f90:247-258: per Prony
+ *   term 6 old and 6 new components of q_n, then the deviatoric strain of the last committed state; a NORTON point has 2: eqvs,
+ *   which is also fstat of the state view, and the accumulated creep strain), zero padding for points
+ *   whose material needs fewer, W = 0 in a context without such a material.  get: *width = W (hist may be NULL to ask for it);
+ *   set: width must be W.  fx_nl_snapshot saves and restores this history with the rest.  (The device keeps it component-major
+ *   over all points, hist[k * n_point + p]: consecutive lanes are consecutive points and read consecutive doubles.) */
+int fx_nl_set_time(fx_context *ctx, double time, double tincr);
+int fx_nl_get_history(fx_context *ctx, double *hist, int32_t *width);
+int fx_nl_set_history(fx_context *ctx, const double *hist, int32_t width);
 
 /* ---- thermal strain in the nonlinear static loop (!TEMPERATURE in an NLSTATIC deck) ----
  * The thermal branches of Update_C3D8Bbar (static_LIB_C3D8.f90:309-455), UPDATE_C3 (static_LIB_3d.f90:602-757) and Update_C3D8Fbar

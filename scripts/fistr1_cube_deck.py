@@ -32,6 +32,14 @@ NLSTATIC decks of the STF_C3 types and of the mixed cube (--etype 341|342|351|35
                                                              the first plastic update every tangent is the elastic one, the sub-steps take 10
                                                              to 40 Newton iterations to CONVERG = 1e-3, and what the linear solves leave
                                                              unconverged stays in the printed stresses (2e-4 of 1.5 at 1e-8).
+  --nl-material visco|visco_inf|norton [--visco-dt DT]       time-dependent MAT1 on ELASTIC 206900 / 0.29 and a `!STEP, TYPE=VISCO` step of
+                                                             SUBSTEPS increments of DT (default 0.5; data line `DT, SUBSTEPS * DT`).
+                                                             visco: `!VISCOELASTIC` with the Prony row 0.5, 1.0 of tutorial 07, total
+                                                             Lagrange; visco_inf: the same with the card's INFINITE parameter.  norton:
+                                                             `!CREEP, TYPE=NORTON` 1e-10, 5, 0 of tutorial 08, updated Lagrange, with a
+                                                             `!STEP, TYPE=STATIC` step of one increment in front (time 0 to 1), so that the
+                                                             VISCO step starts from a stressed state; its boundary group is applied a second
+                                                             time by the VISCO step.  --two-sections: MAT2 is Mises BILINEAR, as for drucker / mohr.
 --form361 FI|BBAR|IC|FBAR (TYPE=361 cubes, linear or NLSTATIC): `!SECTION, SECNUM=1, FORM361=...` (fstr_ctrl_common.f90:303-320), and the
 same for SECNUM=2 with --two-sections; without it the program's default (IC in a linear analysis, B-bar under NLSTATIC).
 --thermal (with --linear): a thermal-stress deck.  `!REFTEMP 20`, `!INITIAL CONDITION, TYPE=TEMPERATURE` (ALL, 25) in the mesh file,
@@ -63,14 +71,22 @@ if "--mixed" in sys.argv:
 nlmat = "multilinear"                # --nl-material (NLSTATIC decks): MAT1 = multilinear (default) | bilinear | elastic_tl | elastic_ul
 if "--nl-material" in sys.argv:
     k = sys.argv.index("--nl-material"); nlmat = sys.argv[k + 1]; del sys.argv[k:k + 2]
-    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul", "neohooke", "mooney", "arruda", "drucker", "mohr"):
-        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl, elastic_ul, neohooke, mooney, arruda, drucker or mohr, without --linear")
+    if linear or nlmat not in ("multilinear", "bilinear", "elastic_tl", "elastic_ul", "neohooke", "mooney", "arruda", "drucker", "mohr",
+                               "visco", "visco_inf", "norton"):
+        sys.exit("--nl-material takes multilinear, bilinear, elastic_tl, elastic_ul, neohooke, mooney, arruda, drucker, mohr, visco, "
+                 "visco_inf or norton, without --linear")
 hyper = nlmat in ("neohooke", "mooney", "arruda")
 yieldf = nlmat in ("drucker", "mohr")
+timed = nlmat in ("visco", "visco_inf", "norton")   # a `!STEP, TYPE=VISCO` step
+visco_dt = 0.5
+if "--visco-dt" in sys.argv:
+    k = sys.argv.index("--visco-dt"); visco_dt = float(sys.argv[k + 1]); del sys.argv[k:k + 2]
+    if not timed:
+        sys.exit("--visco-dt needs --nl-material visco, visco_inf or norton")
 two = "--two-sections" in sys.argv
 if two:
     sys.argv.remove("--two-sections")
-    if not linear and etype == 361 and not mixed and not hyper and not yieldf:
+    if not linear and etype == 361 and not mixed and not hyper and not yieldf and not timed:
         sys.exit("--two-sections needs --linear, or --etype 341|342|351|352|362, or --mixed, or a hyperelastic or drucker / mohr --nl-material")
 thermal = "--thermal" in sys.argv
 if thermal:
@@ -181,12 +197,20 @@ NL_MATERIALS = {
     "arruda": "!HYPERELASTIC, TYPE=ARRUDA-BOYCE\n 0.71, 1.7029, 0.1408\n",
     "drucker": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=DRUCKER-PRAGER\n 300.0, 20.0, 2000.0\n",
     "mohr": "!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MOHR-COULOMB\n 300.0, 5.0, 20000.0\n",
+    "visco": "!ELASTIC\n 206900.0, 0.29\n!VISCOELASTIC\n 0.5, 1.0\n",
+    "visco_inf": "!ELASTIC\n 206900.0, 0.29\n!VISCOELASTIC, INFINITE\n 0.5, 1.0\n",
+    "norton": "!ELASTIC\n 206900.0, 0.29\n!CREEP, TYPE=NORTON\n 1.0e-10, 5.0, 0.0\n",
 }
 MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 70000.0, 0.33\n"
 if hyper:
     MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 2.5, 0.3\n"
-if yieldf:
+if yieldf or timed:
     MAT2 = "!MATERIAL, NAME=MAT2\n!ELASTIC\n 206900.0, 0.29\n!PLASTIC, YIELD=MISES, HARDEN=BILINEAR\n 450.0, 2000.0\n"
+STEPS = "!STEP, SUBSTEPS=%d, CONVERG=1.0e-3\n BOUNDARY, 1\n" % nsub
+if timed:
+    STEPS = "!STEP, TYPE=VISCO, SUBSTEPS=%d, CONVERG=1.0e-3\n %r, %r\n BOUNDARY, 1\n" % (nsub, visco_dt, nsub * visco_dt)
+    if nlmat == "norton":
+        STEPS = "!STEP, TYPE=STATIC, SUBSTEPS=1, CONVERG=1.0e-3\n BOUNDARY, 1\n" + STEPS
 with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
     if not linear:
       fh.write("""!VERSION
@@ -197,16 +221,14 @@ with open(os.path.join(d, "cube.cnt"), "a" if linear else "w") as fh:
  FIX, 1, 3, 0.0
  TOP, 3, 3, %g
  TOP, 1, 1, %g
-!STEP, SUBSTEPS=%d, CONVERG=1.0e-3
- BOUNDARY, 1
-!MATERIAL, NAME=MAT1
+%s!MATERIAL, NAME=MAT1
 %s%s%s!RESTART, FREQUENCY=100000
 !SOLVER,METHOD=%s,PRECOND=%s,ITERLOG=NO,TIMELOG=YES
  5000, 1
  %s, 1.0, 0.0
 !END
-""" % (strain * n, 0.2 * strain * n, nsub, NL_MATERIALS[nlmat],
-       MAT2 if two else "", SECTIONS, method, precond, "1.0e-12" if yieldf else "1.0e-8"))
+""" % (strain * n, 0.2 * strain * n, STEPS, NL_MATERIALS[nlmat],
+       MAT2 if two else "", SECTIONS, method, precond, "1.0e-12" if yieldf or timed else "1.0e-8"))
 with open(os.path.join(d, "hecmw_ctrl.dat"), "w") as fh:
     fh.write("!MESH, NAME=fstrMSH,TYPE=HECMW-ENTIRE\n cube.msh\n!CONTROL,NAME=fstrCNT\n cube.cnt\n"
              "!RESULT,NAME=fstrRES,IO=OUT\n out.res\n!RESTART,NAME=restart_out,IO=OUT\n out.restart\n")
