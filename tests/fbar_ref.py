@@ -307,9 +307,10 @@ def gpu_material(family, nlgeom, c):
     return Y.gpu_material(family, nlgeom, c)
 
 
-def trial_stresses(family, nlgeom, seed):
-    """The trial stresses of a plastic case's first update: the same update with a yield surface no point reaches"""
-    m = H.gpu_mesh(361)
+def trial_stresses(family, nlgeom, seed, mesh=None):
+    """The trial stresses of a plastic case's first update: the same update with a yield surface no point reaches.  mesh: another
+    mesh than hyper_ref.gpu_mesh(361)"""
+    m = H.gpu_mesh(361) if mesh is None else mesh
     ref = Model(m.coord, m.conn, gpu_material(family, nlgeom, 1.0e12))
     ref.unode[:], ref.dunode[:] = H.random_displacement(m.coord, seed, Y.GPU_AMP)
     ref.element_update()
@@ -324,10 +325,13 @@ def margins_hold(family, mat, trial):
     return Y.margins_hold(mat, Y.point_report(mat, trial))
 
 
-def search_plastic_case(family, seeds=range(1, 200)):
-    """How PLASTIC_CASES was filled (yield_ref.search_gpu_case on the F-bar trial stresses, flags INFINITE and TOTALLAG)"""
+def search_plastic_case(family, seeds=range(1, 200), mesh=None, elems=None):
+    """How PLASTIC_CASES was filled (yield_ref.search_gpu_case on the F-bar trial stresses, flags INFINITE and TOTALLAG).  mesh, elems:
+    on another mesh, at the points of those of its elements (SHAPE_CASES)"""
     for seed in seeds:
-        trial = {g: trial_stresses(family, g, seed) for g in (INFINITE, TOTALLAG)}
+        trial = {g: trial_stresses(family, g, seed, mesh) for g in (INFINITE, TOTALLAG)}
+        if elems is not None:
+            trial = {g: t.reshape(-1, 8, 6)[elems].reshape(-1, 6) for g, t in trial.items()}
         if family == "mises":
             crit = T.mises(trial[INFINITE])
         else:

@@ -601,19 +601,40 @@ MOHR_C, MOHR_PHI, MOHR_H = 250.0, 5.0, 20000.0               # the Mohr-Coulomb 
 HYPER_E, HYPER_NU = 2.5, 0.3                                 # the ELASTIC partner of the hyperelastic material (the hyperelastic decks' second section)
 
 
-def material(kind, fam, tables=False, flag=None):
-    """flag: the NLGEOM flag where the kind leaves a choice (default: TOTALLAG for ELASTIC, mises_flag for the elastoplastic ones)"""
+# The cohesion of the Drucker-Prager material in the thermal cases of tests/nl_shapes.py where DRUCKER_C leaves a point within 10 tol
+# of the yield edge (case id -> c): the first of 160, 140, 170, 130, ... at which test_nl_thermal_ref.check_plastic_points holds on
+# the case's mesh, deal and temperatures (search_shape_cohesion).  Every other case keeps DRUCKER_C: 32 .. 71 % of its points yield.
+SHAPE_COHESION = {"362_th_solo_dp_ul": 160.0, "362_th_mix_dp": 160.0}
+
+
+def search_shape_cohesion(case, check, cs=(160, 140, 170, 130, 180, 120, 190, 110, 200)):
+    """case: nl_shapes.ThermalCase; check: test_nl_thermal_ref.check_plastic_points"""
+    for c in cs:
+        case.cohesion = float(c)
+        try:
+            check(case.build())
+            return float(c)
+        except AssertionError:
+            pass
+        finally:
+            case.cohesion = None
+    raise RuntimeError("no cohesion found")
+
+
+def material(kind, fam, tables=False, flag=None, c=None):
+    """flag: the NLGEOM flag where the kind leaves a choice (default: TOTALLAG for ELASTIC, mises_flag for the elastoplastic ones);
+    c: another cohesion (drucker, mohr) or yield stress (mises) than the module's"""
     from oracle.refrun import Material
     if kind == "elastic":
         m = Material(E0, NU0, nlgeom=TOTALLAG if flag is None else flag)
     elif kind == "soft":
         m = Material(HYPER_E, HYPER_NU, nlgeom=TOTALLAG)
     elif kind == "mises":
-        m = Material(E0, NU0, plastic=True, harden=0, plconst=(450.0, 2000.0, 0.0), nlgeom=mises_flag(fam) if flag is None else flag)
+        m = Material(E0, NU0, plastic=True, harden=0, plconst=(450.0 if c is None else c, 2000.0, 0.0), nlgeom=mises_flag(fam) if flag is None else flag)
     elif kind == "drucker":
-        m = Y.drucker_prager(E0, NU0, DRUCKER_C, DRUCKER_PHI, DRUCKER_H, nlgeom=mises_flag(fam) if flag is None else flag)
+        m = Y.drucker_prager(E0, NU0, DRUCKER_C if c is None else c, DRUCKER_PHI, DRUCKER_H, nlgeom=mises_flag(fam) if flag is None else flag)
     elif kind == "mohr":
-        m = Y.mohr_coulomb(E0, NU0, MOHR_C, MOHR_PHI, MOHR_H, nlgeom=mises_flag(fam) if flag is None else flag)
+        m = Y.mohr_coulomb(E0, NU0, MOHR_C if c is None else c, MOHR_PHI, MOHR_H, nlgeom=mises_flag(fam) if flag is None else flag)
     elif kind == "hyper":
         m = H.mooney_rivlin(0.1486, 0.4849, 0.0789)
     else:
@@ -667,17 +688,24 @@ def node_temperatures(coord, lo, hi, seed):
     return lo + (hi - lo) * np.clip(s + 0.15 * rng.uniform(-1, 1, x.shape[0]), 0.0, 1.0)
 
 
-def gpu_case(fam, variant):
-    """-> dict(mesh, groups, mats, elem_mats, ref_temp, temp_init, last_temp, temperature, unode, dunode).  Variants:
+def gpu_case(fam, variant, mesh=None, mats=None, elem_mat=None):
+    """mesh, mats, elem_mat: another mesh of the family with these materials dealt over it (the temperatures of the `tables` variant).
+    -> dict(mesh, groups, mats, elem_mats, ref_temp, temp_init, last_temp, temperature, unode, dunode).  Variants:
     one / cube: ELASTIC total Lagrange, constants; two: ELASTIC and Mises in one group with last_temp, temp_init and ref_temp all
     different; tables: both materials with both tables, node temperatures from below the first row to above the last; yield: the
     same with a Drucker-Prager material (E(T), nu(T) inside its return mapping); mohr: the same with Mohr-Coulomb; hyper: a Mooney-Rivlin material (tt0 is the initial
     condition, the stored strain is dstrain + EPSTH) beside a soft ELASTIC one, tables; infinite: both materials INFINITE;
     updatelag: ELASTIC and Mises both UPDATELAG (at the STF_C3 types the branch that rounds to single precision)."""
     et = family_type(fam)
-    m = family_mesh(fam, {"one": "one", "cube": "cube"}.get(variant, "small"))
+    m = family_mesh(fam, {"one": "one", "cube": "cube"}.get(variant, "small")) if mesh is None else mesh
     two = variant not in ("one", "cube")
     tab = variant in ("tables", "yield", "mohr", "hyper")
+    if mats is not None:
+        lo, hi = -60.0, 380.0
+        unode, dunode = H.random_displacement(m.coord, 17, AMP)
+        return dict(mesh=m, groups=[(et, m.conn, 4 if fam == "361f" else 2, elem_mat)], mats=list(mats), elem_mats=[elem_mat], ref_temp=REF_TEMP,
+                    temp_init=node_temperatures(m.coord, 15.0, 35.0, 3), last_temp=node_temperatures(m.coord, lo, 0.5 * (lo + hi), 5),
+                    temperature=node_temperatures(m.coord, lo, hi, 7), unode=unode, dunode=dunode)
     mats = {"two": ("elastic", "mises"), "tables": ("elastic", "mises"), "yield": ("elastic", "drucker"), "mohr": ("elastic", "mohr"),
             "hyper": ("soft", "hyper"),
             "infinite": ("elastic", "mises"), "updatelag": ("elastic", "mises")}.get(variant, ("elastic",))

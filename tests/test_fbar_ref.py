@@ -157,12 +157,15 @@ def test_too_small_volume_stops():
 GPU_ELASTIC = [("elastic", F.INFINITE), ("elastic", F.TOTALLAG), ("neohooke", F.TOTALLAG), ("mooney", F.TOTALLAG), ("arruda", F.TOTALLAG)]
 
 
-def _longdouble_model(m, mat, unode, dunode):
+def _longdouble_model(m, mat, unode, dunode, elems=None):
+    """mat: one material, or a function of the element index; elems: these elements only (tests/test_nl_shapes.py: a section)"""
     ld = np.longdouble
     coord, u, du = m.coord.astype(ld), unode.astype(ld).reshape(-1, 3), dunode.astype(ld).reshape(-1, 3)
     z = np.zeros(8)
     out = dict(k0=[], qf=[], stress=[], strain=[], k1=[])
-    for nd in m.conn - 1:
+    mat_of = mat if callable(mat) else (lambda e: mat)
+    for e in (range(m.conn.shape[0]) if elems is None else elems):
+        nd, mat = m.conn[e] - 1, mat_of(e)
         out["k0"].append(F.stf_c3d8fbar(coord[nd], u[nd] + du[nd], mat, 0, np.zeros((8, 6), dtype=ld), np.zeros((8, 6), dtype=ld), z, z))
         qf, s, e, _, _ = F.update_c3d8fbar(coord[nd], u[nd], du[nd], mat, z, z.astype(np.int32), z)
         out["k1"].append(F.stf_c3d8fbar(coord[nd], u[nd] + du[nd], mat, 0, e, s, z, z))
@@ -185,10 +188,14 @@ def test_gpu_inputs_are_well_conditioned(name, flag):
     got.update(stress=ref.st["stress"], strain=ref.st["strain"], k1=ref.element_tangents())
     want = _longdouble_model(m, mat, unode, dunode)
     assert np.abs(ref.st["strain"]).max() > 0.02, "the inputs do not strain the material"
+    check_against_longdouble(got, want, "%s %d" % (name, flag))
+
+
+def check_against_longdouble(got, want, tag):
     for k, w in want.items():
         assert w.dtype == np.longdouble
         err = float(np.abs(got[k] - w).max() / np.abs(w).max())
-        print("%s %d %s: float64 vs long double %.2e" % (name, flag, k, err))
+        print("%s %s: float64 vs long double %.2e" % (tag, k, err))
         assert err <= 1e-12, (k, err)
 
 

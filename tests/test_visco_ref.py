@@ -124,6 +124,12 @@ def test_gpu_inputs_are_well_conditioned(cid):
     of 10; every NORTON point takes the same number of iterations in both precisions, at most a quarter of the device's cap; and in
     each update at least half of the NORTON points have a creep strain increment above 1e-6 of their elastic strain increment."""
     parts, amp = ALL_CASES[cid]()
+    check_conditioning(cid, parts, amp)
+
+
+def check_conditioning(cid, parts, amp):
+    """the conditions of test_gpu_inputs_are_well_conditioned on the Models `parts` of one case (tests/test_nl_shapes.py runs them on
+    its meshes too)"""
     ld = np.longdouble
     pts = []
     for model in parts:

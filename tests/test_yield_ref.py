@@ -97,31 +97,37 @@ def test_gpu_inputs_are_well_conditioned(etype, family):
         pytest.skip("np.longdouble is no wider than float64 on this platform")
     for nlgeom in (Y.INFINITE, Y.TOTALLAG, Y.UPDATELAG):
         _, mat, _, _ = Y.gpu_case(etype, family, nlgeom)
-        trial = Y.trial_stresses(etype, family, nlgeom)
-        rep = Y.point_report(mat, trial)
-        # ---- the margins, as conditions
-        assert np.all(np.abs(np.abs(rep["f"]) - Y.TOL) >= 10 * Y.TOL), "a point within 10 tol of the |f| < tol edge"
-        assert not rep["reset"].any(), "a return ended through the dlambda < 0 reset"
-        if family == "mohr":
-            assert np.abs(rep["sin3"]).max() <= 0.95 and np.abs(rep["sin3_ret"]).max() <= 0.95
-            assert rep["gap"].min() >= 1.0e-6
-        plastic = rep["istat"].mean()
-        assert plastic >= 0.25 and 1.0 - plastic >= 0.10, plastic
-        assert Y.margins_hold(mat, rep)
-        # ---- float64 against long double from the same trial stresses
-        smax, dmax = np.abs(rep["stress"]).max(), np.abs(rep["tangent"]).max()
-        fmax = np.abs(rep["fstat"]).max()
-        worst = [0.0, 0.0, 0.0]
-        for k, s in enumerate(trial):
-            sl, il, fl = Y.backward_euler(mat, s.astype(np.longdouble), 0.0, 0, np.longdouble(0))
-            Dl = Y.elastoplastic_matrix(mat, sl, il, fl)
-            assert sl.dtype == np.longdouble and Dl.dtype == np.longdouble and il == rep["istat"][k]
-            worst[0] = max(worst[0], float(np.abs(sl - rep["stress"][k]).max()) / smax)
-            worst[1] = max(worst[1], abs(float(fl) - rep["fstat"][k]) / fmax)
-            worst[2] = max(worst[2], float(np.abs(Dl - rep["tangent"][k]).max()) / dmax)
-        print("%d %s nlgeom %d: %d points, %.0f %% plastic, min ||f| - tol| %.3g, float64 vs long double: stress %.1e fstat %.1e tangent %.1e"
-              % (etype, family, nlgeom, len(trial), 100 * plastic, np.abs(np.abs(rep["f"]) - Y.TOL).min(), *worst))
-        assert max(worst) <= 1e-12
+        check_points(mat, Y.trial_stresses(etype, family, nlgeom), "%d %s nlgeom %d" % (etype, family, nlgeom))
+
+
+def check_points(mat, trial, tag):
+    """the margins and the float64 / long double agreement of test_gpu_inputs_are_well_conditioned on the trial stresses of one
+    material (tests/test_nl_shapes.py runs them on its meshes too)"""
+    family = "mohr" if mat.kind == Y.MOHR else "drucker"
+    rep = Y.point_report(mat, trial)
+    # ---- the margins, as conditions
+    assert np.all(np.abs(np.abs(rep["f"]) - Y.TOL) >= 10 * Y.TOL), "a point within 10 tol of the |f| < tol edge"
+    assert not rep["reset"].any(), "a return ended through the dlambda < 0 reset"
+    if family == "mohr":
+        assert np.abs(rep["sin3"]).max() <= 0.95 and np.abs(rep["sin3_ret"]).max() <= 0.95
+        assert rep["gap"].min() >= 1.0e-6
+    plastic = rep["istat"].mean()
+    assert plastic >= 0.25 and 1.0 - plastic >= 0.10, plastic
+    assert Y.margins_hold(mat, rep)
+    # ---- float64 against long double from the same trial stresses
+    smax, dmax = np.abs(rep["stress"]).max(), np.abs(rep["tangent"]).max()
+    fmax = np.abs(rep["fstat"]).max()
+    worst = [0.0, 0.0, 0.0]
+    for k, s in enumerate(trial):
+        sl, il, fl = Y.backward_euler(mat, s.astype(np.longdouble), 0.0, 0, np.longdouble(0))
+        Dl = Y.elastoplastic_matrix(mat, sl, il, fl)
+        assert sl.dtype == np.longdouble and Dl.dtype == np.longdouble and il == rep["istat"][k]
+        worst[0] = max(worst[0], float(np.abs(sl - rep["stress"][k]).max()) / smax)
+        worst[1] = max(worst[1], abs(float(fl) - rep["fstat"][k]) / fmax)
+        worst[2] = max(worst[2], float(np.abs(Dl - rep["tangent"][k]).max()) / dmax)
+    print("%s: %d points, %.0f %% plastic, min ||f| - tol| %.3g, float64 vs long double: stress %.1e fstat %.1e tangent %.1e"
+          % (tag, len(trial), 100 * plastic, np.abs(np.abs(rep["f"]) - Y.TOL).min(), *worst))
+    assert max(worst) <= 1e-12
 
 
 @pytest.mark.parametrize("etype", [361, 342, 352])

@@ -577,10 +577,10 @@ def gpu_history(model, seed):
     return h
 
 
-def gpu_case(etype, rows="one", nlgeom=TOTALLAG, fbar=False, seed=17, mats=None, elem_mat=None):
+def gpu_case(etype, rows="one", nlgeom=TOTALLAG, fbar=False, seed=17, mats=None, elem_mat=None, mesh=None):
     """(mesh, Model) of a GPU comparison: hyper_ref.gpu_mesh, hyper_ref.random_displacement at GPU_AMP, a committed history, tincr =
-    TINCR.  mats / elem_mat: several sections instead of the one viscoelastic material."""
-    m = H.gpu_mesh(etype)
+    TINCR.  mats / elem_mat: several sections instead of the one viscoelastic material.  mesh: another mesh of the type."""
+    m = H.gpu_mesh(etype) if mesh is None else mesh
     model = Model(etype, m.coord, m.conn, gpu_material(rows, nlgeom) if mats is None else mats, elem_mat, fbar=fbar)
     model.unode[:], model.dunode[:] = H.random_displacement(m.coord, seed, GPU_AMP)
     model.hist = gpu_history(model, seed)
@@ -613,11 +613,11 @@ def creep_material():
     return NortonMaterial(206900.0, 0.29, 1.0e-10, 5.0, 0.0)
 
 
-def creep_case(etype, seed=17, mats=None, elem_mat=None):
+def creep_case(etype, seed=17, mats=None, elem_mat=None, mesh=None):
     """(mesh, Model) of a NORTON GPU comparison: a committed state as a previous sub-step would have left it (stress_bak = D strain_bak,
     a creep strain increment in plstrain, an accumulated one in fstatus(2)), displacement fields of size CREEP_AMP, the time pair
-    (CREEP_TIME, CREEP_TINCR), latch clear."""
-    m = H.gpu_mesh(etype)
+    (CREEP_TIME, CREEP_TINCR), latch clear.  mesh: another mesh of the type than hyper_ref.gpu_mesh."""
+    m = H.gpu_mesh(etype) if mesh is None else mesh
     model = Model(etype, m.coord, m.conn, creep_material() if mats is None else mats, elem_mat)
     model.unode[:], model.dunode[:] = H.random_displacement(m.coord, seed, CREEP_AMP)
     rng = np.random.default_rng(seed)

@@ -576,6 +576,20 @@ GPU_CASES = {(361, "drucker"): (8, 228.0), (361, "mohr"): (19, 337.0), (341, "dr
              (342, "drucker"): (8, 235.0), (342, "mohr"): (76, 245.0), (351, "drucker"): (8, 232.0), (351, "mohr"): (19, 350.0),
              (352, "drucker"): (8, 230.0), (352, "mohr"): (128, 239.0), (362, "drucker"): (8, 220.0),
              (362, "mohr"): (128, 228.0)}          # (etype, family) -> (seed, c), from search_gpu_case
+# The elastoplastic cases of tests/nl_shapes.py, on its meshes: (mesh name of nl_shapes.mesh_of, which) -> (seed, c).  "all":
+# Drucker-Prager on every element, from search_gpu_case(..., mesh=) over seeds 1..39; "colour1": the same with elems= the 48 elements
+# of the mesh's second colour (no seed of 1..39 meets the margins at all 2744 points of the 7^3 cube); "mohr": Mohr-Coulomb, from
+# search_gpu_case(etype, "mohr", mesh=) (gpu352 / gpu362 are hyper_ref.gpu_mesh: GPU_CASES' values); "mises": seed 8 and the yield
+# stress of search_mises_stress on the trial stresses of the case's three sections.
+SHAPE_CASES = {("cube4", "all"): (8, 234.0), ("cubedup4", "all"): (8, 226.0), ("cube7", "colour1"): (8, 219.0), ("3414", "all"): (8, 233.0),
+               ("3423", "all"): (8, 229.0), ("3514", "all"): (8, 233.0), ("gpu352", "all"): (8, 230.0), ("gpu362", "all"): (8, 220.0),
+               # F-bar, from fbar_ref.search_plastic_case(..., mesh=, elems=) on the F-bar trial stresses (INFINITE and TOTALLAG)
+               ("cube4", "fbar"): (1, 412.0), ("cube5", "fbar colours 1, 2"): (1, 414.0), ("cube4", "fbar mohr"): (1, 426.0),
+               ("cube4", "fbar mises"): (8, 508.0),
+               ("cube4", "mohr"): (19, 356.0), ("3414", "mohr"): (71, 420.0), ("3423", "mohr"): (128, 250.0), ("3514", "mohr"): (71, 420.0),
+               ("gpu352", "mohr"): (128, 239.0), ("gpu362", "mohr"): (128, 228.0),
+               ("cube7", "mises"): (8, 524.0), ("3414", "mises"): (8, 521.0), ("3423", "mises"): (8, 524.0), ("3514", "mises"): (8, 523.0),
+               ("gpu352", "mises"): (8, 523.0), ("gpu362", "mises"): (8, 521.0)}
 
 
 def gpu_material(family, nlgeom, c):
@@ -583,18 +597,19 @@ def gpu_material(family, nlgeom, c):
     return f(GPU_E, GPU_NU, c, GPU_PHI, GPU_H, nlgeom=nlgeom)
 
 
-def gpu_case(etype, family, nlgeom, seed=None, c=None):
-    """(mesh, material, unode, dunode) of one GPU comparison"""
+def gpu_case(etype, family, nlgeom, seed=None, c=None, mesh=None):
+    """(mesh, material, unode, dunode) of one GPU comparison.  mesh: another mesh of the type than hyper_ref.gpu_mesh (seed and c
+    are then the caller's, SHAPE_CASES)"""
     if seed is None:
         seed, c = GPU_CASES[(etype, family)]
-    m = H.gpu_mesh(etype)
+    m = H.gpu_mesh(etype) if mesh is None else mesh
     unode, dunode = H.random_displacement(m.coord, seed, GPU_AMP)
     return m, gpu_material(family, nlgeom, c), unode, dunode
 
 
-def trial_stresses(etype, family, nlgeom, seed=None, c=None):
+def trial_stresses(etype, family, nlgeom, seed=None, c=None, mesh=None):
     """The trial stresses of gpu_case's first update: the same update with a cohesion no point reaches"""
-    m, _, unode, dunode = gpu_case(etype, family, nlgeom, seed, c)
+    m, _, unode, dunode = gpu_case(etype, family, nlgeom, seed, c, mesh)
     ref = Model(etype, m.coord, m.conn, gpu_material(family, nlgeom, 1.0e12))
     ref.unode[:], ref.dunode[:] = unode, dunode
     ref.element_update()
@@ -632,11 +647,14 @@ def margins_hold(mat, rep):
     return bool(ok)
 
 
-def search_gpu_case(etype, family, seeds=range(1, 200)):
-    """How GPU_CASES was filled: the first seed, and the cohesion (a round number near the 45th percentile of the points' critical
-    cohesions, then lower ones), at which the margins hold under all three flags."""
+def search_gpu_case(etype, family, seeds=range(1, 200), mesh=None, elems=None):
+    """How GPU_CASES (and, with a mesh, SHAPE_CASES) was filled: the first seed, and the cohesion (a round number near the 45th
+    percentile of the points' critical cohesions, then lower ones), at which the margins hold under all three flags.  elems: at the
+    points of those elements of the mesh only."""
     for seed in seeds:
-        trial = {g: trial_stresses(etype, family, g, seed, 1.0) for g in (INFINITE, TOTALLAG, UPDATELAG)}
+        trial = {g: trial_stresses(etype, family, g, seed, 1.0, mesh) for g in (INFINITE, TOTALLAG, UPDATELAG)}
+        if elems is not None:
+            trial = {g: t.reshape(mesh.conn.shape[0], -1, 6)[elems].reshape(-1, 6) for g, t in trial.items()}
         probe = gpu_material(family, INFINITE, 0.0)
         k = np.cos(probe.plconst[2]) if family == "mohr" else probe.plconst4
         crit = np.array([cal_yield_func(probe, s, 0.0) for s in trial[INFINITE]]) / k
@@ -691,6 +709,23 @@ def mixed_case(etype, other):
     second = (RefMaterial(GPU_E, GPU_NU, plastic=True, harden=0, plconst=(sy, GPU_H, 0.0), nlgeom=UPDATELAG) if other == "mises"
               else RefMaterial(GPU_E, GPU_NU, nlgeom=TOTALLAG))
     return m, [mat, second], mixed_deal(m.n_elem), unode, dunode
+
+
+def mises_margins_hold(trials, sy):
+    """every Mises point 10 tol away from the |f| < tol edge of its return, a tenth of each section's points on either side"""
+    return all(bool(np.all(np.abs(np.abs(mises_f(t, sy)) - TOL) >= 10 * TOL)) and (mises_f(t, sy) > 0).mean() >= 0.10
+               and (mises_f(t, sy) < 0).mean() >= 0.10 for t in trials)
+
+
+def search_mises_stress(trials):
+    """How the yield stresses of SHAPE_CASES were filled: the round number nearest the median Mises stress of the sections' trial
+    stresses (then the next ones on either side) at which mises_margins_hold"""
+    sy0 = float(np.round(np.median(T.mises(np.concatenate(trials))), 0))
+    for d in range(0, 200):
+        for sy in ((sy0 + d, sy0 - d) if d else (sy0,)):
+            if sy > 1.0 and mises_margins_hold(trials, sy):
+                return sy
+    raise RuntimeError("no yield stress found")
 
 
 def mises_f(trial, sy):
