@@ -447,6 +447,7 @@ static void nl_free(fx_context *c);  // fx_nonlinear_host.h
 static void nn_free(fx_context *c);  // fx_nn_host.h
 static void graphs_destroy(fx_context *c);
 static void upd_stage_free(fx_context *c);  // fx_assemble_groups.h
+static void heat_free(fx_context *c);       // fx_heat.h
 static void asm_groups_free(fx_context *c) {  // the cache of the linear assembly: colourings and maps of the last call's groups
   for (ElemColors &ec : c->asm_groups.ec) { dev_free(ec.order); dev_free(ec.pos); dev_free(ec.dup); }
   c->asm_groups = AsmGroups();
@@ -489,6 +490,7 @@ extern "C" void fx_destroy(fx_context *c) {
   nl_free(c);
   nn_free(c);
   upd_stage_free(c);
+  heat_free(c);
   free_precond(c);
   free_matrix(c);
   arena_destroy(c);
@@ -3155,5 +3157,6 @@ extern "C" int fx_get_ssor_ordering(fx_context *c, int32_t *perm, int32_t *color
 #include "fx_assemble_host.h"
 #include "fx_update_linear.h"
 #include "fx_assemble_groups.h"
+#include "fx_heat.h"
 #include "fx_nonlinear_host.h"
 #include "fx_debug_host.h"

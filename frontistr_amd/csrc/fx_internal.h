@@ -215,6 +215,19 @@ struct AsmGroups {
   bool first_write = false;  // the maps carry those flags and every block of the profile is covered: no clearing
 };
 
+// The one cache of the heat assembly (fx_heat.h): the caller's scalar profile with room for its values, one ElemColors per
+// group (by position in the call; `pos` is the position map into that profile, without first-write flags: the matrix is cleared),
+// the quadrature tables of the element types used so far, and what the tests read through fx_heat_get_stats.
+struct HeatAsm {
+  uint64_t prof_key = 0;  // checksum of the profile the device copy (and every map) belongs to; 0 = none
+  int32_t NP = 0, NPL = 0, NPU = 0;
+  int32_t *indexL = nullptr, *itemL = nullptr, *indexU = nullptr, *itemU = nullptr;
+  double *D = nullptr, *AL = nullptr, *AU = nullptr, *B = nullptr;
+  std::vector<ElemColors> ec;
+  double *rule[6][2] = {};  // per type (341, 342, 351, 352, 361, 362): conductivity and capacity tables (H, dR, dS, dT, W)
+  int64_t n_colourings = 0, n_maps = 0, n_profile = 0, n_calls = 0, copy_us = 0;
+};
+
 // Pinned host staging of the results of the linear stress update (grown on demand, owned by the context): 2 x 6 nq doubles per
 // element would otherwise cross PCIe through pageable memory at a fraction of the link rate.  The pointers an update returns
 // are valid until the next update or prepare on the same context, or fx_destroy.
@@ -550,6 +563,7 @@ struct fx_context {
   NlDev nl;
   AsmGroups asm_groups;   // the linear assembly entry points
   UpdStage upd_stage;     // the linear stress update entry points
+  HeatAsm heat;           // fx_heat_assemble_groups
   void *nn = nullptr;  // NnDev (fx_nn_host.h): systems with NDOF != 3
   const void *host_D = nullptr, *host_AL = nullptr, *host_AU = nullptr;  // the caller's arrays of the last value upload (fx_solve)
   // timing

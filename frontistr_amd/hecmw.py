@@ -75,6 +75,18 @@ class _ThermalView(C.Structure):    # fx_thermal_view
     _fields_ = [("temp", C.c_void_p), ("temp0", C.c_void_p), ("ref_temp", C.c_double), ("alpha", C.c_void_p)]
 
 
+class _HeatTable(C.Structure):      # fx_heat_table
+    _fields_ = [("ntab", C.c_int32), ("temp", C.c_void_p), ("funcA", C.c_void_p), ("funcB", C.c_void_p)]
+
+
+class _HeatMaterialView(C.Structure):   # fx_heat_material_view
+    _fields_ = [("cond", _HeatTable), ("cp", _HeatTable), ("rho", _HeatTable)]
+
+
+class _HeatView(C.Structure):       # fx_heat_view
+    _fields_ = [("temp", C.c_void_p), ("temp0", C.c_void_p), ("beta", C.c_double), ("dtime", C.c_double)]
+
+
 def lib():
     """Load libfistr_hip.so (built by `make -C frontistr_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -592,6 +604,65 @@ class SolverContext:
         stress = [_staged(pt[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
         del keep
         return strain, stress, qf, ms.value
+
+    # --- heat conduction (frontistr_amd/heat.py drives these) ----------
+    @staticmethod
+    def _heat_materials(mats):
+        """fx_heat_material_view[] of heat.tHeatMaterial objects (anything with .cond / .cp / .rho = (ntab, temp, funcA, funcB) or
+        None); the arrays are kept alive by the second return value."""
+        mats = list(mats) if isinstance(mats, (list, tuple)) else [mats]
+        tab, keep = (_HeatMaterialView * max(len(mats), 1))(), []
+        for k, m in enumerate(mats):
+            views = []
+            for t in (m.cond, m.cp, m.rho):
+                if t is None:
+                    views.append(_HeatTable(0, None, None, None))
+                    continue
+                arr = [np.ascontiguousarray(a, dtype=np.float64) for a in t[1:]]
+                keep += arr
+                views.append(_HeatTable(int(t[0]), _ptr(arr[0]), _ptr(arr[1]), _ptr(arr[2])))
+            tab[k] = _HeatMaterialView(*views)
+        return tab, keep, len(mats)
+
+    def heat_assemble_groups(self, coord, groups, mats, hecMAT, temp, temp0=None, beta=1.0, dtime=0.0, flux=None, fix=None):
+        """heat_mat_ass_conductivity + heat_mat_ass_capacity (+ !CFLUX, !FIXTEMP) on the device (fx_heat_assemble_groups):
+        ``groups`` = [(etype, conn, None, elem_mat)] of TYPE=341, 342, 351, 352, 361, 362; ``mats`` heat.tHeatMaterial objects;
+        ``hecMAT`` a scalar matrix (NDOF = 1) whose D, AL, AU, B receive the result; temp / temp0 node temperatures;
+        flux (n_node) or None; fix = (nodes 1-based, values) or None.  Returns the kernel milliseconds."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        tab, keep = self._group_table(groups)
+        mt, keep_m, n_mat = self._heat_materials(mats)
+        temp = np.ascontiguousarray(temp, dtype=np.float64)
+        temp0 = None if temp0 is None else np.ascontiguousarray(temp0, dtype=np.float64)
+        flux = None if flux is None else np.ascontiguousarray(flux, dtype=np.float64)
+        fn, fv = ((), ()) if fix is None else fix
+        fn, fv = np.ascontiguousarray(fn, dtype=np.int32), np.ascontiguousarray(fv, dtype=np.float64)
+        hv = _HeatView(_ptr(temp), _ptr(temp0), float(beta), float(dtime))
+        mv = hecMAT.view()
+        ms = C.c_float(0)
+        _chk(lib().fx_heat_assemble_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, n_mat, mt, C.byref(hv),
+                                           C.byref(mv), _ptr(flux), int(fn.size), _ptr(fn), _ptr(fv), C.byref(ms)))
+        del keep, keep_m
+        return ms.value
+
+    def heat_element(self, etype, ecoord, tt, mat, tt0=None, dtime=0.0):
+        """One element through the device kernels (fx_heat_element) -> (SS (nn, nn) at tt, S0 (nn) at tt0 or None)."""
+        ec = np.ascontiguousarray(ecoord, dtype=np.float64)
+        nn = ec.size // 3
+        tt = np.ascontiguousarray(tt, dtype=np.float64)
+        tt0 = None if tt0 is None else np.ascontiguousarray(tt0, dtype=np.float64)
+        mt, keep_m, _ = self._heat_materials([mat])
+        ss, s0 = np.zeros((nn, nn)), np.zeros(nn)
+        _chk(lib().fx_heat_element(self.h, int(etype), _ptr(ec), _ptr(tt), _ptr(tt0), mt, C.c_double(dtime), _ptr(ss), _ptr(s0)))
+        del keep_m
+        return ss, (s0 if dtime > 0 else None)
+
+    def heat_stats(self):
+        """fx_heat_get_stats as a dict."""
+        out = (C.c_int64 * 8)()
+        _chk(lib().fx_heat_get_stats(self.h, out))
+        keys = ("colourings", "maps", "profiles", "calls", "copy_us", "lanes_per_element", "elements_per_workgroup")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_ubyte * 128).from_buffer_copy(bytes(unique_id))

@@ -596,6 +596,46 @@ typedef void (*fx_allreduce_fn)(double *v, int n, void *user);
 int fx_comm_set_host_callbacks(fx_context *ctx, int rank, int nranks, fx_halo_fn halo, fx_allreduce_fn allreduce,
                                void *user);
 
+/* ---- heat conduction (!SOLUTION, TYPE=HEAT) ----------------------------- */
+/* heat_mat_ass_conductivity.f90 + heat_mat_ass_capacity.f90 on the device for TYPE=341, 342, 351, 352, 361, 362 in any mix of
+ * groups: heat_THERMAL_3xx / heat_CAPACITY_3xx / heat_GET_CONDUCTIVITY / _CP / _DENSITY (heat_LIB_THERMAL.f90, heat_LIB_CAPACITY.f90)
+ * restated with their own point sets and, where they have them, their default-real constants.  One table is what heat_init_material (heat_init.f90:197-231) leaves in fstrHEAT: ntab rows,
+ * temp[ntab], funcA[ntab + 1], funcB[ntab + 1]. */
+typedef struct fx_heat_table {
+  int32_t ntab;
+  const double *temp, *funcA, *funcB;
+} fx_heat_table;
+typedef struct fx_heat_material_view {
+  fx_heat_table cond, cp, rho; /* cp and rho are read only with dtime > 0 */
+} fx_heat_material_view;
+typedef struct fx_heat_view {
+  const double *temp, *temp0; /* fstrHEAT%TEMP, %TEMP0 (n_node each; temp0 may be NULL when beta == 1 and dtime == 0) */
+  double beta;                /* 1 steady, 0.5 transient; ALFA = 1 - beta */
+  double dtime;               /* 0: no capacity term */
+} fx_heat_view;
+/* Clears the matrix and B, adds every element's SS(TEMP) * beta, B -= SS * TEMP0 * (1 - beta) and, with dtime > 0, the lumped
+ * S0(TEMP0): D += S0 / dtime, B += S0 * TEMP0 / dtime; then B += flux (!CFLUX; n_node, may be NULL) and hecmw_mat_ass_bc(node, 1,
+ * val) for the n_fix nodes in the order given (!FIXTEMP).  A caller with surface terms (!FILM, !RADIATE, !DFLUX) passes n_fix = 0,
+ * adds them on the host and eliminates there (the order of heat_mat_ass_boundary).
+ *   groups: fx_elem_group as above, elemopt ignored; elem_mat 1-based into mats when n_mat > 1.
+ *   mat: NDOF = 1; the caller's profile, and the caller's D, AL, AU, B as the place the result is WRITTEN (X is not touched).
+ * The scatter is coloured and atomic-free through a position map cached in the context (one cache per context, by group
+ * position, as fx_assemble_groups): a call with the same groups and profile and new temperatures colours and maps nothing, and
+ * results are bitwise reproducible from call to call.
+ * Errors, all before anything is written: unknown etype or mat->NDOF != 1: FX_ERROR_UNSUPPORTED; missing arrays, ids out of
+ * range, ntab < 1, a connectivity entry absent from the profile, an element (of any type) that names a node twice (group and
+ * element named): FX_ERROR_RUNTIME.  A group that cannot be coloured -- a node in more than 64 of its elements, or FX_ASM_ATOMIC
+ * set -- is refused with FX_ERROR_RUNTIME as well: this assembly has no atomic scatter to fall back to (fx_assemble_groups has). */
+int fx_heat_assemble_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                            int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat, const fx_matrix_view *mat,
+                            const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val, float *ms_kernel);
+/* One element through the device kernels (tests): ss (nn x nn) at the node temperatures tt and, with dtime > 0, s0 (nn) at tt0. */
+int fx_heat_element(fx_context *ctx, int32_t etype, const double *ecoord, const double *tt, const double *tt0,
+                    const fx_heat_material_view *mat, double dtime, double *ss, double *s0);
+/* out[0] colourings made, [1] position maps made, [2] profiles uploaded, [3] calls of fx_heat_assemble_groups, [4] microseconds
+ * of the last copy of D, AL, AU, B to the caller, [5] lanes per element, [6] elements per workgroup of the element kernel. */
+int fx_heat_get_stats(fx_context *ctx, int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif
