@@ -1,5 +1,6 @@
 // Heat conduction (!SOLUTION, TYPE=HEAT): heat_mat_ass_conductivity.f90 and heat_mat_ass_capacity.f90 on the device for
-// TYPE=341, 342, 351, 352, 361, 362 (included by fistr_hip.hip after fx_assemble_groups.h).
+// TYPE=341, 342, 351, 352, 361, 362 (included by fistr_hip.hip after fx_assemble_groups.h); the surface terms of
+// heat_mat_ass_boundary are fx_heat_bc.h, included below.
 //
 // What is restated, routine by routine: heat_THERMAL_3xx and heat_GET_CONDUCTIVITY of module m_heat_lib_thermal
 // (heat_LIB_THERMAL.f90: the module heat_mat_ass_conductivity uses through m_heat_lib; heat_LIB_CONDUCTIVITY.f90 holds older
@@ -496,8 +497,10 @@ static int heat_nodes(int32_t etype) {
   return t < 0 ? 0 : nn[t];
 }
 
+static void heat_bc_free(HeatAsm &h);  // fx_heat_bc.h
 static void heat_free(fx_context *c) {
   HeatAsm &h = c->heat;
+  heat_bc_free(h);
   for (ElemColors &ec : h.ec) elem_colors_free(ec);
   h.ec.clear();
   dev_free(h.indexL); dev_free(h.itemL); dev_free(h.indexU); dev_free(h.itemU);
@@ -622,6 +625,8 @@ static int heat_ensure_profile(fx_context *c, const fx_matrix_view *m) {
   return 0;
 }
 
+#include "fx_heat_bc.h"  // the surface terms: kernels, their lists, fx_heat_face
+
 // hecmw_mat_ass_bc (hecmw_mat_ass.f90:292-429) with NDOF = 1 on the caller's arrays, node after node as heat_mat_ass_bc_FIXT calls it
 static void heat_ass_bc(const fx_matrix_view *m, double *D, double *AL, double *AU, double *B, int32_t inode, double RHS) {
   B[inode - 1] = RHS;
@@ -640,10 +645,11 @@ static void heat_ass_bc(const fx_matrix_view *m, double *D, double *AL, double *
   }
 }
 
-extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                                       int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat, const fx_matrix_view *mat,
-                                       const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val, float *ms_kernel) {
-  const char *who = "fx_heat_assemble_groups";
+// fx_heat_assemble_groups (bc null) and fx_heat_assemble_groups_bc: one body, the surface stage between the element kernels and the copy-back
+static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                         int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat, const fx_matrix_view *mat,
+                         const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val, const fx_heat_bc *bc,
+                         float *ms_kernel) {
   if (!c || !heat || !mat) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
   if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
   for (int32_t g = 0; g < n_group; g++)
@@ -689,6 +695,8 @@ extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const doub
       return fx_fail(who, FX_ERROR_RUNTIME, "group %d (TYPE=%d), element %d names a node twice (a degenerate element)", (int)g + 1,
                      (int)G.etype, (int)dup + 1);
   }
+  if (bc)
+    if (int rc = heat_bc_check(who, n_group, groups, bc)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   HeatAsm &h = c->heat;
   h.n_calls++;
@@ -744,6 +752,10 @@ extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const doub
       h.n_maps++;
     }
   }
+  if (bc) {
+    if (int rc = heat_bc_prepare(c, who, n_node, n_group, groups, bc)) return rc;
+    if (!h.ev_surf) HIP_TRY(hipEventCreate(&h.ev_surf));
+  }
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   // hecmw_mat_clear, hecmw_mat_clear_b (heat_mat_ass_conductivity.f90:36-37)
   HIP_TRY(hipMemsetAsync(h.D, 0, np * 8, c->stream));
@@ -766,6 +778,10 @@ extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const doub
     }
   }
   HIP_TRY(hipGetLastError());
+  if (bc) {  // heat_mat_ass_bc_DFLUX, _FILM, _RADIATE
+    HIP_TRY(hipEventRecord(h.ev_surf, c->stream));
+    if (int rc = heat_bc_launch(c, n_group, groups, bc, tmp, d_coord, d_temp, d_err)) return rc;
+  }
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   int32_t herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream));
@@ -773,6 +789,12 @@ extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const doub
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   if (ms_kernel) *ms_kernel = ms;
+  if (bc) {
+    float ms_e = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_e, c->ev0, h.ev_surf));
+    h.elem_us = (int64_t)(1e3 * ms_e);
+    h.surf_us = (int64_t)(1e3 * (ms - ms_e));
+  }
   if (herr) return fx_fail(who, FX_ERROR_RUNTIME, "###ERROR### : cannot find connectivity (element not covered by the profile)");
   // the result goes to the caller's arrays (fx_solve builds the NDOF = 1 layout from host pointers)
   double *D = const_cast<double *>(mat->D), *AL = const_cast<double *>(mat->AL), *AU = const_cast<double *>(mat->AU),
@@ -787,6 +809,21 @@ extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const doub
     for (size_t i = 0; i < np; i++) B[i] = B[i] + flux[i];
   for (int32_t k = 0; k < n_fix; k++) heat_ass_bc(mat, D, AL, AU, B, fix_node[k], fix_val[k]);  // heat_mat_ass_bc_FIXT
   return 0;
+}
+
+extern "C" int fx_heat_assemble_groups(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                       int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat, const fx_matrix_view *mat,
+                                       const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val, float *ms_kernel) {
+  return heat_assemble("fx_heat_assemble_groups", c, n_node, coord, n_group, groups, n_mat, mats, heat, mat, flux, n_fix, fix_node, fix_val,
+                       nullptr, ms_kernel);
+}
+extern "C" int fx_heat_assemble_groups_bc(fx_context *c, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                                          int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat,
+                                          const fx_matrix_view *mat, const double *flux, int32_t n_fix, const int32_t *fix_node,
+                                          const double *fix_val, const fx_heat_bc *bc, float *ms_kernel) {
+  const char *who = "fx_heat_assemble_groups_bc";
+  if (!bc) return fx_fail(who, FX_ERROR_RUNTIME, "bc missing (fx_heat_assemble_groups is the call without surface terms)");
+  return heat_assemble(who, c, n_node, coord, n_group, groups, n_mat, mats, heat, mat, flux, n_fix, fix_node, fix_val, bc, ms_kernel);
 }
 
 extern "C" int fx_heat_element(fx_context *c, int32_t etype, const double *ecoord, const double *tt, const double *tt0,

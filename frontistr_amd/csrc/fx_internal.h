@@ -215,6 +215,16 @@ struct AsmGroups {
   bool first_write = false;  // the maps carry those flags and every block of the profile is covered: no clearing
 };
 
+// One list of faces (or, shape 2, of whole elements under a body flux) of the surface terms of a heat analysis: the faces as
+// elements of nn nodes with a colouring and, for !FILM and !RADIATE, a position map of their own.
+struct HeatFaceList {
+  uint64_t key = 0;            // checksum of the (group, element, face) entries and of the group's connectivity; 0 = none
+  int32_t n = 0, nn = 0;       // faces, nodes per face
+  int32_t *conn = nullptr;     // device: n x nn node ids, in the routine's NOD order
+  int32_t *src = nullptr;      // device: position of each face in the caller's list (its val and sink)
+  ElemColors ec;
+};
+
 // The one cache of the heat assembly (fx_heat.h): the caller's scalar profile with room for its values, one ElemColors per
 // group (by position in the call; `pos` is the position map into that profile, without first-write flags: the matrix is cleared),
 // the quadrature tables of the element types used so far, and what the tests read through fx_heat_get_stats.
@@ -226,6 +236,13 @@ struct HeatAsm {
   std::vector<ElemColors> ec;
   double *rule[6][2] = {};  // per type (341, 342, 351, 352, 361, 362): conductivity and capacity tables (H, dR, dS, dT, W)
   int64_t n_colourings = 0, n_maps = 0, n_profile = 0, n_calls = 0, copy_us = 0;
+  // the surface terms (fx_heat_bc.h): one list per (kind, group, face shape), kept while the caller's list stays the same
+  std::vector<HeatFaceList> fl;
+  double *frule[4] = {};   // face point tables (H, d1, d2, W) of the 4-node and 8-node quadrilateral, the 6-node triangle and
+                           // heat_DFLUX_352's collapsed triangle
+  double *bfrule[6] = {};  // per type: the volume points of heat_DFLUX_3xx (H, dR, dS, dT, W)
+  hipEvent_t ev_surf = nullptr;  // between the element kernels and the surface kernels
+  int64_t n_face_colourings = 0, n_face_maps = 0, elem_us = 0, surf_us = 0;
 };
 
 // Pinned host staging of the results of the linear stress update (grown on demand, owned by the context): 2 x 6 nq doubles per

@@ -87,6 +87,15 @@ class _HeatView(C.Structure):       # fx_heat_view
     _fields_ = [("temp", C.c_void_p), ("temp0", C.c_void_p), ("beta", C.c_double), ("dtime", C.c_double)]
 
 
+class _HeatSurface(C.Structure):    # fx_heat_surface
+    _fields_ = [("n", C.c_int32), ("group", C.c_void_p), ("elem", C.c_void_p), ("face", C.c_void_p), ("val", C.c_void_p),
+                ("sink", C.c_void_p)]
+
+
+class _HeatBc(C.Structure):         # fx_heat_bc
+    _fields_ = [("dflux", _HeatSurface), ("film", _HeatSurface), ("radiate", _HeatSurface), ("tzero", C.c_double)]
+
+
 def lib():
     """Load libfistr_hip.so (built by `make -C frontistr_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -624,11 +633,30 @@ class SolverContext:
             tab[k] = _HeatMaterialView(*views)
         return tab, keep, len(mats)
 
-    def heat_assemble_groups(self, coord, groups, mats, hecMAT, temp, temp0=None, beta=1.0, dtime=0.0, flux=None, fix=None):
+    @staticmethod
+    def _heat_surface(lst, with_sink):
+        """fx_heat_surface of (group, elem, face, val[, sink]) (0-based group and element positions, values with their amplitude
+        applied; a scalar value serves every entry); the arrays are kept alive by the second return value."""
+        if lst is None:
+            return _HeatSurface(0, None, None, None, None, None), []
+        idx = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in lst[:3]]
+        n = idx[0].size
+        if idx[1].size != n or idx[2].size != n or len(lst) < (5 if with_sink else 4):
+            raise ValueError("a surface list is (group, elem, face, val%s) of one length" % (", sink" if with_sink else ""))
+        vals = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+                for v in lst[3:5 if with_sink else 4]] + [None]
+        keep = idx + vals
+        return _HeatSurface(n, _ptr(idx[0]), _ptr(idx[1]), _ptr(idx[2]), _ptr(vals[0]), _ptr(vals[1])), keep
+
+    def heat_assemble_groups(self, coord, groups, mats, hecMAT, temp, temp0=None, beta=1.0, dtime=0.0, flux=None, fix=None,
+                             dflux=None, film=None, radiate=None, tzero=0.0):
         """heat_mat_ass_conductivity + heat_mat_ass_capacity (+ !CFLUX, !FIXTEMP) on the device (fx_heat_assemble_groups):
         ``groups`` = [(etype, conn, None, elem_mat)] of TYPE=341, 342, 351, 352, 361, 362; ``mats`` heat.tHeatMaterial objects;
         ``hecMAT`` a scalar matrix (NDOF = 1) whose D, AL, AU, B receive the result; temp / temp0 node temperatures;
-        flux (n_node) or None; fix = (nodes 1-based, values) or None.  Returns the kernel milliseconds."""
+        flux (n_node) or None; fix = (nodes 1-based, values) or None.  With any of dflux = (group, elem, face, val), film or
+        radiate = (group, elem, face, val, sink) -- 0-based positions of the group and of the element in it, face = LTYPE of the
+        routine (0 in dflux: the body flux), values with their amplitudes applied -- the surface terms are added on the device
+        (fx_heat_assemble_groups_bc; tzero is !ZERO).  Returns the kernel milliseconds."""
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         tab, keep = self._group_table(groups)
         mt, keep_m, n_mat = self._heat_materials(mats)
@@ -640,10 +668,40 @@ class SolverContext:
         hv = _HeatView(_ptr(temp), _ptr(temp0), float(beta), float(dtime))
         mv = hecMAT.view()
         ms = C.c_float(0)
-        _chk(lib().fx_heat_assemble_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, n_mat, mt, C.byref(hv),
-                                           C.byref(mv), _ptr(flux), int(fn.size), _ptr(fn), _ptr(fv), C.byref(ms)))
+        if dflux is None and film is None and radiate is None:
+            _chk(lib().fx_heat_assemble_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, n_mat, mt, C.byref(hv),
+                                               C.byref(mv), _ptr(flux), int(fn.size), _ptr(fn), _ptr(fv), C.byref(ms)))
+        else:
+            (sd, kd), (sf, kf), (sr, kr) = self._heat_surface(dflux, False), self._heat_surface(film, True), self._heat_surface(radiate, True)
+            bc = _HeatBc(sd, sf, sr, float(tzero))
+            _chk(lib().fx_heat_assemble_groups_bc(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, n_mat, mt, C.byref(hv),
+                                                  C.byref(mv), _ptr(flux), int(fn.size), _ptr(fn), _ptr(fv), C.byref(bc), C.byref(ms)))
+            del kd, kf, kr
         del keep, keep_m
         return ms.value
+
+    def heat_face(self, etype, kind, face, ecoord, val, sink=0.0, tt=None, tzero=0.0):
+        """One face of one element through the device kernels (fx_heat_face).  kind: "dflux", "film" or "radiate" (or 0, 1, 2);
+        face: LTYPE of the routine (0 with dflux: the body flux); ecoord (nn, 3) and tt (nn, radiate only) of the whole element.
+        -> (TERM1 (mm, mm), TERM2 (mm), NOD (mm, 1-based)), or for dflux (None, VECT (nn), NOD)."""
+        kind = {"dflux": 0, "film": 1, "radiate": 2}.get(kind, kind)
+        ec = np.ascontiguousarray(ecoord, dtype=np.float64)
+        nn = ec.size // 3
+        tt = None if tt is None else np.ascontiguousarray(tt, dtype=np.float64)
+        t1, t2, nsuf, mm = np.zeros(64), np.zeros(20), np.zeros(20, dtype=np.int32), C.c_int32(0)
+        _chk(lib().fx_heat_face(self.h, int(etype), int(kind), int(face), _ptr(ec), _ptr(tt), C.c_double(val), C.c_double(sink),
+                                C.c_double(tzero), _ptr(t1), _ptr(t2), _ptr(nsuf), C.byref(mm)))
+        m = mm.value
+        if kind == 0:
+            return None, t2[:nn].copy(), nsuf[:m].copy()
+        return t1[:m * m].reshape(m, m).copy(), t2[:m].copy(), nsuf[:m].copy()
+
+    def heat_bc_stats(self):
+        """fx_heat_get_bc_stats as a dict."""
+        out = (C.c_int64 * 8)()
+        _chk(lib().fx_heat_get_bc_stats(self.h, out))
+        keys = ("face_colourings", "face_maps", "elem_us", "surf_us", "lanes_per_face", "faces_per_workgroup")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def heat_element(self, etype, ecoord, tt, mat, tt0=None, dtime=0.0):
         """One element through the device kernels (fx_heat_element) -> (SS (nn, nn) at tt, S0 (nn) at tt0 or None)."""

@@ -615,8 +615,7 @@ typedef struct fx_heat_view {
 } fx_heat_view;
 /* Clears the matrix and B, adds every element's SS(TEMP) * beta, B -= SS * TEMP0 * (1 - beta) and, with dtime > 0, the lumped
  * S0(TEMP0): D += S0 / dtime, B += S0 * TEMP0 / dtime; then B += flux (!CFLUX; n_node, may be NULL) and hecmw_mat_ass_bc(node, 1,
- * val) for the n_fix nodes in the order given (!FIXTEMP).  A caller with surface terms (!FILM, !RADIATE, !DFLUX) passes n_fix = 0,
- * adds them on the host and eliminates there (the order of heat_mat_ass_boundary).
+ * val) for the n_fix nodes in the order given (!FIXTEMP).  Surface terms (!FILM, !RADIATE, !DFLUX): fx_heat_assemble_groups_bc.
  *   groups: fx_elem_group as above, elemopt ignored; elem_mat 1-based into mats when n_mat > 1.
  *   mat: NDOF = 1; the caller's profile, and the caller's D, AL, AU, B as the place the result is WRITTEN (X is not touched).
  * The scatter is coloured and atomic-free through a position map cached in the context (one cache per context, by group
@@ -635,6 +634,44 @@ int fx_heat_element(fx_context *ctx, int32_t etype, const double *ecoord, const 
 /* out[0] colourings made, [1] position maps made, [2] profiles uploaded, [3] calls of fx_heat_assemble_groups, [4] microseconds
  * of the last copy of D, AL, AU, B to the caller, [5] lanes per element, [6] elements per workgroup of the element kernel. */
 int fx_heat_get_stats(fx_context *ctx, int64_t out[8]);
+
+/* The surface terms of heat_mat_ass_boundary for the six solid types: heat_mat_ass_bc_DFLUX (faces S1.. and, as face 0, the body
+ * flux BF; without the weld line), heat_mat_ass_bc_FILM and heat_mat_ass_bc_RADIATE, that is heat_DFLUX_3xx, heat_FILM_3xx and
+ * heat_RADIATE_3xx (heat_LIB_DFLUX.f90, heat_LIB_FILM.f90, heat_LIB_RADIATE.f90) with their own face node tables, point sets, loop
+ * order and default-real Gauss constants.  One list entry is one (element, face) of the reference's Q_SUF / H_SUF / R_SUF lists;
+ * its values arrive already multiplied by their amplitudes (heat_get_amplitude at the call's time, resolved by the caller). */
+typedef struct fx_heat_surface {
+  int32_t n;
+  const int32_t *group, *elem, *face; /* position in groups[] (0-based), element within the group (0-based), LTYPE of the routine */
+  const double *val, *sink;           /* Q | HH | RR, and SINK (NULL for dflux) -- amplitude already applied */
+} fx_heat_surface;
+typedef struct fx_heat_bc {
+  fx_heat_surface dflux, film, radiate; /* face 0 is allowed in dflux only (BF) */
+  double tzero;                         /* hecMESH%zero_temp (!ZERO) */
+} fx_heat_bc;
+/* fx_heat_assemble_groups with the surface terms.  Order: clear, the elements, then DFLUX, FILM and RADIATE on the device copy
+ * of the matrix (D, AL, AU -= TERM1; B -= TERM2 on the diagonal pass; B -= VECT), then the copy-back, then B += flux and the
+ * !FIXTEMP elimination on the host as in fx_heat_assemble_groups.  The reference adds !CFLUX before the surface terms; adding it
+ * after them reorders only a sum into B.
+ * Each list's faces are coloured as elements of mm nodes (3, 4, 6 or 8; per group and face shape) and scattered colour by colour
+ * without atomics through a position map of their own; colouring and map are cached in the context by a checksum of the list and
+ * of its group, beside the groups' (calling fx_heat_assemble_groups in between invalidates neither).  Results are bitwise
+ * reproducible from call to call.  The same (element, face) may appear more than once in a list and is added as often.
+ * Errors, all before anything is written, FX_ERROR_RUNTIME: bc NULL, a group or element index out of range, a face outside
+ * 1..nface (0..nface for dflux), a null array with n > 0, a list that cannot be coloured (a node in more than 64 of its faces, or
+ * FX_ASM_ATOMIC set), a face node pair absent from the profile.  Everything else as fx_heat_assemble_groups. */
+int fx_heat_assemble_groups_bc(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                               int32_t n_mat, const fx_heat_material_view *mats, const fx_heat_view *heat, const fx_matrix_view *mat,
+                               const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val,
+                               const fx_heat_bc *bc, float *ms_kernel);
+/* One face (or, face 0 of kind 0, the body flux) through the device kernels (tests).  kind: 0 dflux, 1 film, 2 radiate; ecoord
+ * (nn x 3) and tt (nn, read by radiate only) of the whole element.  film, radiate: term1 (mm x mm), term2 (mm); dflux: VECT (nn)
+ * in term2, term1 untouched.  nsuf: NOD of the routine (mm, 1-based; 1..nn for the body flux), *mm its length. */
+int fx_heat_face(fx_context *ctx, int32_t etype, int32_t kind, int32_t face, const double *ecoord, const double *tt, double val,
+                 double sink, double tzero, double *term1, double *term2, int32_t *nsuf, int32_t *mm);
+/* out[0] face colourings made, [1] face position maps made, [2] microseconds of the element kernels and [3] of the surface
+ * kernels of the last fx_heat_assemble_groups_bc, [4] lanes per face, [5] faces per workgroup of the face kernel. */
+int fx_heat_get_bc_stats(fx_context *ctx, int64_t out[8]);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ per lane and SIMD on gfx950, granules of 8, at most 8 waves).
     scripts/kernel_resources.py frontistr_amd/libfistr_hip.so [--filter k_nl_] [--against other/libfistr_hip.so]
 
 Every kernel of the library is listed, so new ones need no entry here: `--filter k_heat` gives the six instantiations of the heat
-conduction element kernel (fx_heat.h; the table of DESIGN.md section 4), `--filter k_nl_` the nonlinear element kernels.
+conduction element kernel (fx_heat.h; the table of DESIGN.md section 4) and, as `k_heat_face` / `k_heat_bf`, the kernels of its
+surface terms (fx_heat_bc.h), `--filter k_nl_` the nonlinear element kernels.
 
 With --against: the kernels of both libraries side by side, `same` / `differs` / `new` / `gone` per kernel -- the way to show that
 a change left the existing instantiations alone.  Needs ROCm's llvm-objcopy, clang-offload-bundler, llvm-readelf, and c++filt.
