@@ -448,6 +448,8 @@ static void nn_free(fx_context *c);  // fx_nn_host.h
 static void graphs_destroy(fx_context *c);
 static void upd_stage_free(fx_context *c);  // fx_assemble_groups.h
 static void heat_free(fx_context *c);       // fx_heat.h
+static void nodal_free(fx_context *c);      // fx_nodal_stress.h
+static void nodal_list_free(NodalList &L);
 static void asm_groups_free(fx_context *c) {  // the cache of the linear assembly: colourings and maps of the last call's groups
   for (ElemColors &ec : c->asm_groups.ec) { dev_free(ec.order); dev_free(ec.pos); dev_free(ec.dup); }
   c->asm_groups = AsmGroups();
@@ -491,6 +493,7 @@ extern "C" void fx_destroy(fx_context *c) {
   nn_free(c);
   upd_stage_free(c);
   heat_free(c);
+  nodal_free(c);
   free_precond(c);
   free_matrix(c);
   arena_destroy(c);
@@ -3159,4 +3162,5 @@ extern "C" int fx_get_ssor_ordering(fx_context *c, int32_t *perm, int32_t *color
 #include "fx_assemble_groups.h"
 #include "fx_heat.h"
 #include "fx_nonlinear_host.h"
+#include "fx_nodal_stress.h"
 #include "fx_debug_host.h"

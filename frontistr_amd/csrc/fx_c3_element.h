@@ -43,7 +43,7 @@ struct C3El {
 
 // quadrature point q in natural (tetrahedra: volume) coordinates and its weight (getQuadPoint / getWeight)
 template <int ETYPE>
-__device__ __forceinline__ void c3_gauss(int q, double &xi, double &et, double &ze, double &w) {
+__host__ __device__ __forceinline__ void c3_gauss(int q, double &xi, double &et, double &ze, double &w) {
   const double G2 = 0.577350269189626, G3 = 0.774596669241483;
   if (ETYPE == 341) {
     xi = et = ze = 0.25;

@@ -255,6 +255,25 @@ struct UpdStage {
   int make_err = 0;   // the maker's result: read only after the join (upd_stage_wait)
 };
 
+// fstr_NodalStress3D on the device (fx_nodal_stress.h).  NodalList: per node, in the reference's order of addition, the pairs of
+// vertex records its value is made of; built on the host once per (n_node, groups, connectivity) and kept like the colourings.
+struct NodalList {
+  uint64_t key = 0;          // checksum of what it was built for (fx_nodal_stress_groups); 0 with fx_nl_nodal_stress, whose list lives as long as the nonlinear context
+  int32_t n_node = 0;
+  int64_t n_elem = 0, n_rec = 0, n_ent = 0;  // elements, vertex records and list entries of all groups
+  int32_t *row = nullptr;    // device: n_node + 1
+  int2 *ent = nullptr;       // device: n_ent pairs (record a, record b); a == b: that record, else the half-sum of the two
+  int64_t builds = 0;        // lists made on this context (fx_nodal_get_stats)
+};
+// Results of the pass: one device block and its pinned host copy (the pointers of fx_nodal_result), the vertex records, the error word.
+struct NodalStage {
+  double *dev = nullptr, *host = nullptr;
+  size_t cap = 0;            // doubles of each
+  double *rec = nullptr;     // device: 12 doubles per record
+  size_t rec_cap = 0;
+  int32_t *err = nullptr;
+};
+
 // One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
 // conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
 constexpr int NL_GROUPS = 10;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
@@ -581,6 +600,8 @@ struct fx_context {
   AsmGroups asm_groups;   // the linear assembly entry points
   UpdStage upd_stage;     // the linear stress update entry points
   HeatAsm heat;           // fx_heat_assemble_groups
+  NodalList nodal_list, nodal_list_nl;  // fx_nodal_stress_groups; fx_nl_nodal_stress (freed with the nonlinear context)
+  NodalStage nodal_stage; // both
   void *nn = nullptr;  // NnDev (fx_nn_host.h): systems with NDOF != 3
   const void *host_D = nullptr, *host_AL = nullptr, *host_AU = nullptr;  // the caller's arrays of the last value upload (fx_solve)
   // timing

@@ -31,6 +31,7 @@ static void nl_free(fx_context *c) {
   dev_free(n.mats); dev_free(n.hist); dev_free(n.hist_bk);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
   nl_thermal_free(n.th);
+  nodal_list_free(c->nodal_list_nl);  // fx_nodal_stress.h: the list of fx_nl_nodal_stress belongs to this connectivity
   n = NlDev();
 }
 

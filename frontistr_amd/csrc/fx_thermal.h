@@ -88,14 +88,14 @@ __device__ __forceinline__ bool thermal_coefficients(const ThermalDev &th, int m
 }
 
 // ShapeFunc_hex8n (hex8n.f90), node order of TYPE=361
-__device__ __forceinline__ double hex8_shape_func(int n, double xi, double et, double ze) {
+__host__ __device__ __forceinline__ double hex8_shape_func(int n, double xi, double et, double ze) {
   const double sx = ((n & 3) == 1 || (n & 3) == 2) ? 1.0 : -1.0, sy = (n & 2) ? 1.0 : -1.0, sz = (n & 4) ? 1.0 : -1.0;
   return 0.125 * (1.0 + sx * xi) * (1.0 + sy * et) * (1.0 + sz * ze);
 }
 
 // shape function of node n (getShapeFunc): ShapeFunc_tet4n, tet10n, prism6n, prism15n, hex20n in the node order of c3_shape_deriv
 template <int ETYPE>
-__device__ __forceinline__ double c3_shape_func(int n, double xi, double et, double ze) {
+__host__ __device__ __forceinline__ double c3_shape_func(int n, double xi, double et, double ze) {
   if (ETYPE == 341) {
     return n == 0 ? 1.0 - xi - et - ze : (n == 1 ? xi : (n == 2 ? et : ze));
   } else if (ETYPE == 342) {

@@ -26,80 +26,13 @@
 // Registers: eigen3's three rotations are instantiated for their compile-time (ip, iq), and the maximum / minimum / middle principal
 // stress are picked and updated with selects -- no array is indexed by a run-time value, so none is placed in scratch for that.
 #pragma once
+#include "fx_eigen3.h"  // yield_raise, yield_eigen3 and FX_YERR_JACOBI (5): shared with the nodal stress output
 
 #define FX_MAT_MOHR 4     // fx_material_view::plastic: YIELD=MOHR-COULOMB,  plconst = c, H, phi [rad]
 #define FX_MAT_DRUCKER 5  //                            YIELD=DRUCKER-PRAGER, plconst = c, H, eta; plconst4 = xi
 
 #define FX_YERR_MOHR 3    // error word: `Math Error in Mohr-Coulomb calculation`
 #define FX_YERR_RETURN 4  //             `Math error in return mapping`
-#define FX_YERR_JACOBI 5  //             `Jacobi iteration unable to converge`
-
-// The first condition raised stays (the word is cleared before the launches): which text comes back does not depend on the order in
-// which lanes finish, and a code the assembly has set (1, 2) is not overwritten.
-__device__ __forceinline__ void yield_raise(int32_t *err, int code) {
-  if (err) atomicCAS(err, 0, code);
-}
-
-// position of btens(i, j), i < j, among the three upper off-diagonal terms (0,1) (0,2) (1,2)
-__device__ __forceinline__ constexpr int yield_od(int i, int j) { return i + j - 1; }
-
-// one rotation of eigen3's sweep (utilities.f90:150-193) for the compile-time pair (IP, IQ), 0-based
-template <int IP, int IQ>
-__device__ __forceinline__ void yield_jacobi_rotate(double (&b)[3], double (&ev)[3], double (&pr)[3][3]) {
-  constexpr int IR = 3 - IP - IQ;
-  constexpr int PQ = yield_od(IP, IQ);
-  constexpr int RP = IR < IP ? yield_od(IR, IP) : yield_od(IP, IR);
-  constexpr int RQ = IR < IQ ? yield_od(IR, IQ) : yield_od(IQ, IR);
-  const double od = 100.0 * fabs(b[PQ]);
-  if ((od + fabs(ev[IP]) != fabs(ev[IP])) && (od + fabs(ev[IQ]) != fabs(ev[IQ]))) {
-    const double hd = ev[IQ] - ev[IP];
-    double t;
-    if (fabs(hd) + od == fabs(hd)) {
-      t = b[PQ] / hd;
-    } else {
-      const double theta = 0.5 * hd / b[PQ];
-      t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
-      if (theta < 0.0) t = -t;
-    }
-    const double c = 1.0 / sqrt(1.0 + t * t);
-    const double s = t * c;
-    const double tau = s / (1.0 + c);
-    double h = t * b[PQ];
-    ev[IP] = ev[IP] - h;
-    ev[IQ] = ev[IQ] + h;
-    double g = b[RP];
-    h = b[RQ];
-    b[RP] = g - s * (h + g * tau);
-    b[RQ] = h + s * (g - h * tau);
-#pragma unroll
-    for (int ir = 0; ir < 3; ir++) {
-      g = pr[ir][IP];
-      h = pr[ir][IQ];
-      pr[ir][IP] = g - s * (h + g * tau);
-      pr[ir][IQ] = h + s * (g - h * tau);
-    }
-  }
-  b[PQ] = 0.0;
-}
-
-// eigen3, utilities.f90:107-201: Jacobi iteration on the tensor (11, 22, 33, 12, 23, 31); pr holds the principal vectors as columns
-__device__ __forceinline__ void yield_eigen3(const double (&tensor)[6], double (&ev)[3], double (&pr)[3][3], int32_t *err) {
-  double b[3] = {tensor[3], tensor[5], tensor[4]};  // btens(1,2), btens(1,3), btens(2,3): only the upper triangle is read
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) pr[i][j] = i == j ? 1.0 : 0.0;
-    ev[i] = tensor[i];
-  }
-  for (int is = 0; is < 50; is++) {
-    const double fsum = fabs(b[0]) + fabs(b[1]) + fabs(b[2]);
-    if (fsum < 1.0e-10) return;
-    yield_jacobi_rotate<0, 1>(b, ev, pr);
-    yield_jacobi_rotate<0, 2>(b, ev, pr);
-    yield_jacobi_rotate<1, 2>(b, ev, pr);
-  }
-  yield_raise(err, FX_YERR_JACOBI);  // :200
-}
 
 // J3 of the deviator as BackwardEuler :467-471, cal_equivalent_stress :147-151 and calElastoPlasticMatrix :74-78 write it
 __device__ __forceinline__ double yield_j3(const double (&d)[6]) {

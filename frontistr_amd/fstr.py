@@ -9,6 +9,7 @@
     fstr_UpdateNewton    fistr1/src/analysis/static/fstr_Update.f90:25
     fstr_Update_NDForce  fistr1/src/analysis/static/fstr_Residual.f90:23
     fstr_UpdateState     fistr1/src/analysis/static/fstr_Update.f90:296
+    fstr_NodalStress3D   fistr1/src/analysis/static/fstr_NodalStress.f90:13
     fstr_cutback_save / _load  fistr1/src/analysis/static/fstr_Cutback.f90:108-198
     fstr_Newton          fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
@@ -350,6 +351,13 @@ class fstr_solid:
         if state.get("last_temp") is not None:
             _chk(lib().fx_nl_set_last_temp(self.ctx.h, _ptr(np.ascontiguousarray(state["last_temp"], dtype=np.float64))))
 
+    def nodal_stress(self, principal=0):
+        """fstr_NodalStress3D over the resident stress and strain of this context (fx_nl_nodal_stress): a hecmw.NodalStress; only
+        the results cross the bus.  principal: make_principal's bit mask (hecmw.PRINC_*)."""
+        res, ms = hecmw._NodalResult(), C.c_float(0)
+        _chk(lib().fx_nl_nodal_stress(self.ctx.h, int(principal), C.byref(res), C.byref(ms)))
+        return hecmw.NodalStress(res, ms.value)
+
     def element_tangents(self):
         ke = np.zeros(int(self.tangent_offsets[-1])) if self.etype is None else np.zeros((self.n_elem, 3 * self.nn, 3 * self.nn))
         _chk(lib().fx_nl_element_tangents(self.ctx.h, _ptr(ke)))
@@ -388,6 +396,16 @@ def fstr_UpdateNewton(fstrSOLID):
 
 def fstr_UpdateState(fstrSOLID):
     _chk(lib().fx_nl_commit(fstrSOLID.ctx.h))
+
+
+def fstr_NodalStress3D(fstrSOLID, principal=0):
+    """fstr_NodalStress3D (fstr_NodalStress.f90:13-272): sets fstrSOLID.STRAIN, .STRESS, .MISES, .ESTRAIN, .ESTRESS, .EMISES and,
+    where ``principal`` asks for them, .PSTRESS, .PSTRESS_VECT, .PSTRAIN, .PSTRAIN_VECT, .EPSTRESS, .EPSTRESS_VECT, .EPSTRAIN,
+    .EPSTRAIN_VECT (None otherwise) from the resident state.  Returns the hecmw.NodalStress they come from."""
+    r = fstrSOLID.nodal_stress(principal)
+    for name, _, _ in r._SHAPES:
+        setattr(fstrSOLID, name.upper(), getattr(r, name))
+    return r
 
 
 def fstr_cutback_save(fstrSOLID):

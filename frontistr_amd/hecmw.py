@@ -96,6 +96,51 @@ class _HeatBc(C.Structure):         # fx_heat_bc
     _fields_ = [("dflux", _HeatSurface), ("film", _HeatSurface), ("radiate", _HeatSurface), ("tzero", C.c_double)]
 
 
+class _NodalResult(C.Structure):    # fx_nodal_result
+    _fields_ = [("n_node", C.c_int32), ("n_elem", C.c_int32)] + [(k, C.POINTER(C.c_double)) for k in (
+        "strain", "stress", "mises", "estrain", "estress", "emises", "pstress", "pstress_vect", "pstrain", "pstrain_vect",
+        "epstress", "epstress_vect", "epstrain", "epstrain_vect")]
+
+
+# make_principal's flag bits (fstr_NodalStress.f90:889-980)
+PRINC_NSTRESS, PRINCV_NSTRESS, PRINC_NSTRAIN, PRINCV_NSTRAIN = 1, 2, 4, 8
+PRINC_ESTRESS, PRINCV_ESTRESS, PRINC_ESTRAIN, PRINCV_ESTRAIN = 16, 32, 64, 128
+
+
+class NodalStress:
+    """What fstr_NodalStress3D leaves in fstrSOLID: copies of the arrays of an fx_nodal_result.  strain, stress (n_node, 6),
+    mises (n_node), estrain, estress (n_elem, 6), emises (n_elem); the eight principal arrays -- values (n, 3) in descending
+    order, vectors (n, 3, 3) indexed [item, vector, component], each vector scaled by its value -- or None where the flag of
+    ``principal`` was off.  ms: the kernels' milliseconds."""
+    _SHAPES = (("strain", 0, (6,)), ("stress", 0, (6,)), ("mises", 0, ()), ("estrain", 1, (6,)), ("estress", 1, (6,)),
+               ("emises", 1, ()), ("pstress", 0, (3,)), ("pstress_vect", 0, (3, 3)), ("pstrain", 0, (3,)),
+               ("pstrain_vect", 0, (3, 3)), ("epstress", 1, (3,)), ("epstress_vect", 1, (3, 3)), ("epstrain", 1, (3,)),
+               ("epstrain_vect", 1, (3, 3)))
+    COMPONENTS = ("11", "22", "33", "12", "23", "31")
+
+    def __init__(self, res, ms=0.0):
+        self.n_node, self.n_elem, self.ms = int(res.n_node), int(res.n_elem), float(ms)
+        for name, per_elem, tail in self._SHAPES:
+            p = getattr(res, name)
+            shape = ((self.n_elem if per_elem else self.n_node),) + tail
+            setattr(self, name, np.ctypeslib.as_array(p, shape=shape).copy() if p and shape[0] > 0 else
+                    (np.zeros(shape) if p else None))
+
+    def summary(self, unode=None):
+        """The `Global Summary` block of 0.log as oracle/fistr1_run.read_log returns one step of it: {'Node': {name: (max,
+        min)}, 'Element': {...}} with the five digits the program prints (1PE11.4).  unode (3 * n_node): adds U1..U3."""
+        ext = lambda v: (float("%.4E" % v.max()), float("%.4E" % v.min()))
+        node, elem = {}, {}
+        if unode is not None:
+            U = np.asarray(unode, dtype=np.float64).reshape(-1, 3)
+            node.update({"U%d" % (c + 1): ext(U[:, c]) for c in range(3)})
+        for k, c in enumerate(self.COMPONENTS):
+            node["E" + c], node["S" + c] = ext(self.strain[:, k]), ext(self.stress[:, k])
+            elem["E" + c], elem["S" + c] = ext(self.estrain[:, k]), ext(self.estress[:, k])
+        node["SMS"], elem["SMS"] = ext(self.mises), ext(self.emises)
+        return {"Node": node, "Element": elem}
+
+
 def lib():
     """Load libfistr_hip.so (built by `make -C frontistr_amd/csrc` / __graft_entry__.build())."""
     global _lib
@@ -613,6 +658,41 @@ class SolverContext:
         stress = [_staged(pt[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
         del keep
         return strain, stress, qf, ms.value
+
+    def nodal_stress_groups(self, n_node, groups, strain, stress, principal=0):
+        """fstr_NodalStress3D on the device (fx_nodal_stress_groups) from the quadrature-point arrays of a linear update:
+        ``groups`` as assemble_groups takes them, ``strain`` / ``stress`` the per-group lists update_groups_linear returns (or
+        one flat array, the groups one after the other, [elem][point][6]).  principal: make_principal's bit mask (PRINC_*).
+        Returns a NodalStress.  A connectivity whose row length (or, flat, whose size) does not fit the type's node count is refused
+        here with the code of an unknown type: fx_elem_group carries no row length, so the library cannot see it."""
+        for grp in groups:
+            nn = _C3_NODES.get(int(grp[0]), 8 if int(grp[0]) == 361 else 0)
+            conn = np.asarray(grp[1])
+            if nn and (conn.shape[1] != nn if conn.ndim == 2 else conn.size % nn):     # flat arrays pass as in assemble_groups
+                raise HecmwSolverError(-2, "nodal_stress_groups: TYPE=%d has %d nodes per element, the connectivity has shape %s"
+                                       % (int(grp[0]), nn, conn.shape))
+        tab, keep = self._group_table(groups)
+        flat = lambda v: np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in v])
+                                              if isinstance(v, (list, tuple)) else v, dtype=np.float64).ravel()
+        st, ss = flat(strain), flat(stress)
+        nqs = [8 if tab[g].etype == 361 else _C3_POINTS.get(tab[g].etype, 0) for g in range(len(groups))]
+        want = 6 * sum(q * tab[g].n_elem for g, q in enumerate(nqs))
+        if all(nqs) and (st.size != want or ss.size != want):
+            raise ValueError("nodal_stress_groups: the point arrays hold %d / %d doubles, the groups need %d" % (st.size, ss.size, want))
+        res, ms = _NodalResult(), C.c_float(0)
+        _chk(lib().fx_nodal_stress_groups(self.h, int(n_node), len(groups), tab, _ptr(st), _ptr(ss), int(principal), C.byref(res),
+                                          C.byref(ms)))
+        del keep
+        return NodalStress(res, ms.value)
+
+    def nodal_stats(self):
+        """fx_nodal_get_stats: lists built (linear, nonlinear), entries, records, workgroup size of the node kernel, elements per
+        workgroup of the element kernel by type."""
+        out = (C.c_int64 * 12)()
+        _chk(lib().fx_nodal_get_stats(self.h, out))
+        v = list(out)
+        return {"lists": v[0], "lists_nl": v[1], "entries": v[2], "records": v[3], "node_bs": v[4],
+                "elems_per_wg": dict(zip((341, 342, 351, 352, 361, 362), v[5:11]))}
 
     # --- heat conduction (frontistr_amd/heat.py drives these) ----------
     @staticmethod

@@ -572,6 +572,56 @@ int fx_nl_set_temperature(fx_context *ctx, const double *temp);
 int fx_nl_get_last_temp(fx_context *ctx, double *last_temp);
 int fx_nl_set_last_temp(fx_context *ctx, const double *last_temp);
 
+/* ---- nodal and element stress output (fstr_NodalStress3D, fstr_NodalStress.f90:13-272) ----
+ * What `!WRITE,RESULT` writes and the `Global Summary` block is taken from, for TYPE=341, 342, 351, 352, 361 (every formulation:
+ * the rule depends on the type only) and 362 in any mix of groups (csrc/fx_nodal_stress.h has the rules):
+ *   estrain, estress [n_elem][6]  mean over all quadrature points of the element (ElementStress_C3)
+ *   strain, stress   [n_node][6]  mean over the elements that name the node of the element's nodal values (341, 351: the element
+ *                                 mean; 361, 342, 352, 362: extrapolation with inverse_func's inverse, mid-edge nodes the half-sum of
+ *                                 their two vertices); a node named twice by a collapsed element is added and counted twice; a node
+ *                                 that no element names keeps zeros
+ *   mises [n_node], emises [n_elem]   get_mises of stress / estress
+ * Elements are numbered through the groups in the order given (hecMESH's order with one group per elem_type_item entry); the sum
+ * at a node runs in ascending element number, as the reference's loop does, without atomics: the result is bitwise the same from
+ * run to run.  tnstrain, shells, beams, trusses, 301 and decomposed meshes are not served.
+ * flags: make_principal's bit mask (:889-980).  bit 0 / 1: principal values / vectors of the nodal stress, 2 / 3 of the nodal strain
+ * (shear components as stored, as the reference passes them), 4 / 5 of the element stress, 6 / 7 of the element strain; get_principal
+ * (utilities.f90:362-406): values in descending order, vector j scaled by value j.  Index order of a vector array:
+ * vect[(i * 3 + j) * 3 + r] = component r of vector j of node or element i = PSTRESS_VECT(3 * i + r + 1, j + 1) of the reference
+ * (0-based i, j, r).  An array whose flag is off is NULL.  eigen3's `stop` (`Jacobi iteration unable to converge`): FX_ERROR_RUNTIME.
+ * All pointers lie in pinned staging of the context that belongs to this pass alone (not the staging of the update results), so an
+ * update or prepare call leaves them alone: they are valid until the next nodal-stress call on the same context or fx_destroy. */
+typedef struct fx_nodal_result {
+  int32_t n_node, n_elem;
+  const double *strain, *stress, *mises;       /* STRAIN, STRESS, MISES */
+  const double *estrain, *estress, *emises;    /* ESTRAIN, ESTRESS, EMISES */
+  const double *pstress, *pstress_vect;        /* flags bit 0, 1: [n_node][3], [n_node][3][3] */
+  const double *pstrain, *pstrain_vect;        /* bit 2, 3 */
+  const double *epstress, *epstress_vect;      /* bit 4, 5: [n_elem][3], [n_elem][3][3] */
+  const double *epstrain, *epstrain_vect;      /* bit 6, 7 */
+} fx_nodal_result;
+enum { FX_PRINC_NSTRESS = 1, FX_PRINCV_NSTRESS = 2, FX_PRINC_NSTRAIN = 4, FX_PRINCV_NSTRAIN = 8,
+       FX_PRINC_ESTRESS = 16, FX_PRINCV_ESTRESS = 32, FX_PRINC_ESTRAIN = 64, FX_PRINCV_ESTRAIN = 128 };
+/* The linear path: strain, stress are host arrays in the layout fx_update_groups_linear returns, the groups one after the other,
+ * [elem][point][6] inside a group (nq(etype) points per element); groups / n_group as fx_update_groups_linear takes them (elemopt
+ * and elem_mat are not read).  The node -> element list is built once per (n_node, groups, connectivity) and kept in the context.
+ * fx_elem_group carries no row length, so a connectivity with the wrong number of nodes per element cannot be seen here: conn is
+ * read as nn(etype) ids per element.  The Python layer, which has the array's shape, refuses such a group with the code
+ * FX_ERROR_UNSUPPORTED before the call.
+ * Errors, *out untouched: an etype outside the six: FX_ERROR_UNSUPPORTED; a node id outside 1..n_node (group and element named),
+ * missing arrays, flags outside 0..255: FX_ERROR_RUNTIME. */
+int fx_nodal_stress_groups(fx_context *ctx, int32_t n_node, int32_t n_group, const fx_elem_group *groups, const double *strain,
+                           const double *stress, int32_t flags, fx_nodal_result *out, float *ms_kernel);
+/* The same over the resident stress and strain of a nonlinear context (any fx_nl_init*), whatever groups, F-bar parts and
+ * materials it holds: nothing but the results crosses the bus.  The list is built at the first call after an fx_nl_init*. */
+int fx_nl_nodal_stress(fx_context *ctx, int32_t flags, fx_nodal_result *out, float *ms_kernel);
+/* The inverse the kernels of `etype` take (tests): inv n x n row-major, *n = 8, 4, 6, 8 at 361, 342, 352, 362 and 0 at 341, 351. */
+int fx_nodal_inverse(int32_t etype, double *inv, int32_t *n);
+/* out[0] lists built for fx_nodal_stress_groups on this context, [1] for fx_nl_nodal_stress, [2] entries and [3] vertex records
+ * of the list fx_nodal_stress_groups last used, [4] workgroup size of the node kernel, [5..10] elements per workgroup of the element
+ * kernel of 341, 342, 351, 352, 361, 362. */
+int fx_nodal_get_stats(fx_context *ctx, int64_t out[12]);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------- */
 /* 128-byte ncclUniqueId made by rank 0 and broadcast by the host side
  * (torch.distributed / MPI); then every rank calls fx_comm_init. */
