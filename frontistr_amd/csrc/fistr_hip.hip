@@ -449,6 +449,7 @@ static void graphs_destroy(fx_context *c);
 static void upd_stage_free(fx_context *c);  // fx_assemble_groups.h
 static void heat_free(fx_context *c);       // fx_heat.h
 static void nodal_free(fx_context *c);      // fx_nodal_stress.h
+static void dload_free(fx_context *c);      // fx_dload.h
 static void nodal_list_free(NodalList &L);
 static void asm_groups_free(fx_context *c) {  // the cache of the linear assembly: colourings and maps of the last call's groups
   for (ElemColors &ec : c->asm_groups.ec) { dev_free(ec.order); dev_free(ec.pos); dev_free(ec.dup); }
@@ -493,6 +494,7 @@ extern "C" void fx_destroy(fx_context *c) {
   nn_free(c);
   upd_stage_free(c);
   heat_free(c);
+  dload_free(c);
   nodal_free(c);
   free_precond(c);
   free_matrix(c);
@@ -3161,6 +3163,7 @@ extern "C" int fx_get_ssor_ordering(fx_context *c, int32_t *perm, int32_t *color
 #include "fx_update_linear.h"
 #include "fx_assemble_groups.h"
 #include "fx_heat.h"
+#include "fx_dload.h"
 #include "fx_nonlinear_host.h"
 #include "fx_nodal_stress.h"
 #include "fx_debug_host.h"

@@ -274,6 +274,25 @@ struct NodalStage {
   int32_t *err = nullptr;
 };
 
+// Distributed loads (fx_dload.h).  A checked fx_dload list on the device: one batch per face shape (3, 4, 6, 8 nodes; kind 0..3,
+// the faces of all groups together) and one per element type with volume entries (kind 4..9: 341, 342, 351, 352, 361, 362).
+struct DloadBatch {
+  int kind = 0;
+  int32_t n = 0;
+  int32_t *nodes = nullptr;  // device: n x (nodes of the face | of the element), 1-based node ids in getSubFace's / the element's order
+  double *par = nullptr;     // device: n x 8, PARAMS(0:6) and RHO of the entry's element
+  uint8_t *held = nullptr;   // device: n, 1: the entry takes factor 1
+  int32_t *ltype = nullptr;  // device: n, DL_C3's LTYPE
+};
+struct DloadList {
+  std::vector<DloadBatch> b;
+  int64_t count[5] = {0, 0, 0, 0, 0};  // entries on triangles, on quadrilaterals, BX / BY / BZ, GRAV, CENT
+};
+struct DloadCtx {  // what fx_dload_get_stats reads (the list of an fx_dload_groups call is freed when the call ends)
+  hipEvent_t ev_mid = nullptr;  // between the face kernels and the volume kernels
+  int64_t count[5] = {0, 0, 0, 0, 0}, face_us = 0, vol_us = 0;
+};
+
 // One element group of the nonlinear context: its type, connectivity and colouring.  The element kernels index the history,
 // conn and emat by the element id inside their group, so a part hands them pointers offset to its block of the shared arrays.
 constexpr int NL_GROUPS = 10;  // compile-time groups of the nonlinear element kernels (nl_group_flag, fx_nl_point.h)
@@ -366,6 +385,13 @@ struct NlDev {
     bool bk_valid = false;            // last_temp_bk holds a saved last_temp of THIS thermal set-up
     int32_t *tab_idx = nullptr;       // per material: offset and rows of its alpha table (alpha, T), offset and rows of its elastic table (E, nu, T)
   } th;
+  // Distributed loads (fx_nl_set_dload).  Off: nothing allocated, and every fx_nl_* call runs what it ran without them.
+  struct Dload {
+    bool on = false, follow = false;  // follow: DLOAD_follow, the load is taken on the current configuration and rebuilt in every iteration
+    double factor = 1.0;              // fstrSOLID%factor(2) of the sub-step (fx_nl_set_dload_factor; fx_newton_substep sets factor1)
+    DloadList list;
+    double *nodal = nullptr;          // 3 NP: the nodal part of GL, kept aside so that GL can be rebuilt
+  } dl;
 };
 
 // TIMELOG (hecmw_solver_Iterative.f90:192-208): device time of the three phases the reference reports -- solver/matvec
@@ -600,6 +626,7 @@ struct fx_context {
   AsmGroups asm_groups;   // the linear assembly entry points
   UpdStage upd_stage;     // the linear stress update entry points
   HeatAsm heat;           // fx_heat_assemble_groups
+  DloadCtx dload;         // fx_dload_groups
   NodalList nodal_list, nodal_list_nl;  // fx_nodal_stress_groups; fx_nl_nodal_stress (freed with the nonlinear context)
   NodalStage nodal_stage; // both
   void *nn = nullptr;  // NnDev (fx_nn_host.h): systems with NDOF != 3

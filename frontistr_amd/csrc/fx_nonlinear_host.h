@@ -31,6 +31,7 @@ static void nl_free(fx_context *c) {
   dev_free(n.mats); dev_free(n.hist); dev_free(n.hist_bk);
   for (double *t : n.tabs) { double *q = t; dev_free(q); }
   nl_thermal_free(n.th);
+  nl_dload_free(n);
   nodal_list_free(c->nodal_list_nl);  // fx_nodal_stress.h: the list of fx_nl_nodal_stress belongs to this connectivity
   n = NlDev();
 }
@@ -700,6 +701,8 @@ extern "C" int fx_nl_begin_substep(fx_context *c, const double *GL) {
   HIP_TRY(hipMemsetAsync(n.dunode, 0, np3 * 8, c->stream));
   if (GL) HIP_TRY(hipMemcpyAsync(n.GL, GL, np3 * 8, hipMemcpyHostToDevice, c->stream));
   else HIP_TRY(hipMemsetAsync(n.GL, 0, np3 * 8, c->stream));
+  if (n.dl.on)  // GL = nodal load + factor DLOAD (fstr_ass_load.f90:138-257)
+    if (int rc = nl_dload_rebuild(c, true)) return rc;
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for((int64_t)np3)), dim3(256), 0, c->stream, (int64_t)np3, n.GL, n.qforce,
                      (const uint8_t *)nullptr, c->A.B);
   HIP_TRY(hipGetLastError());
@@ -720,6 +723,8 @@ extern "C" int fx_nl_update(fx_context *c, double out[4], float *ms_update) {
   HIP_TRY(hipMemsetAsync(n.qforce, 0, (size_t)np3 * 8, c->stream));
   if (int rc = nl_run_update(c, nullptr, c->ev1)) return rc;
   if (nl_halo_natural(c, n.qforce)) return FX_ERROR_RUNTIME;
+  if (n.dl.on && n.dl.follow)  // fstr_ass_load again on node + unode + dunode (fstr_solve_NonLinear.f90:103)
+    if (int rc = nl_dload_rebuild(c, false)) return rc;
   hipLaunchKernelGGL(k_nl_residual, dim3(grid_for(np3)), dim3(256), 0, c->stream, np3, n.GL, n.qforce, n.bc_flag, c->A.B);
   HIP_TRY(hipGetLastError());
   if (nl_halo_natural(c, c->A.B)) return FX_ERROR_RUNTIME;
@@ -757,6 +762,8 @@ extern "C" int fx_nl_update_at(fx_context *c, const double *dunode, double *qfor
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   HIP_TRY(hipMemsetAsync(n.qforce, 0, np3, c->stream));
   if (int rc = nl_run_update(c, nullptr, c->ev1)) return rc;
+  if (n.dl.on && n.dl.follow)  // the follower load of the new configuration: fx_nl_get_load hands it to the host's loop
+    if (int rc = nl_dload_rebuild(c, false)) return rc;
   if (qforce) HIP_TRY(hipMemcpyAsync(qforce, n.qforce, np3, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (ms_update) HIP_TRY(hipEventElapsedTime(ms_update, c->ev0, c->ev1));
@@ -1062,6 +1069,7 @@ extern "C" int fx_newton_substep(fx_context *c, double factor0, double factor1, 
     for (size_t i = 0; i < np3; i++) gl[i] = cload[i] * factor1;
   }
   for (int32_t k = 0; k < n_bc; k++) inc[k] = bc_val[k] * (factor1 - factor0);
+  if (c->nl.dl.on) c->nl.dl.factor = factor1;  // fstrSOLID%factor(2)
   int e = fx_nl_begin_substep(c, cload ? gl.data() : nullptr);
   if (e) return e;
   bool done = false, blown = false;

@@ -11,6 +11,7 @@
     fstr_UpdateState     fistr1/src/analysis/static/fstr_Update.f90:296
     fstr_NodalStress3D   fistr1/src/analysis/static/fstr_NodalStress.f90:13
     fstr_cutback_save / _load  fistr1/src/analysis/static/fstr_Cutback.f90:108-198
+    tDload / set_dload   the !DLOAD cards of fstr_ass_load (fistr1/src/analysis/static/fstr_ass_load.f90:138-257, DL_C3)
     fstr_Newton          fistr1/src/analysis/static/fstr_solve_NonLinear.f90:29
     fstr_solve_NLGEOM    fistr1/src/analysis/static/fstr_solve_NLGEOM.f90:32 (sub-step loop, linear load ramp)
 
@@ -148,6 +149,85 @@ class tMaterial:
         return v
 
 
+class tDload:
+    """A list of distributed loads, one entry per (element, LTYPE) of fstr_ass_load's loop over the !DLOAD cards
+    (fstr_ass_load.f90:157-256); values carry their amplitude.  ``group`` is the position of the element group (0 for a
+    single-type mesh) and ``elems`` the 0-based elements in it.  held=True marks a card whose load group was active in the step
+    before: its entries take factor 1 (:141-142).  SolverContext.dload_groups and fstr_solid.set_dload take the object."""
+
+    LTYPE = {"BX": 1, "BY": 2, "BZ": 3, "GRAV": 4, "CENT": 5}
+    # getSubFace (fistr1/src/lib/element/element.f90:181-315): the nodes of face f, 1-based positions in the element
+    SUBFACE = {
+        341: ((1, 2, 3), (4, 2, 1), (4, 3, 2), (4, 1, 3)),
+        342: ((1, 2, 3, 5, 6, 7), (4, 2, 1, 9, 5, 8), (4, 3, 2, 10, 6, 9), (4, 1, 3, 8, 7, 10)),
+        351: ((1, 2, 3), (6, 5, 4), (4, 5, 2, 1), (5, 6, 3, 2), (6, 4, 1, 3)),
+        352: ((1, 2, 3, 7, 8, 9), (6, 5, 4, 11, 10, 12), (4, 5, 2, 1, 10, 14, 7, 13), (5, 6, 3, 2, 11, 15, 8, 14),
+              (6, 4, 1, 3, 12, 13, 9, 15)),
+        361: ((1, 2, 3, 4), (8, 7, 6, 5), (5, 6, 2, 1), (6, 7, 3, 2), (7, 8, 4, 3), (8, 5, 1, 4)),
+        362: ((1, 2, 3, 4, 9, 10, 11, 12), (8, 7, 6, 5, 15, 14, 13, 16), (5, 6, 2, 1, 13, 18, 9, 17),
+              (6, 7, 3, 2, 14, 19, 10, 18), (7, 8, 4, 3, 15, 20, 11, 19), (8, 5, 1, 4, 16, 17, 12, 20)),
+    }
+
+    def __init__(self):
+        self.group, self.elem, self.ltype, self.params, self.held = [], [], [], [], []
+
+    def __len__(self):
+        return len(self.group)
+
+    def add(self, group, elems, ltype, params, held=False):
+        """Entries (group, e, ltype) for every e of ``elems`` with PARAMS(0:6) = params (7 values)."""
+        par = [float(v) for v in params]
+        if len(par) != 7:
+            raise ValueError("params is PARAMS(0:6)")
+        for e in np.atleast_1d(np.asarray(elems, dtype=np.int64)).ravel():
+            self.group.append(int(group)); self.elem.append(int(e)); self.ltype.append(int(ltype))
+            self.params.append(par); self.held.append(1 if held else 0)
+        return self
+
+    def body(self, group, elems, direction, val, held=False):
+        """!DLOAD BX | BY | BZ: a force per volume (not multiplied by the density)."""
+        if direction not in ("BX", "BY", "BZ"):
+            raise ValueError("body: direction is BX, BY or BZ")
+        return self.add(group, elems, self.LTYPE[direction], (val, 0, 0, 0, 0, 0, 0), held)
+
+    def gravity(self, group, elems, val, direction, held=False):
+        """!DLOAD GRAV: acceleration val along ``direction`` (normalised by DL_C3), times the element's density."""
+        return self.add(group, elems, 4, (val,) + tuple(direction) + (0, 0, 0), held)
+
+    def centrifugal(self, group, elems, omega, point, axis, held=False):
+        """!DLOAD CENT: angular velocity omega about the axis through ``point`` along ``axis``."""
+        return self.add(group, elems, 5, (omega,) + tuple(point) + tuple(axis), held)
+
+    def pressure(self, group, elems, face, val, held=False):
+        """!DLOAD P<face>: val times SurfaceNormal of getSubFace's face, which points into the element: a positive value presses.
+        ``face`` a number, or one per element."""
+        elems = np.atleast_1d(np.asarray(elems, dtype=np.int64)).ravel()
+        for e, f in zip(elems, np.broadcast_to(np.asarray(face, dtype=np.int64), elems.shape)):
+            self.add(group, [e], 10 * int(f), (val, 0, 0, 0, 0, 0, 0), held)
+        return self
+
+    def arrays(self):
+        """(group, elem, ltype, params (n, 7), held) as SolverContext._dload takes them."""
+        return (np.array(self.group, dtype=np.int32), np.array(self.elem, dtype=np.int32), np.array(self.ltype, dtype=np.int32),
+                np.array(self.params, dtype=np.float64).reshape(-1, 7), np.array(self.held, dtype=np.uint8))
+
+
+def dload_faces(coord, groups, node_mask):
+    """The (group, element, face) triples -- 0-based group and element, 1-based face of getSubFace -- whose face nodes all lie in
+    ``node_mask`` (n_node booleans): what a surface group of a !DLOAD card resolves to.  groups: [(etype, conn, ...)]."""
+    mask = np.asarray(node_mask, dtype=bool)
+    if mask.shape != (np.asarray(coord).shape[0],):
+        raise ValueError("node_mask: one flag per node")
+    out = []
+    for g, grp in enumerate(groups):
+        etype, conn = int(grp[0]), np.asarray(grp[1])
+        conn = conn.reshape(-1, fstr_solid.NODES[etype])
+        for f, nod in enumerate(tDload.SUBFACE[etype]):
+            hit = mask[conn[:, np.array(nod) - 1] - 1].all(axis=1)
+            out += [(g, int(e), f + 1) for e in np.nonzero(hit)[0]]
+    return sorted(out)
+
+
 class fstr_solid:
     """The resident nonlinear state of one context (created by fx_nl_init)."""
 
@@ -246,6 +326,32 @@ class fstr_solid:
             else:
                 raise ValueError("group_slices: %r is no per-point or per-element array" % (name,))
         return out
+
+    # ---- distributed loads (fx_nl_set_dload)
+    def set_dload(self, dload, rho=None, follow=True):
+        """The !DLOAD cards of the step as a tDload (None clears them): from now on every sub-step adds factor * DLOAD to its
+        nodal load, and with follow (DLOAD_follow, the default; False is `!DLOAD, FOLLOW=NO`) takes it on the current
+        configuration and rebuilds it in every Newton iteration.  rho: one density per material (GRAV and CENT need it).
+        The factor is the load factor at the end of the sub-step (fstr_Newton's factor[1]).  In a `!STEP, TYPE=VISCO` step
+        fstr_solve_NLGEOM hands fstr_Newton the factors (0, 1) and scales the nodal load itself, so there the distributed load
+        is applied whole in every sub-step, like a nodal load with load_held; it is not ramped."""
+        if dload is None:
+            _chk(lib().fx_nl_set_dload(self.ctx.h, 0, None, None, 0))
+            return
+        rho = None if rho is None else np.ascontiguousarray(np.atleast_1d(rho), dtype=np.float64)
+        dv, keep = hecmw.SolverContext._dload(dload)
+        _chk(lib().fx_nl_set_dload(self.ctx.h, 0 if rho is None else int(rho.size), _ptr(rho), C.byref(dv), int(bool(follow))))
+        del keep
+
+    def set_dload_factor(self, factor):
+        """fstrSOLID%factor(2) for a caller that drives fx_nl_begin_substep itself (fstr_Newton sets it)."""
+        _chk(lib().fx_nl_set_dload_factor(self.ctx.h, C.c_double(factor)))
+
+    def get_load(self):
+        """fstrSOLID%GL (3 * n_node) as the device holds it."""
+        gl = np.zeros(3 * self.n_node)
+        _chk(lib().fx_nl_get_load(self.ctx.h, _ptr(gl)))
+        return gl
 
     # ---- thermal strain (fx_nl_set_thermal)
     thermal = False

@@ -96,6 +96,11 @@ class _HeatBc(C.Structure):         # fx_heat_bc
     _fields_ = [("dflux", _HeatSurface), ("film", _HeatSurface), ("radiate", _HeatSurface), ("tzero", C.c_double)]
 
 
+class _Dload(C.Structure):          # fx_dload
+    _fields_ = [("n", C.c_int32), ("group", C.c_void_p), ("elem", C.c_void_p), ("ltype", C.c_void_p), ("params", C.c_void_p),
+                ("held", C.c_void_p)]
+
+
 class _NodalResult(C.Structure):    # fx_nodal_result
     _fields_ = [("n_node", C.c_int32), ("n_elem", C.c_int32)] + [(k, C.POINTER(C.c_double)) for k in (
         "strain", "stress", "mises", "estrain", "estress", "emises", "pstress", "pstress_vect", "pstrain", "pstrain_vect",
@@ -781,6 +786,63 @@ class SolverContext:
         out = (C.c_int64 * 8)()
         _chk(lib().fx_heat_get_bc_stats(self.h, out))
         keys = ("face_colourings", "face_maps", "elem_us", "surf_us", "lanes_per_face", "faces_per_workgroup")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    @staticmethod
+    def _dload(dload):
+        """fx_dload of a fstr.tDload, or of (group, elem, ltype, params[, held]): 0-based positions of the group and of the
+        element in it, DL_C3's LTYPE (1..5, 10 * face), PARAMS(0:6) per entry (n, 7) with the amplitude applied, and optionally
+        the flags of the entries that take factor 1.  The arrays are kept alive by the second return value."""
+        lst = dload.arrays() if hasattr(dload, "arrays") else dload
+        idx = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in lst[:3]]
+        n = idx[0].size
+        par = np.ascontiguousarray(lst[3], dtype=np.float64).reshape(-1)
+        held = None if len(lst) < 5 or lst[4] is None else np.ascontiguousarray(lst[4], dtype=np.uint8).ravel()
+        if idx[1].size != n or idx[2].size != n or par.size != 7 * n or (held is not None and held.size != n):
+            raise ValueError("a dload list is (group, elem, ltype, params (n, 7)[, held]) of one length")
+        keep = idx + [par, held]
+        return _Dload(n, _ptr(idx[0]), _ptr(idx[1]), _ptr(idx[2]), _ptr(par), _ptr(held)), keep
+
+    def dload_groups(self, coord, groups, rho, dload, factor=1.0, disp=None, load=None):
+        """The DLOAD block of fstr_ass_load for the solid element groups (fx_dload_groups): factor * DL_C3 of every entry of
+        ``dload`` (a fstr.tDload, or the tuple of _dload), taken on coord (+ disp), added to ``load`` (3 * n_node, zeros when
+        None).  groups as assemble_groups; rho a density or one per material (None: the list has neither GRAV nor CENT).
+        Returns (the vector, kernel ms); ``load`` itself is not changed."""
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        tab, keep = self._group_table(groups)
+        rho = None if rho is None else np.ascontiguousarray(np.atleast_1d(rho), dtype=np.float64)
+        dv, keep_d = self._dload(dload)
+        disp = None if disp is None else np.ascontiguousarray(disp, dtype=np.float64).ravel()
+        if disp is not None and disp.size != 3 * coord.shape[0]:
+            raise ValueError("disp must hold 3 * n_node values")
+        out = np.zeros(3 * coord.shape[0]) if load is None else np.array(load, dtype=np.float64).ravel()
+        if out.size != 3 * coord.shape[0]:
+            raise ValueError("load must hold 3 * n_node values")
+        ms = C.c_float(0)
+        _chk(lib().fx_dload_groups(self.h, int(coord.shape[0]), _ptr(coord), len(groups), tab, 0 if rho is None else int(rho.size),
+                                   _ptr(rho), C.byref(dv), C.c_double(factor), _ptr(disp), _ptr(out), C.byref(ms)))
+        del keep, keep_d
+        return out, ms.value
+
+    def dload_element(self, etype, ltype, ecoord, params, rho=0.0):
+        """One element through the device kernels (fx_dload_element): DL_C3's VECT (3 * nn) for ecoord (nn, 3), LTYPE and
+        PARAMS(0:6)."""
+        ec = np.ascontiguousarray(ecoord, dtype=np.float64)
+        par = np.ascontiguousarray(params, dtype=np.float64).ravel()
+        if par.size != 7:
+            raise ValueError("params is PARAMS(0:6)")
+        nn = _C3_NODES.get(int(etype), 8)
+        if ec.size != 3 * nn:
+            raise ValueError("ecoord must be (%d, 3) for TYPE=%d" % (nn, etype))
+        vect = np.zeros(3 * nn)
+        _chk(lib().fx_dload_element(self.h, int(etype), int(ltype), _ptr(ec), C.c_double(rho), _ptr(par), _ptr(vect)))
+        return vect
+
+    def dload_stats(self):
+        """fx_dload_get_stats as a dict."""
+        out = (C.c_int64 * 8)()
+        _chk(lib().fx_dload_get_stats(self.h, out))
+        keys = ("tri_entries", "quad_entries", "body_entries", "grav_entries", "cent_entries", "face_us", "vol_us", "lanes_per_face")
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def heat_element(self, etype, ecoord, tt, mat, tt0=None, dtime=0.0):

@@ -723,6 +723,54 @@ int fx_heat_face(fx_context *ctx, int32_t etype, int32_t kind, int32_t face, con
  * kernels of the last fx_heat_assemble_groups_bc, [4] lanes per face, [5] faces per workgroup of the face kernel. */
 int fx_heat_get_bc_stats(fx_context *ctx, int64_t out[8]);
 
+/* ---- distributed loads (!DLOAD) of the six solid types ----
+ * The DLOAD block of fstr_ass_load (fstr_ass_load.f90:138-257) with DL_C3 (static_LIB_3d.f90:210-377): volume loads BX, BY, BZ
+ * (not multiplied by RHO), GRAV (RHO val times the normalised PARAMS(1:3)) and CENT (RHO val^2 times the distance vector from the
+ * axis through PARAMS(1:3) along PARAMS(4:6)) over the element's own quadrature rule (361: the 8 points of gauss3d2 whatever its
+ * elemopt), and pressure on face f (LTYPE 10 f) with getSubFace's node tables, the face type's rule and SurfaceNormal's
+ * un-normalised normal.  A surface group (LTYPE 100) is resolved by the caller into (element, 10 face) entries; an amplitude is
+ * applied by the caller.  Loads on shells, beams, trusses and 2-D types, uloading and torque CLOADs are not served. */
+typedef struct fx_dload {        /* one entry = one (element, LTYPE) of fstr_ass_load's loop :157-256 */
+  int32_t n;
+  const int32_t *group, *elem;   /* position in groups[] and element within it, 0-based (as fx_heat_surface) */
+  const int32_t *ltype;          /* DL_C3's LTYPE: 1..5, or 10*face */
+  const double *params;          /* n x 7: PARAMS(0:6), amplitude already applied */
+  const uint8_t *held;           /* may be NULL; 1: the entry takes factor 1 (fstr_ass_load.f90:141-142) */
+} fx_dload;
+/* factor * VECT of every entry (1 * VECT where held) ADDED to load_inout (3*n_node, host), on coord (+ disp, 3*n_node, when not
+ * NULL): it composes with the `load` of fx_assemble_groups and with fx_thermal_load_groups.  rho: n_mat densities (M_DENSITY),
+ * picked by the group's elem_mat (material 1 without); may be NULL when the list has neither GRAV nor CENT.  Entries that share a
+ * node add with fp64 atomics (as QFORCE): equal to rounding from call to call, not bit for bit; an entry given twice is added
+ * twice.  Needs no profile.  ms_kernel (may be NULL): the face and volume kernels together.
+ * Refused before anything is written, load_inout untouched: an etype outside the six, or a context of more than one rank (the
+ * reference exchanges GL with hecmw_update_3_R): FX_ERROR_UNSUPPORTED.  An ltype that is none of 1..5 and no face of the
+ * element's type, a group or element index out of range, a null array with n > 0, GRAV or CENT without rho, and -- where the
+ * reference divides by zero and carries NaN on -- a zero GRAV direction or CENT axis direction, each named with its entry and
+ * group (1-based), and what fx_assemble_groups refuses of the groups: FX_ERROR_RUNTIME. */
+int fx_dload_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                    int32_t n_mat, const double *rho, const fx_dload *dl, double factor, const double *disp,
+                    double *load_inout, float *ms_kernel);
+/* One element through the device kernels (tests): DL_C3's VECT (3 nn, zero off the face), no factor, no atomics.  ecoord nn x 3,
+ * params PARAMS(0:6).  Refusals as above. */
+int fx_dload_element(fx_context *ctx, int32_t etype, int32_t ltype, const double *ecoord, double rho, const double *params,
+                     double *vect);
+/* The nonlinear loop (after any fx_nl_init*).  The list -- group = position of the element group given to fx_nl_init_groups, 0 for
+ * the single-type set-ups -- is checked as above, resolved to node ids and uploaded once; dl == NULL clears it.  From then on
+ *   fx_nl_begin_substep builds GL = the nodal load it is handed + factor * DLOAD before B = GL - QFORCE, on coord + unode when
+ *     `follow` is set (DLOAD_follow, the reference's default; !DLOAD, FOLLOW=NO clears it) and on coord otherwise;
+ *   with `follow` set, fx_nl_update and fx_nl_update_at rebuild GL on coord + unode + dunode after the stress update and before
+ *     the residual: fstr_Newton's second fstr_ass_load (fstr_solve_NonLinear.f90:103).  The nodal part is kept in a vector of its
+ *     own, allocated only while a list is set.
+ * Without a list every fx_nl_* call runs what it ran before these entry points existed.  factor: fstrSOLID%factor(2), default 1;
+ * fx_newton_substep sets it to its factor1.  fx_nl_get_load: the resident GL (3*NP) back to the host. */
+int fx_nl_set_dload(fx_context *ctx, int32_t n_mat, const double *rho, const fx_dload *dl, int follow);
+int fx_nl_set_dload_factor(fx_context *ctx, double factor);
+int fx_nl_get_load(fx_context *ctx, double *GL);
+/* out[0] entries on triangles and [1] on quadrilaterals, [2] BX / BY / BZ, [3] GRAV and [4] CENT entries of the last list given to
+ * fx_dload_groups or fx_nl_set_dload, [5] microseconds of the face kernels and [6] of the volume kernels of the last
+ * fx_dload_groups, [7] lanes per face (the volume kernels take 4, 16, 8, 16, 8, 32 lanes per element of 341 .. 362). */
+int fx_dload_get_stats(fx_context *ctx, int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

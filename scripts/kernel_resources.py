@@ -8,7 +8,8 @@ per lane and SIMD on gfx950, granules of 8, at most 8 waves).
 Every kernel of the library is listed, so new ones need no entry here: `--filter k_heat` gives the six instantiations of the heat
 conduction element kernel (fx_heat.h; the table of DESIGN.md section 4) and, as `k_heat_face` / `k_heat_bf`, the kernels of its
 surface terms (fx_heat_bc.h), `--filter k_nl_` the nonlinear element kernels, `--filter k_nodal` the kernels of the nodal stress
-output (fx_nodal_stress.h: `k_nodal_element<ETYPE>`, `k_nodal_node`, `k_nodal_tensor_post`).
+output (fx_nodal_stress.h: `k_nodal_element<ETYPE>`, `k_nodal_node`, `k_nodal_tensor_post`), `--filter k_dload` the kernels of the
+distributed loads (fx_dload.h: `k_dload_face<3 | 4 | 6 | 8>`, `k_dload_vol<ETYPE>`).
 
 With --against: the kernels of both libraries side by side, `same` / `differs` / `new` / `gone` per kernel -- the way to show that
 a change left the existing instantiations alone.  With --code as well, `same` also requires the same instruction text: the
