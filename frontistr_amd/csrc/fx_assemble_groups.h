@@ -41,35 +41,39 @@ static int ensure_group_maps(fx_context *c, int32_t n_group, const fx_elem_group
   return 0;
 }
 
-// What the linear entry points and the nonlinear set-up (nl_init_driver) refuse before anything is uploaded: unknown types first (FX_ERROR_UNSUPPORTED), then the arguments,
-// material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group and element (1-based).
-static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
-                        int32_t n_mat, bool have_mats, bool nonlinear = false) {
+static const char SOLID_TYPES_ASCENDING[] = "341, 342, 351, 352, 361, 362";  // the types served, as the heat and load entry points spell them
+// What every entry point over element groups refuses before anything is uploaded, in two halves.  The first: unknown types
+// (FX_ERROR_UNSUPPORTED; `served` is the entry point's own spelling of the list) and, where asked, the elemopt of 361.
+static int check_group_types(const char *who, int32_t n_group, const fx_elem_group *groups, const char *served, bool linear_elemopt = false) {
   if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
   for (int32_t g = 0; g < n_group; g++) {
     if (c3_nodes(groups[g].etype) == 0)
-      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)",
-                         (int)g + 1, (int)groups[g].etype);
-    if (nonlinear) continue;  // nl_init_driver names what it serves of 361 itself
-    if (groups[g].etype == 361 && (groups[g].elemopt < 1 || groups[g].elemopt > 3))
+      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (%s)", (int)g + 1,
+                     (int)groups[g].etype, served);
+    if (linear_elemopt && groups[g].etype == 361 && (groups[g].elemopt < 1 || groups[g].elemopt > 3))
       return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: elemopt must be 1 (IC), 2 (B-bar) or 3 (FI)", (int)g + 1);
   }
-  if (n_node < 1 || !coord) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
-  if (n_mat < 1 || !have_mats) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
+  return 0;
+}
+// The second: per group the arguments, material ids, node ids and degenerate elements (FX_ERROR_RUNTIME), each named with its group
+// and element (1-based).  collapsed_361: a 361 element may name a node twice (collapsed hexahedra are assembled).
+static int check_group_elements(const char *who, int32_t n_node, int32_t n_group, const fx_elem_group *groups, int32_t n_mat, bool collapsed_361) {
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
     if (G.n_elem < 0 || (G.n_elem > 0 && !G.conn)) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: connectivity missing", (int)g + 1);
     if (n_mat > 1 && G.n_elem > 0 && !G.elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: several materials need elem_mat", (int)g + 1);
     const int nn = c3_nodes(G.etype);
+    const bool may_repeat = collapsed_361 && G.etype == 361;
+    const int32_t *conn = G.conn, *emat = G.elem_mat;
     int32_t bad_mat = INT32_MAX, bad_node = INT32_MAX, dup = INT32_MAX;  // lowest offending element (0-based) of each kind
-    parallel_for(G.n_elem, [&](int64_t a, int64_t b) {
+    parallel_for(G.n_elem, [=, &bad_mat, &bad_node, &dup](int64_t a, int64_t b) {  // (what the loop reads, by value: it stays in registers)
       int32_t bm = INT32_MAX, bn = INT32_MAX, dp = INT32_MAX;
       for (int64_t e = a; e < b && bm == INT32_MAX && bn == INT32_MAX && dp == INT32_MAX; e++) {
-        const int32_t *en = G.conn + (size_t)nn * e;
-        if (G.elem_mat && (G.elem_mat[e] < 1 || G.elem_mat[e] > n_mat)) bm = (int32_t)e;
+        const int32_t *en = conn + (size_t)nn * e;
+        if (emat && (emat[e] < 1 || emat[e] > n_mat)) bm = (int32_t)e;
         for (int x = 0; x < nn; x++)
           if (en[x] < 1 || en[x] > n_node) bn = (int32_t)e;
-        if (bn == INT32_MAX && G.etype != 361 && names_a_node_twice(en, nn)) dp = (int32_t)e;  // (361: collapsed hexahedra are assembled)
+        if (bn == INT32_MAX && !may_repeat && names_a_node_twice(en, nn)) dp = (int32_t)e;
       }
       __atomic_fetch_min(&bad_mat, bm, __ATOMIC_RELAXED);
       __atomic_fetch_min(&bad_node, bn, __ATOMIC_RELAXED);
@@ -83,6 +87,44 @@ static int check_groups(const char *who, int32_t n_node, const double *coord, in
   }
   return 0;
 }
+// The linear entry points, fx_dload_groups and the nonlinear set-up (nl_init_driver, which names what it serves of 361 itself).
+static int check_groups(const char *who, int32_t n_node, const double *coord, int32_t n_group, const fx_elem_group *groups,
+                        int32_t n_mat, bool have_mats, bool nonlinear = false) {
+  if (int rc = check_group_types(who, n_group, groups, "361, 341, 342, 351, 352, 362", !nonlinear)) return rc;
+  if (n_node < 1 || !coord) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
+  if (n_mat < 1 || !have_mats) return fx_fail(who, FX_ERROR_RUNTIME, "materials missing");
+  return check_group_elements(who, n_node, n_group, groups, n_mat, true);
+}
+// Entry k (0-based) of the list `name` (dflux, film, radiate, dload) names a group and an element of it.
+static int check_list_entry(const char *who, const char *name, int32_t k, int32_t group, int32_t elem, int32_t n_group,
+                            const fx_elem_group *groups) {
+  if (group < 0 || group >= n_group) return fx_fail(who, FX_ERROR_RUNTIME, "%s, entry %d: group out of range", name, (int)k + 1);
+  if (elem < 0 || elem >= groups[group].n_elem)
+    return fx_fail(who, FX_ERROR_RUNTIME, "%s, entry %d: element %d is not in group %d", name, (int)k + 1, (int)elem, (int)group + 1);
+  return 0;
+}
+
+// Every group's connectivity and material ids on the device (null: an empty group, no elem_mat), on the context's stream.
+static int upload_group_conn(fx_context *c, DevScratch &tmp, int32_t n_group, const fx_elem_group *groups, std::vector<const int32_t *> &conn,
+                             std::vector<const int32_t *> &emat) {
+  conn.assign((size_t)n_group, nullptr);
+  emat.assign((size_t)n_group, nullptr);
+  for (int32_t g = 0; g < n_group; g++) {
+    const fx_elem_group &G = groups[g];
+    if (G.n_elem < 1) continue;
+    const size_t nw = (size_t)c3_nodes(G.etype) * G.n_elem;
+    int32_t *d_conn = nullptr, *d_emat = nullptr;
+    if (tmp.alloc(&d_conn, nw)) return FX_ERROR_RUNTIME;
+    HIP_TRY(hipMemcpyAsync(d_conn, G.conn, nw * 4, hipMemcpyHostToDevice, c->stream));
+    conn[g] = d_conn;
+    if (G.elem_mat) {
+      if (tmp.alloc(&d_emat, (size_t)G.n_elem)) return FX_ERROR_RUNTIME;
+      HIP_TRY(hipMemcpyAsync(d_emat, G.elem_mat, (size_t)G.n_elem * 4, hipMemcpyHostToDevice, c->stream));
+      emat[g] = d_emat;
+    }
+  }
+  return 0;
+}
 
 // The (D11, D12, D44) table of the materials on the device, every group's connectivity and material ids.
 struct GroupUploads {
@@ -93,8 +135,6 @@ struct GroupUploads {
 };
 static int upload_groups(fx_context *c, DevScratch &tmp, int32_t n_group, const fx_elem_group *groups, int32_t n_mat, const double *E,
                          const double *nu, GroupUploads &up) {
-  up.conn.assign((size_t)n_group, nullptr);
-  up.emat.assign((size_t)n_group, nullptr);
   up.tab.resize((size_t)3 * n_mat);
   for (int32_t k = 0; k < n_mat; k++) elastic_constants(E[k], nu[k], up.tab[3 * k], up.tab[3 * k + 1], up.tab[3 * k + 2]);
   up.D11 = up.tab[0]; up.D12 = up.tab[1]; up.D44 = up.tab[2];
@@ -106,21 +146,7 @@ static int upload_groups(fx_context *c, DevScratch &tmp, int32_t n_group, const 
     HIP_TRY(hipMemcpyAsync(d_mtab, up.tab.data(), up.tab.size() * 8, hipMemcpyHostToDevice, c->stream));
     up.mtab = d_mtab;
   }
-  for (int32_t g = 0; g < n_group; g++) {
-    const fx_elem_group &G = groups[g];
-    if (G.n_elem < 1) continue;
-    const size_t nw = (size_t)c3_nodes(G.etype) * G.n_elem;
-    int32_t *d_conn = nullptr, *d_emat = nullptr;
-    if (tmp.alloc(&d_conn, nw)) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(d_conn, G.conn, nw * 4, hipMemcpyHostToDevice, c->stream));
-    up.conn[g] = d_conn;
-    if (G.elem_mat) {
-      if (tmp.alloc(&d_emat, (size_t)G.n_elem)) return FX_ERROR_RUNTIME;
-      HIP_TRY(hipMemcpyAsync(d_emat, G.elem_mat, (size_t)G.n_elem * 4, hipMemcpyHostToDevice, c->stream));
-      up.emat[g] = d_emat;
-    }
-  }
-  return 0;
+  return upload_group_conn(c, tmp, n_group, groups, up.conn, up.emat);
 }
 
 // The assembly of every linear entry point; `who` is the entry point called.  All groups into the resident matrix, group after

@@ -186,6 +186,17 @@ static bool with_solid_type(int32_t etype, F &&f) {
   f(C3Tag<361>());
   return true;
 }
+// f(std::integral_constant<int, MM>()) for the node count of a face: 3, 4, 6 or 8.  false: none of them, f is not called.
+template <class F>
+static bool with_face_nodes(int mm, F &&f) {
+  switch (mm) {
+    case 3: f(std::integral_constant<int, 3>()); return true;
+    case 4: f(std::integral_constant<int, 4>()); return true;
+    case 6: f(std::integral_constant<int, 6>()); return true;
+    case 8: f(std::integral_constant<int, 8>()); return true;
+    default: return false;
+  }
+}
 // nodes and quadrature points per element of the types the device knows (C3_TABLE); 0: none of them
 static int c3_nodes(int32_t etype) { return c3_facts(etype).nn; }
 static int c3_points(int32_t etype) { return c3_facts(etype).nq; }
@@ -228,6 +239,21 @@ static int mat_clear(fx_context *c) {
   return 0;
 }
 
+// k_scatter_map over n elements (or faces) of nn nodes -- a face's 3, 4, 6, 8, an element's 4, 6, 8, 10, 15, 20 -- into pos, for the
+// profile given
+static void launch_scatter_map(fx_context *c, int nn, int32_t n, const int32_t *d_conn, const int32_t *indexL, const int32_t *itemL,
+                               const int32_t *indexU, const int32_t *itemU, int32_t *pos) {
+  const dim3 grid((unsigned)(((int64_t)nn * nn * n + 255) / 256)), bs(256);
+  switch (nn) {
+    case 3: hipLaunchKernelGGL((k_scatter_map<3>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 4: hipLaunchKernelGGL((k_scatter_map<4>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 6: hipLaunchKernelGGL((k_scatter_map<6>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 8: hipLaunchKernelGGL((k_scatter_map<8>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 10: hipLaunchKernelGGL((k_scatter_map<10>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 15: hipLaunchKernelGGL((k_scatter_map<15>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+    case 20: hipLaunchKernelGGL((k_scatter_map<20>), grid, bs, 0, c->stream, n, d_conn, indexL, itemL, indexU, itemU, pos); break;
+  }
+}
 // the position map of k_scatter_map for the resident profile and the device connectivity d_conn of the elements of type etype
 // (FX_ASM_MAP=0: search every time); without first-write flags
 static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, const int32_t *d_conn, int32_t etype) {
@@ -238,10 +264,7 @@ static int ensure_scatter_map(fx_context *c, ElemColors &ec, int32_t n_elem, con
   if (dev_alloc(&ec.pos, (size_t)nmap)) { (void)hipGetLastError(); ec.pos = nullptr; return 0; }  // no memory: keep searching
   const DevCSR &A = c->A;
   ec.first_write = false;
-  with_solid_type(etype, [&](auto t) {
-    hipLaunchKernelGGL((k_scatter_map<C3El<decltype(t)::value>::NN>), dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, c->stream, n_elem, d_conn,
-                       A.indexL, A.itemL, A.indexU, A.itemU, ec.pos);
-  });
+  launch_scatter_map(c, nn, n_elem, d_conn, A.indexL, A.itemL, A.indexU, A.itemU, ec.pos);
   HIP_TRY(hipGetLastError());
   return 0;
 }

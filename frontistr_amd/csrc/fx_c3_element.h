@@ -1,5 +1,5 @@
 // What the kernels and the host know about the solid element types, in one place: the table of nodes, quadrature points
-// and lanes per element (TYPE=361, 341, 342, 351, 352, 362), quadrature and shape-function derivatives of the five types
+// and lanes per element (TYPE=361, 341, 342, 351, 352, 362), their faces (host), quadrature and shape-function derivatives of the five types
 // that STF_C3 (static_LIB_3d.f90:47-205) and UPDATE_C3 (:516-837) serve, and the small steps every element kernel repeats:
 // determinant and inverse of the Jacobian, strain from the displacement gradient, isotropic stress, elastic constants.
 //
@@ -29,6 +29,34 @@ constexpr C3Facts c3_facts(int etype) {  // all zero: not a type the device know
     if (f.etype == etype) return f;
   return C3Facts{0, 0, 0, 0, 0};
 }
+// The same types in the order 341, 342, 351, 352, 361, 362 (the rows above are in another: 361 first), in which the per-type caches
+// and tables of the host are indexed: ti is the type's place in it.  Faces (getSubFace, element.f90:181-315): nf of them, the
+// first ntri are triangles of tn nodes, the others quadrilaterals of qn nodes.
+struct C3FaceFacts {
+  int etype, ti, nf, ntri, tn, qn;
+};
+constexpr C3FaceFacts C3_FACE_TABLE[] = {{341, 0, 4, 4, 3, 0}, {342, 1, 4, 4, 6, 0}, {351, 2, 5, 2, 3, 4},
+                                         {352, 3, 5, 2, 6, 8}, {361, 4, 6, 0, 0, 4}, {362, 5, 6, 0, 0, 8}};
+constexpr C3FaceFacts c3_face_facts(int etype) {  // ti = -1, no faces: not a type the device knows
+  for (const C3FaceFacts &f : C3_FACE_TABLE)
+    if (f.etype == etype) return f;
+  return C3FaceFacts{0, -1, 0, 0, 0, 0};
+}
+constexpr int c3_type_index(int etype) { return c3_face_facts(etype).ti; }
+constexpr int c3_type_at(int ti) { return C3_FACE_TABLE[ti].etype; }
+constexpr int c3_faces(int etype) { return c3_face_facts(etype).nf; }
+// nodes of face `face` (1-based) of a type the device knows
+constexpr int c3_face_nodes(int etype, int face) { return face <= c3_face_facts(etype).ntri ? c3_face_facts(etype).tn : c3_face_facts(etype).qn; }
+// getSubFace's node tables, which heat_FILM_3xx / heat_RADIATE_3xx / heat_DFLUX_3xx repeat as their NOD: 1-based positions in the
+// element, by ti and face (host side)
+static const int8_t C3_FACE_NOD[6][6][8] = {
+    {{1, 2, 3}, {4, 2, 1}, {4, 3, 2}, {4, 1, 3}},
+    {{1, 2, 3, 5, 6, 7}, {4, 2, 1, 9, 5, 8}, {4, 3, 2, 10, 6, 9}, {4, 1, 3, 8, 7, 10}},
+    {{1, 2, 3}, {6, 5, 4}, {4, 5, 2, 1}, {5, 6, 3, 2}, {6, 4, 1, 3}},
+    {{1, 2, 3, 7, 8, 9}, {6, 5, 4, 11, 10, 12}, {4, 5, 2, 1, 10, 14, 7, 13}, {5, 6, 3, 2, 11, 15, 8, 14}, {6, 4, 1, 3, 12, 13, 9, 15}},
+    {{1, 2, 3, 4}, {8, 7, 6, 5}, {5, 6, 2, 1}, {6, 7, 3, 2}, {7, 8, 4, 3}, {8, 5, 1, 4}},
+    {{1, 2, 3, 4, 9, 10, 11, 12}, {8, 7, 6, 5, 15, 14, 13, 16}, {5, 6, 2, 1, 13, 18, 9, 17}, {6, 7, 3, 2, 14, 19, 10, 18},
+     {7, 8, 4, 3, 15, 20, 11, 19}, {8, 5, 1, 4, 16, 17, 12, 20}}};
 
 template <int ETYPE>
 struct C3El {

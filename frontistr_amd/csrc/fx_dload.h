@@ -6,7 +6,7 @@
 // getWeight: fx_c3_element.h's point sets; 361 the 8 points of gauss3d2 whatever its elemopt) with getShapeFunc and the determinant
 // as :311-316 spells it; the products keep the order of :339-341 and :344-374.  BX / BY / BZ are not multiplied by RHO; GRAV is,
 // and every component is scaled by the normalised PARAMS(1:3); CENT is RHO val^2 (x - foot of x on the axis) in all three components.
-// Face loads (LTYPE = 10 f) take getSubFace's node tables (element.f90:181-315, DL_NOD below, resolved on the host), the face type's
+// Face loads (LTYPE = 10 f) take getSubFace's node tables (element.f90:181-315, C3_FACE_NOD, resolved on the host), the face type's
 // rule (gauss2d4: 1 point, gauss2d5: 3, gauss2d2: 4, gauss2d3: 9) and SurfaceNormal's un-normalised cross product (:849-852):
 // VECT += val WG H(I) normal(k).  The kernels are compiled without contraction, as the reference's x86 build has none.
 //
@@ -329,41 +329,14 @@ __global__ __launch_bounds__(DLV_BS) void k_dload_vol(const DloadArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-// getSubFace (element.f90:181-315): 1-based positions in the element, by type index (341, 342, 351, 352, 361, 362) and face
-static const int8_t DL_NOD[6][6][8] = {
-    {{1, 2, 3}, {4, 2, 1}, {4, 3, 2}, {4, 1, 3}},
-    {{1, 2, 3, 5, 6, 7}, {4, 2, 1, 9, 5, 8}, {4, 3, 2, 10, 6, 9}, {4, 1, 3, 8, 7, 10}},
-    {{1, 2, 3}, {6, 5, 4}, {4, 5, 2, 1}, {5, 6, 3, 2}, {6, 4, 1, 3}},
-    {{1, 2, 3, 7, 8, 9}, {6, 5, 4, 11, 10, 12}, {4, 5, 2, 1, 10, 14, 7, 13}, {5, 6, 3, 2, 11, 15, 8, 14}, {6, 4, 1, 3, 12, 13, 9, 15}},
-    {{1, 2, 3, 4}, {8, 7, 6, 5}, {5, 6, 2, 1}, {6, 7, 3, 2}, {7, 8, 4, 3}, {8, 5, 1, 4}},
-    {{1, 2, 3, 4, 9, 10, 11, 12}, {8, 7, 6, 5, 15, 14, 13, 16}, {5, 6, 2, 1, 13, 18, 9, 17}, {6, 7, 3, 2, 14, 19, 10, 18},
-     {7, 8, 4, 3, 15, 20, 11, 19}, {8, 5, 1, 4, 16, 17, 12, 20}}};
-static int dl_type_index(int32_t etype) {
-  static const int32_t T[6] = {341, 342, 351, 352, 361, 362};
-  for (int t = 0; t < 6; t++)
-    if (T[t] == etype) return t;
-  return -1;
-}
-static int dl_faces(int32_t etype) {
-  static const int nf[6] = {4, 4, 5, 5, 6, 6};
-  const int t = dl_type_index(etype);
-  return t < 0 ? 0 : nf[t];
-}
-static int dl_face_nodes(int32_t etype, int32_t face) {  // getNumberOfNodes of getSubFace's outtype
-  switch (etype) {
-    case 341: return 3;
-    case 342: return 6;
-    case 351: return face <= 2 ? 3 : 4;
-    case 352: return face <= 2 ? 6 : 8;
-    case 361: return 4;
-    default: return 8;
-  }
-}
+// getSubFace's node tables are C3_FACE_NOD.  Batch kinds 0..3: faces of DL_FACE_MM[kind] nodes; 4..9: volume entries of the type at
+// place kind - 4 of the order 341, 342, 351, 352, 361, 362 (c3_type_at).
+static const int DL_FACE_MM[4] = {3, 4, 6, 8};
 static int dl_face_kind(int mm) { return mm == 3 ? 0 : (mm == 4 ? 1 : (mm == 6 ? 2 : 3)); }
 // 0: not an LTYPE of DL_C3 for this type; else nodes of the entry (face nodes, or the element's)
 static int dl_entry_nodes(int32_t etype, int32_t ltype) {
   if (ltype >= 1 && ltype <= 5) return c3_nodes(etype);
-  if (ltype >= 10 && ltype % 10 == 0 && ltype / 10 <= dl_faces(etype)) return dl_face_nodes(etype, ltype / 10);
+  if (ltype >= 10 && ltype % 10 == 0 && ltype / 10 <= c3_faces(etype)) return c3_face_nodes(etype, ltype / 10);
   return 0;
 }
 
@@ -379,10 +352,8 @@ static int dload_check(const char *who, int32_t n_group, const fx_elem_group *gr
   if (!dl->group || !dl->elem || !dl->ltype || !dl->params) return fx_fail(who, FX_ERROR_RUNTIME, "dload: list arrays missing");
   for (int32_t k = 0; k < dl->n; k++) {
     const int g = dl->group[k];
-    if (g < 0 || g >= n_group) return fx_fail(who, FX_ERROR_RUNTIME, "dload, entry %d: group out of range", (int)k + 1);
+    if (int rc = check_list_entry(who, "dload", k, g, dl->elem[k], n_group, groups)) return rc;
     const fx_elem_group &G = groups[g];
-    if (dl->elem[k] < 0 || dl->elem[k] >= G.n_elem)
-      return fx_fail(who, FX_ERROR_RUNTIME, "dload, entry %d: element %d is not in group %d", (int)k + 1, (int)dl->elem[k], g + 1);
     const int32_t lt = dl->ltype[k];
     if (dl_entry_nodes(G.etype, lt) == 0)
       return fx_fail(who, FX_ERROR_RUNTIME, "dload, entry %d (group %d): TYPE=%d has no LTYPE %d", (int)k + 1, g + 1, (int)G.etype, (int)lt);
@@ -408,31 +379,29 @@ static int dload_build(fx_context *c, int32_t n_group, const fx_elem_group *grou
   for (int32_t k = 0; k < dl->n; k++) {
     const int32_t et = groups[dl->group[k]].etype, lt = dl->ltype[k];
     if (lt < 10) {
-      pick[4 + dl_type_index(et)].push_back(k);
+      pick[4 + c3_type_index(et)].push_back(k);
       L.count[lt <= 3 ? 2 : lt - 1]++;
     } else {
-      const int mm = dl_face_nodes(et, lt / 10);
+      const int mm = c3_face_nodes(et, lt / 10);
       pick[dl_face_kind(mm)].push_back(k);
       L.count[mm % 3 == 0 ? 0 : 1]++;
     }
   }
-  static const int MMK[4] = {3, 4, 6, 8};
-  static const int32_t TYPES[6] = {341, 342, 351, 352, 361, 362};
   for (int kind = 0; kind < 10; kind++) {
     const std::vector<int32_t> &idx = pick[kind];
     if (idx.empty()) continue;
     DloadBatch b;
     b.kind = kind; b.n = (int32_t)idx.size();
-    const int nn = kind < 4 ? MMK[kind] : c3_nodes(TYPES[kind - 4]);
+    const int nn = kind < 4 ? DL_FACE_MM[kind] : c3_nodes(c3_type_at(kind - 4));
     std::vector<int32_t> nodes((size_t)nn * b.n), lts((size_t)b.n);
     std::vector<double> par((size_t)8 * b.n);
     std::vector<uint8_t> held((size_t)b.n);
     for (int32_t q = 0; q < b.n; q++) {
       const int32_t k = idx[q];
       const fx_elem_group &G = groups[dl->group[k]];
-      const int nne = c3_nodes(G.etype), t = dl_type_index(G.etype);
+      const int nne = c3_nodes(G.etype), t = c3_type_index(G.etype);
       const int32_t *en = G.conn + (size_t)nne * dl->elem[k];
-      for (int i = 0; i < nn; i++) nodes[(size_t)nn * q + i] = kind < 4 ? en[DL_NOD[t][dl->ltype[k] / 10 - 1][i] - 1] : en[i];
+      for (int i = 0; i < nn; i++) nodes[(size_t)nn * q + i] = kind < 4 ? en[C3_FACE_NOD[t][dl->ltype[k] / 10 - 1][i] - 1] : en[i];
       for (int i = 0; i < 7; i++) par[(size_t)8 * q + i] = dl->params[(size_t)7 * k + i];
       const bool needs_rho = dl->ltype[k] == 4 || dl->ltype[k] == 5;  // dload_check has validated the material id of exactly these
       par[(size_t)8 * q + 7] = needs_rho ? rho[G.elem_mat ? G.elem_mat[dl->elem[k]] - 1 : 0] : 0.0;
@@ -453,22 +422,15 @@ static int dload_build(fx_context *c, int32_t n_group, const fx_elem_group *grou
 
 static void dload_launch_batch(fx_context *c, const DloadBatch &b, DloadArgs a) {
   a.n = b.n; a.nodes = b.nodes; a.par = b.par; a.held = b.held; a.ltype = b.ltype;
-  const dim3 fgrid((unsigned)((b.n + DLF_FPB - 1) / DLF_FPB));
-#define DL_VOL(T)                                                                                                          \
-  hipLaunchKernelGGL((k_dload_vol<T>), dim3((unsigned)((b.n + DlVol<T>::EPB - 1) / DlVol<T>::EPB)), dim3(DLV_BS), 0, c->stream, a)
-  switch (b.kind) {
-    case 0: hipLaunchKernelGGL((k_dload_face<3>), fgrid, dim3(DLF_BS), 0, c->stream, a); break;
-    case 1: hipLaunchKernelGGL((k_dload_face<4>), fgrid, dim3(DLF_BS), 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_dload_face<6>), fgrid, dim3(DLF_BS), 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL((k_dload_face<8>), fgrid, dim3(DLF_BS), 0, c->stream, a); break;
-    case 4: DL_VOL(341); break;
-    case 5: DL_VOL(342); break;
-    case 6: DL_VOL(351); break;
-    case 7: DL_VOL(352); break;
-    case 8: DL_VOL(361); break;
-    default: DL_VOL(362); break;
+  if (b.kind < 4) {
+    const dim3 grid((unsigned)((b.n + DLF_FPB - 1) / DLF_FPB));
+    with_face_nodes(DL_FACE_MM[b.kind], [&](auto m) { hipLaunchKernelGGL((k_dload_face<decltype(m)::value>), grid, dim3(DLF_BS), 0, c->stream, a); });
+    return;
   }
-#undef DL_VOL
+  with_solid_type(c3_type_at(b.kind - 4), [&](auto t) {
+    constexpr int T = decltype(t)::value, EPB = DlVol<T>::EPB;
+    hipLaunchKernelGGL((k_dload_vol<T>), dim3((unsigned)((b.n + EPB - 1) / EPB)), dim3(DLV_BS), 0, c->stream, a);
+  });
 }
 // Every batch of the list on the context's stream, the faces first; ev_mid (may be null) is recorded between the two families.
 static int dload_launch(fx_context *c, const DloadList &L, const DloadArgs &a, hipEvent_t ev_mid) {
@@ -552,8 +514,8 @@ extern "C" int fx_dload_groups(fx_context *c, int32_t n_node, const double *coor
 extern "C" int fx_dload_element(fx_context *c, int32_t etype, int32_t ltype, const double *ecoord, double rho, const double *params, double *vect) {
   const char *who = "fx_dload_element";
   if (!c || !ecoord || !params || !vect) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  const int nn = c3_nodes(etype), t = dl_type_index(etype);
-  if (nn == 0 || t < 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (341, 342, 351, 352, 361, 362)", (int)etype);
+  const int nn = c3_nodes(etype), t = c3_type_index(etype);
+  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (%s)", (int)etype, SOLID_TYPES_ASCENDING);
   std::vector<int32_t> conn((size_t)nn);
   for (int i = 0; i < nn; i++) conn[i] = i + 1;
   const fx_elem_group G = {etype, 0, 1, conn.data(), nullptr};
@@ -581,7 +543,7 @@ extern "C" int fx_dload_element(fx_context *c, int32_t etype, int32_t ltype, con
   if (rc) return fx_fail(who, FX_ERROR_RUNTIME, "device error");
   for (int i = 0; i < 3 * nn; i++) vect[i] = 0.0;  // VECT(1:NSIZE) = 0 (:273-274)
   for (int i = 0; i < mm; i++) {
-    const int node = ltype >= 10 ? DL_NOD[t][ltype / 10 - 1][i] - 1 : i;
+    const int node = ltype >= 10 ? C3_FACE_NOD[t][ltype / 10 - 1][i] - 1 : i;
     for (int k = 0; k < 3; k++) vect[3 * node + k] = v[(size_t)3 * i + k];
   }
   return 0;
@@ -601,6 +563,8 @@ static void dload_free(fx_context *c) {
 }
 
 // ---- the nonlinear loop -------------------------------------------------------------------------------------------------------------
+static int nl_parts_to_host(const NlDev &n, bool with_emat, std::vector<std::vector<int32_t>> &conn,
+                            std::vector<std::vector<int32_t>> &emat);  // fx_nonlinear_host.h
 static void nl_dload_free(NlDev &n) {
   dload_list_free(n.dl.list);
   dev_free(n.dl.nodal);
@@ -631,18 +595,11 @@ extern "C" int fx_nl_set_dload(fx_context *c, int32_t n_mat, const double *rho, 
   if (!dl) { nl_dload_free(n); return 0; }
   if (int rc = dload_single_rank(who, c)) return rc;
   // the parts' connectivity and material ids back on the host: the list is resolved to node ids once
-  std::vector<std::vector<int32_t>> conn(n.parts.size()), emat(n.parts.size());
+  std::vector<std::vector<int32_t>> conn, emat;
+  if (int rc = nl_parts_to_host(n, rho != nullptr, conn, emat)) return rc;
   std::vector<fx_elem_group> gv;
-  for (size_t g = 0; g < n.parts.size(); g++) {
-    const NlPart &p = n.parts[g];
-    conn[g].resize((size_t)p.nn * p.n_elem);
-    HIP_TRY(hipMemcpy(conn[g].data(), p.conn, conn[g].size() * 4, hipMemcpyDeviceToHost));
-    if (p.emat && rho) {
-      emat[g].resize((size_t)p.n_elem);
-      HIP_TRY(hipMemcpy(emat[g].data(), p.emat, emat[g].size() * 4, hipMemcpyDeviceToHost));
-    }
-    gv.push_back({p.etype, 2, p.n_elem, conn[g].data(), emat[g].empty() ? nullptr : emat[g].data()});
-  }
+  for (size_t g = 0; g < n.parts.size(); g++)
+    gv.push_back({n.parts[g].etype, 2, n.parts[g].n_elem, conn[g].data(), emat[g].empty() ? nullptr : emat[g].data()});
   if (int rc = dload_check(who, (int32_t)gv.size(), gv.data(), n_mat, rho, dl)) return rc;
   DloadList L;
   double *nodal = nullptr;

@@ -485,18 +485,6 @@ __global__ __launch_bounds__(HEAT_BS) void k_heat(const HeatArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static int heat_type_index(int32_t etype) {
-  switch (etype) {
-    case 341: return 0; case 342: return 1; case 351: return 2; case 352: return 3; case 361: return 4; case 362: return 5;
-    default: return -1;
-  }
-}
-static int heat_nodes(int32_t etype) {
-  static const int nn[6] = {4, 10, 6, 15, 8, 20};
-  const int t = heat_type_index(etype);
-  return t < 0 ? 0 : nn[t];
-}
-
 static void heat_bc_free(HeatAsm &h);  // fx_heat_bc.h
 static void heat_free(fx_context *c) {
   HeatAsm &h = c->heat;
@@ -510,38 +498,44 @@ static void heat_free(fx_context *c) {
   h.prof_key = 0;
 }
 
+// A rule's tables back to back in one device block, uploaded when the slot is still empty (a type's or a face shape's first use);
+// the caller slices the block in the order given.
+static int upload_tables_once(double **slot, std::initializer_list<const std::vector<double> *> tables) {
+  if (*slot) return 0;
+  std::vector<double> all;
+  for (const std::vector<double> *t : tables) all.insert(all.end(), t->begin(), t->end());
+  if (dev_alloc(slot, all.size())) return FX_ERROR_RUNTIME;
+  HIP_TRY(hipMemcpy(*slot, all.data(), all.size() * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+static int heat_rule_dev(double **slot, const fxh::Rule &r, HeatRuleDev &d) {
+  if (upload_tables_once(slot, {&r.H, &r.dR, &r.dS, &r.dT, &r.W})) return FX_ERROR_RUNTIME;
+  const size_t n = (size_t)r.nn * r.nq;
+  const double *b = *slot;
+  d = HeatRuleDev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, r.sign};
+  return 0;
+}
 // the two rules of a type on the device, made at the type's first use
 static int heat_rules(fx_context *c, int32_t etype, HeatRuleDev &rc, HeatRuleDev &rk) {
-  HeatAsm &h = c->heat;
-  const int t = heat_type_index(etype);
   for (int k = 0; k < 2; k++) {
     fxh::Rule r;
     fxh::make_rule(etype, k == 1, r);
-    const size_t n = (size_t)r.nn * r.nq;
-    if (!h.rule[t][k]) {
-      std::vector<double> all;
-      all.insert(all.end(), r.H.begin(), r.H.end()); all.insert(all.end(), r.dR.begin(), r.dR.end());
-      all.insert(all.end(), r.dS.begin(), r.dS.end()); all.insert(all.end(), r.dT.begin(), r.dT.end());
-      all.insert(all.end(), r.W.begin(), r.W.end());
-      if (dev_alloc(&h.rule[t][k], all.size())) return FX_ERROR_RUNTIME;
-      HIP_TRY(hipMemcpy(h.rule[t][k], all.data(), all.size() * 8, hipMemcpyHostToDevice));
-    }
-    const double *b = h.rule[t][k];
-    (k ? rk : rc) = HeatRuleDev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, r.sign};
+    if (heat_rule_dev(&c->heat.rule[c3_type_index(etype)][k], r, k ? rk : rc)) return FX_ERROR_RUNTIME;
   }
   return 0;
 }
 
-static void heat_launch(fx_context *c, int32_t etype, const HeatArgs &a) {
-  const dim3 grid((unsigned)((a.e1 - a.e0 + HEAT_EPB - 1) / HEAT_EPB)), bs(HEAT_BS);
-  switch (etype) {
-    case 341: hipLaunchKernelGGL((k_heat<4, 8, false, true>), grid, bs, 0, c->stream, a); break;
-    case 342: hipLaunchKernelGGL((k_heat<10, 27, true, false>), grid, bs, 0, c->stream, a); break;
-    case 351: hipLaunchKernelGGL((k_heat<6, 6, false, false>), grid, bs, 0, c->stream, a); break;
-    case 352: hipLaunchKernelGGL((k_heat<15, 27, true, false>), grid, bs, 0, c->stream, a); break;
-    case 361: hipLaunchKernelGGL((k_heat<8, 8, false, false>), grid, bs, 0, c->stream, a); break;
-    case 362: hipLaunchKernelGGL((k_heat<20, 27, true, false>), grid, bs, 0, c->stream, a); break;
-  }
+// k_heat's template arguments by type: the points of heat_THERMAL_3xx / heat_CAPACITY_3xx, HRZ and LASTT as the kernel explains them
+template <int ETYPE>
+struct HeatEl {
+  static constexpr int NN = c3_facts(ETYPE).nn, NQ = NN > 8 ? 27 : (ETYPE == 351 ? 6 : 8);
+  static constexpr bool HRZ = NN > 8, LASTT = ETYPE == 341;
+};
+static void heat_launch(fx_context *c, int32_t etype, dim3 grid, const HeatArgs &a) {  // grid: HEAT_EPB elements per workgroup
+  with_solid_type(etype, [&](auto t) {
+    using El = HeatEl<decltype(t)::value>;
+    hipLaunchKernelGGL((k_heat<El::NN, El::NQ, El::HRZ, El::LASTT>), grid, dim3(HEAT_BS), 0, c->stream, a);
+  });
 }
 
 // fx_heat_material_view[] as one device block (HeatArgs); need_cap: the capacity tables are read
@@ -651,11 +645,7 @@ static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const d
                          const double *flux, int32_t n_fix, const int32_t *fix_node, const double *fix_val, const fx_heat_bc *bc,
                          float *ms_kernel) {
   if (!c || !heat || !mat) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
-  for (int32_t g = 0; g < n_group; g++)
-    if (heat_nodes(groups[g].etype) == 0)
-      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (341, 342, 351, 352, 361, 362)",
-                     (int)g + 1, (int)groups[g].etype);
+  if (int rc = check_group_types(who, n_group, groups, SOLID_TYPES_ASCENDING)) return rc;
   if (mat->NDOF != 1) return fx_fail(who, FX_ERROR_UNSUPPORTED, "the heat matrix has NDOF = 1 (got %d)", (int)mat->NDOF);
   const bool cap = heat->dtime > 0.0;
   if (n_node < 1 || !coord) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
@@ -670,31 +660,7 @@ static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const d
   if (n_fix < 0 || (n_fix > 0 && (!fix_node || !fix_val))) return fx_fail(who, FX_ERROR_RUNTIME, "fixed temperatures missing");
   for (int32_t k = 0; k < n_fix; k++)
     if (fix_node[k] < 1 || fix_node[k] > n_node) return fx_fail(who, FX_ERROR_RUNTIME, "fixed node id out of range");
-  for (int32_t g = 0; g < n_group; g++) {
-    const fx_elem_group &G = groups[g];
-    if (G.n_elem < 0 || (G.n_elem > 0 && !G.conn)) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: connectivity missing", (int)g + 1);
-    if (n_mat > 1 && G.n_elem > 0 && !G.elem_mat) return fx_fail(who, FX_ERROR_RUNTIME, "group %d: several materials need elem_mat", (int)g + 1);
-    const int nn = heat_nodes(G.etype);
-    int32_t bad_mat = INT32_MAX, bad_node = INT32_MAX, dup = INT32_MAX;
-    parallel_for(G.n_elem, [&](int64_t a, int64_t b) {
-      int32_t bm = INT32_MAX, bn = INT32_MAX, dp = INT32_MAX;
-      for (int64_t e = a; e < b && bm == INT32_MAX && bn == INT32_MAX && dp == INT32_MAX; e++) {
-        const int32_t *en = G.conn + (size_t)nn * e;
-        if (G.elem_mat && (G.elem_mat[e] < 1 || G.elem_mat[e] > n_mat)) bm = (int32_t)e;
-        for (int x = 0; x < nn; x++)
-          if (en[x] < 1 || en[x] > n_node) bn = (int32_t)e;
-        if (bn == INT32_MAX && names_a_node_twice(en, nn)) dp = (int32_t)e;
-      }
-      __atomic_fetch_min(&bad_mat, bm, __ATOMIC_RELAXED);
-      __atomic_fetch_min(&bad_node, bn, __ATOMIC_RELAXED);
-      __atomic_fetch_min(&dup, dp, __ATOMIC_RELAXED);
-    });
-    if (bad_mat != INT32_MAX) return fx_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: material id out of range", (int)g + 1, (int)bad_mat + 1);
-    if (bad_node != INT32_MAX) return fx_fail(who, FX_ERROR_RUNTIME, "group %d, element %d: node id out of range", (int)g + 1, (int)bad_node + 1);
-    if (dup != INT32_MAX)
-      return fx_fail(who, FX_ERROR_RUNTIME, "group %d (TYPE=%d), element %d names a node twice (a degenerate element)", (int)g + 1,
-                     (int)G.etype, (int)dup + 1);
-  }
+  if (int rc = check_group_elements(who, n_node, n_group, groups, n_mat, false)) return rc;  // (no collapsed hexahedra here)
   if (bc)
     if (int rc = heat_bc_check(who, n_group, groups, bc)) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -716,19 +682,13 @@ static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const d
   if (heat->temp0) HIP_TRY(hipMemcpyAsync(d_temp0, heat->temp0, np * 8, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
   if (int rc = heat_upload_mats(c, tmp, n_mat, mats, cap, md)) return rc;
-  std::vector<int32_t *> d_conn((size_t)n_group, nullptr), d_emat((size_t)n_group, nullptr);
+  std::vector<const int32_t *> d_conn, d_emat;
+  if (int rc = upload_group_conn(c, tmp, n_group, groups, d_conn, d_emat)) return rc;
   for (int32_t g = 0; g < n_group; g++) {
     const fx_elem_group &G = groups[g];
     ElemColors &ec = h.ec[g];
     if (G.n_elem < 1) { elem_colors_free(ec); continue; }
-    const int nn = heat_nodes(G.etype);
-    const size_t nw = (size_t)nn * G.n_elem;
-    if (tmp.alloc(&d_conn[g], nw)) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpyAsync(d_conn[g], G.conn, nw * 4, hipMemcpyHostToDevice, c->stream));
-    if (G.elem_mat) {
-      if (tmp.alloc(&d_emat[g], (size_t)G.n_elem)) return FX_ERROR_RUNTIME;
-      HIP_TRY(hipMemcpyAsync(d_emat[g], G.elem_mat, (size_t)G.n_elem * 4, hipMemcpyHostToDevice, c->stream));
-    }
+    const int nn = c3_nodes(G.etype);
     const uint64_t key0 = ec.key;
     const int32_t *order0 = ec.order;
     if (ensure_elem_colors(c, ec, G.n_elem, G.conn, n_node, nn, G.etype)) return FX_ERROR_RUNTIME;
@@ -736,18 +696,8 @@ static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const d
     if (ec.offsets.empty())
       return fx_fail(who, FX_ERROR_RUNTIME, "group %d cannot be coloured (a node in more than 64 elements, or FX_ASM_ATOMIC set)", (int)g + 1);
     if (!ec.pos) {
-      const int64_t nmap = (int64_t)nn * nn * G.n_elem;
-      if (dev_alloc(&ec.pos, (size_t)nmap)) return FX_ERROR_RUNTIME;
-      const dim3 grid((unsigned)((nmap + 255) / 256));
-      const int32_t ne = G.n_elem, *dc = d_conn[g];
-      switch (nn) {
-        case 4: hipLaunchKernelGGL((k_scatter_map<4>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-        case 6: hipLaunchKernelGGL((k_scatter_map<6>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-        case 8: hipLaunchKernelGGL((k_scatter_map<8>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-        case 10: hipLaunchKernelGGL((k_scatter_map<10>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-        case 15: hipLaunchKernelGGL((k_scatter_map<15>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-        default: hipLaunchKernelGGL((k_scatter_map<20>), grid, dim3(256), 0, c->stream, ne, dc, h.indexL, h.itemL, h.indexU, h.itemU, ec.pos); break;
-      }
+      if (dev_alloc(&ec.pos, (size_t)nn * nn * G.n_elem)) return FX_ERROR_RUNTIME;
+      launch_scatter_map(c, nn, G.n_elem, d_conn[g], h.indexL, h.itemL, h.indexU, h.itemU, ec.pos);
       HIP_TRY(hipGetLastError());
       h.n_maps++;
     }
@@ -772,10 +722,10 @@ static int heat_assemble(const char *who, fx_context *c, int32_t n_node, const d
     a.beta = heat->beta; a.alfa = alfa; a.dtime = heat->dtime; a.with_cap = cap ? 1 : 0;
     a.moff = md.moff; a.mntab = md.mntab; a.mblk = md.mblk; a.pos = ec.pos;
     a.D = h.D; a.AL = h.AL; a.AU = h.AU; a.B = h.B; a.err = d_err;
-    for (size_t k = 0; k + 1 < ec.offsets.size(); k++) {
-      a.e0 = ec.offsets[k]; a.e1 = ec.offsets[k + 1];
-      if (a.e1 > a.e0) heat_launch(c, G.etype, a);
-    }
+    for_colour_ranges(ec.offsets, false, HEAT_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+      a.e0 = e0; a.e1 = e1;
+      heat_launch(c, G.etype, grid, a);
+    });
   }
   HIP_TRY(hipGetLastError());
   if (bc) {  // heat_mat_ass_bc_DFLUX, _FILM, _RADIATE
@@ -830,8 +780,8 @@ extern "C" int fx_heat_element(fx_context *c, int32_t etype, const double *ecoor
                                const fx_heat_material_view *mat, double dtime, double *ss, double *s0) {
   const char *who = "fx_heat_element";
   if (!c || !ecoord || !tt || !mat || !ss) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  const int nn = heat_nodes(etype);
-  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (341, 342, 351, 352, 361, 362)", (int)etype);
+  const int nn = c3_nodes(etype);
+  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (%s)", (int)etype, SOLID_TYPES_ASCENDING);
   const bool cap = dtime > 0.0;
   if (cap && (!tt0 || !s0)) return fx_fail(who, FX_ERROR_RUNTIME, "tt0 and s0 are needed with dtime > 0");
   if (int rc = heat_check_mats(who, 1, mat, cap)) return rc;
@@ -855,7 +805,7 @@ extern "C" int fx_heat_element(fx_context *c, int32_t etype, const double *ecoor
   a.e0 = 0; a.e1 = 1; a.coord = d_coord; a.conn = d_conn; a.temp = d_t; a.temp0 = d_t0;
   a.beta = 1.0; a.alfa = 0.0; a.dtime = dtime; a.with_cap = cap ? 1 : 0;
   a.moff = md.moff; a.mntab = md.mntab; a.mblk = md.mblk; a.ss_out = d_ss; a.s0_out = d_s0; a.err = d_err;
-  heat_launch(c, etype, a);
+  heat_launch(c, etype, dim3(1), a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(ss, d_ss, (size_t)nn * nn * 8, hipMemcpyDeviceToHost));

@@ -382,31 +382,7 @@ __global__ __launch_bounds__(HEAT_BS) void k_heat_bf(const HeatBfArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-// NOD of the routines (1-based positions in the element), by type index (341, 342, 351, 352, 361, 362) and face
-static const int8_t HEAT_NOD[6][6][8] = {
-    {{1, 2, 3}, {4, 2, 1}, {4, 3, 2}, {4, 1, 3}},
-    {{1, 2, 3, 5, 6, 7}, {4, 2, 1, 9, 5, 8}, {4, 3, 2, 10, 6, 9}, {4, 1, 3, 8, 7, 10}},
-    {{1, 2, 3}, {6, 5, 4}, {4, 5, 2, 1}, {5, 6, 3, 2}, {6, 4, 1, 3}},
-    {{1, 2, 3, 7, 8, 9}, {6, 5, 4, 11, 10, 12}, {4, 5, 2, 1, 10, 14, 7, 13}, {5, 6, 3, 2, 11, 15, 8, 14}, {6, 4, 1, 3, 12, 13, 9, 15}},
-    {{1, 2, 3, 4}, {8, 7, 6, 5}, {5, 6, 2, 1}, {6, 7, 3, 2}, {7, 8, 4, 3}, {8, 5, 1, 4}},
-    {{1, 2, 3, 4, 9, 10, 11, 12}, {8, 7, 6, 5, 15, 14, 13, 16}, {5, 6, 2, 1, 13, 18, 9, 17}, {6, 7, 3, 2, 14, 19, 10, 18},
-     {7, 8, 4, 3, 15, 20, 11, 19}, {8, 5, 1, 4, 16, 17, 12, 20}}};
-static int heat_faces(int32_t etype) {
-  static const int nf[6] = {4, 4, 5, 5, 6, 6};
-  const int t = heat_type_index(etype);
-  return t < 0 ? 0 : nf[t];
-}
-// mm of heat_mat_ass_bc_FILM.f90:75-94
-static int heat_face_nodes(int32_t etype, int32_t face) {
-  switch (etype) {
-    case 341: return 3;
-    case 342: return 6;
-    case 351: return face <= 2 ? 3 : 4;
-    case 352: return face <= 2 ? 6 : 8;
-    case 361: return 4;
-    default: return 8;
-  }
-}
+// The routines' NOD tables are getSubFace's (C3_FACE_NOD), mm of heat_mat_ass_bc_FILM.f90:75-94 is c3_face_nodes.
 static int heat_face_form(int kind, int32_t etype, int mm) {
   if (mm == 3) return HEATF_T3;
   if (kind == HEATF_DFLUX) return etype == 342 ? HEATF_T6 : HEATF_WG;
@@ -438,57 +414,25 @@ static int heat_face_rule(fx_context *c, int kind, int32_t etype, int mm, HeatFa
   if (id == 0) fxh::face_q4(r);
   else if (id == 2) fxh::face_t6(r);
   else fxh::face_q8(r, id == 3);
+  if (upload_tables_once(&h.frule[id], {&r.H, &r.d1, &r.d2, &r.W})) return FX_ERROR_RUNTIME;
   const size_t n = (size_t)r.mm * r.nq;
-  if (!h.frule[id]) {
-    std::vector<double> all;
-    all.insert(all.end(), r.H.begin(), r.H.end()); all.insert(all.end(), r.d1.begin(), r.d1.end());
-    all.insert(all.end(), r.d2.begin(), r.d2.end()); all.insert(all.end(), r.W.begin(), r.W.end());
-    if (dev_alloc(&h.frule[id], all.size())) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpy(h.frule[id], all.data(), all.size() * 8, hipMemcpyHostToDevice));
-  }
   const double *b = h.frule[id];
   a.nq = r.nq; a.H = b; a.d1 = b + n; a.d2 = b + 2 * n; a.W = b + 3 * n;
   return 0;
 }
 static int heat_bf_rule(fx_context *c, int32_t etype, HeatBfArgs &a) {
-  HeatAsm &h = c->heat;
-  const int t = heat_type_index(etype);
   fxh::Rule r;
   fxh::make_bf_rule(etype, r);
-  const size_t n = (size_t)r.nn * r.nq;
-  if (!h.bfrule[t]) {
-    std::vector<double> all;
-    all.insert(all.end(), r.H.begin(), r.H.end()); all.insert(all.end(), r.dR.begin(), r.dR.end());
-    all.insert(all.end(), r.dS.begin(), r.dS.end()); all.insert(all.end(), r.dT.begin(), r.dT.end());
-    all.insert(all.end(), r.W.begin(), r.W.end());
-    if (dev_alloc(&h.bfrule[t], all.size())) return FX_ERROR_RUNTIME;
-    HIP_TRY(hipMemcpy(h.bfrule[t], all.data(), all.size() * 8, hipMemcpyHostToDevice));
-  }
-  const double *b = h.bfrule[t];
-  a.r = HeatRuleDev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, r.sign};
   a.nq = r.nq; a.etype = etype;
-  return 0;
+  return heat_rule_dev(&c->heat.bfrule[c3_type_index(etype)], r, a.r);
 }
 
-static void heat_face_launch(fx_context *c, int mm, const HeatFaceArgs &a) {
-  const dim3 grid((unsigned)((a.e1 - a.e0 + HEATF_FPB - 1) / HEATF_FPB)), bs(HEATF_BS);
-  switch (mm) {
-    case 3: hipLaunchKernelGGL((k_heat_face<3>), grid, bs, 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL((k_heat_face<4>), grid, bs, 0, c->stream, a); break;
-    case 6: hipLaunchKernelGGL((k_heat_face<6>), grid, bs, 0, c->stream, a); break;
-    default: hipLaunchKernelGGL((k_heat_face<8>), grid, bs, 0, c->stream, a); break;
-  }
+// grid: HEATF_FPB faces, HEAT_EPB elements per workgroup
+static void heat_face_launch(fx_context *c, int mm, dim3 grid, const HeatFaceArgs &a) {
+  with_face_nodes(mm, [&](auto m) { hipLaunchKernelGGL((k_heat_face<decltype(m)::value>), grid, dim3(HEATF_BS), 0, c->stream, a); });
 }
-static void heat_bf_launch(fx_context *c, const HeatBfArgs &a) {
-  const dim3 grid((unsigned)((a.e1 - a.e0 + HEAT_EPB - 1) / HEAT_EPB)), bs(HEAT_BS);
-  switch (a.etype) {
-    case 341: hipLaunchKernelGGL((k_heat_bf<4>), grid, bs, 0, c->stream, a); break;
-    case 342: hipLaunchKernelGGL((k_heat_bf<10>), grid, bs, 0, c->stream, a); break;
-    case 351: hipLaunchKernelGGL((k_heat_bf<6>), grid, bs, 0, c->stream, a); break;
-    case 352: hipLaunchKernelGGL((k_heat_bf<15>), grid, bs, 0, c->stream, a); break;
-    case 361: hipLaunchKernelGGL((k_heat_bf<8>), grid, bs, 0, c->stream, a); break;
-    default: hipLaunchKernelGGL((k_heat_bf<20>), grid, bs, 0, c->stream, a); break;
-  }
+static void heat_bf_launch(fx_context *c, dim3 grid, const HeatBfArgs &a) {
+  with_solid_type(a.etype, [&](auto t) { hipLaunchKernelGGL((k_heat_bf<C3El<decltype(t)::value>::NN>), grid, dim3(HEAT_BS), 0, c->stream, a); });
 }
 
 static const fx_heat_surface *heat_bc_list(const fx_heat_bc *bc, int kind) {
@@ -504,23 +448,13 @@ static int heat_bc_check(const char *who, int32_t n_group, const fx_elem_group *
     if (!s.group || !s.elem || !s.face || !s.val || (kind != HEATF_DFLUX && !s.sink))
       return fx_fail(who, FX_ERROR_RUNTIME, "%s: list arrays missing", name[kind]);
     for (int32_t k = 0; k < s.n; k++) {
-      if (s.group[k] < 0 || s.group[k] >= n_group) return fx_fail(who, FX_ERROR_RUNTIME, "%s, entry %d: group out of range", name[kind], (int)k + 1);
+      if (int rc = check_list_entry(who, name[kind], k, s.group[k], s.elem[k], n_group, groups)) return rc;
       const fx_elem_group &G = groups[s.group[k]];
-      if (s.elem[k] < 0 || s.elem[k] >= G.n_elem)
-        return fx_fail(who, FX_ERROR_RUNTIME, "%s, entry %d: element %d is not in group %d", name[kind], (int)k + 1, (int)s.elem[k], (int)s.group[k] + 1);
-      if (s.face[k] < (kind == HEATF_DFLUX ? 0 : 1) || s.face[k] > heat_faces(G.etype))
+      if (s.face[k] < (kind == HEATF_DFLUX ? 0 : 1) || s.face[k] > c3_faces(G.etype))
         return fx_fail(who, FX_ERROR_RUNTIME, "%s, entry %d: TYPE=%d has no face %d", name[kind], (int)k + 1, (int)G.etype, (int)s.face[k]);
     }
   }
   return 0;
-}
-
-template <int NN>
-static void heat_face_map(fx_context *c, HeatFaceList &l) {
-  HeatAsm &h = c->heat;
-  const int64_t nmap = (int64_t)NN * NN * l.n;
-  hipLaunchKernelGGL((k_scatter_map<NN>), dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, c->stream, l.n, l.conn, h.indexL, h.itemL,
-                     h.indexU, h.itemU, l.ec.pos);
 }
 
 // The lists of this call as h.fl[(kind * n_group + g) * 3 + shape] (shape 0: the group's triangles, 1: its quadrilaterals, 2: its
@@ -535,7 +469,7 @@ static int heat_bc_prepare(fx_context *c, const char *who, int32_t n_node, int32
     const fx_heat_surface &s = *heat_bc_list(bc, kind);
     for (int32_t k = 0; k < s.n; k++) {
       const int32_t et = groups[s.group[k]].etype;
-      const int shape = s.face[k] == 0 ? 2 : (heat_face_nodes(et, s.face[k]) % 3 == 0 ? 0 : 1);
+      const int shape = s.face[k] == 0 ? 2 : (c3_face_nodes(et, s.face[k]) % 3 == 0 ? 0 : 1);
       pick[((size_t)kind * n_group + s.group[k]) * 3 + shape].push_back(k);
     }
   }
@@ -548,8 +482,8 @@ static int heat_bc_prepare(fx_context *c, const char *who, int32_t n_node, int32
         const std::vector<int32_t> &idx = pick[slot];
         if (idx.empty()) { heat_face_list_free(l); continue; }
         const fx_elem_group &G = groups[g];
-        const int nne = heat_nodes(G.etype), t = heat_type_index(G.etype);
-        const int nn = shape == 2 ? nne : heat_face_nodes(G.etype, s.face[idx[0]]);
+        const int nne = c3_nodes(G.etype), t = c3_type_index(G.etype);
+        const int nn = shape == 2 ? nne : c3_face_nodes(G.etype, s.face[idx[0]]);
         uint64_t key = fnv_mix(fnv_mix(fnv_mix(1469598103934665603ull, h.ec[g].key), (uint64_t)G.etype), h.prof_key);
         for (int32_t k : idx) key = fnv_mix(fnv_mix(fnv_mix(key, (uint64_t)k), (uint64_t)s.elem[k]), (uint64_t)s.face[k]);
         key |= 1;
@@ -559,7 +493,7 @@ static int heat_bc_prepare(fx_context *c, const char *who, int32_t n_node, int32
         std::vector<int32_t> conn((size_t)nn * l.n);
         for (int32_t q = 0; q < l.n; q++) {
           const int32_t *en = G.conn + (size_t)nne * s.elem[idx[q]];
-          for (int i = 0; i < nn; i++) conn[(size_t)nn * q + i] = shape == 2 ? en[i] : en[HEAT_NOD[t][s.face[idx[q]] - 1][i] - 1];
+          for (int i = 0; i < nn; i++) conn[(size_t)nn * q + i] = shape == 2 ? en[i] : en[C3_FACE_NOD[t][s.face[idx[q]] - 1][i] - 1];
         }
         if (dev_alloc(&l.conn, conn.size()) || dev_alloc(&l.src, idx.size())) return FX_ERROR_RUNTIME;
         HIP_TRY(hipMemcpy(l.conn, conn.data(), conn.size() * 4, hipMemcpyHostToDevice));
@@ -571,12 +505,7 @@ static int heat_bc_prepare(fx_context *c, const char *who, int32_t n_node, int32
                          (int)g + 1);
         if (kind != HEATF_DFLUX) {
           if (dev_alloc(&l.ec.pos, (size_t)nn * nn * l.n)) return FX_ERROR_RUNTIME;
-          switch (nn) {
-            case 3: heat_face_map<3>(c, l); break;
-            case 4: heat_face_map<4>(c, l); break;
-            case 6: heat_face_map<6>(c, l); break;
-            default: heat_face_map<8>(c, l); break;
-          }
+          launch_scatter_map(c, nn, l.n, l.conn, h.indexL, h.itemL, h.indexU, h.itemU, l.ec.pos);
           HIP_TRY(hipGetLastError());
           h.n_face_maps++;
         }
@@ -609,10 +538,10 @@ static int heat_bc_launch(fx_context *c, int32_t n_group, const fx_elem_group *g
           HeatBfArgs a{};
           if (heat_bf_rule(c, groups[g].etype, a)) return FX_ERROR_RUNTIME;
           a.list = l.ec.order; a.conn = l.conn; a.src = l.src; a.coord = d_coord; a.val = d_val; a.B = h.B;
-          for (size_t k = 0; k + 1 < off.size(); k++) {
-            a.e0 = off[k]; a.e1 = off[k + 1];
-            if (a.e1 > a.e0) heat_bf_launch(c, a);
-          }
+          for_colour_ranges(off, false, HEAT_EPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+            a.e0 = e0; a.e1 = e1;
+            heat_bf_launch(c, grid, a);
+          });
           continue;
         }
         HeatFaceArgs a{};
@@ -620,10 +549,10 @@ static int heat_bc_launch(fx_context *c, int32_t n_group, const fx_elem_group *g
         a.list = l.ec.order; a.conn = l.conn; a.src = l.src; a.coord = d_coord; a.temp = d_temp; a.val = d_val; a.sink = d_sink;
         a.tzero = bc->tzero; a.kind = kind; a.form = heat_face_form(kind, groups[g].etype, l.nn);
         a.pos = l.ec.pos; a.D = h.D; a.AL = h.AL; a.AU = h.AU; a.B = h.B; a.err = d_err;
-        for (size_t k = 0; k + 1 < off.size(); k++) {
-          a.e0 = off[k]; a.e1 = off[k + 1];
-          if (a.e1 > a.e0) heat_face_launch(c, l.nn, a);
-        }
+        for_colour_ranges(off, false, HEATF_FPB, [&](dim3 grid, int32_t e0, int32_t e1) {
+          a.e0 = e0; a.e1 = e1;
+          heat_face_launch(c, l.nn, grid, a);
+        });
       }
   }
   HIP_TRY(hipGetLastError());
@@ -634,17 +563,17 @@ extern "C" int fx_heat_face(fx_context *c, int32_t etype, int32_t kind, int32_t 
                             double sink, double tzero, double *term1, double *term2, int32_t *nsuf, int32_t *mm_out) {
   const char *who = "fx_heat_face";
   if (!c || !ecoord || !term2 || !nsuf || !mm_out) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  const int nn = heat_nodes(etype), t = heat_type_index(etype);
-  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (341, 342, 351, 352, 361, 362)", (int)etype);
+  const int nn = c3_nodes(etype), t = c3_type_index(etype);
+  if (nn == 0) return fx_fail(who, FX_ERROR_UNSUPPORTED, "element type %d not supported on the device (%s)", (int)etype, SOLID_TYPES_ASCENDING);
   if (kind < HEATF_DFLUX || kind > HEATF_RADIATE) return fx_fail(who, FX_ERROR_RUNTIME, "kind must be 0 (dflux), 1 (film) or 2 (radiate)");
-  if (face < (kind == HEATF_DFLUX ? 0 : 1) || face > heat_faces(etype)) return fx_fail(who, FX_ERROR_RUNTIME, "TYPE=%d has no face %d", (int)etype, (int)face);
+  if (face < (kind == HEATF_DFLUX ? 0 : 1) || face > c3_faces(etype)) return fx_fail(who, FX_ERROR_RUNTIME, "TYPE=%d has no face %d", (int)etype, (int)face);
   if (kind != HEATF_DFLUX && !term1) return fx_fail(who, FX_ERROR_RUNTIME, "term1 missing");
   if (kind == HEATF_RADIATE && !tt) return fx_fail(who, FX_ERROR_RUNTIME, "radiate needs the node temperatures");
   HIP_TRY(hipSetDevice(c->device));
   DevScratch tmp;
-  const int mm = face == 0 ? nn : heat_face_nodes(etype, face);
+  const int mm = face == 0 ? nn : c3_face_nodes(etype, face);
   int32_t conn[20];
-  for (int i = 0; i < mm; i++) conn[i] = face == 0 ? i + 1 : HEAT_NOD[t][face - 1][i];
+  for (int i = 0; i < mm; i++) conn[i] = face == 0 ? i + 1 : C3_FACE_NOD[t][face - 1][i];
   double *d_coord = nullptr, *d_t = nullptr, *d_v = nullptr, *d_t1 = nullptr, *d_t2 = nullptr;
   int32_t *d_conn = nullptr, *d_err = nullptr;
   const double vs[2] = {val, sink};
@@ -661,14 +590,14 @@ extern "C" int fx_heat_face(fx_context *c, int32_t etype, int32_t kind, int32_t 
     HeatBfArgs a{};
     if (heat_bf_rule(c, etype, a)) return FX_ERROR_RUNTIME;
     a.e0 = 0; a.e1 = 1; a.conn = d_conn; a.coord = d_coord; a.val = d_v; a.v_out = d_t2;
-    heat_bf_launch(c, a);
+    heat_bf_launch(c, dim3(1), a);
   } else {
     HeatFaceArgs a{};
     if (heat_face_rule(c, kind, etype, mm, a)) return FX_ERROR_RUNTIME;
     a.e0 = 0; a.e1 = 1; a.conn = d_conn; a.coord = d_coord; a.temp = tt ? d_t : nullptr; a.val = d_v; a.sink = d_v + 1;
     a.tzero = tzero; a.kind = kind; a.form = heat_face_form(kind, etype, mm);
     a.t1_out = kind == HEATF_DFLUX ? nullptr : d_t1; a.t2_out = d_t2; a.err = d_err;
-    heat_face_launch(c, mm, a);
+    heat_face_launch(c, mm, dim3(1), a);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -39,8 +39,9 @@ struct NodalEl {
     return ETYPE == 352 ? (j < 3 ? j : j + 3) : (ETYPE == 362 ? ((j & 1) * 2 + ((j >> 1) & 1) * 6 + (j >> 2) * 18) : j);
   }
 };
-static int nodal_records(int32_t etype) {
-  return etype == 341 || etype == 351 ? 1 : (etype == 342 ? 4 : (etype == 352 ? 6 : (etype == 361 || etype == 362 ? 8 : 0)));
+static int nodal_records(int32_t etype) {  // NodalEl<etype>::NV; 0: not a type the device knows
+  if (c3_facts(etype).nn == 0) return 0;
+  return etype == 341 || etype == 351 ? 1 : (etype == 342 ? 4 : (etype == 352 ? 6 : 8));
 }
 
 // strain, stress: this group's [elem][point][6]; estrain, estress: its [elem][6]; rec: its records, [record][strain | stress][6]
@@ -379,14 +380,7 @@ static int nodal_run(fx_context *c, const char *who, const NodalList &L, const s
   for (const NodalPartIn &p : parts) {
     if (p.n_elem < 1) continue;
     double *es = arr(3) + 6 * e_at, *et = arr(4) + 6 * e_at, *rec = s.rec + 12 * r_at;
-    switch (p.etype) {
-      case 341: nodal_launch_element<341>(c, p, es, et, rec); break;
-      case 342: nodal_launch_element<342>(c, p, es, et, rec); break;
-      case 351: nodal_launch_element<351>(c, p, es, et, rec); break;
-      case 352: nodal_launch_element<352>(c, p, es, et, rec); break;
-      case 361: nodal_launch_element<361>(c, p, es, et, rec); break;
-      default: nodal_launch_element<362>(c, p, es, et, rec); break;
-    }
+    with_solid_type(p.etype, [&](auto t) { nodal_launch_element<decltype(t)::value>(c, p, es, et, rec); });
     e_at += p.n_elem;
     r_at += (int64_t)nodal_records(p.etype) * p.n_elem;
   }
@@ -423,11 +417,7 @@ extern "C" int fx_nodal_stress_groups(fx_context *c, int32_t n_node, int32_t n_g
                                       const double *stress, int32_t flags, fx_nodal_result *out, float *ms_kernel) {
   const char *who = "fx_nodal_stress_groups";
   if (!c || !out) return fx_fail(who, FX_ERROR_RUNTIME, "null argument");
-  if (n_group < 1 || !groups) return fx_fail(who, FX_ERROR_RUNTIME, "n_group must be >= 1");
-  for (int32_t g = 0; g < n_group; g++)
-    if (nodal_records(groups[g].etype) == 0)
-      return fx_fail(who, FX_ERROR_UNSUPPORTED, "group %d: element type %d not supported on the device (361, 341, 342, 351, 352, 362)", (int)g + 1,
-                     (int)groups[g].etype);
+  if (int rc = check_group_types(who, n_group, groups, "361, 341, 342, 351, 352, 362")) return rc;
   if (n_node < 1 || !strain || !stress) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh or missing point arrays");
   if (flags < 0 || flags > 255) return fx_fail(who, FX_ERROR_RUNTIME, "flags outside 0..255");
   std::vector<NodalPartIn> parts;
@@ -463,12 +453,9 @@ extern "C" int fx_nl_nodal_stress(fx_context *c, int32_t flags, fx_nodal_result 
   std::vector<NodalPartIn> parts;
   for (const NlPart &p : n.parts) parts.push_back({p.etype, p.n_elem, nullptr, n.st.strain + 6 * p.pt_off, n.st.stress + 6 * p.pt_off});
   if (!c->nodal_list_nl.row) {  // once per fx_nl_init*: the connectivity lives on the device, the list is made on the host
-    std::vector<std::vector<int32_t>> conn(parts.size());
-    for (size_t g = 0; g < parts.size(); g++) {
-      conn[g].resize((size_t)n.parts[g].nn * n.parts[g].n_elem);
-      if (!conn[g].empty()) HIP_TRY(hipMemcpy(conn[g].data(), n.parts[g].conn, conn[g].size() * 4, hipMemcpyDeviceToHost));
-      parts[g].conn = conn[g].data();
-    }
+    std::vector<std::vector<int32_t>> conn, emat;
+    if (int rc = nl_parts_to_host(n, false, conn, emat)) return rc;
+    for (size_t g = 0; g < parts.size(); g++) parts[g].conn = conn[g].data();
     if (int rc = nodal_ensure_list(c, who, c->nodal_list_nl, 0, c->A.NP, parts)) return rc;
   }
   return nodal_run(c, who, c->nodal_list_nl, parts, flags, out, ms_kernel);

@@ -429,6 +429,23 @@ extern "C" int fx_nl_init_groups(fx_context *c, int32_t n_node, const double *co
   return nl_init_driver(c, "fx_nl_init_groups", n_node, coord, n_group, groups, n_mat, mats);
 }
 
+// The connectivity of the resident parts (and, with_emat, their material ids) back on the host: fx_nl_set_dload and fx_nl_nodal_stress
+// resolve their lists there.
+static int nl_parts_to_host(const NlDev &n, bool with_emat, std::vector<std::vector<int32_t>> &conn, std::vector<std::vector<int32_t>> &emat) {
+  conn.assign(n.parts.size(), {});
+  emat.assign(n.parts.size(), {});
+  for (size_t g = 0; g < n.parts.size(); g++) {
+    const NlPart &p = n.parts[g];
+    conn[g].resize((size_t)p.nn * p.n_elem);
+    if (!conn[g].empty()) HIP_TRY(hipMemcpy(conn[g].data(), p.conn, conn[g].size() * 4, hipMemcpyDeviceToHost));
+    if (with_emat && p.emat && p.n_elem > 0) {
+      emat[g].resize((size_t)p.n_elem);
+      HIP_TRY(hipMemcpy(emat[g].data(), p.emat, emat[g].size() * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  return 0;
+}
+
 #define NL_READY(name)                                                                              \
   HIP_TRY(hipSetDevice(c->device));                                                                 \
   if (!c->nl.ready) { g_fx_error = name ": call fx_nl_init first"; return FX_ERROR_RUNTIME; }

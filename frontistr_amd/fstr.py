@@ -30,6 +30,7 @@ import numpy as np
 
 from . import hecmw
 from .hecmw import _chk, _ptr, lib
+from .mesh import C3_NODES, C3_POINTS, C3_SUBFACE
 
 INFINITE, TOTALLAG, UPDATELAG = 0, 1, 2
 BILINEAR, MULTILINEAR, SWIFT, RAMBERG_OSGOOD = 0, 1, 2, 3
@@ -156,17 +157,7 @@ class tDload:
     before: its entries take factor 1 (:141-142).  SolverContext.dload_groups and fstr_solid.set_dload take the object."""
 
     LTYPE = {"BX": 1, "BY": 2, "BZ": 3, "GRAV": 4, "CENT": 5}
-    # getSubFace (fistr1/src/lib/element/element.f90:181-315): the nodes of face f, 1-based positions in the element
-    SUBFACE = {
-        341: ((1, 2, 3), (4, 2, 1), (4, 3, 2), (4, 1, 3)),
-        342: ((1, 2, 3, 5, 6, 7), (4, 2, 1, 9, 5, 8), (4, 3, 2, 10, 6, 9), (4, 1, 3, 8, 7, 10)),
-        351: ((1, 2, 3), (6, 5, 4), (4, 5, 2, 1), (5, 6, 3, 2), (6, 4, 1, 3)),
-        352: ((1, 2, 3, 7, 8, 9), (6, 5, 4, 11, 10, 12), (4, 5, 2, 1, 10, 14, 7, 13), (5, 6, 3, 2, 11, 15, 8, 14),
-              (6, 4, 1, 3, 12, 13, 9, 15)),
-        361: ((1, 2, 3, 4), (8, 7, 6, 5), (5, 6, 2, 1), (6, 7, 3, 2), (7, 8, 4, 3), (8, 5, 1, 4)),
-        362: ((1, 2, 3, 4, 9, 10, 11, 12), (8, 7, 6, 5, 15, 14, 13, 16), (5, 6, 2, 1, 13, 18, 9, 17),
-              (6, 7, 3, 2, 14, 19, 10, 18), (7, 8, 4, 3, 15, 20, 11, 19), (8, 5, 1, 4, 16, 17, 12, 20)),
-    }
+    SUBFACE = C3_SUBFACE        # getSubFace: the nodes of face f, 1-based positions in the element
 
     def __init__(self):
         self.group, self.elem, self.ltype, self.params, self.held = [], [], [], [], []
@@ -231,8 +222,7 @@ def dload_faces(coord, groups, node_mask):
 class fstr_solid:
     """The resident nonlinear state of one context (created by fx_nl_init)."""
 
-    NODES = {361: 8, 341: 4, 342: 10, 351: 6, 352: 15, 362: 20}     # nodes per element
-    POINTS = {361: 8, 341: 1, 342: 4, 351: 2, 352: 9, 362: 27}      # quadrature points per element (NumOfQuadPoints)
+    NODES, POINTS = C3_NODES, C3_POINTS     # nodes and quadrature points (NumOfQuadPoints) per element
 
     def __init__(self, ctx, hecMESH_coord, hecMESH_conn, material, elem_mat=None, etype=361, groups=None, elemopt=2):
         """material: one tMaterial, or a list of them with elem_mat (1-based material id per element = the section's

@@ -21,6 +21,8 @@ import os
 
 import numpy as np
 
+from .mesh import C3_NODES as _C3_NODES, C3_POINTS as _C3_POINTS      # nodes and quadrature points of the six solid types
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBPATH = os.path.join(_HERE, "libfistr_hip.so")
 _lib = None
@@ -253,10 +255,6 @@ class hecmwST_local_mesh:
                       _ptr(self.export_index), _ptr(self.export_item))
         v._keep = self
         return v
-
-
-_C3_NODES = {341: 4, 342: 10, 351: 6, 352: 15, 362: 20}      # nodes and quadrature points of the types of fx_assemble_c3
-_C3_POINTS = {341: 1, 342: 4, 351: 2, 352: 9, 362: 27}
 
 
 def _bc_arrays(bc, load):
@@ -584,7 +582,7 @@ class SolverContext:
             etype, conn = int(grp[0]), np.ascontiguousarray(grp[1], dtype=np.int32)
             elemopt = int(grp[2]) if len(grp) > 2 and grp[2] is not None else 1
             em = None if len(grp) < 4 or grp[3] is None else np.ascontiguousarray(grp[3], dtype=np.int32)
-            nn = 8 if etype == 361 else _C3_NODES.get(etype, 0)
+            nn = _C3_NODES.get(etype, 0)
             n_elem = conn.size // nn if nn else (conn.shape[0] if conn.ndim == 2 else 0)
             keep += [conn, em]
             tab[g] = _ElemGroup(etype, elemopt, n_elem, _ptr(conn), _ptr(em))
@@ -658,7 +656,7 @@ class SolverContext:
             _chk(lib().fx_update_groups_linear_thermal(self.h, int(coord.shape[0]), _ptr(coord), ng, tab, int(Es.size), _ptr(Es),
                                                        _ptr(nus), C.byref(tv), _ptr(disp), ps, pt, _ptr(qf), C.byref(ms)))
             del keep_t
-        nqs = [8 if tab[g].etype == 361 else _C3_POINTS[tab[g].etype] for g in range(ng)]
+        nqs = [_C3_POINTS[tab[g].etype] for g in range(ng)]
         strain = [_staged(ps[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
         stress = [_staged(pt[g], tab[g].n_elem, nqs[g]) for g in range(ng)]
         del keep
@@ -671,7 +669,7 @@ class SolverContext:
         Returns a NodalStress.  A connectivity whose row length (or, flat, whose size) does not fit the type's node count is refused
         here with the code of an unknown type: fx_elem_group carries no row length, so the library cannot see it."""
         for grp in groups:
-            nn = _C3_NODES.get(int(grp[0]), 8 if int(grp[0]) == 361 else 0)
+            nn = _C3_NODES.get(int(grp[0]), 0)
             conn = np.asarray(grp[1])
             if nn and (conn.shape[1] != nn if conn.ndim == 2 else conn.size % nn):     # flat arrays pass as in assemble_groups
                 raise HecmwSolverError(-2, "nodal_stress_groups: TYPE=%d has %d nodes per element, the connectivity has shape %s"
@@ -680,7 +678,7 @@ class SolverContext:
         flat = lambda v: np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in v])
                                               if isinstance(v, (list, tuple)) else v, dtype=np.float64).ravel()
         st, ss = flat(strain), flat(stress)
-        nqs = [8 if tab[g].etype == 361 else _C3_POINTS.get(tab[g].etype, 0) for g in range(len(groups))]
+        nqs = [_C3_POINTS.get(tab[g].etype, 0) for g in range(len(groups))]
         want = 6 * sum(q * tab[g].n_elem for g, q in enumerate(nqs))
         if all(nqs) and (st.size != want or ss.size != want):
             raise ValueError("nodal_stress_groups: the point arrays hold %d / %d doubles, the groups need %d" % (st.size, ss.size, want))

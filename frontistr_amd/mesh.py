@@ -257,6 +257,17 @@ HEX20_EDGES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (
 C3_NODES = {341: 4, 342: 10, 351: 6, 352: 15, 361: 8, 362: 20}
 C3_POINTS = {341: 1, 342: 4, 351: 2, 352: 9, 361: 8, 362: 27}          # NumOfQuadPoints
 C3_EDGES = {342: TET10_EDGES, 352: PRISM15_EDGES, 362: HEX20_EDGES}
+# getSubFace (fistr1/src/lib/element/element.f90:181-315): the nodes of face f, 1-based positions in the element
+C3_SUBFACE = {
+    341: ((1, 2, 3), (4, 2, 1), (4, 3, 2), (4, 1, 3)),
+    342: ((1, 2, 3, 5, 6, 7), (4, 2, 1, 9, 5, 8), (4, 3, 2, 10, 6, 9), (4, 1, 3, 8, 7, 10)),
+    351: ((1, 2, 3), (6, 5, 4), (4, 5, 2, 1), (5, 6, 3, 2), (6, 4, 1, 3)),
+    352: ((1, 2, 3, 7, 8, 9), (6, 5, 4, 11, 10, 12), (4, 5, 2, 1, 10, 14, 7, 13), (5, 6, 3, 2, 11, 15, 8, 14),
+          (6, 4, 1, 3, 12, 13, 9, 15)),
+    361: ((1, 2, 3, 4), (8, 7, 6, 5), (5, 6, 2, 1), (6, 7, 3, 2), (7, 8, 4, 3), (8, 5, 1, 4)),
+    362: ((1, 2, 3, 4, 9, 10, 11, 12), (8, 7, 6, 5, 15, 14, 13, 16), (5, 6, 2, 1, 13, 18, 9, 17),
+          (6, 7, 3, 2, 14, 19, 10, 18), (7, 8, 4, 3, 15, 20, 11, 19), (8, 5, 1, 4, 16, 17, 12, 20)),
+}
 
 
 def _add_midedge_nodes(coord, conn, edges, curve, lo, hi, spacing):

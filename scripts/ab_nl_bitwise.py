@@ -3,6 +3,7 @@
 
     ab_nl_bitwise.py --dump OUT.npz [--lib PATH]            run the nonlinear cases below in this process, write every output
     ab_nl_bitwise.py --dump-linear OUT.npz [--lib PATH]     the same for the linear case set at the end of this text
+    ab_nl_bitwise.py --dump-fields OUT.npz [--lib PATH]     the same for the heat, load and stress-output case set at the end of this text
     ab_nl_bitwise.py --compare A.npz B.npz                  per array: equal bit for bit, or the first difference; exit 1 on any
 
 Not a test: the second build (the parent commit's) is not in the repository.  Run --dump once with each library, each in a fresh
@@ -27,7 +28,19 @@ Linear case set (the host path of the linear static analysis), on the small dist
 Outputs per case: D / AL / AU / B after assembly without and with load and boundary conditions, strain and stress of the update
 without and with a thermal view; per type the element stiffness.  A refused call is recorded by its return code.  Run it under
 the default, FX_ASM_FIRST=0 and FX_ASM_MAP=0, each in its own process (the switches are read once).  QFORCE and the thermal load
-vector are atomic sums: not compared."""
+vector are atomic sums: not compared.
+
+Field case set (the host paths of heat conduction, distributed loads and stress output):
+  fx_heat_assemble_groups_bc, stationary and transient, with DFLUX (faces and the body flux), FILM and RADIATE lists, and
+  fx_nodal_stress_groups with every principal array, on the small distorted meshes of test_gpu_heat_bc.py (each of the six types,
+  the two three-type mixed meshes) and on a 5^3 mesh of each type (more than one workgroup and more than one colour per launch);
+  fx_heat_element and fx_heat_face for every type, kind and face, fx_dload_element for every type and every LTYPE it has.
+  None of these adds atomically: --compare wants them equal bit for bit.  fx_dload_groups (the meshes and lists of
+  test_gpu_dload.py) and fx_nl_get_load are sums of fp64 atomics: their keys end in "~atomic" and --compare holds them to that
+  test's bound, 1e-11 of the largest entry.  The refusals of tests/test_gpu_refusal_order.py's kind -- a collapsed 361 element in
+  the heat assembly (refused) and in fx_assemble_groups / fx_dload_groups (accepted), an unknown type with NDOF = 3, NDOF = 3 with an
+  empty mesh, a bad node id behind a duplicate, a list entry of dflux, film, radiate and dload with its group, then its element, then
+  its face out of range -- are recorded with code and message."""
 import os
 import sys
 
@@ -40,6 +53,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 STATE = ("stress", "strain", "stress_bak", "strain_bak", "plstrain", "fstat", "istat")
 ETYPES = (361, 341, 342, 351, 352, 362)
 E0, NU0 = 206900.0, 0.29
+ATOMIC_BOUND = 1e-11      # of the largest entry: what tests/test_gpu_dload.py allows a vector summed with fp64 atomics
 
 
 def compare(fa, fb):
@@ -52,6 +66,9 @@ def compare(fa, fb):
         if x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes():
             print("%-60s equal (%d values)" % (k, x.size))
             continue
+        if k.endswith("~atomic") and x.shape == y.shape and np.abs(x - y).max() <= ATOMIC_BOUND * np.abs(y).max():
+            print("%-60s within %.0e of the largest entry: %.2e (%d values)" % (k, ATOMIC_BOUND, np.abs(x - y).max() / np.abs(y).max(), x.size))
+            continue
         bad.append(k)
         if x.shape != y.shape or x.dtype != y.dtype:
             print("%-60s DIFFERS: %s %s against %s %s" % (k, x.dtype, x.shape, y.dtype, y.shape))
@@ -60,7 +77,7 @@ def compare(fa, fb):
         i = int(np.flatnonzero((xb != yb).any(axis=1))[0])
         print("%-60s DIFFERS: %d of %d values, first at %d: %r against %r" % (k, int((xb != yb).any(axis=1).sum()), x.size, i,
                                                                               x.ravel()[i], y.ravel()[i]))
-    print("%d arrays differ" % len(bad) if bad else "all arrays equal bit for bit")
+    print("%d arrays differ" % len(bad) if bad else "all arrays equal bit for bit (the atomic sums, if any: within their bound)")
     return 1 if bad else 0
 
 
@@ -271,6 +288,142 @@ def dump_linear(path):
     return 0
 
 
+def dump_fields(path):
+    import test_gpu_dload as TD
+    import test_gpu_heat as TG
+    import test_gpu_heat_bc as TB
+    import test_gpu_nodal_stress as TN
+    import test_gpu_refusal_order as RO
+    from frontistr_amd import fstr, hecmw as hip
+    from frontistr_amd.heat import heat_matrix
+    from test_dload_ref import skewed_element
+    out = {}
+
+    def record(name, call):
+        """call() -> {key: array}; a refusal is recorded by its code and its message"""
+        try:
+            for k, v in call().items():
+                out["%s/%s" % (name, k)] = np.array(v)
+        except hip.HecmwSolverError as e:
+            out["%s/refused" % name] = np.array([e.code])
+            out["%s/message" % name] = np.array(str(e))
+
+    ctx = hip.SolverContext()
+
+    def heat(m, groups, M, beta, dtime, lists):
+        temp, temp0 = TG.fields(m.coord)
+        ctx.heat_assemble_groups(m.coord, groups, TG.materials(True), M, temp, temp0, beta=beta, dtime=dtime, dflux=lists[0], film=lists[1],
+                                 radiate=lists[2], tzero=TB.TZERO)
+        return {k: getattr(M, k).copy() for k in ("D", "AL", "AU", "B")}
+
+    def nodal(m, groups):
+        st, ss = TN.points(groups, 7)
+        res = ctx.nodal_stress_groups(m.n_node, groups, st, ss, principal=255)
+        return {k: getattr(res, k).copy() for k in TN.ARRAYS}
+
+    meshes = [("small_%s" % k, TB.case_mesh(k)) for k in TG.KINDS] + [("n5_t%d" % et, TG._mesh(et, 5)) for et in TG.TYPES]
+    for name, m in meshes:
+        groups = [(et, conn, None, (1 + (np.arange(conn.shape[0]) % 2)).astype(np.int32)) for et, conn in TG._groups(m)]
+        M = heat_matrix(m.n_node, groups)[1]
+        lists = TB.lists_of(m, groups)
+        for tag, beta, dtime in (("stationary", 1.0, 0.0), ("transient", 0.5, 0.37), ("stationary_again", 1.0, 0.0)):
+            record("%s/heat_%s" % (name, tag), lambda: heat(m, groups, M, beta, dtime, lists))
+        record("%s/nodal_stress" % name, lambda: nodal(m, [g[:2] for g in groups]))
+
+    hmats = TG.materials(True)
+    for et in TG.TYPES:
+        X, _ = skewed_element(et, curve=0.07)
+        nn = X.shape[0]
+        tt, tt0 = 300.0 + 250.0 * np.sin(1.0 + np.arange(nn)), 250.0 + 200.0 * np.cos(2.0 + np.arange(nn))
+        for dtime in (0.0, 0.25):
+            ss, s0 = ctx.heat_element(et, X, tt, hmats[0], tt0=tt0, dtime=dtime)
+            out["t%d/heat_element_dtime%g/ss" % (et, dtime)] = ss
+            if s0 is not None:
+                out["t%d/heat_element_dtime%g/s0" % (et, dtime)] = s0
+        nf = len(fstr.tDload.SUBFACE[et])
+        for kind in ("dflux", "film", "radiate"):
+            for f in range(0 if kind == "dflux" else 1, nf + 1):
+                t1, t2, nod = ctx.heat_face(et, kind, f, X, 25.0, sink=600.0, tt=tt, tzero=TB.TZERO)
+                res = {"term2": t2, "nod": nod}
+                if t1 is not None:
+                    res["term1"] = t1
+                for k, v in res.items():
+                    out["t%d/heat_face_%s_%d/%s" % (et, kind, f, k)] = v
+        cases = [(1, [3.0]), (2, [-2.0]), (3, [1.5]), (4, [9.8, 1.0, -2.0, 2.0]), (5, [3.0, 0.5, -1.0, 0.25, 1.0, 2.0, -0.5])]
+        cases += [(10 * f, [2.5]) for f in range(1, nf + 1)]
+        for ltype, par in cases:
+            out["t%d/dload_element_%d" % (et, ltype)] = ctx.dload_element(et, ltype, X, np.array(list(par) + [0.0] * (7 - len(par))), rho=7.8)
+
+    for name in list(TG.TYPES) + ["mixed"]:
+        m, groups = TD._mesh(name)
+        dl = TD._list(m, groups, name)
+        disp = 0.02 * np.cos(np.arange(3 * m.n_node) * 0.61)
+        record("dload_%s" % name, lambda: {"load~atomic": ctx.dload_groups(m.coord, groups, TD.RHO, dl, factor=0.5)[0],
+                                           "load_displaced~atomic": ctx.dload_groups(m.coord, groups, TD.RHO, dl, factor=0.5, disp=disp)[0]})
+
+    # ---- refusals, and what the other entry points make of the same mesh
+    def nothing(call):
+        """call() for its refusal; accepted, it records nothing"""
+        def run():
+            call()
+            return {}
+        return run
+
+    heat_call = lambda *a, **kw: nothing(RO._heat(hip, ctx, *a, **kw))
+    col, bad = RO._collapsed(RO.HEXES), RO.HEXES[1:].copy()
+    bad[0, 2] = RO.N + 1
+    record("refuse/heat_collapsed_361", heat_call([(361, col)]))
+    record("refuse/heat_unknown_type_ndof3", heat_call([(999, RO.HEXES)], ndof=3))
+    record("refuse/heat_ndof3_empty_mesh", heat_call([(361, RO.HEXES)], ndof=3, coord=np.zeros((0, 3))))
+    two = [(341, RO.TETS), (361, RO.HEXES[1:])]
+    record("refuse/heat_duplicate_then_bad_node", heat_call([(341, RO._collapsed(RO.TETS)), (361, bad)], profile_groups=two))
+    record("refuse/assemble_duplicate_then_bad_node", nothing(lambda: ctx.assemble_groups(RO.COORD, [(341, RO._collapsed(RO.TETS)), (361, bad)], E0, NU0)))
+    for kind in ("dflux", "film", "radiate"):
+        tail = (1.0,) if kind == "dflux" else (1.0, 300.0)
+        for tag, (g, e, f) in (("group", (1, 5, 9)), ("element", (0, 5, 9)), ("face", (0, 1, 9))):
+            record("refuse/heat_%s_%s" % (kind, tag), heat_call([(361, RO.HEXES)], **{kind: (RO.I0 + g, RO.I0 + e, RO.I0 + f) + tail}))
+    for tag, (g, e, lt) in (("group", (1, 5, 90)), ("element", (0, 5, 90)), ("face", (0, 1, 90))):
+        record("refuse/dload_%s" % tag, nothing(lambda: ctx.dload_groups(RO.COORD, [(361, RO.HEXES)], None, (RO.I0 + g, RO.I0 + e, RO.I0 + lt, np.zeros((1, 7))))))
+    press = (RO.I0, RO.I0, RO.I0 + 10, np.array([[2.0, 0, 0, 0, 0, 0, 0]]))
+    record("accept/dload_collapsed_361", lambda: {"load~atomic": ctx.dload_groups(RO.COORD, [(361, col)], None, press)[0]})
+    ctx.close()
+
+    def assemble_collapsed():
+        hm = hip.hecmwST_local_mesh(n_node=RO.N)
+        mat = hip.hecmw_mat_con_groups(hm, hip.hecmwST_matrix(), [(361, col, 1, None)])
+        c = hip.SolverContext()
+        c.upload(mat, what=hip.FX_UP_PROFILE)
+        c.assemble_groups(RO.COORD, [(361, col, 1, None)], E0, NU0)
+        c.download_matrix(mat)
+        c.close()
+        return {k: getattr(mat, k) for k in ("D", "AL", "AU")}
+    record("accept/assemble_collapsed_361", assemble_collapsed)
+
+    # ---- fx_nl_get_load: the resident load vector with a list that follows the displacement and one that does not
+    from frontistr_amd.mesh import CubeMesh
+    m = CubeMesh(3)
+    hm = hip.hecmwST_local_mesh(n_node=m.n_node)
+    hm.nn_elem, hm.elem_node_item = 8, m.conn.ravel()
+    c = hip.SolverContext()
+    c.upload(hip.hecmw_mat_con(hm, hip.hecmwST_matrix()), what=hip.FX_UP_PROFILE)
+    solid = fstr.fstr_solid(c, m.coord, m.conn, fstr.tMaterial(1000.0, 0.3, nlgeom_flag=fstr.TOTALLAG))
+    dl = fstr.tDload()
+    for g, e, f in fstr.dload_faces(m.coord, [(361, m.conn)], m.coord[:, 2] == 3.0):
+        dl.pressure(g, [e], f, 2.0)
+    dl.gravity(0, np.arange(m.conn.shape[0]), 9.8, (0.2, 0.0, -1.0))
+    cload = np.ascontiguousarray(np.sin(np.arange(3 * m.n_node) * 0.23))
+    solid.set_state({"unode": 0.05 * np.cos(np.arange(3 * m.n_node) * 0.41)})
+    for follow in (True, False):
+        solid.set_dload(dl, 0.4, follow=follow)
+        solid.set_dload_factor(0.7)
+        hip._chk(hip.lib().fx_nl_begin_substep(c.h, hip._ptr(cload)))
+        out["nl_get_load/follow%d~atomic" % follow] = solid.get_load()
+    c.close()
+    np.savez(path, **out)
+    print("%d arrays of %d cases written to %s (library %s)" % (len(out), len({k.rsplit("/", 1)[0] for k in out}), path, hip.LIBPATH))
+    return 0
+
+
 if __name__ == "__main__":
     from _libarg import take_lib
     take_lib()
@@ -281,4 +434,6 @@ if __name__ == "__main__":
         sys.exit(dump(args[1]))
     if len(args) == 2 and args[0] == "--dump-linear":
         sys.exit(dump_linear(args[1]))
+    if len(args) == 2 and args[0] == "--dump-fields":
+        sys.exit(dump_fields(args[1]))
     sys.exit(__doc__)

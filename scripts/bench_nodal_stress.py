@@ -148,4 +148,6 @@ def main():
 
 
 if __name__ == "__main__":
+    from _libarg import take_lib
+    take_lib()      # --lib PATH: another build of the library (the parent commit's, say)
     main()
