@@ -16,7 +16,9 @@
 // quadrature point q (the `ulpe` precedent): its Jacobian, WG = weight DET and, for CENT, the three coefficients, left in LDS; then
 // lane I < NN sums PLX, PLY, PLZ of node I over the points in the routine's order.
 // Scatter: every entry's vector times its factor (fstr_ass_load.f90:141-142, :254) is added to the 3 n_node vector with fp64 atomics,
-// as fx_thermal_load_groups and QFORCE are: equal to rounding from call to call, not bit for bit.  An entry that appears twice is
+// as fx_thermal_load_groups and QFORCE are: equal to rounding from call to call, not bit for bit.  The resident list of the
+// nonlinear loop is the exception: its batches are launched colour by colour (dload_colour: no two entries of a launch share a node),
+// so the same inputs give the same GL bit for bit, which a cutback relies on.  An entry that appears twice is
 // added twice.  The kernels cannot fail (the routine has no check of DET either): they leave the context's error word alone.
 #pragma once
 
@@ -371,9 +373,42 @@ static int dload_check(const char *who, int32_t n_group, const fx_elem_group *gr
   return 0;
 }
 
+// The entries `idx` of one batch (nn nodes each, node(k, i) the 1-based id of node i of entry k) sorted by colour, stably: greedy,
+// every entry takes the lowest colour that none of its nodes holds yet.  -> the colour offsets.  The bit masks grow by 64 colours
+// (one word per node) whenever an entry finds none free: a node of a Kuhn mesh with GRAV, CENT and a body force on every
+// element around it holds more than 64 entries.
+template <class Node>
+static std::vector<int32_t> dload_colour(std::vector<int32_t> &idx, int nn, int32_t n_node, Node node) {
+  std::vector<std::vector<uint64_t>> used;
+  std::vector<int32_t> colour(idx.size());
+  int32_t ncol = 0;
+  for (size_t q = 0; q < idx.size(); q++) {
+    int32_t col = -1;
+    for (size_t w = 0; col < 0; w++) {
+      if (w == used.size()) used.emplace_back((size_t)n_node, (uint64_t)0);
+      uint64_t m = 0;
+      for (int i = 0; i < nn; i++) m |= used[w][(size_t)node(idx[q], i) - 1];
+      if (~m) col = (int32_t)(64 * w) + __builtin_ctzll(~m);
+    }
+    for (int i = 0; i < nn; i++) used[(size_t)col / 64][(size_t)node(idx[q], i) - 1] |= (uint64_t)1 << (col % 64);
+    colour[q] = col;
+    ncol = std::max(ncol, col + 1);
+  }
+  std::vector<int32_t> off((size_t)ncol + 1, 0), sorted(idx.size());
+  for (int32_t col : colour) off[(size_t)col + 1]++;
+  for (int32_t k = 0; k < ncol; k++) off[(size_t)k + 1] += off[k];
+  std::vector<int32_t> at(off.begin(), off.end() - 1);
+  for (size_t q = 0; q < idx.size(); q++) sorted[(size_t)at[colour[q]]++] = idx[q];
+  idx.swap(sorted);
+  return off;
+}
+
 // The checked list as batches on the device: faces by shape (all groups together), volume entries by element type.
+// coloured (the resident list of fx_nl_set_dload, n_node its node count): every batch is cut into colours of entries that share no
+// node, one launch each, so that a rebuilt GL is the same bit for bit whenever its inputs are (an entry that names a node twice --
+// a collapsed hexahedron -- still adds to it twice in one launch).
 static int dload_build(fx_context *c, int32_t n_group, const fx_elem_group *groups, int32_t n_mat, const double *rho, const fx_dload *dl,
-                       DloadList &L) {
+                       DloadList &L, bool coloured = false, int32_t n_node = 0) {
   dload_list_free(L);
   std::vector<std::vector<int32_t>> pick(10);
   for (int32_t k = 0; k < dl->n; k++) {
@@ -388,11 +423,17 @@ static int dload_build(fx_context *c, int32_t n_group, const fx_elem_group *grou
     }
   }
   for (int kind = 0; kind < 10; kind++) {
-    const std::vector<int32_t> &idx = pick[kind];
+    std::vector<int32_t> &idx = pick[kind];
     if (idx.empty()) continue;
     DloadBatch b;
     b.kind = kind; b.n = (int32_t)idx.size();
     const int nn = kind < 4 ? DL_FACE_MM[kind] : c3_nodes(c3_type_at(kind - 4));
+    if (coloured)
+      b.color_off = dload_colour(idx, nn, n_node, [&](int32_t k, int i) {
+        const fx_elem_group &G = groups[dl->group[k]];
+        const int32_t *en = G.conn + (size_t)c3_nodes(G.etype) * dl->elem[k];
+        return kind < 4 ? en[C3_FACE_NOD[c3_type_index(G.etype)][dl->ltype[k] / 10 - 1][i] - 1] : en[i];
+      });
     std::vector<int32_t> nodes((size_t)nn * b.n), lts((size_t)b.n);
     std::vector<double> par((size_t)8 * b.n);
     std::vector<uint8_t> held((size_t)b.n);
@@ -420,17 +461,26 @@ static int dload_build(fx_context *c, int32_t n_group, const fx_elem_group *grou
   return 0;
 }
 
-static void dload_launch_batch(fx_context *c, const DloadBatch &b, DloadArgs a) {
-  a.n = b.n; a.nodes = b.nodes; a.par = b.par; a.held = b.held; a.ltype = b.ltype;
+// The entries e0 .. e1 of a batch in one launch
+static void dload_launch_range(fx_context *c, const DloadBatch &b, DloadArgs a, int32_t e0, int32_t e1) {
+  const int32_t n = e1 - e0;
+  if (n <= 0) return;
+  const int nn = b.kind < 4 ? DL_FACE_MM[b.kind] : c3_nodes(c3_type_at(b.kind - 4));
+  a.n = n; a.nodes = b.nodes + (size_t)nn * e0; a.par = b.par + (size_t)8 * e0; a.held = b.held + e0; a.ltype = b.ltype + e0;
   if (b.kind < 4) {
-    const dim3 grid((unsigned)((b.n + DLF_FPB - 1) / DLF_FPB));
+    const dim3 grid((unsigned)((n + DLF_FPB - 1) / DLF_FPB));
     with_face_nodes(DL_FACE_MM[b.kind], [&](auto m) { hipLaunchKernelGGL((k_dload_face<decltype(m)::value>), grid, dim3(DLF_BS), 0, c->stream, a); });
     return;
   }
   with_solid_type(c3_type_at(b.kind - 4), [&](auto t) {
     constexpr int T = decltype(t)::value, EPB = DlVol<T>::EPB;
-    hipLaunchKernelGGL((k_dload_vol<T>), dim3((unsigned)((b.n + EPB - 1) / EPB)), dim3(DLV_BS), 0, c->stream, a);
+    hipLaunchKernelGGL((k_dload_vol<T>), dim3((unsigned)((n + EPB - 1) / EPB)), dim3(DLV_BS), 0, c->stream, a);
   });
+}
+// One launch, or one per colour of a coloured batch
+static void dload_launch_batch(fx_context *c, const DloadBatch &b, const DloadArgs &a) {
+  if (b.color_off.empty()) { dload_launch_range(c, b, a, 0, b.n); return; }
+  for (size_t k = 0; k + 1 < b.color_off.size(); k++) dload_launch_range(c, b, a, b.color_off[k], b.color_off[k + 1]);
 }
 // Every batch of the list on the context's stream, the faces first; ev_mid (may be null) is recorded between the two families.
 static int dload_launch(fx_context *c, const DloadList &L, const DloadArgs &a, hipEvent_t ev_mid) {
@@ -597,13 +647,17 @@ extern "C" int fx_nl_set_dload(fx_context *c, int32_t n_mat, const double *rho, 
   // the parts' connectivity and material ids back on the host: the list is resolved to node ids once
   std::vector<std::vector<int32_t>> conn, emat;
   if (int rc = nl_parts_to_host(n, rho != nullptr, conn, emat)) return rc;
+  // the group table in the caller's numbering: an empty group has no part, and keeps its place with no element
   std::vector<fx_elem_group> gv;
-  for (size_t g = 0; g < n.parts.size(); g++)
-    gv.push_back({n.parts[g].etype, 2, n.parts[g].n_elem, conn[g].data(), emat[g].empty() ? nullptr : emat[g].data()});
+  for (size_t g = 0; g < n.group_part.size(); g++) {
+    const int32_t p = n.group_part[g];
+    if (p < 0) gv.push_back({n.group_etype[g], 2, 0, nullptr, nullptr});
+    else gv.push_back({n.parts[p].etype, 2, n.parts[p].n_elem, conn[p].data(), emat[p].empty() ? nullptr : emat[p].data()});
+  }
   if (int rc = dload_check(who, (int32_t)gv.size(), gv.data(), n_mat, rho, dl)) return rc;
   DloadList L;
   double *nodal = nullptr;
-  int rc = dload_build(c, (int32_t)gv.size(), gv.data(), n_mat, rho, dl, L);
+  int rc = dload_build(c, (int32_t)gv.size(), gv.data(), n_mat, rho, dl, L, true, (int32_t)c->A.NP);  // coloured: GL is rebuilt, not summed up
   if (!rc && dev_alloc(&nodal, (size_t)3 * c->A.NP)) rc = FX_ERROR_RUNTIME;
   if (!rc && hipMemsetAsync(nodal, 0, (size_t)3 * c->A.NP * 8, c->stream) != hipSuccess)
     rc = fx_fail(who, FX_ERROR_RUNTIME, "hipMemsetAsync failed");

@@ -283,6 +283,9 @@ struct DloadBatch {
   double *par = nullptr;     // device: n x 8, PARAMS(0:6) and RHO of the entry's element
   uint8_t *held = nullptr;   // device: n, 1: the entry takes factor 1
   int32_t *ltype = nullptr;  // device: n, DL_C3's LTYPE
+  // Empty: one launch over the n entries.  Otherwise the entries are sorted by colour, colour k is color_off[k]..color_off[k+1] and
+  // gets a launch of its own: no two entries of a colour share a node, so every address is added to in the order of the launches
+  std::vector<int32_t> color_off;
 };
 struct DloadList {
   std::vector<DloadBatch> b;
@@ -332,6 +335,8 @@ static bool for_each_point_array(F &&f, S &...s) {
 struct NlDev {
   bool ready = false;
   std::vector<NlPart> parts;          // in the order given; the per-point arrays and the element outputs hold them one after the other
+  std::vector<int32_t> group_part;    // the caller's group position -> index into parts, -1: an empty group (no part is made for it)
+  std::vector<int32_t> group_etype;   // the caller's group position -> its etype (the empty groups' too)
   bool first_write = false;           // every part's map carries first-write flags in the launch order of ALL parts and every block is covered: no clearing
   bool has_yield = false;             // a Mohr-Coulomb or Drucker-Prager section: the stress update reports through the error word too
   bool has_creep = false;             // a NORTON section: so does its creep iteration (FX_CERR_CREEP)

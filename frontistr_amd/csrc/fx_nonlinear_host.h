@@ -376,7 +376,14 @@ static int nl_init_driver(fx_context *c, const char *who, int32_t n_node, const 
                     groups[g].etype == 361 && groups[g].elemopt == 4});
   if (in.empty()) return fx_fail(who, FX_ERROR_RUNTIME, "empty mesh");
   HIP_TRY(hipSetDevice(c->device));
-  return nl_init_parts(c, n_node, coord, in, n_mat, mats);
+  if (int rc = nl_init_parts(c, n_node, coord, in, n_mat, mats)) return rc;
+  // lists that name a group (fx_nl_set_dload) do so by the caller's position, empty groups counted
+  int32_t part = 0;
+  for (int32_t g = 0; g < n_group; g++) {
+    c->nl.group_part.push_back(groups[g].n_elem > 0 ? part++ : -1);
+    c->nl.group_etype.push_back(groups[g].etype);
+  }
+  return 0;
 }
 // The single-type entry points: the mesh as one group (361: B-bar).  With one material elem_mat is not read, whatever it holds.
 static int nl_init_mesh(fx_context *c, const char *who, const fx_mesh_view *mesh, int32_t etype, int32_t n_mat,

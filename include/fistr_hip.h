@@ -755,12 +755,18 @@ int fx_dload_groups(fx_context *ctx, int32_t n_node, const double *coord, int32_
 int fx_dload_element(fx_context *ctx, int32_t etype, int32_t ltype, const double *ecoord, double rho, const double *params,
                      double *vect);
 /* The nonlinear loop (after any fx_nl_init*).  The list -- group = position of the element group given to fx_nl_init_groups, 0 for
- * the single-type set-ups -- is checked as above, resolved to node ids and uploaded once; dl == NULL clears it.  From then on
+ * the single-type set-ups -- is checked as above, resolved to node ids and uploaded once; dl == NULL clears it.  The positions are
+ * the caller's: a group with n_elem == 0, which fx_nl_init_groups skips, keeps its number, so the groups behind it are named as
+ * the caller numbers them, an entry on the empty group itself is refused ("element E is not in group G"), and every message
+ * carries the caller's 1-based group number.  A refused list leaves the list that was in force untouched.  From then on
  *   fx_nl_begin_substep builds GL = the nodal load it is handed + factor * DLOAD before B = GL - QFORCE, on coord + unode when
  *     `follow` is set (DLOAD_follow, the reference's default; !DLOAD, FOLLOW=NO clears it) and on coord otherwise;
  *   with `follow` set, fx_nl_update and fx_nl_update_at rebuild GL on coord + unode + dunode after the stress update and before
  *     the residual: fstr_Newton's second fstr_ass_load (fstr_solve_NonLinear.f90:103).  The nodal part is kept in a vector of its
  *     own, allocated only while a list is set.
+ * The list is launched in colours of entries that share no node (one launch per colour and batch), so a rebuilt GL depends on
+ * its inputs alone: the same nodal load, list, factor and displacements give the same GL bit for bit (fx_dload_groups makes no
+ * such promise).  An entry that names a node twice, a collapsed hexahedron, is outside this.
  * Without a list every fx_nl_* call runs what it ran before these entry points existed.  factor: fstrSOLID%factor(2), default 1;
  * fx_newton_substep sets it to its factor1.  fx_nl_get_load: the resident GL (3*NP) back to the host. */
 int fx_nl_set_dload(fx_context *ctx, int32_t n_mat, const double *rho, const fx_dload *dl, int follow);

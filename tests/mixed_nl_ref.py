@@ -23,6 +23,7 @@ import numpy as np
 
 import c3_nl_ref as CN
 import c3_ref as R
+import dload_ref as DL
 import hyper_ref as H
 import tet_nl_ref as T
 import yield_ref as Y
@@ -184,15 +185,29 @@ class Model(T.Model):
                 np.add.at(self.qforce, (3 * nd[:, None] + np.arange(3)).ravel(), qf[e])
         return self.qforce
 
-    def newton_substep(self, f0, f1, bc, cload, max_iter, converg, maxres=1.0e10):
+    def load_vector(self, cload, factor, dload=None, disp=None):
+        """fstr_ass_load (fstr_ass_load.f90:64-257): GL = factor cload + the DLOAD block of dload_ref.assemble over the model's
+        groups in the caller's numbering (the empty ones keep their place).  dload = (list, rho, follow): the tuple of
+        dload_ref.entries / tDload.arrays, one density per material (or None), DLOAD_follow; a held entry takes factor 1.
+        disp: the displacement of the configuration, used when the load follows."""
+        GL = np.zeros(self.unode.size) if cload is None else np.asarray(cload, dtype=np.float64) * factor
+        if dload is None:
+            return GL
+        dl, rho, follow = dload
+        groups = [(p["etype"], p["conn"], None, p["elem_mat"]) for p in self.parts]
+        return GL + DL.assemble(self.coord, groups, rho, dl, factor=factor, disp=disp if follow else None)
+
+    def newton_substep(self, f0, f1, bc, cload, max_iter, converg, maxres=1.0e10, dload=None):
         """tet_nl_ref.Model.newton_substep, keeping the norms of every iteration in self.newton_log: rows (iteration, |B|, |X|,
-        |QFORCE|, |dunode|) as fx_newton_substep logs them."""
+        |QFORCE|, |dunode|) as fx_newton_substep logs them.  dload (see load_vector): GL at the start of the sub-step is taken on
+        coord + unode when the load follows (coord otherwise) and, following, is rebuilt on coord + unode + dunode after every
+        stress update and before the residual (fstr_solve_NonLinear.f90:103)."""
         n3 = self.unode.size
         node, dof, val = bc
         idx = 3 * (np.asarray(node) - 1) + np.asarray(dof) - 1
         fixed = np.zeros(n3, dtype=bool)
         fixed[idx] = True
-        GL = np.zeros(n3) if cload is None else np.asarray(cload) * f1
+        GL = self.load_vector(cload, f1, dload, self.unode)
         self.dunode[:] = 0.0
         rhs = GL - self.qforce
         self.newton_log = []
@@ -202,6 +217,8 @@ class Model(T.Model):
             x = np.linalg.solve(K, b)
             self.dunode += x
             self.update()
+            if dload is not None and dload[2]:
+                GL = self.load_vector(cload, f1, dload, self.unode + self.dunode)
             rhs = GL - self.qforce
             rhs[fixed] = 0.0
             res, xn = np.sqrt(rhs @ rhs), np.sqrt(x @ x)
@@ -295,6 +312,41 @@ def group_list(mesh, variant, elem_mat=None):
     elif variant != "mesh_order":
         raise ValueError(variant)
     return groups
+
+
+def top_side_dload(mesh, groups, pressure, grav, cent=None):
+    """The list of the group comparisons as a fstr.tDload, built over the caller's group list (group numbers are the caller's
+    positions, an empty group gets no entry): `pressure` on every face whose nodes all lie on the top side (on MixedMesh the
+    quadrilaterals of the x-axis wedges and the triangles of the tetrahedra), GRAV (val, direction) on every element of every group and,
+    with cent = (omega, point, axis), CENT on every third element of each group."""
+    from frontistr_amd import fstr
+    top = np.zeros(mesh.n_node, dtype=bool)
+    top[np.asarray(mesh.top_nodes) - 1] = True
+    dl = fstr.tDload()
+    for g, e, f in fstr.dload_faces(mesh.coord, groups, top):
+        dl.pressure(g, [e], f, pressure)
+    for g, G in enumerate(groups):
+        ne = np.asarray(G[1]).reshape(-1, NODES[int(G[0])]).shape[0]
+        dl.gravity(g, np.arange(ne), grav[0], grav[1])
+        if cent is not None:
+            dl.centrifugal(g, np.arange(0, ne, 3), *cent)
+    return dl
+
+
+# The whole sub-step loop under a follower load (test_gpu_mixed_nonlinear.py, test_newton_substeps_with_a_follower_load): the "n2"
+# mesh with the wedges split, the bottom clamped, nothing prescribed at the top; Mises BILINEAR beside ELASTIC, both TOTALLAG, the
+# constants of test_newton_substeps_with_mises.  Pressure on the top side, gravity on everything, in FOLLOWER["nsub"] sub-steps to
+# CONVERG = 1e-3.  tests/test_dload_nl_ref.py asserts on the CPU what the values were chosen for: the restatement converges in every
+# sub-step within 50 iterations and leaves a plastic point.
+FOLLOWER = dict(pressure=400.0, grav=(9.8, (0.2, 0.0, -1.0)), rho=(2.0, 3.5), nsub=3, converg=1.0e-3, max_iter=50)
+
+
+def follower_case(order):
+    """-> (mesh, groups, mats, bc, tDload) of the follower-load loop"""
+    from oracle.refrun import Material
+    mats = [Material(206900.0, 0.29, plastic=True, harden=0, plconst=(450.0, 2000.0, 0.0), nlgeom=TOTALLAG), Material(70000.0, 0.33, nlgeom=TOTALLAG)]
+    mesh, groups, _, _, _ = gpu_case("n2", order, "split_wedges", mats, True, history=False)
+    return mesh, groups, mats, mesh.dirichlet(), top_side_dload(mesh, groups, FOLLOWER["pressure"], FOLLOWER["grav"])
 
 
 def gpu_case(mesh_name, order, variant, mats, two, seed=17, history=True):

@@ -249,6 +249,47 @@ def test_newton_substeps_with_mises(hip, oracle, order):
     ctx.close()
 
 
+@pytest.mark.parametrize("order", [1, 2])
+def test_newton_substeps_with_a_follower_load(hip, oracle, order):
+    """The same loop driven by a distributed load alone (mixed_nl_ref.follower_case: the bottom clamped, nothing prescribed at the
+    top, follower pressure on the top side and gravity, the materials of test_newton_substeps_with_mises; CG + SSOR to 1e-12)
+    beside the restatement's loop with its load rebuilt in every iteration, sub-step by sub-step: equal Newton counts, the norms
+    to rtol 1e-6 / atol 1e-9 and unode to 1e-9, the bounds of the test above for the reason given there.  Then once with
+    FOLLOW=NO: other counts or norms.  tests/test_dload_nl_ref.py asserts that the restatement alone converges on these values
+    and leaves a plastic point."""
+    from frontistr_amd import fstr
+    from oracle.refrun import default_params
+    F = M.FOLLOWER
+    m, groups, mats, bc, dl = M.follower_case(order)
+    nsub = F["nsub"]
+    logs = {}
+    for follow in (True, False):
+        ref = M.Model(m.coord, groups, mats)
+        ctx, hecMAT, solid = _solid(hip, m, groups, mats)
+        I, Rr = default_params(method=1, precond=1, maxit=5000, tol=1e-12)
+        hecMAT.Iarray[:] = I
+        hecMAT.Rarray[:] = Rr
+        solid.set_dload(dl, F["rho"], follow=follow)
+        logs[follow] = []
+        for sub in range(1, nsub + 1):
+            f = ((sub - 1) / nsub, sub / nsub)
+            ok, it = ref.newton_substep(f[0], f[1], bc, None, F["max_iter"], F["converg"], dload=(dl.arrays(), F["rho"], follow))
+            assert ok
+            okd, log = fstr.fstr_Newton(solid, hecMAT, f, bc, None, F["max_iter"], F["converg"])
+            want = np.array(ref.newton_log)
+            print("follow %s sub-step %d: Newton iterations %d (restatement %d)\n%s\n%s" % (follow, sub, log.shape[0], it, log[:, 3:], want[:, 1:]))
+            assert okd and log.shape[0] == it
+            np.testing.assert_allclose(log[:, 3:], want[:, 1:], rtol=1e-6, atol=1e-9)
+            logs[follow].append(log[:, 3:].copy())
+        assert (ref.flat("plstrain") > 0).any(), "no plastic point"
+        s = solid.get_state()
+        _close(s["unode"], ref.unode, 1e-9, "unode, follow %s" % follow)
+        assert np.array_equal(s["istat"], ref.flat("istat"))
+        ctx.close()
+    same = all(a.shape == b.shape and np.allclose(a, b, rtol=1e-6, atol=1e-9) for a, b in zip(logs[True], logs[False]))
+    assert not same, "FOLLOW=NO gave the follower run's counts and norms"
+
+
 def test_snapshot_restores_every_group_bitwise(hip, oracle):
     from frontistr_amd import fstr
     mats, two = materials("two_sections", M.UPDATELAG)
